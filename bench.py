@@ -16,8 +16,14 @@ barrier and the max-over-ranks.
 One JSON line is printed by rank 0.  `roofline` is for the dominant kernel of the headline tier: `achieved` =
 MFMA flops that kernel EXECUTES per launch / its average launch duration, measured with HIP events on the launch
 stream inside the timed region (`frac` <= 1); the algorithmic (direct-convolution) rate is reported beside it.
-`cpu_baseline` times the CPU oracle (oracle/unet_oracle.py, a port of the reference's float model) on the host
-cores for a bounded sample of the same workload.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the line.  `--full` adds
+everything else, each in runs of its own after the timed steps: the output check against the reference's golden
+logits, the same K steps without the per-launch events, the other tiers (fp32 or f16x3, f16q8, bf16, int8), the
+640x640 configuration, the single-frame latency and camera legs, the training step and `cpu_baseline` (the CPU oracle,
+oracle/unet_oracle.py, a port of the reference's float model, timed on the host cores for a bounded sample of the
+same workload).  `--dump-outputs DIR` writes the logits of the last timed step to DIR/logits.npy (see dump_outputs);
+with N > 1 only rank 0's batch (each rank times its own seeded frames, seed = rank).
 """
 import argparse
 import json
@@ -143,6 +149,24 @@ def cpu_baseline(seconds_budget=24.0):
             "batch1": res[1], "batch8": res[8]}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, logits):
+    """--dump-outputs: the (N, 1, H, W) float32 logits of the last timed step as <out_dir>/logits.npy.  When they exceed
+    64 MB, whole frames are kept: a fixed sample (seed 0) of as many as fit, in batch order."""
+    n = logits.shape[0]
+    per_frame = logits[0].numel() * logits.element_size()
+    keep = min(n, DUMP_MAX_BYTES // per_frame)
+    if keep < 1:
+        raise SystemExit(f"--dump-outputs: one frame of logits ({per_frame} bytes) exceeds {DUMP_MAX_BYTES} bytes")
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        logits = logits[torch.from_numpy(idx).to(logits.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "logits.npy"), logits.float().cpu().numpy())
+
+
 def free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
@@ -226,6 +250,12 @@ def main():
                          "averages of a rocprofv3 run of this command)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only "
                                                       "for rehearsing the multi-rank path on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the output check, the untraced re-timing and every side leg "
+                         "above (other tiers, latency, 640x640, int8, bf16, training, CPU baseline); without it, only "
+                         "the headline steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the last timed step (rank 0) to DIR/logits.npy, float32")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -296,17 +326,21 @@ def main():
     dev_status = model.device_error()
     if dev_status != 0:
         raise SystemExit(f"kernel-side failure during the timed region (status {dev_status})")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, logits)
     # the same K steps without the per-launch events
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        logits = model.run_u8(frames, precision=precision)
-    sync_all()
-    dt_plain = max_over_ranks(time.perf_counter() - t0)
+    dt_plain = None
+    if args.full:
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            logits = model.run_u8(frames, precision=precision)
+        sync_all()
+        dt_plain = max_over_ranks(time.perf_counter() - t0)
 
     # ---- what the timed batch computed: checksums of its first and last frame, the batch-position check, and (when
     #      the batch starts with the frames of tests/golden/modelA_synth2.npz) the distance to the reference's logits ----
     check = None
-    if rank == 0 and not args.no_check:
+    if rank == 0 and args.full and not args.no_check:
         lg = logits[:, 0]
         n = lg.shape[0]
         check = {"frame0": {"sum": float(lg[0].double().sum().item()), "abs_sum": float(lg[0].double().abs().sum().item())},
@@ -324,7 +358,7 @@ def main():
 
     # ---- the other fp32-parity tier on the same batch ----
     other = None
-    if args.other_tier_steps > 0:
+    if args.full and args.other_tier_steps > 0:
         oprec = "fp32" if precision == "f16x3" else "f16x3"
         ol = model.run_u8(frames, precision=oprec)
         sync_all()
@@ -352,7 +386,7 @@ def main():
     # ---- the f16q8 tier on the same batch (f16x3 with the cross terms of the wide 3x3 convolutions on the fp8 matrix
     #      pipe: its own accuracy tier, north_star's 1e-3 rather than the 2e-4 the headline is tested to) ----
     q8 = None
-    if args.q8_steps > 0 and precision == "f16x3" and args.size == 224:
+    if args.full and args.q8_steps > 0 and precision == "f16x3" and args.size == 224:
         ql = model.run_u8(frames, precision="f16q8")     # first call: rebuilds the operators with the fp8 fragments
         sync_all()
         model.profile(True)
@@ -387,7 +421,7 @@ def main():
     #      10 warm-up + 100 timed predicts of one 224x224 frame, host numpy in / host numpy out) and the
     #      PCIe-inclusive batch rate (host uint8 frames -> device -> forward -> uint8 mask back on the host) ----
     latency = None
-    if rank == 0 and args.latency_iters > 0:
+    if rank == 0 and args.full and args.latency_iters > 0:
         frame = S.synthetic_frames(1, args.size, args.size, seed=7)
         fdev = torch.empty((1, args.size, args.size, 3), dtype=torch.uint8, device=dev)
 
@@ -449,7 +483,7 @@ def main():
 
     # ---- large-input configuration (BASELINE.json configs[4]): 640x640, the per-GPU share (64) of batch 512 ----
     large = None
-    if args.large_steps > 0:
+    if args.full and args.large_steps > 0:
         ls, lb = args.large_size, args.large_batch
         lframes = torch.from_numpy(S.synthetic_frames(lb, ls, ls, seed=200 + rank)).to(dev)
         ll = model.run_u8(lframes, precision=precision)      # warm-up: grows the workspace
@@ -490,7 +524,7 @@ def main():
 
     # ---- int8 tier of the deployed network (model B): calibrate on the fp32 tier, quantise, time ----
     int8 = None
-    if rank == 0 and args.int8_steps > 0:
+    if rank == 0 and args.full and args.int8_steps > 0:
         from unet_lane_detection_amd import quant
         from unet_lane_detection_amd.int8 import UNetInt8, calibrate
         sdb = S.seeded_state_dict([32, 64, 128], seed=0)
@@ -539,7 +573,7 @@ def main():
 
     # ---- bf16 tier (BASELINE.json configs[2]): bf16 storage, fp32 accumulate, batch 1024 ----
     bf16 = None
-    if args.bf16_steps > 0:
+    if args.full and args.bf16_steps > 0:
         bframes = torch.from_numpy(S.synthetic_frames(args.bf16_batch, args.size, args.size, seed=1 + rank)).to(dev)
         model.run_u8(bframes, precision="bf16")       # warm-up: packs bf16 weights, allocates the workspace
         sync_all()
@@ -575,7 +609,7 @@ def main():
 
     # ---- training leg (BASELINE.json configs[3]): batch 64/GPU, BCE-with-logits + Adam, DP all-reduce ----
     train = None
-    if args.train_steps > 0:
+    if args.full and args.train_steps > 0:
         model.release()     # give the activation workspace back before the trainer allocates its own
         model = None
         torch.cuda.empty_cache()
@@ -745,7 +779,7 @@ def main():
             "distributed": {"world_size": world, "backend": backend_name,
                             "launcher": os.environ.get("TORCHELASTIC_RUN_ID") and "torch.distributed.run" or
                                         ("bench.py self-launch" if world > 1 else "single process")},
-            "ms_per_step_without_events": dt_plain / args.steps * 1e3,
+            "ms_per_step_without_events": dt_plain / args.steps * 1e3 if dt_plain is not None else None,
             # `achieved` = MFMA flops the dominant kernel EXECUTES (Winograd F(2x2,3x3): 16/36 of the direct-convolution
             # count; split operands: 3x it, on the fp16 pipe) / its launch time; `algorithmic_tflops` = the direct-convolution count / the same time.
             "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
@@ -787,7 +821,7 @@ def main():
             out["bf16"] = bf16
         if train is not None:
             out["train"] = train
-        if not args.no_cpu_baseline and world == 1:      # a reported baseline, timed once: at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # a reported baseline, timed once: at N = 1 only
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if model is not None:
