@@ -315,6 +315,28 @@ int unet_op_conv3x3_x3_head(int device, const float* x_dev, int n, int h, int w,
 int unet_op_upconv2x2_x3(int device, const float* x_dev, int n, int h, int w, int cin, const float* w_host,
                          const float* bias_host, int cout, float* y_dev, void* stream);
 
+/* One decoder step of the split-operand tier - ConvTranspose2d(2f -> f, k2, s2, bias) -> cat([skip, up]) ->
+ * Conv3x3(2f -> f) -> scale/shift (+ ReLU) (reference README.md:1476-1479) - as the composed operator
+ * (csrc/conv_x3_dec.h: the transposed convolution folded into the 3x3 convolution's up half on the host, float64).
+ * skip (N,H,W,f) and x (N,H/2,W/2,2f) fp32 NHWC -> y (N,H,W,f); w_t (2f,f,2,2), b_t (f), w3 (f,2f,3,3), scale / shift (f)
+ * on the host.  f 64 or 128, W % 28 == 0, H even; UNET_ERR_INVALID_ARG otherwise.  Not bit-identical to the two-kernel
+ * path (a different summation). */
+int unet_op_upcat_conv3x3_x3(int device, const float* skip_dev, const float* x_dev, int n, int h, int w, int f,
+                             const float* wt_host, const float* bt_host, const float* w3_host, const float* scale_host,
+                             const float* shift_host, int relu, float* y_dev, void* stream);
+/* Test hook, host arithmetic only: the float64 composition behind unet_op_upcat_conv3x3_x3.  wp_out [4][f][2f][2][2]:
+ * for output parity (a, b) = (p >> 1, p & 1) the 2 x 2 taps over x rows i + a - 1 + {0, 1}, columns j + b - 1 + {0, 1};
+ * bias_out [9][f]: the transposed convolution's bias through the 3x3 up half for border class 3 * row class + column
+ * class (0 = first row / column of the image, 1 = interior, 2 = last). */
+int unet_host_compose_upcat(const float* wt_host, const float* bt_host, const float* w3_host, int f, double* wp_out,
+                            double* bias_out);
+/* Process-wide switch for the composed decoder step in the f16x3 tier's forward (not the f16q8 tier, not training):
+ * -1 = automatic (default) - the levels with f <= 128 on maps of width 28k with a work item for half of the CUs;
+ * 0 = off: ConvTranspose2d + the 3x3 convolution as two kernels everywhere; 1 = wherever the shape rules allow.
+ * Environment UNET_X3_COMPOSE=0 sets the initial value to 0.  A captured HIP graph keeps the setting it was captured
+ * with.  Returns the previous setting. */
+int unet_set_x3_compose(int mode);
+
 /* Which kernel structure the split-operand tier's ConvTranspose2d (and the plain GEMMs of its training path) run on
  * (reference README.md:1442, :1476): -1 = automatic - the one-wave-per-SIMD kernel (csrc/upconv_x3_r512.h: 224-pixel
  * tiles, weights straight from L2) where Cin % 128 == 0 and there is a work item for at least half of the CUs, the

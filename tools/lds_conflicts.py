@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """ds_read_b128 bank-conflict count of the r512 kernels' pixel-operand reads (csrc/conv_x3_r512.h); --blocks: of the third
 structure's 4 x 4-block fragments (csrc/conv_x3_t448.h); --q8: of the q-plane reads (csrc/conv_q8_r512.h); --wino: of the
-Winograd raw-tile reads (csrc/wino_f32.h); --i8: of the int8 tier's pixel reads (csrc/conv_i8.h).
+Winograd raw-tile reads (csrc/wino_f32.h); --i8: of the int8 tier's pixel reads (csrc/conv_i8.h); --dec: of the composed
+decoder step's parity fragments (csrc/conv_x3_dec.h).
 
 A tile is TH x TWX pixels = 14 fragments of 16 consecutive pixels in row-major order; lane (li = lane & 15, lq = lane >> 4)
 of fragment f reads 16 bytes of LDS pixel position pos = (i // TWX) * P + i % TWX + ky * P + kx (i = 16 f + li) at byte
@@ -149,6 +150,35 @@ def analyze_i8(cin, pad, taps):
     return tot / n, worst
 
 
+def analyze_dec(half, pitch, swz):
+    """The reads of csrc/conv_x3_dec.h: a fragment is 16 pixels of one parity class (a, b), lane li = (li >> 1, li & 1)
+    of an 8 x 2 block of that class.  half "skip": high-resolution halo position (2 (li >> 1) + a + ky, 2 (li & 1) + 4 cb
+    + b + kx); half "x": low-resolution (li >> 1) + a + di, (li & 1) + 2 cb + b + dj.  Byte address (r * pitch + c) * 64 +
+    ((lq ^ swz(r)) << 4)."""
+    tot = worst = n = 0
+    taps = [(ky, kx) for ky in range(3) for kx in range(3)] if half == "skip" else [(d, e) for d in range(2) for e in range(2)]
+    for a in range(2):
+        for b in range(2):
+            for cb in range(7):
+                for ty, tx in taps:
+                    cyc = 0
+                    for g in GROUPS:
+                        slots = {}
+                        for lane in g:
+                            li, lq = lane & 15, lane >> 4
+                            if half == "skip":
+                                r, c = 2 * (li >> 1) + a + ty, 2 * (li & 1) + 4 * cb + b + tx
+                            else:
+                                r, c = (li >> 1) + a + ty, (li & 1) + 2 * cb + b + tx
+                            addr = (r * pitch + c) * 64 + ((lq ^ swz(r)) << 4)
+                            slots.setdefault((addr // 16) % 16, set()).add(addr)
+                        cyc += max(len(v) for v in slots.values())
+                    tot += cyc
+                    n += 1
+                    worst = max(worst, cyc)
+    return tot / n, worst
+
+
 if __name__ == "__main__":
     import sys
     if "--i8" in sys.argv:
@@ -158,6 +188,15 @@ if __name__ == "__main__":
                     mean, worst = analyze_i8(cin, pad, taps)
                     print(f"int8 tier, {cin:3d} channels, {taps} tap(s), pad {pad:2d} bytes: {mean:.2f} cycles per read (worst {worst})" +
                           ("   <- conflict free" if worst == 4 else ""))
+        sys.exit(0)
+    if "--dec" in sys.argv:
+        swzs = (("2 (r & 1)", lambda r: 2 * (r & 1)), ("2 ((r >> 1) & 1)", lambda r: 2 * ((r >> 1) & 1)))
+        for half, pitches in (("skip", (30, 32, 34)), ("x", (16, 17, 18))):
+            for p in pitches:
+                for name, swz in swzs:
+                    mean, worst = analyze_dec(half, p, swz)
+                    print(f"decoder parity fragments, {half:4s} half, pitch {p:2d}, part ^ {name}: {mean:.2f} cycles per read "
+                          f"(worst {worst})" + ("   <- conflict free" if worst == 4 else ""))
         sys.exit(0)
     if "--wino" in sys.argv:
         for tht, twt, where in ((16, 8, "224 x 224, 112 x 112"), (9, 14, "56 x 56, 28 x 28"), (18, 7, "14 x 14")):

@@ -107,6 +107,10 @@ SIGNATURES = {
     "unet_set_bf16_persistent": (C.c_int, [C.c_int]),
     "unet_set_x3_upconv_r512": (C.c_int, [C.c_int]),
     "unet_set_x3_cross_fp8": (C.c_int, [C.c_int]),
+    "unet_set_x3_compose": (C.c_int, [C.c_int]),
+    "unet_op_upcat_conv3x3_x3": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "unet_host_compose_upcat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "unet_ipm_prestage_u8": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "unet_resize_u8": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -32,6 +32,7 @@
 #include "conv_x3_ws.h"
 #include "conv_x3_r512.h"
 #include "conv_x3_t448.h"
+#include "conv_x3_dec.h"
 #include "conv_q8_r512.h"
 #include "conv_bf16_r512.h"
 #include "upconv_x3_ws.h"

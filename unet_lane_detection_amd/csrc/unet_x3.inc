@@ -1042,6 +1042,215 @@ hipError_t run_gemm1x1_x3(const uint16_t* wt, const uint16_t* zeros, const uint1
   return hipGetLastError();
 }
 
+// ---- the decoder's composed first convolution (conv_x3_dec.h) ----
+
+// ConvTranspose2d(2f -> f, k2, s2, bias bt) followed by the up half W3[:, f:2f] of a 3x3 convolution (pad 1), composed in
+// float64 (DESIGN.md, "The decoder's composed first convolution"): for the output pixel (2i + a, 2j + b), high-resolution
+// tap ky reads the transposed convolution's output row 2i + a + ky - 1 = 2 (i + floor((a + ky - 1) / 2)) + ((a + ky - 1) & 1):
+// low-resolution row i + a - 1 + di with di = floor((a + ky - 1) / 2) - (a - 1) in {0, 1}, kernel row (a + ky - 1) & 1.
+//   wp [parity a * 2 + b][co][ci (2f)][di * 2 + dj], bias [class][co] with class = row class * 3 + column class (0 first
+//   row / column of the image, 1 interior, 2 last): the sum over the taps whose high-resolution pixel lies inside the
+//   image (a high-resolution row is inside iff its low-resolution row is: H = 2h)
+void compose_upcat(const float* wt, const float* bt, const float* w3, int f, std::vector<double>& wp, std::vector<double>& bias) {
+  const int c2 = 2 * f;
+  wp.assign((size_t)4 * f * c2 * 4, 0.0);
+  bias.assign((size_t)9 * f, 0.0);
+  std::vector<double> w3u((size_t)f * f), wtp((size_t)c2 * f), m((size_t)f * c2);
+  auto fl2 = [](int v) { return v >= 0 ? v / 2 : -((1 - v) / 2); };   // floor(v / 2)
+  for (int ky = 0; ky < 3; ++ky)
+    for (int kx = 0; kx < 3; ++kx) {
+      for (int co = 0; co < f; ++co)
+        for (int c = 0; c < f; ++c) w3u[(size_t)co * f + c] = w3[(((size_t)co * c2 + f + c) * 3 + ky) * 3 + kx];
+      for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 2; ++b) {
+          const int py = (a + ky - 1) & 1, px = (b + kx - 1) & 1;
+          const int di = fl2(a + ky - 1) - (a - 1), dj = fl2(b + kx - 1) - (b - 1);
+          for (int ci = 0; ci < c2; ++ci)
+            for (int c = 0; c < f; ++c) wtp[(size_t)ci * f + c] = wt[(((size_t)ci * f + c) * 2 + py) * 2 + px];
+          for (int co = 0; co < f; ++co) {
+            const double* wr = &w3u[(size_t)co * f];
+            double* out = &wp[((size_t)(a * 2 + b) * f + co) * c2 * 4];
+            for (int ci = 0; ci < c2; ++ci) {
+              const double* tr = &wtp[(size_t)ci * f];
+              double s = 0.0;
+              for (int c = 0; c < f; ++c) s += wr[c] * tr[c];
+              out[(size_t)ci * 4 + di * 2 + dj] += s;
+            }
+          }
+        }
+      // the bias through this tap, into every class whose pixels see the tap inside the image
+      for (int co = 0; co < f; ++co) {
+        double v = 0.0;
+        for (int c = 0; c < f; ++c) v += w3u[(size_t)co * f + c] * (double)bt[c];
+        for (int rc = 0; rc < 3; ++rc)
+          for (int cc = 0; cc < 3; ++cc)
+            if (!(rc == 0 && ky == 0) && !(rc == 2 && ky == 2) && !(cc == 0 && kx == 0) && !(cc == 2 && kx == 2))
+              bias[(size_t)(rc * 3 + cc) * f + co] += v;
+      }
+    }
+}
+
+struct DecOpX3 {
+  int f = 0, relu = 0;
+  uint16_t* wt = nullptr;   // UpcatX3Args::wt
+  float* scale = nullptr;
+  float* shift = nullptr;
+  float* dshift = nullptr;
+  void free_dev() {
+    for (void* p : {(void*)wt, (void*)scale, (void*)shift, (void*)dshift})
+      if (p) hipFree(p);
+    wt = nullptr;
+    scale = shift = dshift = nullptr;
+  }
+};
+
+// the composed operator of one decoder step: wt (2f,f,2,2), bt (f), w3 (f,2f,3,3) with BatchNorm scale / shift folded;
+// skipIn / xIn / out: activation scales of the skip, of x (the transposed convolution's input) and of the output
+int build_upcat_x3(std::string& err, DecOpX3& op, const float* wt, const float* bt, const float* w3, int f, const float* scale,
+                   const float* shift, int relu, const ActScale* skipIn, const ActScale* xIn, const ActScale* out) {
+  op.free_dev();
+  op.f = f;
+  op.relu = relu;
+  const int c2 = 2 * f;
+  std::vector<double> wp, bias;
+  compose_upcat(wt, bt, w3, f, wp, bias);
+  // both halves with their inputs' scales divided out (exact: powers of two), as float
+  std::vector<float> ws((size_t)f * f * 9), wx((size_t)4 * f * c2 * 4);
+  for (int co = 0; co < f; ++co)
+    for (int ci = 0; ci < f; ++ci)
+      for (int t = 0; t < 9; ++t)
+        ws[((size_t)co * f + ci) * 9 + t] = w3[((size_t)co * c2 + ci) * 9 + t] / (skipIn ? skipIn->act[ci] : 1.f);
+  for (int p = 0; p < 4; ++p)
+    for (int co = 0; co < f; ++co)
+      for (int ci = 0; ci < c2; ++ci)
+        for (int t = 0; t < 4; ++t) {
+          const size_t i = (((size_t)p * f + co) * c2 + ci) * 4 + t;
+          wx[i] = (float)wp[i] / (xIn ? xIn->act[ci] : 1.f);
+        }
+  // one power-of-two pre-scale per output channel over both halves (they feed one accumulator)
+  std::vector<float> pre(f);
+  for (int co = 0; co < f; ++co) {
+    float mx = 0.f;
+    for (size_t i = 0; i < (size_t)f * 9; ++i) mx = std::max(mx, std::fabs(ws[(size_t)co * f * 9 + i]));
+    for (int p = 0; p < 4; ++p)
+      for (size_t i = 0; i < (size_t)c2 * 4; ++i) mx = std::max(mx, std::fabs(wx[((size_t)p * f + co) * c2 * 4 + i]));
+    pre[co] = prescale_pow2(mx);
+  }
+  std::vector<float> sc(f), sh(f), dsh((size_t)9 * f);
+  for (int co = 0; co < f; ++co) {
+    const float o = out ? out->act[co] : 1.f;
+    sc[co] = scale[co] / pre[co] * o;
+    double cls[9];
+    for (int k = 0; k < 9; ++k) cls[k] = ((double)shift[co] + (double)scale[co] * bias[(size_t)k * f + co]) * o;
+    sh[co] = (float)cls[4];
+    for (int k = 0; k < 9; ++k) dsh[(size_t)k * f + co] = k == 4 ? 0.f : (float)(cls[k] - (double)sh[co]);
+  }
+  // pack: per 64-channel tile the f / 32 skip chunks [tap 9][plane][cs][lane][8], then the 2f / 32 x chunks
+  // [parity 4][tap 4][plane][cs][lane][8]; row j of subtile cs is channel 64 ct + 16 (j >> 2) + 4 cs + (j & 3)
+  const int nS = f / 32, nX = c2 / 32, nCt = f / 64;
+  const size_t frag = 64 * 8, skipChunk = 9 * 2 * 4 * frag, xChunk = 16 * 2 * 4 * frag;
+  const size_t perCt = nS * skipChunk + nX * xChunk;
+  std::vector<uint16_t> packed(nCt * perCt, 0);
+  auto put = [&](size_t base, int ct, int kc, auto&& val) {   // one tap: [plane][cs][lane][8]
+    for (int cs = 0; cs < 4; ++cs)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int j = lane & 15, lq = lane >> 4;
+        const int co = 64 * ct + 16 * (j >> 2) + 4 * cs + (j & 3);
+        for (int e = 0; e < 8; ++e) {
+          const int ci = kc * 32 + lq * 8 + e;
+          uint16_t* dh = packed.data() + base + ((size_t)(0 * 4 + cs) * 64 + lane) * 8 + e;
+          uint16_t* dl = packed.data() + base + ((size_t)(1 * 4 + cs) * 64 + lane) * 8 + e;
+          host_split_f16(val(co, ci) * pre[co], *dh, *dl);
+        }
+      }
+  };
+  for (int ct = 0; ct < nCt; ++ct) {
+    for (int kc = 0; kc < nS; ++kc)
+      for (int t = 0; t < 9; ++t)
+        put(ct * perCt + kc * skipChunk + t * 2 * 4 * frag, ct, kc,
+            [&](int co, int ci) { return ws[((size_t)co * f + ci) * 9 + t]; });
+    for (int kc = 0; kc < nX; ++kc)
+      for (int p = 0; p < 4; ++p)
+        for (int t = 0; t < 4; ++t)
+          put(ct * perCt + nS * skipChunk + kc * xChunk + (p * 4 + t) * 2 * 4 * frag, ct, kc,
+              [&](int co, int ci) { return wx[(((size_t)p * f + co) * c2 + ci) * 4 + t]; });
+  }
+  int rc = upload_bf(err, &op.wt, packed);
+  if (!rc) rc = upload(err, &op.scale, sc);
+  if (!rc) rc = upload(err, &op.shift, sh);
+  if (!rc) rc = upload(err, &op.dshift, dsh);
+  return rc;
+}
+
+// unet_set_x3_compose: -1 = automatic (default; UNET_X3_COMPOSE=0 in the environment makes it 0), 0 = the two-kernel
+// path everywhere, 1 = the composed operator wherever its shape rules allow (also below the work-item threshold)
+int& x3_compose_mode() {
+  static int mode = [] {
+    const char* e = getenv("UNET_X3_COMPOSE");
+    return (e && e[0] == '0') ? 0 : -1;
+  }();
+  return mode;
+}
+
+// the composed decoder step: skip planes (n,h,w) pixel stride ldSkip, x planes (n,h/2,w/2,2f) -> out planes (n,h,w,f)
+// pixel stride ldo.  Returns false (nothing launched) where the shape rules or, with forced == false, the work count do
+// not allow it: f % 64 == 0 and f <= 128 (the 8-row, 256-channel tiles of the wider levels are not built), w % 28 == 0,
+// h even, a work item for half of the CUs and 16-row tiles filled to >= 90 %
+bool run_upcat_x3(const DecOpX3& op, const uint16_t* zeros, const uint16_t* skip, size_t skipLo, int ldSkip, const uint16_t* x,
+                  size_t xLo, int n, int h, int w, uint16_t* out, size_t outLo, int ldo, bool forced, hipStream_t s,
+                  hipError_t* err) {
+  *err = hipSuccess;
+  const int f = op.f;
+  if (!op.wt || f % 64 || f > 128 || w % 28 || h % 2 || h < 2) return false;
+  // 64 output channels per block at both levels: the 128-channel form (two column parities per wave, 14 fragments)
+  // spills 200 registers to scratch beside its 224 accumulators and the four-tap weight ring
+  const int wco = 1;
+  unet::UpcatX3Args a;
+  a.skip = skip;
+  a.skipLo = skipLo;
+  a.x = x;
+  a.xLo = xLo;
+  a.wt = op.wt;
+  a.zeros = zeros;
+  a.scale = op.scale;
+  a.shift = op.shift;
+  a.dshift = op.dshift;
+  a.out = out;
+  a.outLo = outLo;
+  a.N = n;
+  a.H = h;
+  a.W = w;
+  a.F = f;
+  a.ldSkip = ldSkip;
+  a.ldo = ldo;
+  a.tilesX = w / 28;
+  a.tilesY = (h + 15) / 16;
+  a.nS = f / 32;
+  a.nX = 2 * f / 32;
+  a.relu = op.relu;
+  a.coTiles = f / (64 * wco);
+  a.pixTiles = n * a.tilesY * a.tilesX;
+  a.err = g_errWord ? g_errWord : op_err_word();
+  const long items = (long)a.pixTiles * a.coTiles;
+  if (!forced && (items < 128 || 10 * h < 9 * 16 * a.tilesY)) return false;
+  const int grid = (int)std::max<long>(8, std::min<long>(256, items / 8 * 8));
+  const double px = (double)n * h * w;
+  // executed multiply-adds: 9 f^2 (skip) + 8 f^2 (x: 4 taps x 2f) per pixel
+  prof_begin("upcat_conv3x3_dec_f16x3", 2.0 * px * 17.0 * f * f,
+             4.0 * (px * f + px / 4 * 2 * f + px * f) + 2.0 * (9.0 * f * f + 32.0 * f * f), s);
+  auto launch = [&](auto kern) {
+    hipError_t e = ensure_dyn_lds((const void*)kern, unet::X3DShape::LDS_BYTES);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), (size_t)unet::X3DShape::LDS_BYTES, s, a);
+      e = hipGetLastError();
+    }
+    return e;
+  };
+  *err = launch(unet::upcat_conv3x3_dec_f16x3_kernel<1>);
+  prof_end(s);
+  return true;
+}
+
 }  // namespace
 
 struct X3Net {
@@ -1050,6 +1259,7 @@ struct X3Net {
   uint16_t* zeros = nullptr;
   float* headW = nullptr;        // head weights with the last activation's scale divided out
   std::vector<GemmOpX3> enc, bott, up, dec;
+  std::vector<DecOpX3> comp;     // per decoder step j: the composed up + dec[2 j] operator (conv_x3_dec.h), where built
   char* ws = nullptr;
   size_t wsBytes = 0;
   bool hasQ8 = false;            // the operators carry their fp8 cross-term fragments (f16q8 tier)
@@ -1061,6 +1271,7 @@ static void x3_free(unet_ctx* h) {
   if (!h->x3) return;
   for (auto* v : {&h->x3->enc, &h->x3->bott, &h->x3->up, &h->x3->dec})
     for (auto& op : *v) op.free_dev();
+  for (auto& op : h->x3->comp) op.free_dev();
   if (h->x3->ws) hipFree(h->x3->ws);
   if (h->x3->qbuf) hipFree(h->x3->qbuf);
   if (h->x3->zeros) hipFree(h->x3->zeros);
@@ -1127,6 +1338,7 @@ int x3_build(unet_ctx* h) {
   X->enc.assign(2 * c.depth, GemmOpX3());
   X->dec.assign(2 * c.depth, GemmOpX3());
   X->up.assign(c.depth, GemmOpX3());
+  X->comp.assign(c.depth, DecOpX3());
   X->bott.assign(2, GemmOpX3());
   int rc;
   int cin = 3;
@@ -1157,6 +1369,21 @@ int x3_build(unet_ctx* h) {
     const ActScale cat = act_concat(skip[l], upOut);   // torch.cat([skip, x]) (reference README.md:1478)
     const std::string pd = "decoder_blocks." + std::to_string(2 * j + 1);
     if ((rc = conv(X->dec[2 * j], pd, 0, 1, 2 * f, f, false, &cat, &tmp))) return rc;
+    if (f % 64 == 0 && f <= 128) {
+      // the same step composed (conv_x3_dec.h): x = the transposed convolution's input, scale `cur`
+      const std::string bn = pd + ".1.";
+      const auto &g = P[bn + "weight"], &b = P[bn + "bias"], &m = P[bn + "running_mean"], &v = P[bn + "running_var"];
+      std::vector<float> sc(f), sh(f);
+      for (int i = 0; i < f; ++i) {
+        const float inv = 1.0f / std::sqrt(v[i] + kBnEps);
+        sc[i] = g[i] * inv;
+        sh[i] = b[i] - m[i] * sc[i];
+      }
+      if ((rc = build_upcat_x3(h->err, X->comp[j], P[pu + ".weight"].data(), P[pu + ".bias"].data(), P[pd + ".0.weight"].data(),
+                               f, sc.data(), sh.data(), 1, useAct ? &skip[l] : nullptr, useAct ? &cur : nullptr,
+                               useAct ? &tmp : nullptr)))
+        return rc;
+    }
     if ((rc = conv(X->dec[2 * j + 1], pd, 3, 4, f, f, false, &tmp, &cur))) return rc;
   }
   {   // the 1x1 head reads the last activation: its scale goes into the head's weights
@@ -1357,18 +1584,30 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
     const int l = c.depth - 1 - j;
     const int f = c.features[l];
     // ConvTranspose writes the upper channel half of the concat buffer: torch.cat([skip, x]) elided
-    X3Q8Link lku;
-    lku.wantOutQ = catQ[l];
-    HIPCHK(h->err, run_upconv_x3(X->up[j], X->zeros, U(*cur), cur->elems, n, ch, cw, U(p.cat[l]), p.cat[l].elems, 2 * f, f, s,
-                                 &lku));
+    const bool headNext = j == c.depth - 1 && f == 64;
+    // the composed operator (conv_x3_dec.h) in place of upconv + dec[2 j] in the f16x3 tier without the fp8 cross
+    // terms, where its shape rules allow (unet_set_x3_compose); it reads the skip half of the concat buffer and x
+    // itself and writes tmpA like dec[2 j]
+    bool composed = false;
+    if (!qs && x3_compose_mode() != 0) {
+      hipError_t ec;
+      composed = run_upcat_x3(X->comp[j], X->zeros, U(p.cat[l]), p.cat[l].elems, 2 * f, U(*cur), cur->elems, n, 2 * ch, 2 * cw,
+                              U(p.tmpA), p.tmpA.elems, f, x3_compose_mode() == 1, s, &ec);
+      HIPCHK(h->err, ec);
+    }
     ch *= 2;
     cw *= 2;
-    const bool headNext = j == c.depth - 1 && f == 64;
     lk1 = X3Q8Link();
-    lk1.inIsQ = catQ[l];
-    lk1.wantOutQ = qs && x3_q8_auto(X->dec[2 * j + 1], n, ch, cw, headNext, false, false);
-    HIPCHK(h->err, run_conv_x3(X->dec[2 * j], X->zeros, U(p.cat[l]), p.cat[l].elems, n, ch, cw, U(p.tmpA), p.tmpA.elems, f, 0, s,
-                               nullptr, 0, nullptr, nullptr, nullptr, &sk, nullptr, nullptr, qs, &lk1));
+    if (!composed) {
+      X3Q8Link lku;
+      lku.wantOutQ = catQ[l];
+      HIPCHK(h->err, run_upconv_x3(X->up[j], X->zeros, U(*cur), cur->elems, n, ch / 2, cw / 2, U(p.cat[l]), p.cat[l].elems,
+                                   2 * f, f, s, &lku));
+      lk1.inIsQ = catQ[l];
+      lk1.wantOutQ = qs && x3_q8_auto(X->dec[2 * j + 1], n, ch, cw, headNext, false, false);
+      HIPCHK(h->err, run_conv_x3(X->dec[2 * j], X->zeros, U(p.cat[l]), p.cat[l].elems, n, ch, cw, U(p.tmpA), p.tmpA.elems, f, 0,
+                                 s, nullptr, 0, nullptr, nullptr, nullptr, &sk, nullptr, nullptr, qs, &lk1));
+    }
     lk2 = X3Q8Link();
     lk2.inIsQ = lk1.wroteQ;
     if (j == c.depth - 1 && f == 64) {
@@ -1524,6 +1763,71 @@ int unet_op_conv3x3_x3_head(int device, const float* x, int n, int hh, int ww, i
 // Test hook (host arithmetic only, no device): the power-of-two activation scale the f16x3 tier picks for a BatchNorm
 // channel with these parameters (act_from_bn)
 float unet_debug_act_scale(float gamma, float beta) { return act_from_bn(&gamma, &beta, 1).act[0]; }
+
+// Test entry point: the decoder step ConvTranspose2d(2f -> f, k2, s2, bias) -> cat([skip, up]) -> Conv3x3(2f -> f) ->
+// scale / shift (+ ReLU) as the composed operator (conv_x3_dec.h): skip (n,h,w,f) and x (n,h/2,w/2,2f) fp32 NHWC on the
+// device -> y (n,h,w,f); wt (2f,f,2,2), bt (f), w3 (f,2f,3,3), scale / shift (f) on the host
+int unet_op_upcat_conv3x3_x3(int device, const float* skip, const float* x, int n, int hh, int ww, int f, const float* wt,
+                             const float* bt, const float* w3, const float* scale, const float* shift, int relu, float* y,
+                             void* stream) {
+  if (!skip || !x || !wt || !bt || !w3 || !scale || !shift || !y || n < 1 || f % 64 || f > 128 || ww % 28 || hh % 2 || hh < 2)
+    return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  DecOpX3 op;
+  int rc = build_upcat_x3(g_opErr, op, wt, bt, w3, f, scale, shift, relu, nullptr, nullptr, nullptr);
+  const size_t px = (size_t)n * hh * ww;
+  const size_t es = px * f, ex = px / 4 * 2 * f, eo = px * f;
+  uint16_t *zeros = nullptr, *ps = nullptr, *pxl = nullptr, *po = nullptr;
+  auto cleanup = [&]() {
+    op.free_dev();
+    for (uint16_t* q : {zeros, ps, pxl, po})
+      if (q) hipFree(q);
+  };
+  if (!rc) {
+    hipError_t e = hipMalloc((void**)&zeros, 4096);
+    if (e == hipSuccess) e = hipMemset(zeros, 0, 4096);
+    if (e == hipSuccess) e = hipMalloc((void**)&ps, 2 * es * 2);
+    if (e == hipSuccess) e = hipMalloc((void**)&pxl, 2 * ex * 2);
+    if (e == hipSuccess) e = hipMalloc((void**)&po, 2 * eo * 2);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(unet::split_planes_kernel, dim3(grid_for(es / 2)), dim3(256), 0, s, skip, es / 2,
+                         reinterpret_cast<uint32_t*>(ps), reinterpret_cast<uint32_t*>(ps + es));
+      hipLaunchKernelGGL(unet::split_planes_kernel, dim3(grid_for(ex / 2)), dim3(256), 0, s, x, ex / 2,
+                         reinterpret_cast<uint32_t*>(pxl), reinterpret_cast<uint32_t*>(pxl + ex));
+      if (!run_upcat_x3(op, zeros, ps, es, f, pxl, ex, n, hh, ww, po, eo, f, true, s, &e) && e == hipSuccess)
+        e = hipErrorInvalidValue;
+    }
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(unet::merge_planes_kernel, dim3(grid_for(eo / 2)), dim3(256), 0, s,
+                         reinterpret_cast<const uint32_t*>(po), reinterpret_cast<const uint32_t*>(po + eo), eo / 2, y);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      g_opErr = hipGetErrorString(e);
+      rc = UNET_ERR_HIP;
+    }
+  }
+  cleanup();
+  return rc;
+}
+
+// Test hook (host arithmetic only, no device): the float64 composition the operator above is built from (compose_upcat)
+int unet_host_compose_upcat(const float* wt, const float* bt, const float* w3, int f, double* wp, double* bias) {
+  if (!wt || !bt || !w3 || !wp || !bias || f < 1) return UNET_ERR_INVALID_ARG;
+  std::vector<double> a, b;
+  compose_upcat(wt, bt, w3, f, a, b);
+  std::copy(a.begin(), a.end(), wp);
+  std::copy(b.begin(), b.end(), bias);
+  return UNET_OK;
+}
+
+int unet_set_x3_compose(int mode) {
+  const int prev = x3_compose_mode();
+  x3_compose_mode() = mode < 0 ? -1 : (mode > 1 ? 1 : mode);
+  return prev;
+}
 
 int unet_set_x3_cross_fp8(int mode) {
   const int prev = g_x3CrossFp8;
