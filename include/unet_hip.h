@@ -315,6 +315,46 @@ int unet_op_conv3x3_x3_head(int device, const float* x_dev, int n, int h, int w,
 int unet_op_upconv2x2_x3(int device, const float* x_dev, int n, int h, int w, int cin, const float* w_host,
                          const float* bias_host, int cout, float* y_dev, void* stream);
 
+/* The bf16 tier's operators, one at a time (test entry points; the network runs the same packing, dispatch and kernels).
+ * Activations are dense bf16 NHWC device tensors (uint16 bit patterns); weights, scale / shift, bias and head weights are
+ * fp32 HOST arrays in PyTorch layout, packed internally by the functions the network's build uses.  cin, cout: multiples
+ * of 32.  kernel: 0 = what the network picks for this shape under the current unet_set_bf16_persistent mode; 1 = the
+ * 2x2-wave kernel (csrc/igemm_bf16.h); 2 = the wave-specialised kernel (csrc/conv_bf16_ws.h / csrc/upconv_bf16_ws.h);
+ * 3 = the one-wave-per-SIMD kernel (csrc/conv_bf16_r512.h / csrc/upconv_bf16_r512.h).  A forced kernel that cannot take
+ * the shape returns UNET_ERR_INVALID_ARG without launching anything.  path_out (optional, int[3]) receives {kernel that
+ * ran (0 = none), 2x2 max-pool fused, 1x1 head fused}.  ldo: pixel stride of y in elements (0 = cout), co_off: the first
+ * channel written (multiples of 32); channels outside [co_off, co_off + cout) are not touched.
+ *
+ * y = relu?(conv3x3(x, w) * scale + shift) rounded to bf16: x (N,H,W,cin) -> y (N,H,W,ldo); w_host (cout,cin,3,3);
+ * y_pool (optional, dense (N,H/2,W/2,cout)): MaxPool2d(2,2) of y, written only where the kernel fuses it (path_out[1]). */
+int unet_op_conv3x3_bf16(int device, const uint16_t* x_dev, int n, int h, int w, int cin, const float* w_host,
+                         const float* scale_host, const float* shift_host, int cout, int relu, int kernel, int ldo,
+                         int co_off, uint16_t* y_dev, uint16_t* y_pool_dev, int* path_out, void* stream);
+/* The network's last convolution with the 1x1 head (cout -> 1, bias) fused into its epilogue where the kernel allows it
+ * (path_out[2]); otherwise the activation is stored and the unfused head kernel runs, as in the forward.
+ * logits / probs (N,H,W) fp32, mask (N,H,W) uint8 = 255 where logit > thr; each optional. */
+int unet_op_conv3x3_bf16_head(int device, const uint16_t* x_dev, int n, int h, int w, int cin, const float* w_host,
+                              const float* scale_host, const float* shift_host, int cout, int relu, int kernel,
+                              const float* head_w_host, float head_bias, float thr, float* logits_dev, float* probs_dev,
+                              uint8_t* mask_dev, int* path_out, void* stream);
+/* ConvTranspose2d k=2 s=2 with bias: x (N,H,W,cin) -> y (N,2H,2W,ldo), channels [co_off, co_off + cout);
+ * w_host (cin,cout,2,2). */
+int unet_op_upconv2x2_bf16(int device, const uint16_t* x_dev, int n, int h, int w, int cin, const float* w_host,
+                           const float* bias_host, int cout, int kernel, int ldo, int co_off, uint16_t* y_dev, int* path_out,
+                           void* stream);
+/* The first convolution: uint8 (N,H,W,3) frames -> (x - mean) / std -> 3x3 conv -> scale / shift (+ ReLU) -> dense
+ * (N,H,W,cout) bf16.  mean_host / std_host: 3 floats each.  kernel: 0 = the forward's choice, 1 = csrc/conv_first_bf16x3.h
+ * (H % 8 == 0, cout % 64 == 0), 2 = the fp32 kernel with a bf16 store. */
+int unet_op_conv_first_bf16(int device, const uint8_t* frames_dev, int n, int h, int w, const float* w_host,
+                            const float* scale_host, const float* shift_host, int cout, int relu, const float* mean_host,
+                            const float* std_host, int kernel, uint16_t* y_dev, int* path_out, void* stream);
+/* MaxPool2d(2,2) on bf16: x (N,H,W,ldi) channels [0,c) -> dense y (N,H/2,W/2,c); c, ldi multiples of 8 (ldi 0 = c). */
+int unet_op_maxpool2x2_bf16(int device, const uint16_t* x_dev, int n, int h, int w, int c, int ldi, uint16_t* y_dev,
+                            void* stream);
+/* The unfused 1x1 head on dense bf16 (N,H,W,c) (c % 8 == 0): logits / probs / mask as unet_op_conv3x3_bf16_head. */
+int unet_op_head1x1_bf16(int device, const uint16_t* x_dev, int n, int h, int w, int c, const float* w_host, float bias,
+                         float thr, float* logits_dev, float* probs_dev, uint8_t* mask_dev, void* stream);
+
 /* One decoder step of the split-operand tier - ConvTranspose2d(2f -> f, k2, s2, bias) -> cat([skip, up]) ->
  * Conv3x3(2f -> f) -> scale/shift (+ ReLU) (reference README.md:1476-1479) - as the composed operator
  * (csrc/conv_x3_dec.h: the transposed convolution folded into the 3x3 convolution's up half on the host, float64).

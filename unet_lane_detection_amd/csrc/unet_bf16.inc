@@ -70,6 +70,101 @@ int upload_bf(std::string& err, uint16_t** dst, const std::vector<uint16_t>& v) 
   return UNET_OK;
 }
 
+// The bf16 operators of a 3x3 convolution / a transposed convolution from the fp32 operator built for the same layer
+// (build_conv3x3 / build_upconv: GEMM shape, folded scale / shift or bias, borrowed), w in PyTorch layout on the host.
+// Used by bf16_build and by the unet_op_*_bf16 test entry points alike.  `zeros`: the tier's zero page (8192 elements).
+int pack_conv_bf(std::string& err, GemmOpBf& o, const GemmOp& f, const float* w, const uint16_t* zeros) {
+  o.taps = 9;
+  o.cin = f.cinReal;
+  o.cout = f.cout;
+  o.coutPad = f.coutPad;
+  o.nTotal = f.nTotal;
+  o.relu = f.relu;
+  o.scale = f.scale;
+  o.shift = f.shift;
+  const int cinR = f.cinReal, coutR = f.cout;
+  auto packed = pack_fragments_bf16(o.nTotal, o.cin, 9, [&](int n, int ci, int t) -> float {
+    return (n < coutR && ci < cinR) ? w[((size_t)n * cinR + ci) * 9 + t] : 0.f;
+  });
+  int rc = upload_bf(err, &o.wt, packed);
+  if (rc) return rc;
+  if (cinR % 64 == 0 && coutR % 64 == 0) {
+    auto pw = pack_fragments_ws(coutR, cinR, [&](int n, int ci, int t) -> float {
+      return w[((size_t)n * cinR + ci) * 9 + t];
+    });
+    rc = upload_bf(err, &o.wtWs, pw);
+    o.zeros = zeros;
+  }
+  return rc;
+}
+
+int pack_upconv_bf(std::string& err, GemmOpBf& o, const GemmOp& f, const float* w, const uint16_t* zeros) {
+  o.taps = 1;
+  o.cin = f.cinReal;
+  o.cout = f.cout;
+  o.coutPad = f.coutPad;
+  o.nTotal = f.nTotal;
+  o.relu = 0;
+  o.scale = f.scale;
+  o.shift = f.shift;
+  const int cp = o.coutPad, coutR = o.cout, cinR = o.cin;
+  auto packed = pack_fragments_bf16(o.nTotal, o.cin, 1, [&](int n, int ci, int) -> float {
+    const int ab = n / cp, co = n % cp;
+    return (ab < 4 && co < coutR && ci < cinR) ? w[((size_t)ci * coutR + co) * 4 + ab] : 0.f;
+  });
+  int rc;
+  if ((rc = upload_bf(err, &o.wt, packed))) return rc;
+  if (cinR % 64 == 0 && coutR % 64 == 0) {
+    // upconv_bf16_ws.h: [coTile(64)][chunk(64 ch)][kstep(2)][ab(4)][cs(4)][lane][8]; row j of subtile cs =
+    // channel 64*ct + 16*(j>>2) + 4*cs + (j&3), k = chunk*64 + kstep*32 + 8*(lane>>4) + e
+    const int nCt = coutR / 64, nCh = cinR / 64;
+    std::vector<uint16_t> pw((size_t)nCt * nCh * 32 * 64 * 8, 0);
+    for (int ct = 0; ct < nCt; ++ct)
+      for (int kc = 0; kc < nCh; ++kc)
+        for (int ks = 0; ks < 2; ++ks)
+          for (int ab = 0; ab < 4; ++ab)
+            for (int cs = 0; cs < 4; ++cs) {
+              uint16_t* dst = pw.data() + (((((size_t)ct * nCh + kc) * 2 + ks) * 4 + ab) * 4 + cs) * 64 * 8;
+              for (int lane = 0; lane < 64; ++lane) {
+                const int jr = lane & 15, lq = lane >> 4;
+                const int co = 64 * ct + 16 * (jr >> 2) + 4 * cs + (jr & 3);
+                for (int e = 0; e < 8; ++e) {
+                  const int ci = kc * 64 + ks * 32 + lq * 8 + e;
+                  dst[lane * 8 + e] = host_f2bf(w[((size_t)ci * coutR + co) * 4 + ab]);
+                }
+              }
+            }
+    if ((rc = upload_bf(err, &o.wtWs, pw))) return rc;
+    o.zeros = zeros;
+  }
+  return UNET_OK;
+}
+
+// First convolution as one K = 27 bf16 MFMA per tile with hi/lo split operands (conv_first_bf16x3.h), w (f0,3,3,3):
+// [coTile][cs][hi|lo][lane][8], row j of subtile cs = channel 64*ct + 16*(j>>2) + 4*cs + (j&3), k = tap*3 + ci
+int pack_first_bf16x3(std::string& err, uint16_t** dst, const float* w, int f0) {
+  std::vector<uint16_t> pw((size_t)(f0 / 64) * 4 * 2 * 64 * 8, 0);
+  for (int ct = 0; ct < f0 / 64; ++ct)
+    for (int cs = 0; cs < 4; ++cs)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int j = lane & 15, lq = lane >> 4;
+        const int co = 64 * ct + 16 * (j >> 2) + 4 * cs + (j & 3);
+        for (int e = 0; e < 8; ++e) {
+          const int k = lq * 8 + e;
+          float v = 0.f;
+          if (k < 27) v = w[((size_t)co * 3 + (k % 3)) * 9 + k / 3];
+          const uint16_t hi = host_f2bf(v);
+          uint32_t hb = (uint32_t)hi << 16;
+          float hf;
+          std::memcpy(&hf, &hb, 4);
+          const uint16_t lo = host_f2bf(v - hf);
+          pw[((((size_t)ct * 4 + cs) * 2 + 0) * 64 + lane) * 8 + e] = hi;
+          pw[((((size_t)ct * 4 + cs) * 2 + 1) * 64 + lane) * 8 + e] = lo;
+        }
+      }
+  return upload_bf(err, dst, pw);
+}
+
 template <int TAPS, int MODE>
 hipError_t launch_bf(const unet::ConvArgsBf& a, dim3 grid, int ms, int ns, hipStream_t s) {
   constexpr int NLD7 = 6, NLD4 = 4;
@@ -97,16 +192,50 @@ struct BfFuse {
   uint8_t* mask = nullptr;
 };
 
-// Returns through `fused` which of the requested epilogue fusions the launch performed.
-hipError_t run_conv_ws(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo, int coOff,
-                       hipStream_t s, BfFuse* fuse, bool* fusedPool, bool* fusedHead);
-bool conv_ws_eligible(const GemmOpBf& op, int n, int h, int w);
-hipError_t run_upconv_ws(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo, int coOff,
-                         hipStream_t s);
-bool upconv_ws_eligible(const GemmOpBf& op, int n, int h, int w);
+// Kernel choices of run_gemm_bf (also what the unet_op_*_bf16 test entry points force and report): 0 = none (the forced
+// kernel cannot take the shape), 1 = igemm_bf16.h, 2 = the wave-specialised kernel (conv_bf16_ws.h / upconv_bf16_ws.h),
+// 3 = the one-wave-per-SIMD kernel (conv_bf16_r512.h / upconv_bf16_r512.h).
+enum : int { BF_NONE = 0, BF_IGEMM = 1, BF_WS = 2, BF_R512 = 3 };
+
+// The eligibility rules take the unet_set_bf16_persistent mode explicitly: -1 automatic, 0 the 2x2-wave kernel alone,
+// 1 the wave-specialised kernels wherever the shape allows, 2 the one-wave-per-SIMD kernels wherever the shape allows.
+std::atomic<int> g_bfWsMode{-1};   // unet_set_bf16_persistent
+
+// ---- the persistent wave-specialised kernel (conv_bf16_ws.h) for wide layers ----
+bool conv_ws_eligible(const GemmOpBf& op, int n, int h, int w, int mode) {
+  static const int minW = [] { const char* e = getenv("UNET_BF16_WS_MINW"); return e ? atoi(e) : 100; }();
+  if (mode == 0 || !op.wtWs || !op.zeros || op.taps != 9 || h % 16 || op.cout > unet::WsShape::MAX_COUT)
+    return false;
+  const long work = (long)((w + 31) / 32) * (n * h / 16) * (op.cout / 64);
+  if (mode == 1) return work >= 8;    // the persistent grid is work / 8 * 8 blocks: none below that
+  return w >= minW && work >= 1024;   // at least four tiles per CU, else the 2x2-wave kernel's finer grain wins
+}
 
 // ---- the one-wave-per-SIMD kernel (conv_bf16_r512.h) for the 56 x 56 ... 14 x 14 levels ----
-extern std::atomic<int> g_bfWsMode;
+struct BfR512Plan {
+  int twx, thx, wpx;
+  bool flat;
+  long tiles, items;
+};
+BfR512Plan conv_bf_r512_plan(const GemmOpBf& op, int n, int h, int w) {
+  BfR512Plan p;
+  p.twx = w == 14 ? 14 : 28;
+  p.thx = 224 / p.twx;
+  p.flat = n > 1 && h % p.thx != 0 && 2 * h >= p.thx;
+  p.tiles = p.flat ? (long)((n * h + p.thx - 1) / p.thx) * (w / p.twx) : (long)n * ((h + p.thx - 1) / p.thx) * (w / p.twx);
+  auto balance = [](long items) { return (double)items / (double)((items + 255) / 256 * 256); };
+  p.wpx = 2;
+  if (op.cout % 256 == 0) p.wpx = balance(p.tiles * (op.cout / 256)) >= 0.93 * balance(p.tiles * (op.cout / 128)) ? 1 : 2;
+  p.items = p.tiles * (op.cout / (256 / p.wpx));
+  return p;
+}
+// mode 2: wherever the shape allows; automatic: once there is an item for half the CUs; modes 0 and 1 never (the 2x2-wave
+// kernel alone / the wave-specialised kernel forced)
+bool conv_bf_r512_eligible(const GemmOpBf& op, int n, int h, int w, int mode) {
+  if (!op.wtWs || !op.zeros || op.taps != 9 || op.cin % 32 || op.cout % 128 || !(w % 28 == 0 || w == 14)) return false;
+  if (mode == 0 || mode == 1) return false;
+  return mode == 2 || conv_bf_r512_plan(op, n, h, w).items >= 128;
+}
 template <int TWX, int WPX>
 hipError_t launch_bf_r512(const unet::ConvBfRArgs& a, int grid, bool flat, hipStream_t s) {
   using S = unet::BfRShape<TWX>;
@@ -117,21 +246,9 @@ hipError_t launch_bf_r512(const unet::ConvBfRArgs& a, int grid, bool flat, hipSt
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), (size_t)S::LDS_BYTES, s, a);
   return hipGetLastError();
 }
-bool conv_bf_r512_try(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo, int coOff,
-                      hipStream_t s, hipError_t* err) {
-  // mode 2 (unet_set_bf16_persistent): wherever the shape allows; automatic: once there is an item for half the CUs;
-  // modes 0 and 1 never (the 2x2-wave kernel alone / the wave-specialised kernel forced)
-  if (!op.wtWs || !op.zeros || op.taps != 9 || op.cin % 32 || op.cout % 128 || !(w % 28 == 0 || w == 14)) return false;
-  const int mode = g_bfWsMode;
-  if (mode == 0 || mode == 1) return false;
-  const int twx = w == 14 ? 14 : 28, thx = 224 / twx;
-  const bool flat = n > 1 && h % thx != 0 && 2 * h >= thx;
-  const long tiles = flat ? (long)((n * h + thx - 1) / thx) * (w / twx) : (long)n * ((h + thx - 1) / thx) * (w / twx);
-  auto balance = [](long items) { return (double)items / (double)((items + 255) / 256 * 256); };
-  int wpx = 2;
-  if (op.cout % 256 == 0) wpx = balance(tiles * (op.cout / 256)) >= 0.93 * balance(tiles * (op.cout / 128)) ? 1 : 2;
-  const long items = tiles * (op.cout / (256 / wpx));
-  if (mode != 2 && items < 128) return false;
+hipError_t run_conv_bf_r512(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo,
+                            int coOff, hipStream_t s) {
+  const BfR512Plan p = conv_bf_r512_plan(op, n, h, w);
   unet::ConvBfRArgs a;
   a.in = in;
   a.wt = op.wtWs;
@@ -139,122 +256,134 @@ bool conv_bf_r512_try(const GemmOpBf& op, const uint16_t* in, int n, int h, int 
   a.scale = op.scale;
   a.shift = op.shift;
   a.out = out;
-  a.N = flat ? 1 : n;
-  a.H = flat ? n * h : h;
+  a.N = p.flat ? 1 : n;
+  a.H = p.flat ? n * h : h;
   a.W = w;
   a.Cin = op.cin;
   a.Cout = op.cout;
   a.ldo = ldo;
   a.co_off = coOff;
-  a.tilesX = w / twx;
-  a.tilesY = (a.H + thx - 1) / thx;
+  a.tilesX = w / p.twx;
+  a.tilesY = (a.H + p.thx - 1) / p.thx;
   a.nChunks = op.cin / 32;
   a.relu = op.relu;
   a.pixTiles = a.N * a.tilesY * a.tilesX;
-  a.coTiles = op.cout / (256 / wpx);
+  a.coTiles = op.cout / (256 / p.wpx);
   a.coGroup = a.coTiles;
   a.imgH = h;
-  const int grid = (int)std::max<long>(8, std::min<long>(256, items / 8 * 8));
+  const int grid = (int)std::max<long>(8, std::min<long>(256, p.items / 8 * 8));
   const double px = (double)n * h * w;
   prof_begin("conv3x3_r512_bf16", 2.0 * px * 9 * op.cin * op.cout, 2.0 * (px * op.cin + px * op.cout + 9.0 * op.cin * op.cout), s);
-  if (twx == 28)
-    *err = wpx == 1 ? launch_bf_r512<28, 1>(a, grid, flat, s) : launch_bf_r512<28, 2>(a, grid, flat, s);
+  hipError_t e;
+  if (p.twx == 28)
+    e = p.wpx == 1 ? launch_bf_r512<28, 1>(a, grid, p.flat, s) : launch_bf_r512<28, 2>(a, grid, p.flat, s);
   else
-    *err = wpx == 1 ? launch_bf_r512<14, 1>(a, grid, flat, s) : launch_bf_r512<14, 2>(a, grid, flat, s);
-  prof_end(s);
-  return true;
-}
-
-bool upconv_r512_wanted(const GemmOpBf& op, int n, int h, int w);
-hipError_t run_gemm_bf(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo, int coOff,
-                       hipStream_t s, BfFuse* fuse = nullptr, bool* fusedPool = nullptr, bool* fusedHead = nullptr) {
-  if (conv_ws_eligible(op, n, h, w)) return run_conv_ws(op, in, n, h, w, out, ldo, coOff, s, fuse, fusedPool, fusedHead);
-  {
-    hipError_t e = hipSuccess;
-    if (conv_bf_r512_try(op, in, n, h, w, out, ldo, coOff, s, &e)) {   // no fused pooling / head: the caller's passes run
-      if (fusedPool) *fusedPool = false;
-      if (fusedHead) *fusedHead = false;
-      return e;
-    }
-  }
-  if (upconv_r512_wanted(op, n, h, w) || upconv_ws_eligible(op, n, h, w)) return run_upconv_ws(op, in, n, h, w, out, ldo, coOff, s);
-  const TileChoice t = choose_tile(n * h, w, 16, op.taps == 9);   // same 64-byte pixel rows as fp32 CK=16
-  unet::ConvArgsBf a;
-  a.pool = nullptr;
-  a.headW = nullptr;
-  a.headB = a.headThr = 0.f;
-  a.logits = a.probs = nullptr;
-  a.mask = nullptr;
-  a.storeOut = 1;
-  if (fusedPool) *fusedPool = false;
-  if (fusedHead) *fusedHead = false;
-  a.in = in;
-  a.wt = op.wt;
-  a.scale = op.scale;
-  a.shift = op.shift;
-  a.out = out;
-  a.N = n;
-  a.H = h;
-  a.W = w;
-  a.Cin = op.cin;
-  a.Cout = op.cout;
-  a.CoutPad = op.coutPad;
-  a.ldo = ldo;
-  a.co_off = coOff;
-  a.TH = t.th;
-  a.TW = t.tw;
-  a.tilesX = (w + t.tw - 1) / t.tw;
-  a.nChunks = op.cin / 32;
-  a.relu = op.relu;
-  const int tilesY = (n * h + t.th - 1) / t.th;
-  // 128-channel tiles halve the LDS reads of the input tile per MFMA (the bf16 kernel is LDS-bound, not MFMA-bound)
-  static const bool wide = [] { const char* e = getenv("UNET_BF16_NS"); return !(e && e[0] == '2'); }();
-  const int ns = (op.nTotal % 128 == 0 && (t.ms == 4 || wide)) ? 4 : 2;
-  a.pixTiles = a.tilesX * tilesY;
-  a.coTiles = op.nTotal / (32 * ns);
-  a.coGroup = 1;
-  for (int g : {8, 4, 2})
-    if (a.coTiles % g == 0) {
-      a.coGroup = g;
-      break;
-    }
-  if (fuse && op.taps == 9) {
-    if (fuse->pool && t.th % 4 == 0 && t.tw % 2 == 0 && h % 2 == 0 && w % 2 == 0) {
-      a.pool = fuse->pool;
-      if (fusedPool) *fusedPool = true;
-    }
-    if (fuse->headW && a.coTiles == 1 && op.cout % 4 == 0) {
-      a.headW = fuse->headW;
-      a.headB = fuse->headB;
-      a.headThr = fuse->headThr;
-      a.logits = fuse->logits;
-      a.probs = fuse->probs;
-      a.mask = fuse->mask;
-      a.storeOut = 0;
-      if (fusedHead) *fusedHead = true;
-    }
-  }
-  const double px = (double)n * h * w;
-  const double nOut = (op.taps == 9) ? op.cout : 4.0 * op.cout;
-  prof_begin(op.taps == 9 ? "conv3x3_igemm_bf16" : "upconv2x2_igemm_bf16", 2.0 * px * op.taps * op.cin * nOut,
-             2.0 * (px * op.cin + px * nOut + (double)op.taps * op.cin * nOut), s);
-  dim3 grid((unsigned)((size_t)a.pixTiles * a.coTiles));
-  hipError_t e = (op.taps == 9) ? launch_bf<9, 0>(a, grid, t.ms, ns, s) : launch_bf<1, 1>(a, grid, t.ms, ns, s);
+    e = p.wpx == 1 ? launch_bf_r512<14, 1>(a, grid, p.flat, s) : launch_bf_r512<14, 2>(a, grid, p.flat, s);
   prof_end(s);
   return e;
 }
 
-// ---- the persistent wave-specialised kernel (conv_bf16_ws.h) for wide layers ----
-std::atomic<int> g_bfWsMode{-1};   // unet_set_bf16_persistent
-bool conv_ws_eligible(const GemmOpBf& op, int n, int h, int w) {
-  static const int minW = [] { const char* e = getenv("UNET_BF16_WS_MINW"); return e ? atoi(e) : 100; }();
-  if (g_bfWsMode == 0 || !op.wtWs || !op.zeros || op.taps != 9 || h % 16 || op.cout > unet::WsShape::MAX_COUT)
+// upconv_bf16_r512.h: shapes it takes (Cin % 128 == 0, w >= 4); mode 2 (unet_set_bf16_persistent) whenever the shape
+// allows, automatic once there is a work item for half of the CUs, modes 0 / 1 never
+bool upconv_r512_wanted(const GemmOpBf& op, int n, int h, int w, int mode) {
+  if (!(op.taps == 1 && op.wtWs && op.zeros && op.cin % 128 == 0 && op.cout % 64 == 0 && w >= 4 &&
+        op.cout <= unet::UpconvWsShape::MAX_COUT))
     return false;
-  const long work = (long)((w + 31) / 32) * (n * h / 16) * (op.cout / 64);
-  if (g_bfWsMode == 1) return work >= 8;
-  return w >= minW && work >= 1024;   // at least four tiles per CU, else the 2x2-wave kernel's finer grain wins
+  const long workR = ((long)n * h * w + 223) / 224 * (op.cout / 64);
+  return mode == 2 || (mode < 0 && workR >= 128);
 }
 
+// ---- the persistent wave-specialised transposed convolution (upconv_bf16_ws.h) ----
+bool upconv_ws_eligible(const GemmOpBf& op, int n, int h, int w, int mode) {
+  static const bool on = [] { const char* e = getenv("UNET_BF16_UPWS"); return !(e && e[0] == '0'); }();
+  if (!on || mode == 0 || op.taps != 1 || !op.wtWs || !op.zeros || op.cout > unet::UpconvWsShape::MAX_COUT)
+    return false;
+  const long work = ((long)n * h * w + 127) / 128 * (op.cout / 64);
+  return mode == 1 ? work >= 8 : work >= 1024;
+}
+
+unet::UpconvWsArgs upconv_bf_args(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo,
+                                  int coOff, int tp) {
+  unet::UpconvWsArgs a;
+  a.in = in;
+  a.wt = op.wtWs;
+  a.zeros = op.zeros;
+  a.bias = op.shift;   // (a,b) = (0,0) block of the per-column shifts = the bias
+  a.out = out;
+  a.npix = (long)n * h * w;
+  a.h = h;
+  a.w = w;
+  a.Cin = op.cin;
+  a.Cout = op.cout;
+  a.ldo = ldo;
+  a.co_off = coOff;
+  a.nChunks = op.cin / 64;
+  a.coTiles = op.cout / 64;
+  a.pixTiles = (int)((a.npix + tp - 1) / tp);
+  return a;
+}
+
+// the one-wave-per-SIMD structure (upconv_bf16_r512.h; bit-identical to the wave-specialised kernel)
+hipError_t run_upconv_bf_r512(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo,
+                              int coOff, hipStream_t s) {
+  using R = unet::UpconvBfRShape;
+  const unet::UpconvWsArgs a = upconv_bf_args(op, in, n, h, w, out, ldo, coOff, R::TP);
+  const long workR = (long)a.pixTiles * a.coTiles;
+  auto kernR = unet::upconv2x2_bf16_r512_kernel;
+  hipError_t e = ensure_dyn_lds((const void*)kernR, R::LDS_BYTES);
+  if (e != hipSuccess) return e;
+  const int gridR = (int)std::max<long>(8, std::min<long>(256, workR / 8 * 8));
+  const double pxr = (double)a.npix;
+  prof_begin("upconv2x2_r512_bf16", 2.0 * pxr * op.cin * 4.0 * op.cout, 2.0 * (pxr * op.cin + 4.0 * pxr * op.cout), s);
+  hipLaunchKernelGGL(kernR, dim3(gridR), dim3(256), (size_t)R::LDS_BYTES, s, a);
+  prof_end(s);
+  return hipGetLastError();
+}
+
+hipError_t run_upconv_ws(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo, int coOff,
+                         hipStream_t s) {
+  using S = unet::UpconvWsShape;
+  const unet::UpconvWsArgs a = upconv_bf_args(op, in, n, h, w, out, ldo, coOff, S::TP);
+  auto kern = unet::upconv2x2_bf16_ws_kernel;
+  {
+    hipError_t e = ensure_dyn_lds((const void*)kern, S::LDS_BYTES);
+    if (e != hipSuccess) return e;
+  }
+  const long work = (long)a.pixTiles * a.coTiles;
+  const int grid = (int)std::min<long>(256, work / 8 * 8);
+  const double px = (double)a.npix;
+  prof_begin("upconv2x2_ws_bf16", 2.0 * px * op.cin * 4.0 * op.cout, 2.0 * (px * op.cin + 4.0 * px * op.cout), s);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), (size_t)S::LDS_BYTES, s, a);
+  prof_end(s);
+  return hipGetLastError();
+}
+
+// Which kernel run_gemm_bf launches for this operator and shape: `force` BF_IGEMM / BF_WS / BF_R512 asks for that
+// kernel (BF_NONE if it cannot take the shape), 0 = the automatic choice under the current unet_set_bf16_persistent mode.
+int bf_kernel_for(const GemmOpBf& op, int n, int h, int w, int force) {
+  const bool conv = op.taps == 9;
+  switch (force) {
+    case BF_IGEMM:
+      return BF_IGEMM;
+    case BF_WS:
+      return (conv ? conv_ws_eligible(op, n, h, w, 1) : upconv_ws_eligible(op, n, h, w, 1)) ? BF_WS : BF_NONE;
+    case BF_R512:
+      return (conv ? conv_bf_r512_eligible(op, n, h, w, 2) : upconv_r512_wanted(op, n, h, w, 2)) ? BF_R512 : BF_NONE;
+    default:
+      break;
+  }
+  const int mode = g_bfWsMode;
+  if (conv) {
+    if (conv_ws_eligible(op, n, h, w, mode)) return BF_WS;
+    if (conv_bf_r512_eligible(op, n, h, w, mode)) return BF_R512;   // no fused pooling / head: the caller's passes run
+    return BF_IGEMM;
+  }
+  if (upconv_r512_wanted(op, n, h, w, mode)) return BF_R512;
+  if (upconv_ws_eligible(op, n, h, w, mode)) return BF_WS;
+  return BF_IGEMM;
+}
+
+// Returns through `fusedPool` / `fusedHead` which of the requested epilogue fusions the launch performed.
 hipError_t run_conv_ws(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo, int coOff,
                        hipStream_t s, BfFuse* fuse, bool* fusedPool, bool* fusedHead) {
   using S = unet::WsShape;
@@ -345,74 +474,155 @@ hipError_t run_conv_ws(const GemmOpBf& op, const uint16_t* in, int n, int h, int
   return hipGetLastError();
 }
 
-// upconv_bf16_r512.h: shapes it takes (Cin % 128 == 0, w >= 4); mode 2 (unet_set_bf16_persistent) whenever the shape
-// allows, automatic once there is a work item for half of the CUs, modes 0 / 1 never
-bool upconv_r512_wanted(const GemmOpBf& op, int n, int h, int w) {
-  if (!(op.taps == 1 && op.wtWs && op.zeros && op.cin % 128 == 0 && op.cout % 64 == 0 && w >= 4 &&
-        op.cout <= unet::UpconvWsShape::MAX_COUT))
-    return false;
-  const int mode = g_bfWsMode;
-  const long workR = ((long)n * h * w + 223) / 224 * (op.cout / 64);
-  return mode == 2 || (mode < 0 && workR >= 128);
-}
 
-// ---- the persistent wave-specialised transposed convolution (upconv_bf16_ws.h) ----
-bool upconv_ws_eligible(const GemmOpBf& op, int n, int h, int w) {
-  static const bool on = [] { const char* e = getenv("UNET_BF16_UPWS"); return !(e && e[0] == '0'); }();
-  if (!on || g_bfWsMode == 0 || op.taps != 1 || !op.wtWs || !op.zeros || op.cout > unet::UpconvWsShape::MAX_COUT)
-    return false;
-  const long work = ((long)n * h * w + 127) / 128 * (op.cout / 64);
-  return g_bfWsMode == 1 ? work >= 8 : work >= 1024;
-}
-
-hipError_t run_upconv_ws(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo, int coOff,
-                         hipStream_t s) {
-  using S = unet::UpconvWsShape;
-  unet::UpconvWsArgs a;
+// ---- the 2x2-wave kernel (igemm_bf16.h): every shape, the 3x3 convolution and the transposed convolution ----
+hipError_t run_igemm_bf(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo, int coOff,
+                        hipStream_t s, BfFuse* fuse, bool* fusedPool, bool* fusedHead) {
+  const TileChoice t = choose_tile(n * h, w, 16, op.taps == 9);   // same 64-byte pixel rows as fp32 CK=16
+  unet::ConvArgsBf a;
+  a.pool = nullptr;
+  a.headW = nullptr;
+  a.headB = a.headThr = 0.f;
+  a.logits = a.probs = nullptr;
+  a.mask = nullptr;
+  a.storeOut = 1;
+  if (fusedPool) *fusedPool = false;
+  if (fusedHead) *fusedHead = false;
   a.in = in;
-  a.wt = op.wtWs;
-  a.zeros = op.zeros;
-  a.bias = op.shift;   // (a,b) = (0,0) block of the per-column shifts = the bias
+  a.wt = op.wt;
+  a.scale = op.scale;
+  a.shift = op.shift;
   a.out = out;
-  a.npix = (long)n * h * w;
-  a.h = h;
-  a.w = w;
+  a.N = n;
+  a.H = h;
+  a.W = w;
   a.Cin = op.cin;
   a.Cout = op.cout;
+  a.CoutPad = op.coutPad;
   a.ldo = ldo;
   a.co_off = coOff;
-  a.nChunks = op.cin / 64;
-  a.coTiles = op.cout / 64;
-  a.pixTiles = (int)((a.npix + S::TP - 1) / S::TP);
-  // the one-wave-per-SIMD structure (upconv_bf16_r512.h; bit-identical): mode 2 whenever the shape allows, automatic once
-  // there is a work item for half of the CUs, modes 0 / 1 never
-  if (upconv_r512_wanted(op, n, h, w)) {
-    {
-      using R = unet::UpconvBfRShape;
-      const int pixTilesR = (int)((a.npix + R::TP - 1) / R::TP);
-      const long workR = (long)pixTilesR * a.coTiles;
-      a.pixTiles = pixTilesR;
-      auto kernR = unet::upconv2x2_bf16_r512_kernel;
-      hipError_t e = ensure_dyn_lds((const void*)kernR, R::LDS_BYTES);
-      if (e != hipSuccess) return e;
-      const int gridR = (int)std::max<long>(8, std::min<long>(256, workR / 8 * 8));
-      const double pxr = (double)a.npix;
-      prof_begin("upconv2x2_r512_bf16", 2.0 * pxr * op.cin * 4.0 * op.cout, 2.0 * (pxr * op.cin + 4.0 * pxr * op.cout), s);
-      hipLaunchKernelGGL(kernR, dim3(gridR), dim3(256), (size_t)R::LDS_BYTES, s, a);
-      prof_end(s);
-      return hipGetLastError();
+  a.TH = t.th;
+  a.TW = t.tw;
+  a.tilesX = (w + t.tw - 1) / t.tw;
+  a.nChunks = op.cin / 32;
+  a.relu = op.relu;
+  const int tilesY = (n * h + t.th - 1) / t.th;
+  // 128-channel tiles halve the LDS reads of the input tile per MFMA (the bf16 kernel is LDS-bound, not MFMA-bound)
+  static const bool wide = [] { const char* e = getenv("UNET_BF16_NS"); return !(e && e[0] == '2'); }();
+  const int ns = (op.nTotal % 128 == 0 && (t.ms == 4 || wide)) ? 4 : 2;
+  a.pixTiles = a.tilesX * tilesY;
+  a.coTiles = op.nTotal / (32 * ns);
+  a.coGroup = 1;
+  for (int g : {8, 4, 2})
+    if (a.coTiles % g == 0) {
+      a.coGroup = g;
+      break;
+    }
+  if (fuse && op.taps == 9) {
+    if (fuse->pool && t.th % 4 == 0 && t.tw % 2 == 0 && h % 2 == 0 && w % 2 == 0) {
+      a.pool = fuse->pool;
+      if (fusedPool) *fusedPool = true;
+    }
+    if (fuse->headW && a.coTiles == 1 && op.cout % 4 == 0) {
+      a.headW = fuse->headW;
+      a.headB = fuse->headB;
+      a.headThr = fuse->headThr;
+      a.logits = fuse->logits;
+      a.probs = fuse->probs;
+      a.mask = fuse->mask;
+      a.storeOut = 0;
+      if (fusedHead) *fusedHead = true;
     }
   }
-  auto kern = unet::upconv2x2_bf16_ws_kernel;
-  {
-    hipError_t e = ensure_dyn_lds((const void*)kern, S::LDS_BYTES);
-    if (e != hipSuccess) return e;
+  const double px = (double)n * h * w;
+  const double nOut = (op.taps == 9) ? op.cout : 4.0 * op.cout;
+  prof_begin(op.taps == 9 ? "conv3x3_igemm_bf16" : "upconv2x2_igemm_bf16", 2.0 * px * op.taps * op.cin * nOut,
+             2.0 * (px * op.cin + px * nOut + (double)op.taps * op.cin * nOut), s);
+  dim3 grid((unsigned)((size_t)a.pixTiles * a.coTiles));
+  hipError_t e = (op.taps == 9) ? launch_bf<9, 0>(a, grid, t.ms, ns, s) : launch_bf<1, 1>(a, grid, t.ms, ns, s);
+  prof_end(s);
+  return e;
+}
+
+hipError_t run_gemm_bf(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo, int coOff,
+                       hipStream_t s, BfFuse* fuse = nullptr, bool* fusedPool = nullptr, bool* fusedHead = nullptr,
+                       int force = 0, int* ran = nullptr) {
+  const int k = bf_kernel_for(op, n, h, w, force);
+  if (ran) *ran = k;
+  if (fusedPool) *fusedPool = false;
+  if (fusedHead) *fusedHead = false;
+  const bool conv = op.taps == 9;
+  switch (k) {
+    case BF_WS:
+      return conv ? run_conv_ws(op, in, n, h, w, out, ldo, coOff, s, fuse, fusedPool, fusedHead)
+                  : run_upconv_ws(op, in, n, h, w, out, ldo, coOff, s);
+    case BF_R512:
+      return conv ? run_conv_bf_r512(op, in, n, h, w, out, ldo, coOff, s) : run_upconv_bf_r512(op, in, n, h, w, out, ldo, coOff, s);
+    case BF_IGEMM:
+      return run_igemm_bf(op, in, n, h, w, out, ldo, coOff, s, fuse, fusedPool, fusedHead);
+    default:
+      return hipErrorInvalidValue;
   }
-  const long work = (long)a.pixTiles * a.coTiles;
-  const int grid = (int)std::min<long>(256, work / 8 * 8);
-  const double px = (double)a.npix;
-  prof_begin("upconv2x2_ws_bf16", 2.0 * px * op.cin * 4.0 * op.cout, 2.0 * (px * op.cin + 4.0 * px * op.cout), s);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), (size_t)S::LDS_BYTES, s, a);
+}
+
+// MaxPool2d(2,2) of (N,H,W,ldi) bf16 -> dense (N,H/2,W/2,C) (when the convolution before it could not fuse it)
+hipError_t run_maxpool_bf(const uint16_t* in, uint16_t* out, int n, int h, int w, int c, int ldi, hipStream_t s) {
+  const size_t total = (size_t)n * (h / 2) * (w / 2) * (c / 8);
+  prof_begin("maxpool2x2_bf16", 0.0, 2.0 * total * 8 * 5, s);
+  hipLaunchKernelGGL(unet::maxpool2x2_bf16_kernel, dim3(grid_for(total)), dim3(256), 0, s, in, out, n, h, w, c, ldi);
+  prof_end(s);
+  return hipGetLastError();
+}
+
+// 1x1 head on dense (npix, c) bf16 activations (when the last convolution could not fuse it); headW on the device
+hipError_t run_head_bf(const uint16_t* in, const float* headW, float headB, size_t npix, int c, float* logits,
+                       float* probs, uint8_t* mask, float thr, hipStream_t s) {
+  int lpp = 1;
+  while (lpp < 16 && lpp * 2 * 8 <= c) lpp *= 2;
+  const unsigned g = grid_for(npix, 256 / lpp);
+  prof_begin("head1x1_bf16", 2.0 * npix * c, 2.0 * npix * c + 4.0 * npix, s);
+#define HEADBF(L)                                                                                                  \
+  hipLaunchKernelGGL((unet::head1x1_bf16_kernel<L>), dim3(g), dim3(256), 0, s, in, headW, headB, npix, c, logits, \
+                     probs, mask, thr)
+  switch (lpp) {
+    case 1: HEADBF(1); break;
+    case 2: HEADBF(2); break;
+    case 4: HEADBF(4); break;
+    case 8: HEADBF(8); break;
+    default: HEADBF(16); break;
+  }
+#undef HEADBF
+  prof_end(s);
+  return hipGetLastError();
+}
+
+// First convolution on conv_first_bf16x3.h: uint8 (N,H,W,3) frames -> dense (N,H,W,Cout) bf16 (H % 8 == 0,
+// Cout % 64 == 0); wt from pack_first_bf16x3
+hipError_t run_first_bf16x3(const uint8_t* frames, const uint16_t* wt, const float* scale, const float* shift,
+                            uint16_t* out, int n, int h, int w, int cout, int relu, const float* mean, const float* std_,
+                            hipStream_t s) {
+  unet::ConvFirstArgs fa;
+  fa.frames = frames;
+  fa.wt = wt;
+  fa.scale = scale;
+  fa.shift = shift;
+  fa.out = out;
+  fa.N = n;
+  fa.H = h;
+  fa.W = w;
+  fa.Cout = cout;
+  fa.ldo = cout;
+  fa.tilesX = (w + 31) / 32;
+  fa.relu = relu;
+  fa.m0 = mean[0];
+  fa.m1 = mean[1];
+  fa.m2 = mean[2];
+  fa.s0 = std_[0];
+  fa.s1 = std_[1];
+  fa.s2 = std_[2];
+  const double px = (double)n * h * w;
+  prof_begin("conv3x3_first_bf16x3", 2.0 * px * 27 * cout, px * 3 + 2.0 * px * cout, s);
+  hipLaunchKernelGGL(unet::conv_first_bf16x3_kernel, dim3((unsigned)(fa.tilesX * (n * h / 8))), dim3(256), 0, s, fa);
   prof_end(s);
   return hipGetLastError();
 }
@@ -451,57 +661,12 @@ int bf16_build(unet_ctx* h) {
   h->bf = new Bf16Net();
   Bf16Net* B = h->bf;
   auto conv = [&](GemmOpBf& o, const GemmOp& f, const std::string& wname) -> int {
-    const auto& w = h->params[wname];
-    o.taps = 9;
-    o.cin = f.cinReal;
-    o.cout = f.cout;
-    o.coutPad = f.coutPad;
-    o.nTotal = f.nTotal;
-    o.relu = f.relu;
-    o.scale = f.scale;
-    o.shift = f.shift;
-    const int cinR = f.cinReal, coutR = f.cout;
-    auto packed = pack_fragments_bf16(o.nTotal, o.cin, 9, [&](int n, int ci, int t) -> float {
-      return (n < coutR && ci < cinR) ? w[((size_t)n * cinR + ci) * 9 + t] : 0.f;
-    });
-    int rc = upload_bf(h->err, &o.wt, packed);
-    if (rc) return rc;
-    if (cinR % 64 == 0 && coutR % 64 == 0) {
-      auto pw = pack_fragments_ws(coutR, cinR, [&](int n, int ci, int t) -> float {
-        return w[((size_t)n * cinR + ci) * 9 + t];
-      });
-      rc = upload_bf(h->err, &o.wtWs, pw);
-      o.zeros = B->zeros;
-    }
-    return rc;
+    return pack_conv_bf(h->err, o, f, h->params[wname].data(), B->zeros);
   };
   HIPCHK(h->err, hipMalloc((void**)&B->zeros, 8192 * sizeof(uint16_t)));
   HIPCHK(h->err, hipMemset(B->zeros, 0, 8192 * sizeof(uint16_t)));
   if (c.in_channels == 3 && c.features[0] % 64 == 0) {
-    // first convolution as one K = 27 bf16 MFMA per tile with hi/lo split operands (conv_first_bf16x3.h):
-    // [coTile][cs][hi|lo][lane][8], row j of subtile cs = channel 64*ct + 16*(j>>2) + 4*cs + (j&3), k = tap*3 + ci
-    const auto& w = h->params["encoder_blocks.0.0.weight"];
-    const int f0 = c.features[0];
-    std::vector<uint16_t> pw((size_t)(f0 / 64) * 4 * 2 * 64 * 8, 0);
-    for (int ct = 0; ct < f0 / 64; ++ct)
-      for (int cs = 0; cs < 4; ++cs)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int j = lane & 15, lq = lane >> 4;
-          const int co = 64 * ct + 16 * (j >> 2) + 4 * cs + (j & 3);
-          for (int e = 0; e < 8; ++e) {
-            const int k = lq * 8 + e;
-            float v = 0.f;
-            if (k < 27) v = w[((size_t)co * 3 + (k % 3)) * 9 + k / 3];
-            const uint16_t hi = host_f2bf(v);
-            uint32_t hb = (uint32_t)hi << 16;
-            float hf;
-            std::memcpy(&hf, &hb, 4);
-            const uint16_t lo = host_f2bf(v - hf);
-            pw[((((size_t)ct * 4 + cs) * 2 + 0) * 64 + lane) * 8 + e] = hi;
-            pw[((((size_t)ct * 4 + cs) * 2 + 1) * 64 + lane) * 8 + e] = lo;
-          }
-        }
-    const int rcw = upload_bf(h->err, &B->firstWt, pw);
+    const int rcw = pack_first_bf16x3(h->err, &B->firstWt, h->params["encoder_blocks.0.0.weight"].data(), c.features[0]);
     if (rcw) return rcw;
   }
   int rc;
@@ -520,46 +685,9 @@ int bf16_build(unet_ctx* h) {
     const std::string pd = "decoder_blocks." + std::to_string(2 * j + 1);
     if ((rc = conv(B->dec[2 * j], h->dec[2 * j], pd + ".0.weight"))) return rc;
     if ((rc = conv(B->dec[2 * j + 1], h->dec[2 * j + 1], pd + ".3.weight"))) return rc;
-    const GemmOp& f = h->up[j];
-    GemmOpBf& o = B->up[j];
-    const auto& w = h->params["decoder_blocks." + std::to_string(2 * j) + ".weight"];
-    o.taps = 1;
-    o.cin = f.cinReal;
-    o.cout = f.cout;
-    o.coutPad = f.coutPad;
-    o.nTotal = f.nTotal;
-    o.relu = 0;
-    o.scale = f.scale;
-    o.shift = f.shift;
-    const int cp = o.coutPad, coutR = o.cout, cinR = o.cin;
-    auto packed = pack_fragments_bf16(o.nTotal, o.cin, 1, [&](int n, int ci, int) -> float {
-      const int ab = n / cp, co = n % cp;
-      return (ab < 4 && co < coutR && ci < cinR) ? w[((size_t)ci * coutR + co) * 4 + ab] : 0.f;
-    });
-    if ((rc = upload_bf(h->err, &o.wt, packed))) return rc;
-    if (cinR % 64 == 0 && coutR % 64 == 0) {
-      // upconv_bf16_ws.h: [coTile(64)][chunk(64 ch)][kstep(2)][ab(4)][cs(4)][lane][8]; row j of subtile cs =
-      // channel 64*ct + 16*(j>>2) + 4*cs + (j&3), k = chunk*64 + kstep*32 + 8*(lane>>4) + e
-      const int nCt = coutR / 64, nCh = cinR / 64;
-      std::vector<uint16_t> pw((size_t)nCt * nCh * 32 * 64 * 8, 0);
-      for (int ct = 0; ct < nCt; ++ct)
-        for (int kc = 0; kc < nCh; ++kc)
-          for (int ks = 0; ks < 2; ++ks)
-            for (int ab = 0; ab < 4; ++ab)
-              for (int cs = 0; cs < 4; ++cs) {
-                uint16_t* dst = pw.data() + (((((size_t)ct * nCh + kc) * 2 + ks) * 4 + ab) * 4 + cs) * 64 * 8;
-                for (int lane = 0; lane < 64; ++lane) {
-                  const int jr = lane & 15, lq = lane >> 4;
-                  const int co = 64 * ct + 16 * (jr >> 2) + 4 * cs + (jr & 3);
-                  for (int e = 0; e < 8; ++e) {
-                    const int ci = kc * 64 + ks * 32 + lq * 8 + e;
-                    dst[lane * 8 + e] = host_f2bf(w[((size_t)ci * coutR + co) * 4 + ab]);
-                  }
-                }
-              }
-      if ((rc = upload_bf(h->err, &o.wtWs, pw))) return rc;
-      o.zeros = B->zeros;
-    }
+    if ((rc = pack_upconv_bf(h->err, B->up[j], h->up[j], h->params["decoder_blocks." + std::to_string(2 * j) + ".weight"].data(),
+                             B->zeros)))
+      return rc;
   }
   return UNET_OK;
 }
@@ -653,30 +781,8 @@ int unet_forward_u8_bf16(unet_handle_t h, const uint8_t* frames, int n, int heig
   for (int l = 0; l < c.depth; ++l) {
     const int f = c.features[l];
     if (l == 0 && firstFused) {
-      unet::ConvFirstArgs fa;
-      fa.frames = frames;
-      fa.wt = B->firstWt;
-      fa.scale = h->enc[0].scale;
-      fa.shift = h->enc[0].shift;
-      fa.out = tmpA;
-      fa.N = n;
-      fa.H = ch;
-      fa.W = cw;
-      fa.Cout = f;
-      fa.ldo = f;
-      fa.tilesX = (cw + 31) / 32;
-      fa.relu = h->enc[0].relu;
-      fa.m0 = c.input_mean[0];
-      fa.m1 = c.input_mean[1];
-      fa.m2 = c.input_mean[2];
-      fa.s0 = c.input_std[0];
-      fa.s1 = c.input_std[1];
-      fa.s2 = c.input_std[2];
-      const double px = (double)npix;
-      prof_begin("conv3x3_first_bf16x3", 2.0 * px * 27 * f, px * 3 + 2.0 * px * f, s);
-      hipLaunchKernelGGL(unet::conv_first_bf16x3_kernel, dim3((unsigned)(fa.tilesX * (n * ch / 8))), dim3(256), 0, s, fa);
-      prof_end(s);
-      HIPCHK(h->err, hipGetLastError());
+      HIPCHK(h->err, run_first_bf16x3(frames, B->firstWt, h->enc[0].scale, h->enc[0].shift, tmpA, n, ch, cw, f,
+                                      h->enc[0].relu, c.input_mean, c.input_std, s));
     } else if (l == 0) {
       // first convolution on the fp32 kernel, output rounded to bf16
       HIPCHK(h->err, run_gemm_op(h->enc[0], x0, n, ch, cw, reinterpret_cast<float*>(tmpA), f, 0, s, 1));
@@ -687,14 +793,7 @@ int unet_forward_u8_bf16(unet_handle_t h, const uint8_t* frames, int n, int heig
     fz.pool = U(p.pool[l]);
     bool pooled = false;
     HIPCHK(h->err, run_gemm_bf(B->enc[2 * l + 1], tmpA, n, ch, cw, U(p.cat[l]), 2 * f, 0, s, &fz, &pooled));
-    if (!pooled) {
-      const size_t total = (size_t)n * (ch / 2) * (cw / 2) * (f / 8);
-      prof_begin("maxpool2x2_bf16", 0.0, 2.0 * total * 8 * 5, s);
-      hipLaunchKernelGGL(unet::maxpool2x2_bf16_kernel, dim3(grid_for(total)), dim3(256), 0, s, U(p.cat[l]),
-                         U(p.pool[l]), n, ch, cw, f, 2 * f);
-      prof_end(s);
-      HIPCHK(h->err, hipGetLastError());
-    }
+    if (!pooled) HIPCHK(h->err, run_maxpool_bf(U(p.cat[l]), U(p.pool[l]), n, ch, cw, f, 2 * f, s));
     cur = U(p.pool[l]);
     ch /= 2;
     cw /= 2;
@@ -727,27 +826,213 @@ int unet_forward_u8_bf16(unet_handle_t h, const uint8_t* frames, int n, int heig
     }
     cur = tmpB;
   }
-  if (!headFused) {
-    const int f0 = c.features[0];
-    int lpp = 1;
-    while (lpp < 16 && lpp * 2 * 8 <= f0) lpp *= 2;
-    const unsigned g = grid_for(npix, 256 / lpp);
-    prof_begin("head1x1_bf16", 2.0 * npix * f0, 2.0 * npix * f0 + 4.0 * npix, s);
-#define HEADBF(L)                                                                                                  \
-  hipLaunchKernelGGL((unet::head1x1_bf16_kernel<L>), dim3(g), dim3(256), 0, s, cur, h->headW, h->headB, npix, f0, \
-                     logits, probs, mask, thr)
-    switch (lpp) {
-      case 1: HEADBF(1); break;
-      case 2: HEADBF(2); break;
-      case 4: HEADBF(4); break;
-      case 8: HEADBF(8); break;
-      default: HEADBF(16); break;
-    }
-#undef HEADBF
-    prof_end(s);
-    HIPCHK(h->err, hipGetLastError());
-  }
+  if (!headFused) HIPCHK(h->err, run_head_bf(cur, h->headW, h->headB, npix, c.features[0], logits, probs, mask, thr, s));
   return h->async_error();
+}
+
+}  // extern "C"
+
+// ---- single operators of the tier (test entry points): bf16 NHWC device tensors in and out, weights in PyTorch layout
+//      on the host, packed by the same functions as bf16_build; include/unet_hip.h ----
+
+namespace {
+
+// Device scratch of one test operator call, freed on every exit path
+struct BfOpScratch {
+  GemmOp f;
+  GemmOpBf op;
+  uint16_t* zeros = nullptr;
+  uint16_t* wtFirst = nullptr;
+  uint16_t* act = nullptr;
+  float* x0 = nullptr;
+  float* headW = nullptr;
+  ~BfOpScratch() {
+    op.free_dev();
+    f.free_dev();
+    for (uint16_t* q : {zeros, wtFirst, act})
+      if (q) hipFree(q);
+    if (x0) hipFree(x0);
+    if (headW) hipFree(headW);
+  }
+  // the network's zero page (bf16_build): the out-of-image halo source of the wave-specialised / one-wave-per-SIMD kernels
+  hipError_t alloc_zeros() {
+    hipError_t e = hipMalloc((void**)&zeros, 8192 * sizeof(uint16_t));
+    return e == hipSuccess ? hipMemset(zeros, 0, 8192 * sizeof(uint16_t)) : e;
+  }
+};
+
+void clear_path(int* path) {
+  if (path) path[0] = path[1] = path[2] = 0;
+}
+
+int op_finish(hipError_t e, hipStream_t s) {
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    g_opErr = hipGetErrorString(e);
+    return UNET_ERR_HIP;
+  }
+  return UNET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int unet_op_conv3x3_bf16(int device, const uint16_t* x, int n, int hh, int ww, int cin, const float* wHost,
+                         const float* scale, const float* shift, int cout, int relu, int kernel, int ldo, int coOff,
+                         uint16_t* y, uint16_t* yPool, int* pathOut, void* stream) {
+  clear_path(pathOut);
+  if (ldo == 0) ldo = cout;
+  if (!x || !wHost || !scale || !shift || !y || n < 1 || hh < 1 || ww < 1 || cin < 32 || cin % 32 || cout < 32 ||
+      cout % 32 || kernel < 0 || kernel > 3 || ldo % 32 || coOff < 0 || coOff % 32 || coOff + cout > ldo ||
+      (yPool && (hh % 2 || ww % 2)))
+    return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  BfOpScratch t;
+  int rc = build_conv3x3(g_opErr, t.f, wHost, cout, cin, scale, shift, relu ? 1 : 0);
+  if (rc) return rc;
+  HIPCHK(g_opErr, t.alloc_zeros());
+  if ((rc = pack_conv_bf(g_opErr, t.op, t.f, wHost, t.zeros))) return rc;
+  if (bf_kernel_for(t.op, n, hh, ww, kernel) == BF_NONE) {
+    g_opErr = "the forced bf16 kernel does not take this shape";
+    return UNET_ERR_INVALID_ARG;
+  }
+  BfFuse fz;
+  fz.pool = yPool;
+  bool pooled = false;
+  int ran = BF_NONE;
+  hipError_t e = run_gemm_bf(t.op, x, n, hh, ww, y, ldo, coOff, s, yPool ? &fz : nullptr, &pooled, nullptr, kernel, &ran);
+  if (pathOut) {
+    pathOut[0] = ran;
+    pathOut[1] = pooled ? 1 : 0;
+  }
+  return op_finish(e, s);
+}
+
+int unet_op_conv3x3_bf16_head(int device, const uint16_t* x, int n, int hh, int ww, int cin, const float* wHost,
+                              const float* scale, const float* shift, int cout, int relu, int kernel,
+                              const float* headWHost, float headB, float thr, float* logits, float* probs, uint8_t* mask,
+                              int* pathOut, void* stream) {
+  clear_path(pathOut);
+  if (!x || !wHost || !scale || !shift || !headWHost || n < 1 || hh < 1 || ww < 1 || cin < 32 || cin % 32 ||
+      cout < 32 || cout % 32 || kernel < 0 || kernel > 3)
+    return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  BfOpScratch t;
+  int rc = build_conv3x3(g_opErr, t.f, wHost, cout, cin, scale, shift, relu ? 1 : 0);
+  if (rc) return rc;
+  HIPCHK(g_opErr, t.alloc_zeros());
+  if ((rc = pack_conv_bf(g_opErr, t.op, t.f, wHost, t.zeros))) return rc;
+  if (bf_kernel_for(t.op, n, hh, ww, kernel) == BF_NONE) {
+    g_opErr = "the forced bf16 kernel does not take this shape";
+    return UNET_ERR_INVALID_ARG;
+  }
+  const size_t npix = (size_t)n * hh * ww;
+  HIPCHK(g_opErr, hipMalloc((void**)&t.headW, cout * sizeof(float)));
+  HIPCHK(g_opErr, hipMemcpy(t.headW, headWHost, cout * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(g_opErr, hipMalloc((void**)&t.act, npix * cout * sizeof(uint16_t)));
+  BfFuse fz;
+  fz.headW = t.headW;
+  fz.headB = headB;
+  fz.headThr = thr;
+  fz.logits = logits;
+  fz.probs = probs;
+  fz.mask = mask;
+  bool headFused = false;
+  int ran = BF_NONE;
+  hipError_t e = run_gemm_bf(t.op, x, n, hh, ww, t.act, cout, 0, s, &fz, nullptr, &headFused, kernel, &ran);
+  // as the forward: the unfused head reads the stored activation
+  if (e == hipSuccess && !headFused) e = run_head_bf(t.act, t.headW, headB, npix, cout, logits, probs, mask, thr, s);
+  if (pathOut) {
+    pathOut[0] = ran;
+    pathOut[2] = headFused ? 1 : 0;
+  }
+  return op_finish(e, s);
+}
+
+int unet_op_upconv2x2_bf16(int device, const uint16_t* x, int n, int hh, int ww, int cin, const float* wHost,
+                           const float* bias, int cout, int kernel, int ldo, int coOff, uint16_t* y, int* pathOut,
+                           void* stream) {
+  clear_path(pathOut);
+  if (ldo == 0) ldo = cout;
+  if (!x || !wHost || !bias || !y || n < 1 || hh < 1 || ww < 1 || cin < 32 || cin % 32 || cout < 32 || cout % 32 ||
+      kernel < 0 || kernel > 3 || ldo % 32 || coOff < 0 || coOff % 32 || coOff + cout > ldo)
+    return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  BfOpScratch t;
+  int rc = build_upconv(g_opErr, t.f, wHost, cin, cout, bias);
+  if (rc) return rc;
+  HIPCHK(g_opErr, t.alloc_zeros());
+  if ((rc = pack_upconv_bf(g_opErr, t.op, t.f, wHost, t.zeros))) return rc;
+  if (bf_kernel_for(t.op, n, hh, ww, kernel) == BF_NONE) {
+    g_opErr = "the forced bf16 kernel does not take this shape";
+    return UNET_ERR_INVALID_ARG;
+  }
+  int ran = BF_NONE;
+  hipError_t e = run_gemm_bf(t.op, x, n, hh, ww, y, ldo, coOff, s, nullptr, nullptr, nullptr, kernel, &ran);
+  if (pathOut) pathOut[0] = ran;
+  return op_finish(e, s);
+}
+
+int unet_op_conv_first_bf16(int device, const uint8_t* frames, int n, int hh, int ww, const float* wHost,
+                            const float* scale, const float* shift, int cout, int relu, const float* meanHost,
+                            const float* stdHost, int kernel, uint16_t* y, int* pathOut, void* stream) {
+  clear_path(pathOut);
+  if (!frames || !wHost || !scale || !shift || !meanHost || !stdHost || !y || n < 1 || hh < 1 || ww < 1 ||
+      cout < 32 || cout % 32 || kernel < 0 || kernel > 2)
+    return UNET_ERR_INVALID_ARG;
+  // the forward's choice (unet_forward_u8_bf16): conv_first_bf16x3.h where H % 8 == 0 and Cout % 64 == 0, else the fp32
+  // kernel with a bf16 store
+  static const bool firstOk = [] { const char* e = getenv("UNET_BF16_FIRST"); return !(e && e[0] == '0'); }();
+  const bool fusedOk = hh % 8 == 0 && cout % 64 == 0;
+  if (kernel == 1 && !fusedOk) {
+    g_opErr = "conv_first_bf16x3 needs H % 8 == 0 and Cout % 64 == 0";
+    return UNET_ERR_INVALID_ARG;
+  }
+  const int k = kernel ? kernel : (firstOk && fusedOk ? 1 : 2);
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  BfOpScratch t;
+  int rc = build_conv3x3(g_opErr, t.f, wHost, cout, 3, scale, shift, relu ? 1 : 0);
+  if (rc) return rc;
+  hipError_t e;
+  if (k == 1) {
+    if ((rc = pack_first_bf16x3(g_opErr, &t.wtFirst, wHost, cout))) return rc;
+    e = run_first_bf16x3(frames, t.wtFirst, t.f.scale, t.f.shift, y, n, hh, ww, cout, t.f.relu, meanHost, stdHost, s);
+  } else {
+    const size_t npix = (size_t)n * hh * ww;
+    HIPCHK(g_opErr, hipMalloc((void**)&t.x0, npix * 4 * sizeof(float)));
+    hipLaunchKernelGGL(unet::pack_u8_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, frames, t.x0, npix, meanHost[0],
+                       meanHost[1], meanHost[2], stdHost[0], stdHost[1], stdHost[2]);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = run_gemm_op(t.f, t.x0, n, hh, ww, reinterpret_cast<float*>(y), cout, 0, s, 1);
+  }
+  if (pathOut) pathOut[0] = k;
+  return op_finish(e, s);
+}
+
+int unet_op_maxpool2x2_bf16(int device, const uint16_t* x, int n, int hh, int ww, int c, int ldi, uint16_t* y,
+                            void* stream) {
+  if (ldi == 0) ldi = c;
+  if (!x || !y || n < 1 || hh < 2 || ww < 2 || hh % 2 || ww % 2 || c < 8 || c % 8 || ldi % 8 || ldi < c)
+    return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  return op_finish(run_maxpool_bf(x, y, n, hh, ww, c, ldi, s), s);
+}
+
+int unet_op_head1x1_bf16(int device, const uint16_t* x, int n, int hh, int ww, int c, const float* wHost, float bias,
+                         float thr, float* logits, float* probs, uint8_t* mask, void* stream) {
+  if (!x || !wHost || n < 1 || hh < 1 || ww < 1 || c < 8 || c % 8) return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  BfOpScratch t;
+  HIPCHK(g_opErr, hipMalloc((void**)&t.headW, c * sizeof(float)));
+  HIPCHK(g_opErr, hipMemcpy(t.headW, wHost, c * sizeof(float), hipMemcpyHostToDevice));
+  return op_finish(run_head_bf(x, t.headW, bias, (size_t)n * hh * ww, c, logits, probs, mask, thr, s), s);
 }
 
 }  // extern "C"
