@@ -211,6 +211,37 @@ int unet_train_repack(unet_handle_t h, void* stream);
 int unet_dice_metric(int device, const float* logits_dev, const float* targets_dev, size_t numel,
                      float threshold_logit, float smooth, float* out_dev, void* stream);
 
+/* Eval-mode forward on a training handle: `model.eval(); with torch.no_grad(): outputs = model(images)` of the
+ * reference's validate() (README.md:2087-2099) on the parameters and BatchNorm buffers attached right now
+ * (unet_train_attach) - no host round trip, no second copy of the weights.  BatchNorm uses the running statistics
+ * (scale = gamma / sqrt(running_var + 1e-5), shift = beta - running_mean * scale, folded on the device at every call);
+ * the convolutions run on the operand packs the training step keeps current, with the same kernel dispatch
+ * (unet_set_train_x3).  Logits (N,1,H,W) go to logits_dev.  Uses the training workspace (unet_train_workspace_bytes) and
+ * writes nothing a training step reads later: parameters, gradients, Adam moments, running statistics, the loss
+ * configuration and the step's saved statistics stay as they are.  The fp16 range watch stays armed (unet_device_error).
+ * UNET_ERR_STATE without unet_train_attach, UNET_ERR_SHAPE as the train entry points. */
+int unet_train_eval_u8(unet_handle_t h, const uint8_t* frames_dev, int n, int height, int width, float* logits_dev,
+                       void* stream);
+int unet_train_eval_f32(unet_handle_t h, const float* image_nchw_dev, int n, int height, int width, float* logits_dev,
+                        void* stream);
+
+/* Segmentation metrics and validation loss of one batch as one device reduction, added to running accumulators: the
+ * body of the reference's validate() loop (README.md:2101-2110: criterion, compute_dice :2115-2120, per-batch values
+ * averaged over the batches) and the confusion counts behind its published IoU / Dice / Precision / Recall / F1 /
+ * pixel accuracy (README.md:4177-4184).  acc_dev: 16 doubles owned by the caller, zeroed by the caller before the first
+ * batch:
+ *   [0..3]  TP FP FN TN pixel counts over all batches so far, exact integers stored as doubles (exact below 2^53), with
+ *           pred = logit > threshold_logit, truth = target > 0.5 (uint8 targets: target != 0)
+ *   [4..6]  sum over the batches of the batch's (total, bce, dice) loss: loss_mode 0 = BCEWithLogits(mean) (total = bce,
+ *           dice = 0), 1 = bce_weight * BCE(pos_weight) + dice_weight * Dice(smooth), as unet_train_set_loss
+ *   [7]     sum over the batches of the batch's compute_dice(pred, target, smooth)
+ *   [8]     number of batches      [9] number of pixels      [10..15] reserved
+ * targets_dev: `numel` floats (0/1), or with targets_are_u8 `numel` bytes (0 / non-zero, e.g. 0 / 255 masks).  No host
+ * synchronisation; takes a bare device index like unet_dice_metric, so it serves logits from any tier. */
+int unet_seg_metrics_accumulate(int device, const float* logits_dev, const void* targets_dev, int targets_are_u8,
+                                size_t numel, float threshold_logit, int loss_mode, float bce_weight, float dice_weight,
+                                float pos_weight, float smooth, double* acc_dev, void* stream);
+
 const char* unet_last_error(unet_handle_t h);
 const char* unet_version(void);
 

@@ -3,6 +3,7 @@
 Public surface:
   UNetHIP                      forward(image) -> logits, run_u8(frames)
   RKNN_model_container         drop-in for the reference's model container
+  SegMetrics                   loss / Dice / IoU / precision / recall of a validation pass (metrics.py)
   seeded_state_dict, ...       reproducible weights / synthetic inputs
 """
 from .state import (DEFAULT_FEATURES, INPUT_MEAN, INPUT_STD, num_parameters, seeded_state_dict,  # noqa: F401
@@ -16,4 +17,7 @@ def __getattr__(name):  # lazy: importing the package must not need torch.cuda o
     if name == "RKNN_model_container":
         from .py_utils.rknn_executor import RKNN_model_container
         return RKNN_model_container
+    if name == "SegMetrics":
+        from .metrics import SegMetrics
+        return SegMetrics
     raise AttributeError(name)

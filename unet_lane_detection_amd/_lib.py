@@ -111,6 +111,10 @@ SIGNATURES = {
     "unet_train_grad_split": (C.c_size_t, [C.c_void_p]),
     "unet_dice_metric": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_void_p,
                                    C.c_void_p]),
+    "unet_train_eval_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "unet_train_eval_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "unet_seg_metrics_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_int,
+                                              C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "unet_device_error": (C.c_int, [C.c_void_p]),
     "unet_device_error_on": (C.c_int, [C.c_void_p, C.c_void_p]),
     "unet_device_status_to": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -28,6 +28,7 @@ struct ConvUnit {
   uint16_t *x3Fwd = nullptr, *x3Dgrad = nullptr;
   size_t offW = 0, offG = 0, offB = 0, offRM = 0, offRV = 0;
   float *scale = nullptr, *shift = nullptr, *mean = nullptr, *invstd = nullptr;
+  float *evScale = nullptr, *evShift = nullptr;   // BatchNorm folded with the running statistics (eval pass, TrainState::evalArena)
 };
 
 struct UpUnit {
@@ -60,6 +61,8 @@ struct TrainPlan {
 };
 
 }  // namespace
+
+#include "validate_kernels.h"
 
 struct TrainState {
   float *params = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr, *bn = nullptr;
@@ -101,6 +104,12 @@ struct TrainState {
   unsigned* gzKeys = nullptr; // 8 order keys per conv unit, zeroed every step: [0..4] the maxima behind bn_bwd_scale_exponent,
                               // [7] max |dZ| (fp16 range scaling of dZ when it is split by a separate pass)
   float* gzInv = nullptr;     // per conv unit: 2^-k undoing that scaling
+  // Eval-mode forward (unet_train_eval_*): per-unit folded scale / shift, rewritten by one launch at the start of every
+  // eval pass from the live gamma / beta / running statistics; apart from the step's own scale / shift / mean / invstd,
+  // which a later backward pass reads
+  float* evalArena = nullptr;
+  unet::BnFoldDesc* evalDescs = nullptr;
+  int nEvalUnits = 0;
   int dbgStage = -1;       // debug: copy an internal gradient buffer out at a numbered checkpoint
   float* dbgDst = nullptr;
   size_t dbgMax = 0;
@@ -1349,6 +1358,225 @@ int train_prologue(unet_ctx* h, const void* in, const float* targets, float* los
   return UNET_OK;
 }
 
+// ---- eval-mode forward on the attached parameters (reference README.md:2089-2099: model.eval(); no_grad) --------
+//
+// The same operand packs and the same dispatch as unit_forward, with BatchNorm in eval form: one launch folds gamma,
+// beta and the running statistics of every unit into scale / shift (bn_eval_fold_kernel), and the convolution applies
+// them and the ReLU in its epilogue.  Nothing of z is stored where a unit runs on the split-operand kernels: planes in,
+// planes (or the fp32 activation) out, the encoder's pooling in the same epilogue.  An exact-fp32 unit writes its fp32
+// activation from the convolution's epilogue as well; only where its consumer wants operand planes (the first
+// convolution in planes mode) it writes raw z and bn_apply_relu_kernel produces the planes.
+// It writes the eval arena, the workspace (every buffer of which a training step rewrites before it reads it) and the
+// caller's logits - and nothing else: no parameter, gradient, moment, running statistic or saved per-unit statistic.
+
+int eval_init(unet_ctx* h) {
+  TrainState* T = h->train;
+  if (T->evalArena) return UNET_OK;
+  size_t floats = 0;
+  for (auto* vec : {&T->enc, &T->bott, &T->dec})
+    for (auto& u : *vec) floats += 2 * (size_t)round_up(u.cout, 128);
+  HIPCHK(h->err, hipMalloc((void**)&T->evalArena, floats * sizeof(float)));
+  std::vector<unet::BnFoldDesc> d;
+  float* sp = T->evalArena;
+  for (auto* vec : {&T->enc, &T->bott, &T->dec})
+    for (auto& u : *vec) {
+      const int cp = round_up(u.cout, 128);
+      u.evScale = sp;
+      u.evShift = sp + cp;
+      sp += 2 * cp;
+      d.push_back({T->params + u.offG, T->params + u.offB, T->bn + u.offRM, T->bn + u.offRV, u.evScale, u.evShift, u.cout, cp});
+    }
+  T->nEvalUnits = (int)d.size();
+  HIPCHK(h->err, hipMalloc((void**)&T->evalDescs, d.size() * sizeof(unet::BnFoldDesc)));
+  HIPCHK(h->err, hipMemcpy(T->evalDescs, d.data(), d.size() * sizeof(unet::BnFoldDesc), hipMemcpyHostToDevice));
+  return UNET_OK;
+}
+
+// One conv unit in eval form.  Output: operand planes (o.planes, optionally with the pooled planes o.pooled) or fp32
+// (o.f32), never both.  z: scratch for raw z (exact-fp32 unit with a planes output only)
+int eval_unit(unet_ctx* h, ConvUnit& u, const float* in, const float* inPlanes, int n, int hh, int ww, float* z,
+              const ActOut& o, float* planes, hipStream_t s) {
+  TrainState* T = h->train;
+  const size_t P = (size_t)n * hh * ww;
+  if (inPlanes && !u.x3Fwd) {
+    h->err = "training plan inconsistent: a unit outside the split-operand path was handed an input in planes";
+    return UNET_ERR_STATE;
+  }
+  if (inPlanes || (u.x3Fwd && train_x3_enabled())) {
+    if (!inPlanes) {
+      split_to_planes(in, P * u.cin, planes, s);
+      inPlanes = planes;
+    }
+    GemmOpX3 op;   // borrowed pointers: never freed through this object
+    op.taps = 9;
+    op.cin = u.cin;
+    op.cout = u.cout;
+    op.relu = 1;
+    op.wt = u.x3Fwd;
+    op.scale = u.evScale;
+    op.shift = u.evShift;
+    const uint16_t* zp = reinterpret_cast<const uint16_t*>(zero_page());
+    const uint16_t* ip = reinterpret_cast<const uint16_t*>(inPlanes);
+    hipError_t e;
+    if (o.planes) {
+      X3Fuse fz;
+      fz.pool = reinterpret_cast<uint16_t*>(o.pooled);
+      fz.poolLo = (P / 4) * (size_t)u.cout;
+      e = run_conv_x3(op, zp, ip, P * u.cin, n, hh, ww, reinterpret_cast<uint16_t*>(o.planes), P * (size_t)o.ldp, o.ldp,
+                      o.offp, s, o.pooled ? &fz : nullptr, 0, nullptr, o.pooled ? "eval_conv3x3_pool_f16x3" : "eval_conv3x3_f16x3");
+    } else {
+      e = run_conv_x3(op, zp, ip, P * u.cin, n, hh, ww, nullptr, 0, o.ld, o.off, s, nullptr, 0, o.f32, "eval_conv3x3_f16x3");
+    }
+    op.wt = nullptr;
+    op.scale = op.shift = nullptr;
+    HIPCHK(h->err, e);
+    return UNET_OK;
+  }
+  if (o.planes) {
+    GemmOp op = u.fwd;   // a copy of plain pointers (ones / zeros epilogue: raw z)
+    op.name = "eval_conv3x3_igemm_f32";
+    op.nameWino = "eval_conv3x3_wino_f32";
+    HIPCHK(h->err, run_gemm_op(op, in, n, hh, ww, z, u.cout, 0, s));
+    prof_begin("eval_bn_apply_relu", 0.0, 8.0 * P * u.cout, s);
+    hipLaunchKernelGGL(unet::bn_apply_relu_kernel, dim3(grid_for(P * (u.cout / 4))), dim3(256), 0, s, z, u.evScale,
+                       u.evShift, P, u.cout, (float*)nullptr, 0, 0, reinterpret_cast<uint32_t*>(o.planes),
+                       P * (size_t)o.ldp / 2, o.ldp, o.offp, g_errWord, (const float*)nullptr, (const float*)nullptr,
+                       (float*)nullptr);
+    prof_end(s);
+    HIPCHK(h->err, hipGetLastError());
+    if (o.pooled) {
+      h->err = "eval pass: a pooled planes output was asked of an exact-fp32 unit";
+      return UNET_ERR_STATE;
+    }
+    return UNET_OK;
+  }
+  GemmOp op = u.fwd;   // the folded BatchNorm and the ReLU in the convolution's epilogue
+  op.scale = u.evScale;
+  op.shift = u.evShift;
+  op.relu = 1;
+  op.name = "eval_conv3x3_igemm_f32";
+  op.nameWino = "eval_conv3x3_wino_f32";
+  HIPCHK(h->err, run_gemm_op(op, in, n, hh, ww, o.f32, o.ld, o.off, s));
+  return UNET_OK;
+}
+
+int train_eval_forward(unet_ctx* h, int n, int height, int width, float* logitsOut, hipStream_t s, const TrainPlan& p) {
+  TrainState* T = h->train;
+  const unet_config& c = h->cfg;
+  const int D = c.depth;
+  LaunchScope scope(h);
+  float* ws = reinterpret_cast<float*>(T->ws);
+  float* planes = ws + p.xPlanes;
+  int rc;
+  if (T->packedX3 != (train_x3_enabled() ? 1 : 0) && (rc = train_repack(h, s))) return rc;   // unet_set_train_x3 since
+  if ((rc = eval_init(h))) return rc;
+  prof_begin("eval_bn_fold", 0.0, 24.0 * T->B, s);
+  const hipError_t ef = unet::launch_bn_eval_fold(T->evalDescs, T->nEvalUnits, kBnEps, s);
+  prof_end(s);
+  HIPCHK(h->err, ef);
+
+  const bool PM = p.planes;
+  auto actOut = [&](float* ptr, int ld, bool asPlanes) {
+    ActOut o;
+    if (asPlanes) {
+      o.planes = ptr;
+      o.ldp = ld;
+    } else {
+      o.f32 = ptr;
+      o.ld = ld;
+    }
+    return o;
+  };
+  const float* cur = ws + p.x0;   // fp32 activation, or planes where PM says so
+  int ch = height, cw = width;
+  for (int l = 0; l < D; ++l) {
+    const int f = c.features[l];
+    const bool inP = PM && l > 0;
+    if ((rc = eval_unit(h, T->enc[2 * l], inP ? nullptr : cur, inP ? cur : nullptr, n, ch, cw, ws + p.encZ1[l],
+                        actOut(ws + p.encA1[l], f, PM), planes, s)))
+      return rc;
+    // the skip half of the concat buffer; in planes mode with the pooled planes from the same epilogue
+    ActOut skip = actOut(PM ? ws + p.catP[l] : ws + p.cat[l], 2 * f, PM);
+    if (PM) skip.pooled = ws + p.pool[l];
+    if ((rc = eval_unit(h, T->enc[2 * l + 1], PM ? nullptr : ws + p.encA1[l], PM ? ws + p.encA1[l] : nullptr, n, ch, cw,
+                        ws + p.encZ2[l], skip, planes, s)))
+      return rc;
+    if (!PM) HIPCHK(h->err, run_maxpool(ws + p.cat[l], ws + p.pool[l], n, ch, cw, f, 2 * f, s));
+    cur = ws + p.pool[l];
+    ch /= 2;
+    cw /= 2;
+  }
+  const int fb = 2 * c.features[D - 1];
+  if ((rc = eval_unit(h, T->bott[0], PM ? nullptr : cur, PM ? cur : nullptr, n, ch, cw, ws + p.botZ1,
+                      actOut(ws + p.botA1, fb, PM), planes, s)))
+    return rc;
+  // the output of a unit that feeds a transposed convolution: planes where that runs on the split-operand kernel
+  auto upInOut = [&](float* f32, int j, int chn) {
+    const bool asP = PM && j < D && T->up[j].x3Fwd;
+    return actOut(asP ? ws + p.upInP[j] : f32, chn, asP);
+  };
+  if ((rc = eval_unit(h, T->bott[1], PM ? nullptr : ws + p.botA1, PM ? ws + p.botA1 : nullptr, n, ch, cw, ws + p.botZ2,
+                      upInOut(ws + p.botA2, 0, fb), planes, s)))
+    return rc;
+  cur = ws + p.botA2;
+  for (int j = 0; j < D; ++j) {
+    const int l = D - 1 - j;
+    const int f = c.features[l];
+    const bool upX3 = PM && T->up[j].x3Fwd;
+    if (upX3) {   // planes in, planes out: straight into the upper channel half of the concat buffer's operand form
+      GemmOpX3 op;   // borrowed pointers
+      op.taps = 1;
+      op.cin = 2 * f;
+      op.cout = f;
+      op.wt = T->up[j].x3Fwd;
+      op.scale = T->ones;
+      op.shift = T->params + T->up[j].offB;
+      const size_t Pin = (size_t)n * ch * cw;
+      const hipError_t e = run_upconv_x3(op, reinterpret_cast<const uint16_t*>(zero_page()),
+                                         reinterpret_cast<const uint16_t*>(ws + p.upInP[j]), Pin * 2 * f, n, ch, cw,
+                                         reinterpret_cast<uint16_t*>(ws + p.catP[l]), Pin * 4 * 2 * f, 2 * f, f, s);
+      op.wt = nullptr;
+      op.scale = op.shift = nullptr;
+      HIPCHK(h->err, e);
+    } else {
+      HIPCHK(h->err, run_gemm_op(T->up[j].fwd, cur, n, ch, cw, ws + p.cat[l], 2 * f, f, s));
+    }
+    ch *= 2;
+    cw *= 2;
+    if (PM && !upX3) {   // upper half of the concat buffer -> operand form
+      const size_t Pl = (size_t)n * ch * cw;
+      prof_begin("split_planes", 0.0, 8.0 * Pl * f, s);
+      hipLaunchKernelGGL(unet::split_planes_strided_kernel, dim3(grid_for(Pl * (f / 4))), dim3(256), 0, s, ws + p.cat[l],
+                         2 * f, f, Pl, f, reinterpret_cast<uint32_t*>(ws + p.catP[l]), Pl * (size_t)(2 * f) / 2, 2 * f, f);
+      prof_end(s);
+      HIPCHK(h->err, hipGetLastError());
+    }
+    if ((rc = eval_unit(h, T->dec[2 * j], PM ? nullptr : ws + p.cat[l], PM ? ws + p.catP[l] : nullptr, n, ch, cw,
+                        ws + p.decZ1[l], actOut(ws + p.decA1[l], f, PM), planes, s)))
+      return rc;
+    // the last unit feeds the 1x1 head: fp32
+    const ActOut lastOut = j == D - 1 ? actOut(ws + p.decA2[l], f, false) : upInOut(ws + p.decA2[l], j + 1, f);
+    if ((rc = eval_unit(h, T->dec[2 * j + 1], PM ? nullptr : ws + p.decA1[l], PM ? ws + p.decA1[l] : nullptr, n, ch, cw,
+                        ws + p.decZ2[l], lastOut, planes, s)))
+      return rc;
+    cur = ws + p.decA2[l];
+  }
+  HIPCHK(h->err, run_head(cur, T->params + T->offHeadW, 0.f, (size_t)n * height * width, c.features[0], logitsOut, nullptr,
+                          nullptr, 0.f, s, T->params + T->offHeadB));
+  return h->async_error();
+}
+
+int eval_prologue(unet_ctx* h, const void* in, float* logits, int n, int height, int width, TrainPlan& plan) {
+  if (!h) return UNET_ERR_INVALID_ARG;
+  if (!h->train || !h->train->packed) {
+    h->err = "unet_train_attach has not been called";
+    return UNET_ERR_STATE;
+  }
+  if (!in || !logits) return UNET_ERR_INVALID_ARG;
+  // (train_prologue only checks its targets / loss pointers for null: an eval pass has neither)
+  return train_prologue(h, in, logits, logits, n, height, width, plan);
+}
+
 }  // namespace
 
 static void train_free(unet_ctx* h) {
@@ -1377,6 +1605,8 @@ static void train_free(unet_ctx* h) {
   if (T->zeros) hipFree(T->zeros);
   if (T->statArena) hipFree(T->statArena);
   if (T->lossCoef) hipFree(T->lossCoef);
+  if (T->evalArena) hipFree(T->evalArena);
+  if (T->evalDescs) hipFree(T->evalDescs);
   if (T->lateGradsReady) hipEventDestroy(T->lateGradsReady);
   if (T->side) {
     hipStreamSynchronize(T->side);
@@ -1692,6 +1922,55 @@ int unet_train_adam_step(unet_handle_t h, int step, float lr, float beta1, float
   int rc = train_repack(h, s);
   prof_end(s);
   return rc;
+}
+
+// Eval-mode forward on the attached parameters and BatchNorm buffers (reference README.md:2087-2099): see
+// train_eval_forward.  Logits (N,1,H,W) to logitsDev; no training state is written.
+int unet_train_eval_u8(unet_handle_t h, const uint8_t* frames, int n, int height, int width, float* logitsDev,
+                       void* stream) {
+  TrainPlan p;
+  int rc = eval_prologue(h, frames, logitsDev, n, height, width, p);
+  if (rc) return rc;
+  if (h->cfg.in_channels != 3) return UNET_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t npix = (size_t)n * height * width;
+  const unet_config& c = h->cfg;
+  hipLaunchKernelGGL(unet::pack_u8_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, frames,
+                     reinterpret_cast<float*>(h->train->ws) + p.x0, npix, c.input_mean[0], c.input_mean[1],
+                     c.input_mean[2], c.input_std[0], c.input_std[1], c.input_std[2]);
+  HIPCHK(h->err, hipGetLastError());
+  return train_eval_forward(h, n, height, width, logitsDev, s, p);
+}
+
+int unet_train_eval_f32(unet_handle_t h, const float* image, int n, int height, int width, float* logitsDev,
+                        void* stream) {
+  TrainPlan p;
+  int rc = eval_prologue(h, image, logitsDev, n, height, width, p);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t npix = (size_t)n * height * width;
+  hipLaunchKernelGGL(unet::pack_nchw_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, image,
+                     reinterpret_cast<float*>(h->train->ws) + p.x0, n, (size_t)height * width, h->cfg.in_channels);
+  HIPCHK(h->err, hipGetLastError());
+  return train_eval_forward(h, n, height, width, logitsDev, s, p);
+}
+
+// Segmentation metrics and validation loss of one batch, added to 16 running accumulators on the device (reference
+// README.md:2101-2110, :2115-2120, :4177-4184): see include/unet_hip.h.  No host synchronisation.
+int unet_seg_metrics_accumulate(int device, const float* logitsDev, const void* targetsDev, int targetsAreU8,
+                                size_t numel, float thresholdLogit, int lossMode, float bceWeight, float diceWeight,
+                                float posWeight, float smooth, double* accDev, void* stream) {
+  if (!logitsDev || !targetsDev || !accDev || numel == 0 || (lossMode != 0 && lossMode != 1)) return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned nb = std::min<unsigned>(grid_for(numel), 1024);
+  double* partial = nullptr;
+  HIPCHK(g_opErr, hipMallocAsync((void**)&partial, (size_t)nb * unet::SEG_PARTIALS * sizeof(double), s));
+  const hipError_t e = unet::launch_seg_metrics(logitsDev, targetsDev, targetsAreU8 != 0, numel, thresholdLogit, lossMode,
+                                                  bceWeight, diceWeight, posWeight, smooth, partial, nb, accDev, s);
+  HIPCHK(g_opErr, hipFreeAsync(partial, s));
+  HIPCHK(g_opErr, e);
+  return UNET_OK;
 }
 
 // Dice metric of the validation loop (reference README.md:2115-2120) on device buffers; out_dev holds 4 floats.

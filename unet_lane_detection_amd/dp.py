@@ -52,3 +52,12 @@ def max_over_ranks(value: float, device, group=None) -> float:
     t = torch.tensor([value], dtype=torch.float64, device=device)
     dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
     return float(t.item())
+
+
+def allreduce_accumulators(acc: torch.Tensor, group=None) -> torch.Tensor:
+    """SUM all-reduce (in place) of the 16 float64 accumulators of a validation pass, so that every rank builds the same
+    SegMetrics: counts and batch numbers add up, per-batch sums add up, the means divide by the summed batch count."""
+    _, ws = world(group)
+    if ws > 1:
+        dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=group)
+    return acc

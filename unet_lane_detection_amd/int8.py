@@ -98,6 +98,14 @@ class UNetInt8:
         self._check(rc, "unet_i8_forward_u8")
         return _pack(logits, probs, mask, return_probs, return_mask)
 
+    def evaluate(self, frames, targets, threshold=0.5, batch=None):
+        """Segmentation metrics of the int8 tier over uint8 `frames` against `targets`: as UNetHIP.evaluate."""
+        from . import metrics
+        self._require_live()
+        return metrics.evaluate_batches(self._lib, self.device, frames, targets, batch, threshold,
+                                        lambda: C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),
+                                        self.run_u8)
+
     def read_tensor(self, name, n, h, w):
         """int8 activation tensor `name` of the last forward as an (N,C,h,w) numpy array (parity tests); h, w are that
         tensor's spatial size."""

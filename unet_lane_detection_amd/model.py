@@ -164,6 +164,19 @@ class UNetHIP:
         _lib.check(rc, f"unet_forward_u8[{precision}]", self._h)
         return _pack(logits, probs, mask, return_probs, return_mask)
 
+    # ---- segmentation metrics of a tier (reference README.md:4177-4184, :3437) ----------------------------
+    def evaluate(self, frames, targets, precision="fp32", threshold=0.5, batch=None):
+        """IoU / Dice / precision / recall / F1 / pixel accuracy (and mean BCE-with-logits loss) of one arithmetic tier
+        over `frames` ((N,H,W,3) uint8 -> run_u8, or (N,3,H,W) float32 normalised -> forward) against `targets`
+        (N,1,H,W) or (N,H,W), float 0/1 or uint8 0 / non-zero; `batch` frames at a time (default: all at once).  The
+        logits stay on the device: each batch is reduced there (unet_seg_metrics_accumulate) and 16 numbers are read
+        at the end.  Returns metrics.SegMetrics."""
+        from . import metrics
+        self._require_live()
+        return metrics.evaluate_batches(self._lib, self.device, frames, targets, batch, threshold, self._stream,
+                                        lambda f: self.run_u8(f, precision=precision) if f.dtype == torch.uint8
+                                        else self.forward(f, precision=precision))
+
     # ---- per-launch timing ------------------------------------------------------------
     def profile(self, on=True):
         """Bracket every kernel launch of later forward calls with HIP events (clears old records)."""

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, checkpoint, dp
+from . import _lib, checkpoint, dp, loop, metrics
 from .model import infer_features
 from .state import INPUT_MEAN, INPUT_STD
 
@@ -228,6 +228,58 @@ class UNetTrainer:
                                  self._lib.unet_last_error(self._h).decode() if local else "")
         self.optimizer_step(scale)
         return self.loss
+
+    # ---- validation (reference README.md:2087-2112) and the loop around both (README.md:2185-2231) ----------
+    def eval_logits(self, images):
+        """Eval-mode forward (running statistics, nothing of the training state written) on the parameters as they are
+        on the device right now; images as forward_backward takes them -> logits (N,1,H,W) on the device."""
+        images = images.to(self.device).contiguous()
+        if images.dtype == torch.uint8:
+            n, h, w, _ = images.shape
+            fn = self._lib.unet_train_eval_u8
+        else:
+            images = images.to(torch.float32)
+            n, _, h, w = images.shape
+            fn = self._lib.unet_train_eval_f32
+        logits = torch.empty((n, 1, h, w), dtype=torch.float32, device=self.device)
+        _lib.check(fn(self._h, self._p(images), n, h, w, self._p(logits), self._stream()), "unet_train_eval", self._h)
+        return logits
+
+    def validate(self, batches, threshold=0.5, return_logits=False):
+        """The reference's validate(): eval-mode forward over `batches` (an iterable of (images, targets); images as
+        forward_backward takes them, targets float 0/1 or uint8 0 / non-zero), the loss set by set_loss and the
+        segmentation metrics reduced on the device, one host read at the end.  No state of the trainer moves:
+        parameters, BatchNorm buffers, gradients, moments, step_count and num_batches_tracked stay as they are, and
+        BatchNorm buffers are not broadcast.  Under a process group every rank validates its own batches and the
+        accumulators are summed, so all ranks return the same SegMetrics.  Raises like step() when the device reports
+        a failed launch or an activation beyond the fp16 range for the pass.  With return_logits: (SegMetrics, [logits
+        per batch])."""
+        acc = torch.zeros(metrics.NUM_ACCUMULATORS, dtype=torch.float64, device=self.device)
+        kept = []
+        for images, targets in batches:
+            logits = self.eval_logits(images)
+            metrics.accumulate(self._lib, self.device.index, logits, torch.as_tensor(targets), acc, self._stream(),
+                               threshold=threshold, loss_cfg=self._loss_cfg)
+            if return_logits:
+                kept.append(logits)
+        rc = self.device_error(current_stream_only=True)
+        _, ws = dp.world(self.group)
+        if ws > 1:
+            # the ranks fail together: this rank's status rides in a reserved accumulator
+            acc[metrics.NUM_ACCUMULATORS - 1] = 1.0 if rc else 0.0
+            dp.allreduce_accumulators(acc, self.group)
+        host = acc.cpu().numpy()
+        if rc != 0 or host[metrics.NUM_ACCUMULATORS - 1] != 0.0:
+            raise _lib.UnetError(rc or _lib.UNET_ERR_HIP, "unet_device_error: the validation pass is invalid, no metrics "
+                                 "are returned", self._lib.unet_last_error(self._h).decode() if rc else "")
+        host[metrics.NUM_ACCUMULATORS - 1] = 0.0
+        m = metrics.SegMetrics(host)
+        return (m, kept) if return_logits else m
+
+    def fit(self, train_batches, val_batches, epochs, scheduler=None, save_dir=None, patience=None, on_epoch=None):
+        """The reference's train(config) loop: see loop.fit."""
+        return loop.fit(self, train_batches, val_batches, epochs, scheduler=scheduler, save_dir=save_dir,
+                        patience=patience, on_epoch=on_epoch)
 
     # ---- views in the reference's state_dict naming -----------------------------------------------
     def _view(self, flat_p, flat_b):
