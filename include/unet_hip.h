@@ -154,6 +154,30 @@ size_t unet_train_workspace_bytes(unet_handle_t h, int n, int height, int width)
 int unet_train_set_loss(unet_handle_t h, int mode, float bce_weight, float dice_weight, float pos_weight,
                         float smooth);
 
+/* The loss as one structure.  mode 0 / 1: as unet_train_set_loss (focal_weight, alpha, gamma are ignored).
+ * mode 2: the general loss of the reference's loss family (README.md:1694 BCELoss, :1781 DiceLoss, :1855 BCEDiceLoss,
+ * :1914-1939 FocalLoss; table of which to use when :1942-1951, "Focal + Dice, gamma = 2.0" for masks under 5 % lane):
+ *   L = bce_weight * BCEWithLogits(pos_weight) + focal_weight * Focal(alpha, gamma) + dice_weight * Dice(smooth)
+ * with, per element (x the logit, t the target, any float in [0, 1]; p = sigmoid(x)),
+ *   ce = max(x,0) - x t + log1p(exp(-|x|)),   q = p (1 - t) + (1 - p) t  [= 1 - p_t, formed without the subtraction],
+ *   a_t = alpha t + (1 - alpha)(1 - t),   Focal = mean_i(a_t q^gamma ce).
+ * All three terms are always computed and reported; the weights decide the total and the gradient. */
+typedef struct unet_loss_config {
+    int mode;
+    float bce_weight, focal_weight, dice_weight, pos_weight, alpha, gamma, smooth;
+} unet_loss_config;
+
+/* Stands in for the `criterion = ...` line of a training script that picks a loss of that family (README.md:2169-2170).
+ * loss_dev of unet_train_forward_backward_* then receives four floats {total, bce, dice, focal}; the profile record of
+ * the mode-2 passes is "focal_loss_grad".  Modes 0 and 1 behave exactly like unet_train_set_loss.
+ * Mode 2 accepts: every weight >= 0 and not all of them zero; pos_weight > 0; 0 <= alpha <= 1; smooth > 0; gamma == 0
+ * (alpha-weighted BCE, no power is evaluated) or gamma >= 1.  Everything else, NaN and Inf included, is
+ * UNET_ERR_INVALID_ARG - checked first, so the answer does not depend on the handle's state.  0 < gamma < 1 is rejected
+ * on purpose: d/dx q^gamma is unbounded at q = 0, which a saturated logit reaches in fp32 (the reference's own autograd
+ * returns NaN there).  Inside the domain no finite logit produces NaN or Inf.  UNET_ERR_STATE without
+ * unet_train_attach. */
+int unet_train_set_loss_cfg(unet_handle_t h, const unet_loss_config* cfg);
+
 /* Forward in train mode (batch statistics, running stats updated with momentum 0.1), mean
  * BCE-with-logits against targets_dev (N,1,H,W float 0/1), full backward.  Writes every parameter
  * gradient into grads_dev (overwriting: this is zero_grad + backward), the scalar loss into
@@ -241,6 +265,22 @@ int unet_train_eval_f32(unet_handle_t h, const float* image_nchw_dev, int n, int
 int unet_seg_metrics_accumulate(int device, const float* logits_dev, const void* targets_dev, int targets_are_u8,
                                 size_t numel, float threshold_logit, int loss_mode, float bce_weight, float dice_weight,
                                 float pos_weight, float smooth, double* acc_dev, void* stream);
+/* The same with the loss as a structure, so a validation pass (README.md:2101-2110) can report the general loss:
+ * modes 0 and 1 are unet_seg_metrics_accumulate itself; with mode 2 slots [4..6] receive (total, bce, dice) of the
+ * general loss and slot [10] the sum over the batches of the batch's focal term (README.md:1914-1939).  Slots [0..3],
+ * [7..9] and [15] keep their meaning; [11..14] stay reserved.  The loss sums are formed by the code the training step
+ * runs: the values equal what the step reports for the same logits. */
+int unet_seg_metrics_accumulate_cfg(int device, const float* logits_dev, const void* targets_dev, int targets_are_u8,
+                                    size_t numel, float threshold_logit, const unet_loss_config* cfg, double* acc_dev,
+                                    void* stream);
+
+/* Positive pixels per mask, the statistic behind the reference's two remedies for class imbalance (README.md:2514-2530
+ * `calculate_pos_weight`: positive_pixels += (mask > 127).sum(); :2544-2553 `get_sample_weights`: the lane ratio of each
+ * image): masks_dev holds n images of pixels_per_image bytes back to back, counts_dev[i] = number of pixels of image i
+ * with mask > threshold (the reference binarises with > 127, README.md:2022, :2522).  One pass over the masks, integer
+ * arithmetic: exact and deterministic.  No host synchronisation. */
+int unet_mask_positive_counts(int device, const uint8_t* masks_dev, int n, size_t pixels_per_image, int threshold,
+                              unsigned long long* counts_dev, void* stream);
 
 const char* unet_last_error(unet_handle_t h);
 const char* unet_version(void);
@@ -436,6 +476,13 @@ int unet_set_x3_cross_fp8(int mode);
  * 200+j: its space-to-depth gradient; 300+u / 400+u / 500+u: dZ, z and the saved BatchNorm statistics
  * of conv unit u (encoder, bottleneck, decoder order); -1 disables. */
 int unet_train_debug_snapshot(unet_handle_t h, int stage, float* dst_dev, size_t max_floats);
+
+/* Test entry for the general loss (mode 2 only; parameters checked as by unet_train_set_loss_cfg): what `criterion(pred,
+ * masks)` and `total_loss.backward()` leave for the logits (README.md:1904-1906) - loss_terms_dev[0..3] = {total, bce,
+ * dice, focal}, dlogits_dev = dL/dlogits - through the launch sequence the training step runs.  Any numel > 0; 128-bit
+ * accesses where the three buffers are 16-byte aligned.  Two runs on the same inputs give the same bits. */
+int unet_op_loss_grad(int device, const float* logits_dev, const float* targets_dev, size_t numel,
+                      const unet_loss_config* cfg, float* loss_terms_dev, float* dlogits_dev, void* stream);
 
 /* dW of a 3x3 convolution (training backward): dz (N,H,W,Cout), x (N,H,W,Cin) -> dw_dev (Cout,Cin,3,3). */
 int unet_op_wgrad3x3(int device, const float* dz_dev, const float* x_dev, int n, int h, int w, int cin, int cout,

@@ -4,6 +4,9 @@ Public surface:
   UNetHIP                      forward(image) -> logits, run_u8(frames)
   RKNN_model_container         drop-in for the reference's model container
   SegMetrics                   loss / Dice / IoU / precision / recall of a validation pass (metrics.py)
+  LossSpec                     the general BCE + focal + Dice loss as UNetTrainer.set_loss keeps it (metrics.py)
+  positive_counts, pos_weight_from_masks, sample_weights
+                               mask statistics for sparse lanes (imbalance.py)
   seeded_state_dict, ...       reproducible weights / synthetic inputs
 """
 from .state import (DEFAULT_FEATURES, INPUT_MEAN, INPUT_STD, num_parameters, seeded_state_dict,  # noqa: F401
@@ -20,4 +23,10 @@ def __getattr__(name):  # lazy: importing the package must not need torch.cuda o
     if name == "SegMetrics":
         from .metrics import SegMetrics
         return SegMetrics
+    if name == "LossSpec":
+        from .metrics import LossSpec
+        return LossSpec
+    if name in ("positive_counts", "pos_weight_from_masks", "sample_weights"):
+        from . import imbalance
+        return getattr(imbalance, name)
     raise AttributeError(name)

@@ -26,6 +26,20 @@ class UnetConfig(C.Structure):
     ]
 
 
+class LossConfig(C.Structure):
+    """unet_loss_config of include/unet_hip.h"""
+    _fields_ = [
+        ("mode", C.c_int),
+        ("bce_weight", C.c_float),
+        ("focal_weight", C.c_float),
+        ("dice_weight", C.c_float),
+        ("pos_weight", C.c_float),
+        ("alpha", C.c_float),
+        ("gamma", C.c_float),
+        ("smooth", C.c_float),
+    ]
+
+
 STATUS = {0: "UNET_OK", 1: "UNET_ERR_INVALID_ARG", 2: "UNET_ERR_SHAPE", 3: "UNET_ERR_STATE", 4: "UNET_ERR_HIP",
           5: "UNET_ERR_NOMEM", 6: "UNET_ERR_UNKNOWN_PARAM", 7: "UNET_ERR_RANGE"}
 UNET_ERR_HIP = 4     # a HIP runtime call or a kernel-side check failed
@@ -115,6 +129,12 @@ SIGNATURES = {
     "unet_train_eval_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "unet_seg_metrics_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_int,
                                               C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "unet_train_set_loss_cfg": (C.c_int, [C.c_void_p, C.POINTER(LossConfig)]),
+    "unet_seg_metrics_accumulate_cfg": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_float,
+                                                  C.POINTER(LossConfig), C.c_void_p, C.c_void_p]),
+    "unet_op_loss_grad": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(LossConfig), C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "unet_mask_positive_counts": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "unet_device_error": (C.c_int, [C.c_void_p]),
     "unet_device_error_on": (C.c_int, [C.c_void_p, C.c_void_p]),
     "unet_device_status_to": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -63,6 +63,7 @@ struct TrainPlan {
 }  // namespace
 
 #include "validate_kernels.h"
+#include "loss_kernels.h"
 
 struct TrainState {
   float *params = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr, *bn = nullptr;
@@ -86,8 +87,9 @@ struct TrainState {
   int nPackX3 = 0;
   unsigned packX3Blocks = 0;
   int packedX3 = -1;                 // which table the last repack used (train_x3_enabled() at that time)
-  int lossMode = 0;          // 0: BCEWithLogits(mean); 1: bce_w * BCE(pos_weight) + dice_w * Dice
+  int lossMode = 0;          // 0: BCEWithLogits(mean); 1: bce_w * BCE(pos_weight) + dice_w * Dice; 2: + focal_w * Focal
   float bceW = 1.f, diceW = 0.f, posWeight = 1.f, diceSmooth = 1e-6f;
+  float focalW = 0.f, focalAlpha = 0.25f, focalGamma = 2.f;   // mode 2 only (loss_kernels.h)
   float* lossCoef = nullptr; // 2 floats (device) for the Dice gradient
   hipStream_t commStream = nullptr;   // data-parallel overlap: see unet_train_set_comm_stream
   hipEvent_t lateGradsReady = nullptr;
@@ -1134,7 +1136,14 @@ int train_forward_backward(unet_ctx* h, int n, int height, int width, const floa
     HIPCHK(h->err, hipMemcpyAsync(logitsOut, ws + p.logits, P0 * sizeof(float), hipMemcpyDeviceToDevice, s));
 
   // ------------------------------- loss (a12) -------------------------------
-  if (T->lossMode == 1) {
+  if (T->lossMode == 2) {
+    // the reduction scratch holds kRedBlocks * 2 * 4096 floats, far beyond loss_scratch_bytes of any batch
+    const unet::LossParams lp{T->bceW, T->focalW, T->diceW, T->posWeight, T->focalAlpha, T->focalGamma, T->diceSmooth};
+    prof_begin("focal_loss_grad", 0.0, 20.0 * P0, s);
+    const hipError_t e = unet::launch_loss_grad(ws + p.logits, targets, P0, lp, partial, lossDev, ws + p.dlogits, s);
+    prof_end(s);
+    HIPCHK(h->err, e);
+  } else if (T->lossMode == 1) {
     const int nb = red_blocks(P0);
     prof_begin("bce_dice_loss_grad", 0.0, 20.0 * P0, s);
     hipLaunchKernelGGL(unet::bce_dice_partial_kernel, dim3(nb), dim3(256), 0, s, ws + p.logits, targets, P0,
@@ -1822,6 +1831,32 @@ int unet_train_set_loss(unet_handle_t h, int mode, float bceWeight, float diceWe
   return UNET_OK;
 }
 
+namespace {
+unet::LossParams loss_params_of(const unet_loss_config& c) {
+  return unet::LossParams{c.bce_weight, c.focal_weight, c.dice_weight, c.pos_weight, c.alpha, c.gamma, c.smooth};
+}
+}  // namespace
+
+// The loss of the step from one structure: modes 0 and 1 are unet_train_set_loss; mode 2 is the general loss of
+// loss_kernels.h, its parameters checked before anything else (so the check needs no attached training state).
+int unet_train_set_loss_cfg(unet_handle_t h, const unet_loss_config* cfg) {
+  if (!h || !cfg) return UNET_ERR_INVALID_ARG;
+  if (cfg->mode == 0 || cfg->mode == 1)
+    return unet_train_set_loss(h, cfg->mode, cfg->bce_weight, cfg->dice_weight, cfg->pos_weight, cfg->smooth);
+  if (cfg->mode != 2 || !unet::loss_params_valid(loss_params_of(*cfg))) return UNET_ERR_INVALID_ARG;
+  if (!h->train) return UNET_ERR_STATE;
+  TrainState* T = h->train;
+  T->lossMode = 2;
+  T->bceW = cfg->bce_weight;
+  T->diceW = cfg->dice_weight;
+  T->posWeight = cfg->pos_weight;
+  T->diceSmooth = cfg->smooth;
+  T->focalW = cfg->focal_weight;
+  T->focalAlpha = cfg->alpha;
+  T->focalGamma = cfg->gamma;
+  return UNET_OK;
+}
+
 // Re-derive every packed MFMA operand from the attached parameter buffer (after the caller overwrote it, e.g. on
 // checkpoint load).  Keeps the TrainState: loss configuration and workspace survive, unlike a second attach.
 int unet_train_repack(unet_handle_t h, void* stream) {
@@ -1970,6 +2005,55 @@ int unet_seg_metrics_accumulate(int device, const float* logitsDev, const void* 
                                                   bceWeight, diceWeight, posWeight, smooth, partial, nb, accDev, s);
   HIPCHK(g_opErr, hipFreeAsync(partial, s));
   HIPCHK(g_opErr, e);
+  return UNET_OK;
+}
+
+// The same reduction with the loss given as a structure; mode 2 runs the general loss (loss_kernels.h) and adds the
+// batch's focal term to accumulator 10.
+int unet_seg_metrics_accumulate_cfg(int device, const float* logitsDev, const void* targetsDev, int targetsAreU8,
+                                    size_t numel, float thresholdLogit, const unet_loss_config* cfg, double* accDev,
+                                    void* stream) {
+  if (!cfg) return UNET_ERR_INVALID_ARG;
+  if (cfg->mode == 0 || cfg->mode == 1)
+    return unet_seg_metrics_accumulate(device, logitsDev, targetsDev, targetsAreU8, numel, thresholdLogit, cfg->mode,
+                                       cfg->bce_weight, cfg->dice_weight, cfg->pos_weight, cfg->smooth, accDev, stream);
+  const unet::LossParams lp = loss_params_of(*cfg);
+  if (!logitsDev || !targetsDev || !accDev || numel == 0 || cfg->mode != 2 || !unet::loss_params_valid(lp))
+    return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  void* scratch = nullptr;
+  HIPCHK(g_opErr, hipMallocAsync(&scratch, unet::seg_metrics_cfg_scratch_bytes(numel), s));
+  const hipError_t e = unet::launch_seg_metrics_cfg(logitsDev, targetsDev, targetsAreU8 != 0, numel, thresholdLogit, lp,
+                                                      scratch, accDev, s);
+  HIPCHK(g_opErr, hipFreeAsync(scratch, s));
+  HIPCHK(g_opErr, e);
+  return UNET_OK;
+}
+
+// Test entry: the general loss and its logit gradient through launch_loss_grad, the helper the training step calls.
+int unet_op_loss_grad(int device, const float* logitsDev, const float* targetsDev, size_t numel,
+                      const unet_loss_config* cfg, float* lossTermsDev, float* dlogitsDev, void* stream) {
+  if (!logitsDev || !targetsDev || !cfg || !lossTermsDev || !dlogitsDev || numel == 0 || cfg->mode != 2)
+    return UNET_ERR_INVALID_ARG;
+  const unet::LossParams lp = loss_params_of(*cfg);
+  if (!unet::loss_params_valid(lp)) return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  void* scratch = nullptr;
+  HIPCHK(g_opErr, hipMallocAsync(&scratch, unet::loss_scratch_bytes(numel), s));
+  const hipError_t e = unet::launch_loss_grad(logitsDev, targetsDev, numel, lp, scratch, lossTermsDev, dlogitsDev, s);
+  HIPCHK(g_opErr, hipFreeAsync(scratch, s));
+  HIPCHK(g_opErr, e);
+  return UNET_OK;
+}
+
+// Positive pixels per mask (reference README.md:2514-2530, :2544-2553): see include/unet_hip.h.
+int unet_mask_positive_counts(int device, const uint8_t* masksDev, int n, size_t pixelsPerImage, int threshold,
+                              unsigned long long* countsDev, void* stream) {
+  if (!masksDev || !countsDev || n <= 0 || pixelsPerImage == 0) return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  HIPCHK(g_opErr, unet::launch_mask_positive_counts(masksDev, n, pixelsPerImage, threshold, countsDev, (hipStream_t)stream));
   return UNET_OK;
 }
 

@@ -17,6 +17,26 @@ import numpy as np
 
 NUM_ACCUMULATORS = 16
 TP, FP, FN, TN, LOSS, BCE, DICE_LOSS, DICE, BATCHES, PIXELS = range(10)
+FOCAL = 10      # sum of the per-batch focal terms (unet_seg_metrics_accumulate_cfg, mode 2); 0 under the other modes
+
+
+class LossSpec:
+    """The general loss bce_weight * BCE(pos_weight) + focal_weight * Focal(alpha, gamma) + dice_weight * Dice(smooth)
+    (mode 2 of include/unet_hip.h) as UNetTrainer.set_loss keeps it for the validation pass."""
+    __slots__ = ("kind", "bce_weight", "focal_weight", "dice_weight", "pos_weight", "alpha", "gamma", "smooth")
+
+    def __init__(self, kind, bce_weight, focal_weight, dice_weight, pos_weight, alpha, gamma, smooth):
+        self.kind = kind
+        self.bce_weight, self.focal_weight, self.dice_weight = float(bce_weight), float(focal_weight), float(dice_weight)
+        self.pos_weight, self.alpha, self.gamma, self.smooth = float(pos_weight), float(alpha), float(gamma), float(smooth)
+
+    def to_c(self):
+        from . import _lib
+        return _lib.LossConfig(2, self.bce_weight, self.focal_weight, self.dice_weight, self.pos_weight, self.alpha,
+                               self.gamma, self.smooth)
+
+    def __repr__(self):
+        return "LossSpec(%s)" % ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__)
 
 
 def _ratio(num, den):
@@ -50,6 +70,11 @@ class SegMetrics:
         return self._mean(DICE_LOSS)
 
     @property
+    def focal(self):
+        """Mean of the per-batch focal term (reference README.md:1914-1939); 0.0 for the losses that have none."""
+        return self._mean(FOCAL)
+
+    @property
     def dice(self):
         """Mean of the per-batch compute_dice: the reference's avg_dice."""
         return self._mean(DICE)
@@ -76,7 +101,8 @@ class SegMetrics:
         return _ratio(self.tp + self.tn, self.tp + self.fp + self.fn + self.tn)
 
     def as_dict(self):
-        return {"loss": self.loss, "bce": self.bce, "dice_loss": self.dice_loss, "dice": self.dice, "iou": self.iou,
+        return {"loss": self.loss, "bce": self.bce, "dice_loss": self.dice_loss, "focal": self.focal, "dice": self.dice,
+                "iou": self.iou,
                 "precision": self.precision, "recall": self.recall, "f1": self.f1,
                 "pixel_accuracy": self.pixel_accuracy, "tp": self.tp, "fp": self.fp, "fn": self.fn, "tn": self.tn,
                 "batches": self.batches, "pixels": self.pixels}
@@ -89,8 +115,9 @@ class SegMetrics:
 
 def accumulate(lib, device_index, logits, targets, acc, stream, threshold=0.5, loss_cfg=None):
     """Add one batch to the device accumulators `acc` (16 float64 on the logits' device).  logits: float32 device
-    tensor; targets: float (0/1) or uint8 (0 / non-zero) tensor of the same number of elements.  loss_cfg: the tuple
-    UNetTrainer.set_loss keeps, or None for plain BCE-with-logits."""
+    tensor; targets: float (0/1) or uint8 (0 / non-zero) tensor of the same number of elements.  loss_cfg: what
+    UNetTrainer.set_loss keeps - the 5-tuple of 'bce' / 'bce_dice' or the LossSpec of the general loss - or None for
+    plain BCE-with-logits."""
     import ctypes as C
 
     import torch
@@ -103,6 +130,13 @@ def accumulate(lib, device_index, logits, targets, acc, stream, threshold=0.5, l
         targets, u8 = targets.to(logits.device, torch.float32).contiguous(), 0
     if logits.numel() != targets.numel():
         raise ValueError("logits and targets differ in size")
+    if isinstance(loss_cfg, LossSpec):
+        cfg = loss_cfg.to_c()
+        rc = lib.unet_seg_metrics_accumulate_cfg(int(device_index), C.c_void_p(logits.data_ptr()),
+                                                 C.c_void_p(targets.data_ptr()), u8, logits.numel(), _logit(threshold),
+                                                 C.byref(cfg), C.c_void_p(acc.data_ptr()), stream)
+        _lib.check(rc, "unet_seg_metrics_accumulate_cfg")
+        return
     kind, bce_w, dice_w, pos_w, smooth = loss_cfg if loss_cfg else ("bce", 1.0, 0.0, 1.0, 1e-6)
     if kind == "bce":
         mode, bce_w, dice_w, pos_w = 0, 1.0, 0.0, 1.0

@@ -74,7 +74,7 @@ class UNetTrainer:
         self.grads = self._bucket[self.STATUS_PAD:]
         self.exp_avg = torch.zeros_like(self.params)
         self.exp_avg_sq = torch.zeros_like(self.params)
-        self.loss_terms = torch.zeros(4, dtype=torch.float32, device=self.device)   # total, bce, dice, -
+        self.loss_terms = torch.zeros(4, dtype=torch.float32, device=self.device)   # total, bce, dice, focal
         self.loss = self.loss_terms[:1]
         self.num_batches_tracked = 0
         self._loss_cfg = None
@@ -89,17 +89,41 @@ class UNetTrainer:
     def _p(t):
         return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
-    def set_loss(self, kind="bce", bce_weight=0.5, dice_weight=0.5, pos_weight=3.0, smooth=1e-6):
-        """'bce': BCEWithLogitsLoss (reference README.md:1694-1709, BASELINE.json config);
+    def set_loss(self, kind="bce", bce_weight=0.5, dice_weight=0.5, pos_weight=3.0, smooth=1e-6, focal_weight=None,
+                 alpha=0.25, gamma=2.0):
+        """The reference's `criterion = ...` line (INTEGRATION.md has the mapping).
+        'bce': BCEWithLogitsLoss (reference README.md:1694-1709, BASELINE.json config);
         'bce_dice': the training script's BCEDiceLoss(0.5, 0.5, pos_weight=3) (README.md:1855-1893, :2169-2170);
-        self.loss_terms then holds (total, bce, dice)."""
+        'focal': focal_weight (default 1) * FocalLoss(alpha, gamma) (README.md:1914-1939);
+        'dice': dice_weight (as given; DiceLoss itself is dice_weight=1) * DiceLoss(smooth) (README.md:1781-1807);
+        'focal_dice': focal_weight (default 0.5) * FocalLoss + dice_weight * DiceLoss - the table's choice for masks
+        under 5 % lane (README.md:1949);
+        'combo': bce_weight * BCE(pos_weight) + focal_weight * Focal + dice_weight * Dice, all three weights given.
+        self.loss_terms then holds (total, bce, dice, focal); every term is reported whatever its weight."""
         if kind == "bce":
             rc = self._lib.unet_train_set_loss(self._h, 0, 1.0, 0.0, 1.0, smooth)
         elif kind == "bce_dice":
             rc = self._lib.unet_train_set_loss(self._h, 1, bce_weight, dice_weight, pos_weight, smooth)
+        elif kind in ("focal", "dice", "focal_dice", "combo"):
+            if kind == "combo":
+                if focal_weight is None:
+                    raise ValueError("'combo' takes bce_weight, focal_weight and dice_weight explicitly")
+                wb, wf, wd = bce_weight, focal_weight, dice_weight
+            elif kind == "focal":
+                wb, wf, wd = 0.0, 1.0 if focal_weight is None else focal_weight, 0.0
+            elif kind == "dice":
+                wb, wf, wd = 0.0, 0.0, dice_weight
+            else:
+                wb, wf, wd = 0.0, 0.5 if focal_weight is None else focal_weight, dice_weight
+            spec = metrics.LossSpec(kind, wb, wf, wd, pos_weight, alpha, gamma, smooth)
+            cfg = spec.to_c()
+            _lib.check(self._lib.unet_train_set_loss_cfg(self._h, C.byref(cfg)), "unet_train_set_loss_cfg", self._h)
+            self._loss_cfg = spec
+            return
         else:
             raise ValueError(kind)
         _lib.check(rc, "unet_train_set_loss", self._h)
+        self.loss_terms[3:].zero_()     # these two losses have no focal term and never write the slot
         self._loss_cfg = (kind, bce_weight, dice_weight, pos_weight, smooth)
 
     def dice_metric(self, logits, targets, threshold=0.5, smooth=1e-6):
