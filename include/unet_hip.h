@@ -545,6 +545,26 @@ int unet_ipm_prestage_u8(int device, const uint8_t* img_dev, int height, int wid
 int unet_resize_u8(int device, const uint8_t* src_dev, int height, int width, int channels, int out_w, int out_h,
                    uint8_t* dst_dev, void* stream);
 
+/* ---- training-time augmentation on the GPU ---------------------------------------------------------------------
+ * The reference's train_transform (README.md:2035-2055, `get_transforms`): HorizontalFlip, Rotate,
+ * RandomBrightnessContrast, HueSaturationValue and GaussianBlur of a batch gathered from a device-resident data set,
+ * and the masks' targets (`mask > 127`, README.md:2022), in one launch.  The arithmetic is stated in
+ * unet_lane_detection_amd/augment.py and reproduced bit for bit; parity against albumentations / cv2 themselves is
+ * unpinned (neither is installed and the reference has no fixture for this stage).
+ *
+ * images_dev: (n_source, height, width, 3) uint8; masks_dev: (n_source, height, width) uint8, or NULL together with
+ * targets_out_dev for images only.  params_dev: n_out records on the device, one per output sample, laid out as
+ * augment.PARAMS_DTYPE (csrc/augment_kernels.h): source index, inverse affine, enable bits, colour parameters, blur
+ * size.  images_out_dev: (n_out, height, width, 3) uint8; targets_out_dev: (n_out, 1, height, width) float 0/1.
+ * The source index is clamped into [0, n_source) and every coordinate is folded into the frame, so no table reads
+ * outside the data set; the Python layer rejects such tables before the launch.  height and width at least 8.
+ * No host synchronisation. */
+int unet_augment_u8(int device, const uint8_t* images_dev, const uint8_t* masks_dev, int n_source, int height, int width,
+                    const void* params_dev, int n_out, int mask_threshold, uint8_t* images_out_dev,
+                    float* targets_out_dev, void* stream);
+/* sizeof one record, so a binding can check its layout against the library */
+size_t unet_augment_param_bytes(void);
+
 #ifdef __cplusplus
 }
 #endif

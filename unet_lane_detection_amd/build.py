@@ -27,8 +27,8 @@ CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(CSRC, "libunet_hip.so")
 HASHFILE = LIB + ".srchash"
-# the second and third: kernels of the validation pass and of the general loss, code objects of their own
-SOURCES = ["unet_hip.cpp", "validate_kernels.cpp", "loss_kernels.cpp"]
+# the others: kernels of the validation pass, of the general loss and of the augmentation stage, code objects of their own
+SOURCES = ["unet_hip.cpp", "validate_kernels.cpp", "loss_kernels.cpp", "augment_kernels.cpp"]
 FLAGS = ["-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result",
          "-Wno-unused-value"]
 
