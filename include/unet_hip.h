@@ -386,6 +386,53 @@ int unet_op_conv3x3_x3_head(int device, const float* x_dev, int n, int h, int w,
 int unet_op_upconv2x2_x3(int device, const float* x_dev, int n, int h, int w, int cin, const float* w_host,
                          const float* bias_host, int cout, float* y_dev, void* stream);
 
+/* The split-operand tier's operators on planes (test entry points, tests/test_x3_ops_gpu.py; the network runs the same
+ * packing, dispatch and kernels).  An activation tensor is a caller-owned pair of fp16 NHWC planes (uint16 bit patterns):
+ * the hi plane at the pointer, the lo plane `*_lo_off` elements behind it (a multiple of 8); the tensor stands for
+ * hi + lo.  Weights, scale / shift, bias, head weights and activation scales are fp32 HOST arrays, packed and folded by the
+ * functions the network's build uses.  ldo: pixel stride of y in elements (0 = cout), co_off: the first channel written
+ * (multiples of 64, co_off + cout <= ldo); nothing outside those channels is touched.  range_out (optional int) receives
+ * 1 if a kernel of the call reported a value outside the fp16 range (word 1 of an error block of the call's own), else 0.
+ *
+ * 3x3 convolution through the network's dispatch: x (N,H,W,cin) -> y channels [co_off, co_off + cout) of (N,H,W,ldo) =
+ * out_act * relu?(conv3x3(x / in_act, w) * scale + shift).  tile_width as unet_op_conv3x3_x3 (not 428 / 414).  in_act
+ * (cin) / out_act (cout): optional per-channel power-of-two activation scales.  split_k != 0: the call gets the split-K
+ * scratch the forward hands over, so small maps run as partial sums + the finish kernel.  pool (optional): the 2x2
+ * max-pool (N,H/2,W/2,cout), dense.  head_w_host (optional, cout == 64; y may then be NULL): the fused 1x1 head,
+ * logits / probs (N,H,W) fp32 and mask uint8 = 255 where logit > head_thr, each optional.
+ * path_out (optional int[8]): {structure (1 conv_x3_ws.h, 2 conv_x3_r512.h, 3 conv_x3_t448.h), pixel-tile width, epilogue
+ * (0 planes, 1 planes + fused pool, 2 fused head), batch tiled as one tall image, kSplit (1 = no split-K), waves along the
+ * pixels (structure 2) or channels (structure 3), pooled copy written by the separate pooling pass, 0}. */
+int unet_op_conv3x3_x3_planes(int device, const uint16_t* x_dev, size_t x_lo_off, int n, int h, int w, int cin,
+                              const float* w_host, const float* scale_host, const float* shift_host, int cout, int relu,
+                              int tile_width, const float* in_act_host, const float* out_act_host, int split_k,
+                              uint16_t* y_dev, size_t y_lo_off, int ldo, int co_off, uint16_t* pool_dev, size_t pool_lo_off,
+                              const float* head_w_host, float head_bias, float head_thr, float* logits_dev,
+                              float* probs_dev, uint8_t* mask_dev, int* path_out, int* range_out, void* stream);
+/* ConvTranspose2d k=2 s=2 with bias: x (N,H,W,cin) -> y channels [co_off, co_off + cout) of (N,2H,2W,ldo); w_host
+ * (cin,cout,2,2).  path_out (optional int[8]): {structure (1 upconv_x3_ws.h, 2 upconv_x3_r512.h, see
+ * unet_set_x3_upconv_r512), 0, 0, 0, 1, work items per (a,b) split of structure 1, 0, 0}. */
+int unet_op_upconv2x2_x3_planes(int device, const uint16_t* x_dev, size_t x_lo_off, int n, int h, int w, int cin,
+                                const float* w_host, const float* bias_host, int cout, const float* in_act_host,
+                                uint16_t* y_dev, size_t y_lo_off, int ldo, int co_off, int* path_out, int* range_out,
+                                void* stream);
+/* The first convolution: is_u8 != 0: uint8 (N,H,W,3) frames, normalised with mean_host / std_host (3 floats each);
+ * else fp32 (N,3,H,W), already normalised -> y channels [0, cout) of (N,H,W,ldo); w_host (cout,3,3,3). */
+int unet_op_conv_first_x3_planes(int device, const void* input_dev, int is_u8, int n, int h, int w, const float* w_host,
+                                 const float* scale_host, const float* shift_host, int cout, int relu,
+                                 const float* mean_host, const float* std_host, const float* out_act_host, uint16_t* y_dev,
+                                 size_t y_lo_off, int ldo, int* range_out, void* stream);
+/* MaxPool2d(2,2) on planes: channels [0, c) of x (N,H,W,ldi) -> dense y (N,H/2,W/2,c); c, ldi even (ldi 0 = c). */
+int unet_op_maxpool2x2_x3_planes(int device, const uint16_t* x_dev, size_t x_lo_off, int n, int h, int w, int c, int ldi,
+                                 uint16_t* y_dev, size_t y_lo_off, void* stream);
+/* The unfused 1x1 head on dense planes (N,H,W,c): logits / probs / mask as unet_op_conv3x3_x3_planes. */
+int unet_op_head1x1_x3_planes(int device, const uint16_t* x_dev, size_t x_lo_off, int n, int h, int w, int c,
+                              const float* w_host, float bias, float thr, float* logits_dev, float* probs_dev,
+                              uint8_t* mask_dev, void* stream);
+/* fp32 -> planes: `count` (even) values, clamped to +-65504, hi = rn(v), lo = rn(v - hi). */
+int unet_op_split_planes_x3(int device, const float* x_dev, size_t count, uint16_t* y_dev, size_t y_lo_off, int* range_out,
+                            void* stream);
+
 /* The bf16 tier's operators, one at a time (test entry points; the network runs the same packing, dispatch and kernels).
  * Activations are dense bf16 NHWC device tensors (uint16 bit patterns); weights, scale / shift, bias and head weights are
  * fp32 HOST arrays in PyTorch layout, packed internally by the functions the network's build uses.  cin, cout: multiples

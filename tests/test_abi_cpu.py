@@ -80,3 +80,24 @@ def test_act_scale_of_nearly_dead_bn_channel(lib):
     s = lib.unet_debug_act_scale(1e-20, 0.0)                            # tiny but alive: clamped to 2^40
     assert s == 2.0 ** 40
     assert lib.unet_debug_act_scale(1e30, 0.0) == 2.0 ** -40
+
+
+def test_x3_plane_entry_points_check_arguments_first(lib):
+    """the plane-level f16x3 entry points (tests/test_x3_ops_gpu.py) reject what they cannot run before touching a device"""
+    buf = (C.c_uint16 * 64)()
+    f = (C.c_float * 64)()
+    p, q = C.cast(buf, C.c_void_p), C.cast(f, C.c_void_p)
+
+    def conv(cin=64, cout=64, tw=0, ldo=0, co_off=0, x_lo=64, pool=None, head=None, y=p, h=8, w=8):
+        return lib.unet_op_conv3x3_x3_planes(0, p, x_lo, 1, h, w, cin, q, q, q, cout, 1, tw, None, None, 0, y, 64, ldo, co_off,
+                                             pool, 0, head, 0.0, 0.0, q if head else None, None, None, None, None, None)
+    assert conv(cin=32) == 1 and conv(cout=96) == 1 and conv(cout=2048) == 1
+    assert conv(tw=428) == 1 and conv(tw=414) == 1 and conv(tw=24) == 1          # the f16q8 widths are not this entry's
+    assert conv(ldo=64, co_off=64) == 1 and conv(ldo=96) == 1 and conv(ldo=128, co_off=32) == 1
+    assert conv(x_lo=63) == 1 and conv(y=None) == 1
+    assert conv(pool=p, h=7) == 1 and conv(pool=p, head=q) == 1 and conv(cout=128, head=q, y=None) == 1
+    assert lib.unet_op_upconv2x2_x3_planes(0, p, 64, 1, 4, 4, 64, q, q, 64, None, p, 64, 128, 128, None, None, None) == 1
+    assert lib.unet_op_conv_first_x3_planes(0, p, 1, 1, 8, 8, q, q, q, 64, 1, None, None, None, p, 64, 0, None, None) == 1
+    assert lib.unet_op_maxpool2x2_x3_planes(0, p, 64, 1, 3, 4, 8, 0, p, 64, None) == 1
+    assert lib.unet_op_head1x1_x3_planes(0, p, 64, 1, 2, 2, 8, q, 0.0, 0.0, None, None, None, None) == 1
+    assert lib.unet_op_split_planes_x3(0, q, 3, p, 64, None, None) == 1

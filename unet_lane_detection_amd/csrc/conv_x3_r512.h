@@ -71,13 +71,16 @@ __device__ __forceinline__ void mfma_x3_acc(f32x4& c, const f32x4& a, const f32x
   asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
 }
 
-// split_pk_f16 without the clamp (out-of-range values become inf; the caller watches the range), in 4 instructions per
-// pair: hi = v_cvt_pk_f16_f32, lo = rn16(v - hi) as one mixed-precision FMA per value that reads hi as fp16 and writes
-// its fp16 result into one half of the destination (v - hi is exact in fp32, so the single rounding is the same as in
-// split_pk_f16: the two kernel structures stay bit-identical, tests/test_x3_gpu.py)
+// split_pk_f16 (values clamped to the fp16 range, as conv_x3_ws.h promises: an out-of-range value is stored as +-65504 and
+// reported through amax, never as inf) in 6 instructions per pair: two v_med3_f32, hi = v_cvt_pk_f16_f32, lo = rn16(v - hi)
+// as one mixed-precision FMA per value that reads hi as fp16 and writes its fp16 result into one half of the destination
+// (v - hi is exact in fp32, so the single rounding is the same as in split_pk_f16: the two kernel structures stay
+// bit-identical, tests/test_x3_gpu.py).  Callers take amax from the unclamped values first.
 __device__ __forceinline__ void split_pk_f16_mix(float v0, float v1, uint32_t& hi, uint32_t& lo) {
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+  v0 = __builtin_amdgcn_fmed3f(v0, -65504.f, 65504.f);
+  v1 = __builtin_amdgcn_fmed3f(v1, -65504.f, 65504.f);
   hi = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v0, v1}, f16x2));
   asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\t"
       "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
@@ -479,7 +482,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       } else {
         uint32_t ph[8], pl[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {   // not clamped: out-of-range values become inf and are reported (amax)
+        for (int e = 0; e < 8; ++e) {   // amax before the clamp in split_pk_f16_mix: out-of-range values are stored as +-65504 and reported
           amax3(amax, v[2 * e], v[2 * e + 1]);
           split_pk_f16_mix(v[2 * e], v[2 * e + 1], ph[e], pl[e]);
         }

@@ -327,7 +327,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       } else {
         uint32_t ph[8], pl[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {   // not clamped: out-of-range values become inf and are reported (amax)
+        for (int e = 0; e < 8; ++e) {   // amax before the clamp in split_pk_f16_mix: out-of-range values are stored as +-65504 and reported
           amax3(amax, v[2 * e], v[2 * e + 1]);
           split_pk_f16_mix(v[2 * e], v[2 * e + 1], ph[e], pl[e]);
         }

@@ -337,6 +337,20 @@ struct X3SplitK {
   const float* zerosF = nullptr;
 };
 
+// What run_conv_x3 / run_upconv_x3 launched (the plane-level test entry points report it; nothing reads it otherwise)
+struct X3Path {
+  int structure = 0;   // 1 = conv_x3_ws.h / upconv_x3_ws.h, 2 = conv_x3_r512.h / upconv_x3_r512.h, 3 = conv_x3_t448.h, 4 = conv_q8_r512.h
+  int tileW = 0;       // pixel-tile width
+  int epi = 0;         // the kernel's epilogue: 0 planes, 1 planes + fused 2x2 max-pool, 2 fused head, 3 fp32
+  int flat = 0;        // the batch tiled as one tall image
+  int kSplit = 1;      // > 1: split-K partial sums + x3_splitk_finish_kernel
+  int waves = 0;       // r512: waves along the pixels (1 / 2); t448: waves along the channels (1 / 2 / 4); upconv ws: abSplit
+  int poolPass = 0;    // the pooled copy came from maxpool2x2_planes_kernel, not from the epilogue
+  void set(int st, int tw, int e, bool fl, int ks, int wv, bool pp) {
+    structure = st, tileW = tw, epi = e, flat = fl ? 1 : 0, kSplit = ks, waves = wv, poolPass = pp ? 1 : 0;
+  }
+};
+
 template <int TW, int EPI, bool FLAT = false>
 hipError_t launch_conv_x3(const unet::ConvX3Args& a, int grid, hipStream_t s) {
   using S = unet::X3Shape<TW>;
@@ -476,7 +490,8 @@ hipError_t run_conv_x3(const GemmOpX3& op, const uint16_t* zeros, const uint16_t
                        uint16_t* out, size_t outLo, int ldo, int coOff, hipStream_t s, const X3Fuse* fuse = nullptr,
                        int forceTw = 0, float* outF = nullptr, const char* label = nullptr,
                        const float* dynScale = nullptr, const X3SplitK* splitK = nullptr, float* statPartial = nullptr,
-                       int* statRows = nullptr, uint8_t* qScratch = nullptr, X3Q8Link* q8Link = nullptr) {
+                       int* statRows = nullptr, uint8_t* qScratch = nullptr, X3Q8Link* q8Link = nullptr,
+                       X3Path* path = nullptr) {
   // qScratch (f16q8 tier): room for the input's q plane (n * h * w * cin * 2 bytes); with it, op.wq and the tier switched
   // on, a layer the second structure would run as 224 x 256 tiles runs on conv_q8_r512.h instead (forceTw 428 / 414
   // force it)
@@ -626,6 +641,7 @@ hipError_t run_conv_x3(const GemmOpX3& op, const uint16_t* zeros, const uint16_t
           e = launch_conv_t448<32, 1>(b, grid, epi, false, s);
         prof_end(s);
         if (e != hipSuccess) return e;
+        if (path) path->set(3, twt, epi, flatT, 1, wco, false);
         return hipGetLastError();
       }
     }
@@ -741,6 +757,7 @@ hipError_t run_conv_x3(const GemmOpX3& op, const uint16_t* zeros, const uint16_t
           prof_end(s);
         }
       }
+      if (path) path->set(4, tq, outQ ? 4 : 0, flatQ, 1, 1, epi == 1);
       return hipGetLastError();
     }
     if (q8Forced) return hipErrorInvalidValue;
@@ -814,6 +831,7 @@ hipError_t run_conv_x3(const GemmOpX3& op, const uint16_t* zeros, const uint16_t
                            reinterpret_cast<uint32_t*>(fuse->pool), fuse->poolLo / 2);
         prof_end(s);
       }
+      if (path) path->set(2, twx, outF ? 3 : 0, flatR, 1, wpx, epi == 1);
       return hipGetLastError();
     }
     if (forced) return hipErrorInvalidValue;
@@ -854,11 +872,12 @@ hipError_t run_conv_x3(const GemmOpX3& op, const uint16_t* zeros, const uint16_t
     hipLaunchKernelGGL(unet::x3_splitk_finish_kernel, dim3(grid_for(P * (op.cout / 4))), dim3(256), 0, s,
                        (const float*)splitK->scratch, kSplit, P, op.cout, (const float*)op.scale, (const float*)op.shift,
                        op.relu, reinterpret_cast<uint32_t*>(out), outLo / 2, ldo, coOff, a.err);
-    if (epi == 1)   // the pooled copy the fused epilogue would have written
+    if (epi == 1)   // the pooled copy the fused epilogue would have written (of the channels at coOff, as above)
       hipLaunchKernelGGL(unet::maxpool2x2_planes_kernel, dim3(grid_for(P / 4 * (op.cout / 2))), dim3(256), 0, s,
-                         reinterpret_cast<const uint32_t*>(out), outLo / 2, n, h, w, op.cout, ldo,
+                         reinterpret_cast<const uint32_t*>(out + coOff), outLo / 2, n, h, w, op.cout, ldo,
                          reinterpret_cast<uint32_t*>(fuse->pool), fuse->poolLo / 2);
     prof_end(s);
+    if (path) path->set(1, tw, 0, flat, kSplit, 0, epi == 1);
     return hipGetLastError();
   }
   const long work = (long)a.pixTiles * a.coTiles;
@@ -896,6 +915,7 @@ hipError_t run_conv_x3(const GemmOpX3& op, const uint16_t* zeros, const uint16_t
         : epi == 2 ? launch_conv_x3<16, 2>(a, grid, s)
                    : launch_conv_x3<16, 3>(a, grid, s);
   prof_end(s);
+  if (path) path->set(1, tw, epi, flat, 1, 0, false);
   return e;
 }
 
@@ -944,7 +964,8 @@ bool launch_upconv_r512(unet::UpconvX3Args a, const char* label, double flops, d
 // q8Link (f16q8 tier): wantOutQ - write the output's q plane in its lo plane's place (only asked for where
 // x3_upconv_r512_auto holds; an error otherwise, because the consumer has been told)
 hipError_t run_upconv_x3(const GemmOpX3& op, const uint16_t* zeros, const uint16_t* in, size_t inLo, int n, int h, int w,
-                         uint16_t* out, size_t outLo, int ldo, int coOff, hipStream_t s, X3Q8Link* q8Link = nullptr) {
+                         uint16_t* out, size_t outLo, int ldo, int coOff, hipStream_t s, X3Q8Link* q8Link = nullptr,
+                         X3Path* path = nullptr) {
   using S = unet::UpconvX3Shape;
   unet::UpconvX3Args a;
   a.in = in;
@@ -981,9 +1002,12 @@ hipError_t run_upconv_x3(const GemmOpX3& op, const uint16_t* zeros, const uint16
       return hipErrorInvalidValue;
     }
     if (launch_upconv_r512<0>(a, "upconv2x2_r512_f16x3", 2.0 * pxr * op.cin * 4.0 * op.cout,
-                              4.0 * (pxr * op.cin + 4.0 * pxr * op.cout), s, &er))
+                              4.0 * (pxr * op.cin + 4.0 * pxr * op.cout), s, &er)) {
+      if (path) path->set(2, 0, 0, false, 1, 1, false);
       return er;
+    }
   }
+  if (path) path->set(1, 0, 0, false, 1, a.abSplit, false);
   auto kern = unet::upconv2x2_x3_ws_kernel<0>;
   hipError_t e = ensure_dyn_lds((const void*)kern, S::LDS_BYTES);
   if (e != hipSuccess) return e;
@@ -1639,6 +1663,47 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
   return h->async_error();
 }
 
+// The plane-level test entry points (unet_op_*_x3_planes) watch the range with a word of their own: for the scope's
+// lifetime the calling thread's launches report into it instead of the per-device word of the other entry points
+struct OpRangeScope {
+  unsigned* dev = nullptr;
+  unsigned* prev = nullptr;
+  bool armed = false;
+  hipError_t arm() {
+    hipError_t e = hipMalloc((void**)&dev, 2 * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemset(dev, 0, 2 * sizeof(unsigned));
+    if (e != hipSuccess) return e;
+    prev = g_errWord;
+    g_errWord = dev;
+    armed = true;
+    return hipSuccess;
+  }
+  // after the stream has been synchronised: did a kernel of the call set word 1?
+  hipError_t read(int* rangeOut) {
+    unsigned host[2] = {0, 0};
+    const hipError_t e = hipMemcpy(host, dev, sizeof(host), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rangeOut) *rangeOut = host[1] != 0 ? 1 : 0;
+    return e;
+  }
+  ~OpRangeScope() {
+    if (armed) g_errWord = prev;
+    if (dev) hipFree(dev);
+  }
+};
+
+ActScale act_from_host(const float* act, int c) {
+  ActScale a;
+  a.act.assign(act, act + c);
+  a.mag.assign(c, 0.f);
+  return a;
+}
+
+void path_to_ints(const X3Path& p, int* out) {
+  if (!out) return;
+  const int v[8] = {p.structure, p.tileW, p.epi, p.flat, p.kSplit, p.waves, p.poolPass, 0};
+  std::copy(v, v + 8, out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1877,6 +1942,227 @@ int unet_op_upconv2x2_x3(int device, const float* x, int n, int hh, int ww, int 
   for (uint16_t* q : {zeros, pin, pout})
     if (q) hipFree(q);
   return rc;
+}
+
+// ---- plane-level test entry points: caller-owned fp16 hi / lo planes in and out, the network's own packing, dispatch
+//      and kernels (include/unet_hip.h, "The split-operand tier's operators on planes") ----
+
+int unet_op_conv3x3_x3_planes(int device, const uint16_t* x, size_t xLo, int n, int hh, int ww, int cin, const float* wHost,
+                              const float* scale, const float* shift, int cout, int relu, int tileWidth, const float* inAct,
+                              const float* outAct, int splitK, uint16_t* y, size_t yLo, int ldo, int coOff, uint16_t* pool,
+                              size_t poolLo, const float* headW, float headB, float headThr, float* logits, float* probs,
+                              uint8_t* mask, int* pathOut, int* rangeOut, void* stream) {
+  static const int kWidths[] = {0, 16, 32, 28, 14, 228, 214, 332, 316, 308, 532, 628, 632, 728};
+  if (ldo == 0) ldo = cout;
+  if (!x || !wHost || !scale || !shift || n < 1 || hh < 1 || ww < 1 || cin < 64 || cin % 64 || cout < 64 || cout % 64 ||
+      cout > unet::X3Shape<32>::MAX_COUT || std::find(std::begin(kWidths), std::end(kWidths), tileWidth) == std::end(kWidths) ||
+      xLo % 8 || yLo % 8 || poolLo % 8 || ldo % 64 || coOff < 0 || coOff % 64 || coOff + cout > ldo ||
+      (pool && (headW || hh % 2 || ww % 2)) || (headW ? (cout != 64 || !(logits || probs || mask)) : !y))
+    return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  GemmOpX3 op;
+  ActScale ia, oa;
+  if (inAct) ia = act_from_host(inAct, cin);
+  if (outAct) oa = act_from_host(outAct, cout);
+  int rc = build_conv_x3(g_opErr, op, wHost, cout, cin, scale, shift, relu, false, inAct ? &ia : nullptr,
+                         outAct ? &oa : nullptr, false);
+  uint16_t* zeros = nullptr;
+  float *ones = nullptr, *scratch = nullptr, *hwDev = nullptr;
+  OpRangeScope range;
+  X3Path path;
+  if (!rc) {
+    hipError_t e = hipMalloc((void**)&zeros, 4096);
+    if (e == hipSuccess) e = hipMemset(zeros, 0, 4096);
+    if (e == hipSuccess && splitK) {   // as x3_build / forward_x3 set the X3SplitK up
+      const std::vector<float> one(1024, 1.f);
+      e = hipMalloc((void**)&ones, 4096);
+      if (e == hipSuccess) e = hipMemcpy(ones, one.data(), 4096, hipMemcpyHostToDevice);
+      if (e == hipSuccess) e = hipMalloc((void**)&scratch, kSplitFloats * sizeof(float));
+    }
+    if (e == hipSuccess && headW) {
+      e = hipMalloc((void**)&hwDev, 64 * sizeof(float));
+      if (e == hipSuccess) e = hipMemcpy(hwDev, headW, 64 * sizeof(float), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = range.arm();
+    if (e == hipSuccess) {
+      X3Fuse fz;
+      if (pool) {
+        fz.pool = pool;
+        fz.poolLo = poolLo;
+      } else if (headW) {
+        fz.headW = hwDev;
+        fz.headB = headB;
+        fz.headThr = headThr;
+        fz.logits = logits;
+        fz.probs = probs;
+        fz.mask = mask;
+      }
+      X3SplitK sk;
+      sk.scratch = scratch;
+      sk.floats = kSplitFloats;
+      sk.ones = ones;
+      sk.zerosF = reinterpret_cast<const float*>(zeros);
+      e = run_conv_x3(op, zeros, x, xLo, n, hh, ww, y, yLo, ldo, coOff, s, (pool || headW) ? &fz : nullptr, tileWidth, nullptr,
+                      nullptr, nullptr, splitK ? &sk : nullptr, nullptr, nullptr, nullptr, nullptr, &path);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = range.read(rangeOut);
+    if (e != hipSuccess) {
+      g_opErr = hipGetErrorString(e);
+      rc = UNET_ERR_HIP;
+    }
+  }
+  path_to_ints(path, pathOut);
+  op.free_dev();
+  for (void* q : {(void*)zeros, (void*)ones, (void*)scratch, (void*)hwDev})
+    if (q) hipFree(q);
+  return rc;
+}
+
+int unet_op_upconv2x2_x3_planes(int device, const uint16_t* x, size_t xLo, int n, int hh, int ww, int cin, const float* wHost,
+                                const float* bias, int cout, const float* inAct, uint16_t* y, size_t yLo, int ldo, int coOff,
+                                int* pathOut, int* rangeOut, void* stream) {
+  if (ldo == 0) ldo = cout;
+  if (!x || !wHost || !bias || !y || n < 1 || hh < 1 || ww < 1 || cin < 64 || cin % 64 || cout < 64 || cout % 64 ||
+      cout > unet::UpconvX3Shape::MAX_COUT || xLo % 8 || yLo % 8 || ldo % 64 || coOff < 0 || coOff % 64 || coOff + cout > ldo)
+    return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  GemmOpX3 op;
+  ActScale ia;
+  if (inAct) ia = act_from_host(inAct, cin);
+  int rc = build_upconv_x3(g_opErr, op, wHost, cin, cout, bias, inAct ? &ia : nullptr, nullptr);
+  uint16_t* zeros = nullptr;
+  OpRangeScope range;
+  X3Path path;
+  if (!rc) {
+    hipError_t e = hipMalloc((void**)&zeros, 4096);
+    if (e == hipSuccess) e = hipMemset(zeros, 0, 4096);
+    if (e == hipSuccess) e = range.arm();
+    if (e == hipSuccess) e = run_upconv_x3(op, zeros, x, xLo, n, hh, ww, y, yLo, ldo, coOff, s, nullptr, &path);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = range.read(rangeOut);
+    if (e != hipSuccess) {
+      g_opErr = hipGetErrorString(e);
+      rc = UNET_ERR_HIP;
+    }
+  }
+  path_to_ints(path, pathOut);
+  op.free_dev();
+  if (zeros) hipFree(zeros);
+  return rc;
+}
+
+int unet_op_conv_first_x3_planes(int device, const void* input, int isU8, int n, int hh, int ww, const float* wHost,
+                                 const float* scale, const float* shift, int cout, int relu, const float* mean,
+                                 const float* stdv, const float* outAct, uint16_t* y, size_t yLo, int ldo, int* rangeOut,
+                                 void* stream) {
+  if (ldo == 0) ldo = cout;
+  if (!input || !wHost || !scale || !shift || !y || (isU8 && (!mean || !stdv)) || n < 1 || hh < 1 || ww < 1 || cout < 64 ||
+      cout % 64 || yLo % 8 || ldo % 64 || cout > ldo)
+    return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  GemmOpX3 op;
+  ActScale oa;
+  if (outAct) oa = act_from_host(outAct, cout);
+  int rc = build_conv_x3(g_opErr, op, wHost, cout, 3, scale, shift, relu, true, nullptr, outAct ? &oa : nullptr, false);
+  OpRangeScope range;
+  if (!rc) {
+    hipError_t e = range.arm();
+    if (e == hipSuccess) {
+      unet::ConvFirstX3Args fa;   // as forward_x3 fills it
+      fa.frames = input;
+      fa.wt = op.wt;
+      fa.scale = op.scale;
+      fa.shift = op.shift;
+      fa.out = y;
+      fa.outLo = yLo;
+      fa.N = n;
+      fa.H = hh;
+      fa.W = ww;
+      fa.Cout = cout;
+      fa.ldo = ldo;
+      fa.tilesX = (ww + 31) / 32;
+      fa.tilesY = (hh + 7) / 8;
+      fa.relu = relu;
+      fa.m0 = mean ? mean[0] : 0.f;
+      fa.m1 = mean ? mean[1] : 0.f;
+      fa.m2 = mean ? mean[2] : 0.f;
+      fa.s0 = stdv ? stdv[0] : 1.f;
+      fa.s1 = stdv ? stdv[1] : 1.f;
+      fa.s2 = stdv ? stdv[2] : 1.f;
+      fa.err = g_errWord;
+      const dim3 grid((unsigned)(fa.tilesX * fa.tilesY * n));
+      if (isU8)
+        hipLaunchKernelGGL(unet::conv_first_x3_kernel<true>, grid, dim3(256), 0, s, fa);
+      else
+        hipLaunchKernelGGL(unet::conv_first_x3_kernel<false>, grid, dim3(256), 0, s, fa);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = range.read(rangeOut);
+    if (e != hipSuccess) {
+      g_opErr = hipGetErrorString(e);
+      rc = UNET_ERR_HIP;
+    }
+  }
+  op.free_dev();
+  return rc;
+}
+
+int unet_op_maxpool2x2_x3_planes(int device, const uint16_t* x, size_t xLo, int n, int hh, int ww, int c, int ldi, uint16_t* y,
+                                 size_t yLo, void* stream) {
+  if (ldi == 0) ldi = c;
+  if (!x || !y || n < 1 || hh < 2 || ww < 2 || hh % 2 || ww % 2 || c < 2 || c % 2 || ldi % 2 || c > ldi || xLo % 2 || yLo % 2)
+    return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t P = (size_t)n * hh * ww;
+  hipLaunchKernelGGL(unet::maxpool2x2_planes_kernel, dim3(grid_for(P / 4 * (c / 2))), dim3(256), 0, s,
+                     reinterpret_cast<const uint32_t*>(x), xLo / 2, n, hh, ww, c, ldi, reinterpret_cast<uint32_t*>(y), yLo / 2);
+  HIPCHK(g_opErr, hipGetLastError());
+  HIPCHK(g_opErr, hipStreamSynchronize(s));
+  return UNET_OK;
+}
+
+int unet_op_head1x1_x3_planes(int device, const uint16_t* x, size_t xLo, int n, int hh, int ww, int c, const float* wHost,
+                              float bias, float thr, float* logits, float* probs, uint8_t* mask, void* stream) {
+  if (!x || !wHost || !(logits || probs || mask) || n < 1 || hh < 1 || ww < 1 || c < 2 || c % 2 || xLo % 2)
+    return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  float* wd = nullptr;
+  HIPCHK(g_opErr, hipMalloc((void**)&wd, c * sizeof(float)));
+  hipError_t e = hipMemcpy(wd, wHost, c * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    const size_t npix = (size_t)n * hh * ww;
+    hipLaunchKernelGGL(unet::head1x1_planes_kernel, dim3(grid_for(npix)), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(x),
+                       xLo / 2, wd, bias, npix, c, logits, probs, mask, thr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  hipFree(wd);
+  HIPCHK(g_opErr, e);
+  return UNET_OK;
+}
+
+int unet_op_split_planes_x3(int device, const float* x, size_t count, uint16_t* y, size_t yLo, int* rangeOut, void* stream) {
+  if (!x || !y || count < 2 || count % 2 || yLo % 2) return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  OpRangeScope range;
+  hipError_t e = range.arm();
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(unet::split_planes_kernel, dim3(grid_for(count / 2)), dim3(256), 0, s, x, count / 2,
+                       reinterpret_cast<uint32_t*>(y), reinterpret_cast<uint32_t*>(y + yLo), g_errWord);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = range.read(rangeOut);
+  HIPCHK(g_opErr, e);
+  return UNET_OK;
 }
 
 }  // extern "C"
