@@ -541,6 +541,45 @@ int unet_op_wgrad3x3(int device, const float* dz_dev, const float* x_dev, int n,
 int unet_op_wgrad3x3_x3(int device, const float* dz_dev, const float* x_dev, int n, int h, int w, int cin, int cout,
                         float* dw_dev, int scaled, void* stream);
 
+/* ---- The training step's f16x3 operators (test entry points) ---------------------------------------------------------
+ * The MFMA operators of the training step on the launch sequences the step itself runs (the same run_* helpers), with
+ * what feeds them: the device-side weight packers (fp32 device weights in PyTorch layout, as in the flat parameter
+ * buffer; no pre-scaling), the power-of-two operand scaling of gradients and the fp32 epilogues.  Every call owns its
+ * scratch, keys and range word, synchronises the stream before it returns and writes nothing outside the outputs named
+ * here.  UNET_ERR_INVALID_ARG for what it cannot run (checked before a device is touched, except for a forced tile
+ * width the shape does not fit).
+ *
+ * 3x3 convolution with fp32 output, y[p][off + co] (pixel stride ldo, 0 = cout; ldo, off multiples of 64).  cin / cout
+ * are the channel counts of the convolution that runs (multiples of 64, <= 1024).  mode 0: the forward operator,
+ * w_dev (cout, cin, 3, 3); mode 1: the input-gradient operator of the forward convolution whose weight w_dev
+ * (cin, cout, 3, 3) is: channels swapped, taps flipped.  packer 0: pack_x3_kernel, 1: pack_x3_lds_multi_kernel (w_dev
+ * 16-byte aligned).  Input: either x_planes (fp16 hi plane, the lo plane directly behind it: N*H*W*cin halfs each), or
+ * x_f32 (N,H,W,cin) which the call splits - with scaled != 0 after scaling by the power of two that brings max |x| into
+ * [2^13, 2^14) (absmax_key_kernel, split_planes_scaled_kernel), undone in the epilogue; *inv_out is 2^-k (1 unscaled).
+ * tile_width / path_out (8 ints) as unet_op_conv3x3_x3_planes.  stat_partial_dev (optional, stat_cap_rows x 2 x cout
+ * floats): handed to the epilogue as the step hands it its reduction scratch; it receives the raw rows [row][2][cout] of
+ * per-channel sum / sum of squares and *stat_rows_out their count - 0 and the buffer untouched where the structure that
+ * ran does not fuse them.  The grid is only known inside the dispatch, so the capacity must cover its largest (256
+ * blocks x 4 rows = 1024 rows); less is UNET_ERR_INVALID_ARG with 1024 reported, before a device is touched. */
+int unet_op_train_conv3x3_x3(int device, const uint16_t* x_planes, const float* x_f32, int scaled, int n, int h, int w,
+                             int cin, int cout, const float* w_dev, int mode, int packer, int tile_width, float* y_dev,
+                             int ldo, int off, float* stat_partial_dev, int stat_cap_rows, int* stat_rows_out,
+                             float* inv_out, int* path_out, int* range_out, void* stream);
+/* ConvTranspose2d(2f -> f, k2 s2) backward as the step runs it on the f16x3 kernels: dy_dev is the fp32 gradient
+ * (N, 2h, 2w, ldd), f channels at offset offd (multiples of 4); in_planes the transposed convolution's input (N,h,w,2f)
+ * as fp16 hi plane + lo plane directly behind; w_dev (2f, f, 2, 2).  Column sum + maximum, space-to-depth into scaled
+ * operand planes, the 1x1 weight gradient and the input-gradient GEMM.  -> db_dev (f), dw_dev (2f, f, 2, 2), din_dev
+ * (N,h,w,2f), *inv_out = 2^-k of the operand scaling, *structure_out = 1 (upconv_x3_ws.h) / 2 (upconv_x3_r512.h, see
+ * unet_set_x3_upconv_r512) for the GEMM.  f a multiple of 64, <= 512. */
+int unet_op_upconv_bwd_x3(int device, const float* dy_dev, int ldd, int offd, const uint16_t* in_planes,
+                          const float* w_dev, int n, int h, int w, int f, float* db_dev, float* dw_dev, float* din_dev,
+                          float* inv_out, int* structure_out, void* stream);
+/* ConvTranspose2d forward of the training step: as unet_op_upconv2x2_x3_planes, but w_dev (cin, cout, 2, 2) and bias_dev
+ * (cout) are fp32 device tensors and the operand comes from pack_upconv_x3_kernel (un-prescaled, unit scale). */
+int unet_op_upconv_fwd_train_x3(int device, const uint16_t* x, size_t x_lo, int n, int h, int w, int cin,
+                                const float* w_dev, const float* bias_dev, int cout, uint16_t* y, size_t y_lo, int ldo,
+                                int co_off, int* path_out, int* range_out, void* stream);
+
 /* ---- int8 tier of the deployed network ("model B") --------------------------------------
  * Stands in for the quantised .rknn blob behind rknn.inference (src/py_utils/rknn_executor.py:36): per-tensor
  * asymmetric int8 activations, per-output-channel asymmetric int8 weights as the reference configures its conversion

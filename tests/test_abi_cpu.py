@@ -101,3 +101,34 @@ def test_x3_plane_entry_points_check_arguments_first(lib):
     assert lib.unet_op_maxpool2x2_x3_planes(0, p, 64, 1, 3, 4, 8, 0, p, 64, None) == 1
     assert lib.unet_op_head1x1_x3_planes(0, p, 64, 1, 2, 2, 8, q, 0.0, 0.0, None, None, None, None) == 1
     assert lib.unet_op_split_planes_x3(0, q, 3, p, 64, None, None) == 1
+
+
+def test_train_x3_entry_points_check_arguments_first(lib):
+    """the training step's operator entry points (tests/test_train_x3_ops_gpu.py) reject what they cannot run before
+    touching a device"""
+    buf = (C.c_uint16 * 64)()
+    f = (C.c_float * 64)()
+    p, q = C.cast(buf, C.c_void_p), C.cast(f, C.c_void_p)
+
+    def conv(planes=p, x32=None, scaled=0, cin=64, cout=64, mode=0, packer=0, tw=0, ldo=0, off=0, y=q, stat=None, cap=0,
+             rows=None, w=q):
+        return lib.unet_op_train_conv3x3_x3(0, planes, x32, scaled, 1, 8, 8, cin, cout, w, mode, packer, tw, y, ldo, off, stat,
+                                            cap, rows, None, None, None, None)
+    assert conv(cin=32) == 1 and conv(cout=96) == 1 and conv(cout=2048) == 1 and conv(cin=2048) == 1
+    assert conv(planes=None) == 1 and conv(x32=q) == 1 and conv(scaled=1) == 1          # exactly one input; scaled needs fp32
+    assert conv(mode=2) == 1 and conv(packer=2) == 1 and conv(w=None) == 1 and conv(y=None) == 1
+    assert conv(packer=1, w=C.c_void_p(C.addressof(f) + 4)) == 1                        # the LDS packer's float4 loads
+    assert conv(tw=428) == 1 and conv(tw=414) == 1 and conv(tw=24) == 1
+    assert conv(ldo=64, off=64) == 1 and conv(ldo=96) == 1 and conv(ldo=128, off=32) == 1
+    assert conv(stat=q) == 1 and conv(stat=q, cap=4) == 1                               # rows requested without a count word
+
+    def bwd(f_=64, ldd=128, offd=64, dy=q, planes=p):
+        return lib.unet_op_upconv_bwd_x3(0, dy, ldd, offd, planes, q, 1, 4, 4, f_, q, q, q, None, None, None)
+    assert bwd(f_=32) == 1 and bwd(f_=96) == 1 and bwd(f_=1024) == 1      # 4 f and 2 f must be multiples of 128
+    assert bwd(ldd=64) == 1 and bwd(offd=2) == 1 and bwd(ldd=130) == 1 and bwd(dy=None) == 1 and bwd(planes=None) == 1
+    assert lib.unet_op_upconv_fwd_train_x3(0, p, 64, 1, 4, 4, 64, q, q, 64, p, 64, 128, 128, None, None, None) == 1
+    assert lib.unet_op_upconv_fwd_train_x3(0, p, 64, 1, 4, 4, 96, q, q, 64, p, 64, 0, 0, None, None, None) == 1
+    assert lib.unet_op_upconv_fwd_train_x3(0, p, 64, 1, 4, 4, 64, q, None, 64, p, 64, 0, 0, None, None, None) == 1
+    # the 3x3 weight gradient: channel counts multiples of 64, even heights
+    assert lib.unet_op_wgrad3x3_x3(0, q, q, 1, 7, 8, 64, 64, q, 0, None) == 1
+    assert lib.unet_op_wgrad3x3_x3(0, q, q, 1, 8, 8, 96, 64, q, 0, None) == 1

@@ -53,10 +53,13 @@ def _wgrad_case(lib, n, cin, cout, h, w):
 @pytest.mark.parametrize("scaled,magnitude", [(0, 1.0), (1, 1.0), (1, 3e-8)])
 @pytest.mark.parametrize("n,cin,cout,h,w", [(3, 64, 64, 28, 28), (2, 128, 64, 16, 48), (2, 64, 128, 56, 56),
                                              (2, 64, 64, 20, 36), (5, 128, 128, 14, 14), (1, 64, 192, 2, 2),
-                                             (3, 64, 64, 6, 10), (1, 64, 64, 224, 224), (7, 256, 128, 4, 17)])
+                                             (3, 64, 64, 6, 10), (1, 64, 64, 224, 224), (7, 256, 128, 4, 17),
+                                             (2, 64, 128, 16, 40)])
 def test_wgrad3x3_f16x3(n, cin, cout, h, w, scaled, magnitude):
-    """The split-operand weight-gradient kernel (wgrad_x3_ws.h): widths that are not multiples of the 16-column strip,
-    maps smaller than a K-step, more splits than K-steps, gradients far below the fp16 range (scaled path)."""
+    """The split-operand weight-gradient kernel (wgrad_x3_ws.h): widths that are not multiples of the 16-column strip
+    (with cin != cout), maps smaller than a K-step, more splits than K-steps, gradients far below the fp16 range (scaled
+    path).  Beside the whole-tensor ratio, every element is held to the float64 model of the kernel's three products
+    (tests/x3_model.py): |got - r| <= 2^-23 |r| + 2^-15 |s| B."""
     from unet_lane_detection_amd import _lib
     lib = _lib.load(build_if_missing=False)
     g = torch.Generator().manual_seed(cin + cout + h)
@@ -71,6 +74,11 @@ def test_wgrad3x3_f16x3(n, cin, cout, h, w, scaled, magnitude):
                                  C.c_void_p(dw.data_ptr()), scaled, None)
     assert rc == 0
     assert _rel(dw.cpu().numpy(), wt.grad.numpy()) < 2e-5
+    import x3_model as M
+    dz_nhwc, x_nhwc = dz.permute(0, 2, 3, 1).contiguous(), x.permute(0, 2, 3, 1).contiguous()
+    dzh, dzl, k = M.scaled_split(dz_nhwc) if scaled else (*M.split_f16(dz_nhwc), 0)
+    m = M.model_wgrad3(dzh, dzl, *M.split_f16(x_nhwc), k, device="cuda")
+    M.check_f32(dw, m["r"], m["s"], m["B"], f"wgrad3x3_f16x3 {(n, h, w, cin, cout)} scaled {scaled} dz~{magnitude}")
 
 
 def _check_grads(tr, ref_grads, loss_ref, gtol):

@@ -14,31 +14,15 @@ accumulation term covers in units of |s| B (profiles/r08/x3_ops.md keeps the mea
 import ctypes as C
 import functools
 import math
-import zlib
 
 import pytest
 import torch
 
 import x3_model as M
+from x3_gpu_helpers import (ERR_HIP, ERR_INVALID_ARG, R512, SENTINEL, T448, WS, Planes, _h, _p, path_str, seed_of,  # noqa: F401
+                            to_dev)
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0x7DC1          # an fp16 signalling-NaN pattern: marks halfs a kernel must not write / has not written
-WS, R512, T448 = 1, 2, 3
-ERR_INVALID_ARG, ERR_HIP = 1, 4
-
-
-def seed_of(*key):
-    return zlib.crc32(repr(key).encode()) % 100003
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _h(a):
-    """host float32 tensor -> pointer (the tensor must stay alive for the call)"""
-    return C.c_void_p(a.data_ptr()) if a is not None else None
 
 
 @pytest.fixture(scope="module")
@@ -50,54 +34,6 @@ def lib():
     yield lib
     lib.unet_set_x3_upconv_r512(prev)
     lib.unet_set_x3_cross_fp8(prev_q8)
-
-
-# ---- planes with guards -------------------------------------------------------------------------------------------
-
-class Planes:
-    """hi / lo planes (n,h,w,ld) inside one sentinel-filled allocation: [guard | hi | guard | lo | guard], the guard at
-    least one image row"""
-
-    def __init__(self, n, h, w, ld):
-        self.shape = (n, h, w, ld)
-        self.elems = n * h * w * ld
-        self.guard = (max(w * ld, 64) + 63) // 64 * 64
-        self.buf = torch.full((3 * self.guard + 2 * self.elems,), SENTINEL, dtype=torch.int16, device="cuda")
-        self.lo_off = self.elems + self.guard
-
-    @property
-    def ptr(self):
-        return C.c_void_p(self.buf.data_ptr() + 2 * self.guard)
-
-    def _plane(self, k):
-        o = self.guard + k * self.lo_off
-        return self.buf[o:o + self.elems].view(self.shape)
-
-    def bits(self, c0=0, c1=None):
-        """(hi, lo) int16 views of channels [c0, c1)"""
-        return self._plane(0)[..., c0:c1], self._plane(1)[..., c0:c1]
-
-    def halves(self, c0=0, c1=None):
-        hi, lo = self.bits(c0, c1)
-        return hi.contiguous().view(torch.float16).cpu(), lo.contiguous().view(torch.float16).cpu()
-
-    def assert_written_only(self, c0, c1, label):
-        """every half of channels [c0, c1) written, every other half of the allocation still the sentinel"""
-        hi, lo = self.bits(c0, c1)
-        assert not (hi == SENTINEL).any() and not (lo == SENTINEL).any(), f"{label}: output elements not written"
-        g, e = self.guard, self.elems
-        for name, a, b in (("before hi", 0, g), ("between the planes", g + e, 2 * g + e), ("after lo", 2 * g + 2 * e, 3 * g + 2 * e)):
-            assert (self.buf[a:b] == SENTINEL).all(), f"{label}: guard {name} overwritten"
-        for k in (0, 1):
-            pl = self._plane(k)
-            assert (pl[..., :c0] == SENTINEL).all() and (pl[..., c1:] == SENTINEL).all(), \
-                f"{label}: channels outside [{c0}, {c1}) overwritten"
-
-
-def to_dev(hi, lo):
-    """fp16 planes (CPU) -> one device tensor [hi | lo], its pointer and the lo offset in elements"""
-    x = torch.stack([hi, lo]).contiguous().cuda()
-    return x, x[0].numel()
 
 
 def conv_params(cin, cout, gen):
@@ -163,12 +99,6 @@ def run_conv(lib, hi, lo, w, scale, shift, relu, tw, *, ldo=0, co_off=0, pool=Fa
     assert rc == expect_rc, (rc, tw, tuple(hi.shape), cout)
     torch.cuda.synchronize()
     return dict(out=y, pool=yp, logits=logits, probs=probs, mask=mask, path=tuple(path)[:7], range=rng.value)
-
-
-def path_str(p):
-    names = {0: "none", WS: "ws", R512: "r512", T448: "t448"}
-    return (f"{names.get(p[0], p[0])} tw{p[1]} epi{p[2]}{' flat' if p[3] else ''} kSplit{p[4]} waves{p[5]}"
-            f"{' +pool pass' if p[6] else ''}")
 
 
 def pool_model(r):

@@ -15,6 +15,7 @@ using unet::WgradArgs;
 
 constexpr float kBnMomentum = 0.1f;  // nn.BatchNorm2d default
 constexpr int kRedBlocks = 1024;     // blocks of the two-stage column reductions (4 per CU)
+constexpr size_t kPartialFloats = (size_t)kRedBlocks * 2 * 4096;   // the reductions' scratch (TrainPlan::partial)
 
 struct ConvUnit {
   std::string prefix;
@@ -186,6 +187,50 @@ bool train_x3_enabled();
 bool train_x3_wgrad_enabled();
 bool train_pool_fused();
 
+// ---- the split-operand (fp16 hi + lo) copies of the operators: sizes, table and launches, shared by train_repack /
+//      unet_train_create and the operator test entry points ----
+size_t x3_conv_pack_halfs(int cout, int cin) { return (size_t)cout * cin * 9 * 2; }   // hi + lo, either operator
+size_t x3_upconv_pack_halfs(int cin, int cout) { return (size_t)cin * cout * 4 * 2; }
+// [tiles of 256 columns][4 cout / 32 chunks][2 planes][16][64][8]
+size_t x3_upconv_dgrad_pack_halfs(int cin, int cout) {
+  return (size_t)((cin + 255) / 256) * (4 * cout / 32) * 2 * 16 * 64 * 8;
+}
+// one 3x3 unit's entries of pack_x3_lds_multi_kernel's table: the forward operator, then the input-gradient operator
+// ("cout" of the input-gradient convolution = the forward cin); either destination may be null
+void pack_x3_table_add(std::vector<unet::PackX3Desc>& d, std::vector<unsigned>& start, const float* w, uint16_t* x3Fwd,
+                       uint16_t* x3Dgrad, int cout, int cin) {
+  if (x3Fwd) {
+    d.push_back({w, x3Fwd, cout, cin, 0});
+    start.push_back(start.back() + (unsigned)((cout / 64) * (cin / 32)));
+  }
+  if (x3Dgrad) {
+    d.push_back({w, x3Dgrad, cin, cout, 1});
+    start.push_back(start.back() + (unsigned)((cin / 64) * (cout / 32)));
+  }
+}
+hipError_t launch_pack_x3_lds_multi(const unet::PackX3Desc* descs, const unsigned* start, int n, unsigned blocks,
+                                    hipStream_t s) {
+  const hipError_t e = ensure_dyn_lds((const void*)unet::pack_x3_lds_multi_kernel, unet::kPackX3LdsBytes);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(unet::pack_x3_lds_multi_kernel, dim3(blocks), dim3(256), (size_t)unet::kPackX3LdsBytes, s, descs, start,
+                     n);
+  return hipGetLastError();
+}
+// the gathering packer, one operator: mode 0 forward (cout, cin), mode 1 input gradient (its cout = the forward cin)
+void launch_pack_x3(const float* w, uint16_t* out, int cout, int cin, int mode, hipStream_t s) {
+  hipLaunchKernelGGL(unet::pack_x3_kernel, dim3(grid_for((size_t)cout * cin * 9 / 8)), dim3(256), 0, s, w, out, cout, cin,
+                     mode);
+}
+void launch_pack_upconv_x3(const float* w, uint16_t* out, int cin, int cout, hipStream_t s) {
+  hipLaunchKernelGGL(unet::pack_upconv_x3_kernel, dim3(grid_for((size_t)cin * cout * 4 / 8)), dim3(256), 0, s, w, out, cin,
+                     cout);
+}
+void launch_pack_upconv_dgrad_x3(const float* w, uint16_t* out, int cin, int cout, hipStream_t s) {
+  hipLaunchKernelGGL(unet::pack_upconv_dgrad_x3_kernel,
+                     dim3(grid_for((size_t)((cin + 255) / 256) * (4 * cout / 32) * 16 * 64)), dim3(256), 0, s, w, out, cin,
+                     cout);
+}
+
 // Re-derive every packed operand from the flat parameter buffer (after load and after each Adam step): one
 // multi-operand launch over a descriptor table built on first use (all pointers are fixed once attached).
 int train_repack(unet_ctx* h, hipStream_t s) {
@@ -253,16 +298,7 @@ int train_repack(unet_ctx* h, hipStream_t s) {
       std::vector<unet::PackX3Desc> d;
       std::vector<unsigned> start{0};
       for (auto* vec : {&T->enc, &T->bott, &T->dec})
-        for (auto& u : *vec) {
-          if (u.x3Fwd) {
-            d.push_back({T->params + u.offW, u.x3Fwd, u.cout, u.cin, 0});
-            start.push_back(start.back() + (unsigned)((u.cout / 64) * (u.cin / 32)));
-          }
-          if (u.x3Dgrad) {   // "cout" of the input-gradient convolution = the forward cin
-            d.push_back({T->params + u.offW, u.x3Dgrad, u.cin, u.cout, 1});
-            start.push_back(start.back() + (unsigned)((u.cin / 64) * (u.cout / 32)));
-          }
-        }
+        for (auto& u : *vec) pack_x3_table_add(d, start, T->params + u.offW, u.x3Fwd, u.x3Dgrad, u.cout, u.cin);
       T->nPackX3 = (int)d.size();
       T->packX3Blocks = start.back();
       if (T->nPackX3) {
@@ -272,31 +308,17 @@ int train_repack(unet_ctx* h, hipStream_t s) {
         HIPCHK(h->err, hipMemcpy(T->packX3Start, start.data(), start.size() * sizeof(unsigned), hipMemcpyHostToDevice));
       }
     }
-    if (T->nPackX3) {
-      HIPCHK(h->err, ensure_dyn_lds((const void*)unet::pack_x3_lds_multi_kernel, unet::kPackX3LdsBytes));
-      hipLaunchKernelGGL(unet::pack_x3_lds_multi_kernel, dim3(T->packX3Blocks), dim3(256), (size_t)unet::kPackX3LdsBytes, s,
-                         T->packX3Descs, T->packX3Start, T->nPackX3);
-    }
+    if (T->nPackX3) HIPCHK(h->err, launch_pack_x3_lds_multi(T->packX3Descs, T->packX3Start, T->nPackX3, T->packX3Blocks, s));
   } else {
     for (auto* vec : {&T->enc, &T->bott, &T->dec})
       for (auto& u : *vec) {
-        const size_t items = (size_t)u.cout * u.cin * 9 / 8;
-        if (u.x3Fwd)
-          hipLaunchKernelGGL(unet::pack_x3_kernel, dim3(grid_for(items)), dim3(256), 0, s, T->params + u.offW, u.x3Fwd,
-                             u.cout, u.cin, 0);
-        if (u.x3Dgrad)
-          hipLaunchKernelGGL(unet::pack_x3_kernel, dim3(grid_for(items)), dim3(256), 0, s, T->params + u.offW, u.x3Dgrad,
-                             u.cin, u.cout, 1);
+        if (u.x3Fwd) launch_pack_x3(T->params + u.offW, u.x3Fwd, u.cout, u.cin, 0, s);
+        if (u.x3Dgrad) launch_pack_x3(T->params + u.offW, u.x3Dgrad, u.cin, u.cout, 1, s);
       }
   }
   for (auto& u : T->up) {
-    if (u.x3Fwd)
-      hipLaunchKernelGGL(unet::pack_upconv_x3_kernel, dim3(grid_for((size_t)u.cin * u.cout * 4 / 8)), dim3(256), 0, s,
-                         T->params + u.offW, u.x3Fwd, u.cin, u.cout);
-    if (u.x3Dgrad)
-      hipLaunchKernelGGL(unet::pack_upconv_dgrad_x3_kernel,
-                         dim3(grid_for((size_t)((u.cin + 255) / 256) * (4 * u.cout / 32) * 16 * 64)), dim3(256), 0, s,
-                         T->params + u.offW, u.x3Dgrad, u.cin, u.cout);
+    if (u.x3Fwd) launch_pack_upconv_x3(T->params + u.offW, u.x3Fwd, u.cin, u.cout, s);
+    if (u.x3Dgrad) launch_pack_upconv_dgrad_x3(T->params + u.offW, u.x3Dgrad, u.cin, u.cout, s);
   }
   HIPCHK(h->err, hipGetLastError());
   T->packed = true;
@@ -413,7 +435,7 @@ TrainPlan plan_train(const unet_config& c, int n, int h, int w) {
   p.s2dFloats = maxAct;
   p.slabFloats = maxSlab;
   p.slab = take(maxSlab);
-  p.partial = take((size_t)kRedBlocks * 2 * 4096);
+  p.partial = take(kPartialFloats);
   p.total = off;
   return p;
 }
@@ -673,7 +695,9 @@ void split_to_planes(const float* x, size_t elems, float* planes, hipStream_t s,
 // weights); inv: the device scalar split_to_planes left for a scaled input, or null
 hipError_t run_train_conv_x3_planes(TrainState* T, const uint16_t* wt, int cin, int cout, const float* planes, int n,
                                     int hh, int ww, float* y, int ldo, int off, const char* label, hipStream_t s,
-                                    const float* inv = nullptr, float* statPartial = nullptr, int* statRows = nullptr) {
+                                    const float* inv = nullptr, float* statPartial = nullptr, int* statRows = nullptr,
+                                    int forceTw = 0, X3Path* path = nullptr) {
+  // forceTw / path: run_conv_x3's forced tile width and path report (the test entry point; the step passes neither)
   const size_t elems = (size_t)n * hh * ww * cin;
   GemmOpX3 op;   // borrowed pointers: never freed through this object
   op.taps = 9;
@@ -685,7 +709,7 @@ hipError_t run_train_conv_x3_planes(TrainState* T, const uint16_t* wt, int cin, 
   op.shift = T->zeros;
   const hipError_t e = run_conv_x3(op, reinterpret_cast<const uint16_t*>(zero_page()),
                                    reinterpret_cast<const uint16_t*>(planes), elems, n, hh, ww, nullptr, 0, ldo, off, s,
-                                   nullptr, 0, y, label, inv, nullptr, statPartial, statRows);
+                                   nullptr, forceTw, y, label, inv, nullptr, statPartial, statRows, nullptr, nullptr, path);
   op.wt = nullptr;
   op.scale = op.shift = nullptr;
   return e;
@@ -839,6 +863,49 @@ hipError_t side_fork(TrainState* T, hipStream_t s) {
   return e;
 }
 
+// ConvTranspose2d(2f -> f) of the training forward on planes: planes (n,h,w,cin) in, planes out with pixel stride ldo at
+// channel offset coOff; wt from pack_upconv_x3_kernel (un-prescaled: unit scale), bias the fp32 parameter itself
+hipError_t run_train_upconv_x3(TrainState* T, const uint16_t* wt, const float* bias, int cin, int cout, const uint16_t* in,
+                               size_t inLo, int n, int h, int w, uint16_t* out, size_t outLo, int ldo, int coOff,
+                               hipStream_t s, X3Path* path = nullptr) {
+  GemmOpX3 op;   // borrowed pointers
+  op.taps = 1;
+  op.cin = cin;
+  op.cout = cout;
+  op.wt = const_cast<uint16_t*>(wt);
+  op.scale = T->ones;
+  op.shift = const_cast<float*>(bias);
+  const hipError_t e = run_upconv_x3(op, reinterpret_cast<const uint16_t*>(zero_page()), in, inLo, n, h, w, out, outLo, ldo,
+                                     coOff, s, nullptr, path);
+  op.wt = nullptr;
+  op.scale = op.shift = nullptr;
+  return e;
+}
+
+// ConvTranspose2d backward, f16x3: the bias gradient is the column sum of the gradient slice dY (P hi-res pixels, pixel
+// stride ldd, f channels at offset offd); the same pass leaves max |.| of the slice in *key (zeroed by the caller)
+hipError_t run_up_bias_grad_x3(const float* dY, int ldd, int offd, size_t Ph, int f, float* partial, unsigned* key, float* db,
+                               hipStream_t s) {
+  const int nb = red_blocks(Ph);
+  prof_begin("bias_grad", 0.0, 4.0 * Ph * f, s);
+  hipLaunchKernelGGL(unet::colsum_partial_kernel, dim3(nb), dim3(256), 0, s, dY, ldd, offd, Ph, f, partial, key);
+  hipLaunchKernelGGL(unet::colsum_finalize_kernel, dim3((f + unet::FIN_CH - 1) / unet::FIN_CH), dim3(256), 0, s, partial, nb, f, f,
+                     db);
+  prof_end(s);
+  return hipGetLastError();
+}
+
+// ... and the slice in space-to-depth order as scaled operand planes S (n,lh,lw,4f), 2^-k left in *inv
+hipError_t run_up_s2d_planes_x3(const float* dY, int ldd, int offd, int n, int lh, int lw, int f, const unsigned* key, float* S,
+                                float* inv, hipStream_t s) {
+  const size_t Pl = (size_t)n * lh * lw;
+  prof_begin("space_to_depth", 0.0, 8.0 * Pl * 4 * f, s);
+  hipLaunchKernelGGL(unet::space_to_depth_planes_kernel, dim3(grid_for(Pl * 4 * (f / 4))), dim3(256), 0, s, dY, ldd, offd, n, lh,
+                     lw, f, key, reinterpret_cast<uint32_t*>(S), Pl * 4 * (size_t)f / 2, inv);
+  prof_end(s);
+  return hipGetLastError();
+}
+
 // Where a unit's activation goes: fp32 (pixel stride ld, channel offset off) and / or fp16 hi + lo planes (pixel
 // stride ldp, channel offset offp; the lo plane behind a hi plane of P * ldp halfs) - either may be null
 struct ActOut {
@@ -859,9 +926,11 @@ int unit_forward(unet_ctx* h, ConvUnit& u, const float* in, const float* inPlane
   const size_t P = (size_t)n * hh * ww;
   // the second and third convolution structures sum the statistics' first pass in their epilogues (statRows rows of
   // `partial`; UNET_TRAIN_FUSED_STATS=0 restores the separate pass over z).  Measured (batch 64): bn_stats 1.43 -> 0.84 ms,
-  // forward convolutions +0.05 ms.  The statistics agree with the separate pass to 1e-7 per channel; the other summation
-  // order moves which near-zero BatchNorm outputs take which side of the ReLU, and with it the BatchNorm-weight gradient
-  // norms of the reference's batch-4 golden step: 1.75e-3 from a float64 run of the reference's network against 1.15e-3
+  // forward convolutions +0.05 ms.  The rows are sums of the same stored fp32 values z over the image's pixels only (each
+  // pixel once, no padded or out-of-image pixel): exact up to the fp32 summation order, which
+  // tests/test_train_x3_ops_gpu.py proves bit for bit on integer-valued inputs.  The other summation order moves which
+  // near-zero BatchNorm outputs take which side of the ReLU, and with it the BatchNorm-weight gradient norms of the
+  // reference's batch-4 golden step: 1.75e-3 from a float64 run of the reference's network against 1.15e-3
   // with the separate pass - and 1.71e-3 for this library's exact-fp32 kernels, 1.14e-3 for the reference's own fp32 run
   // (tools/probes/gradnorm_dev.py, profiles/r04/gradnorm_vs_f64.txt).  The test bound is twice the reference's own distance
   // (tests/test_train_gpu.py, GRADNORM_K), so the fused form is the default since round 4.
@@ -1083,21 +1152,11 @@ int train_forward_backward(unet_ctx* h, int n, int height, int width, const floa
     const int f = c.features[l];
     const bool upX3 = PM && T->up[j].x3Fwd;
     if (upX3) {   // planes in, planes out: straight into the upper channel half of the concat buffer's operand form
-      GemmOpX3 op;   // borrowed pointers
-      op.taps = 1;
-      op.cin = 2 * f;
-      op.cout = f;
-      op.wt = T->up[j].x3Fwd;
-      op.scale = T->ones;
-      op.shift = T->params + T->up[j].offB;
       const size_t Pin = (size_t)n * ch * cw;
       uint16_t* outHi = reinterpret_cast<uint16_t*>(ws + p.catP[l]);
-      const hipError_t e = run_upconv_x3(op, reinterpret_cast<const uint16_t*>(zero_page()),
+      HIPCHK(h->err, run_train_upconv_x3(T, T->up[j].x3Fwd, T->params + T->up[j].offB, 2 * f, f,
                                          reinterpret_cast<const uint16_t*>(ws + p.upInP[j]), Pin * 2 * f, n, ch, cw, outHi,
-                                         Pin * 4 * 2 * f, 2 * f, f, s);
-      op.wt = nullptr;
-      op.scale = op.shift = nullptr;
-      HIPCHK(h->err, e);
+                                         Pin * 4 * 2 * f, 2 * f, f, s));
     } else {
       HIPCHK(h->err, run_gemm_op(T->up[j].fwd, cur, n, ch, cw, ws + p.cat[l], 2 * f, f, s));
     }
@@ -1214,13 +1273,7 @@ int train_forward_backward(unet_ctx* h, int n, int height, int width, const floa
       const size_t nUnits = T->enc.size() + T->bott.size() + T->dec.size();
       unsigned* key = T->gzKeys + 8 * (nUnits + j);
       float* inv = T->gzInv + nUnits + j;
-      const size_t Ph = Pl * 4;
-      const int nb = red_blocks(Ph);
-      prof_begin("bias_grad", 0.0, 4.0 * Ph * f, s);
-      hipLaunchKernelGGL(unet::colsum_partial_kernel, dim3(nb), dim3(256), 0, s, ws + p.dCat[l], 2 * f, f, Ph, f, partial, key);
-      hipLaunchKernelGGL(unet::colsum_finalize_kernel, dim3((f + unet::FIN_CH - 1) / unet::FIN_CH), dim3(256), 0, s, partial, nb, f, f,
-                         T->grads + U.offB);
-      prof_end(s);
+      HIPCHK(h->err, run_up_bias_grad_x3(ws + p.dCat[l], 2 * f, f, Pl * 4, f, partial, key, T->grads + U.offB, s));
       const bool side = side_on(T);
       if (side) {
         HIPCHK(h->err, side_init(T));
@@ -1229,12 +1282,7 @@ int train_forward_backward(unet_ctx* h, int n, int height, int width, const floa
       } else {
         HIPCHK(h->err, side_join(T, s));
       }
-      prof_begin("space_to_depth", 0.0, 8.0 * Pl * 4 * f, s);
-      hipLaunchKernelGGL(unet::space_to_depth_planes_kernel, dim3(grid_for(Pl * 4 * (f / 4))), dim3(256), 0, s,
-                         ws + p.dCat[l], 2 * f, f, n, lh, lw, f, (const unsigned*)key, reinterpret_cast<uint32_t*>(S),
-                         Pl * 4 * (size_t)f / 2, inv);
-      prof_end(s);
-      HIPCHK(h->err, hipGetLastError());
+      HIPCHK(h->err, run_up_s2d_planes_x3(ws + p.dCat[l], 2 * f, f, n, lh, lw, f, key, S, inv, s));
       auto up_wgrad = [&](hipStream_t ws_) {
         return run_wgrad1_x3(S, 4 * f, 4 * f, ws + p.upInP[j], U.cin, U.cin, (long)Pl, ws + p.slab, p.slabFloats,
                              T->grads + U.offW, 1, f, inv, ws_);
@@ -1533,20 +1581,10 @@ int train_eval_forward(unet_ctx* h, int n, int height, int width, float* logitsO
     const int f = c.features[l];
     const bool upX3 = PM && T->up[j].x3Fwd;
     if (upX3) {   // planes in, planes out: straight into the upper channel half of the concat buffer's operand form
-      GemmOpX3 op;   // borrowed pointers
-      op.taps = 1;
-      op.cin = 2 * f;
-      op.cout = f;
-      op.wt = T->up[j].x3Fwd;
-      op.scale = T->ones;
-      op.shift = T->params + T->up[j].offB;
       const size_t Pin = (size_t)n * ch * cw;
-      const hipError_t e = run_upconv_x3(op, reinterpret_cast<const uint16_t*>(zero_page()),
+      HIPCHK(h->err, run_train_upconv_x3(T, T->up[j].x3Fwd, T->params + T->up[j].offB, 2 * f, f,
                                          reinterpret_cast<const uint16_t*>(ws + p.upInP[j]), Pin * 2 * f, n, ch, cw,
-                                         reinterpret_cast<uint16_t*>(ws + p.catP[l]), Pin * 4 * 2 * f, 2 * f, f, s);
-      op.wt = nullptr;
-      op.scale = op.shift = nullptr;
-      HIPCHK(h->err, e);
+                                         reinterpret_cast<uint16_t*>(ws + p.catP[l]), Pin * 4 * 2 * f, 2 * f, f, s));
     } else {
       HIPCHK(h->err, run_gemm_op(T->up[j].fwd, cur, n, ch, cw, ws + p.cat[l], 2 * f, f, s));
     }
@@ -1772,7 +1810,7 @@ int unet_train_attach(unet_handle_t h, float* params, float* grads, float* expAv
         maxN = std::max(maxN, u.dgrad.nTotal);
       }
       if (u.cin % 64 == 0 && u.cout % 64 == 0 && u.cin <= 1024 && u.cout <= 1024) {
-        const size_t halfs = (size_t)u.cout * u.cin * 9 * 2;   // hi + lo, the same count for both operators
+        const size_t halfs = x3_conv_pack_halfs(u.cout, u.cin);   // the same count for both operators
         HIPCHK(h->err, hipMalloc((void**)&u.x3Fwd, halfs * sizeof(uint16_t)));
         if (u.needDgrad) HIPCHK(h->err, hipMalloc((void**)&u.x3Dgrad, halfs * sizeof(uint16_t)));
       }
@@ -1785,10 +1823,8 @@ int unet_train_attach(unet_handle_t h, float* params, float* grads, float* expAv
     U.dgrad.plain = 1;
     U.dgrad.name = "upconv_dgrad_igemm_f32";
     if (U.cin % 64 == 0 && U.cout % 64 == 0 && U.cout <= 1024) {
-      HIPCHK(h->err, hipMalloc((void**)&U.x3Fwd, (size_t)U.cin * U.cout * 4 * 2 * sizeof(uint16_t)));
-      // [tiles of 256 columns][4 cout / 32 chunks][2 planes][16][64][8]
-      const size_t halfs = (size_t)((U.cin + 255) / 256) * (4 * U.cout / 32) * 2 * 16 * 64 * 8;
-      HIPCHK(h->err, hipMalloc((void**)&U.x3Dgrad, halfs * sizeof(uint16_t)));
+      HIPCHK(h->err, hipMalloc((void**)&U.x3Fwd, x3_upconv_pack_halfs(U.cin, U.cout) * sizeof(uint16_t)));
+      HIPCHK(h->err, hipMalloc((void**)&U.x3Dgrad, x3_upconv_dgrad_pack_halfs(U.cin, U.cout) * sizeof(uint16_t)));
     }
     maxN = std::max(maxN, std::max(U.fwd.nTotal, U.dgrad.nTotal));
   }
@@ -2126,6 +2162,203 @@ int unet_op_wgrad3x3_x3(int device, const float* dz, const float* x, int n, int 
   hipFree(key);
   if (e != hipSuccess) g_opErr = e;
   return e == hipSuccess ? UNET_OK : UNET_ERR_HIP;
+}
+
+// ---- test entry points of the training step's MFMA operators (include/unet_hip.h, "The training step's f16x3 operators"):
+//      fp32 device weights in PyTorch layout, packed by the device packers; the run_* helpers of unit_forward /
+//      unit_backward / the transposed convolution's backward; scratch, keys and range word owned by the call ----
+
+}  // extern "C"
+
+namespace {
+struct OpScratch {   // device allocations of one call, freed when it returns; cleared, where asked, on the call's stream
+  std::vector<void*> all;
+  hipStream_t s = nullptr;
+  template <class T>
+  hipError_t get(T** p, size_t bytes, bool zero = false) {
+    hipError_t e = hipMalloc((void**)p, std::max<size_t>(bytes, 64));
+    if (e != hipSuccess) return e;
+    all.push_back(*p);
+    return zero ? hipMemsetAsync(*p, 0, std::max<size_t>(bytes, 64), s) : hipSuccess;
+  }
+  ~OpScratch() {
+    for (void* q : all) hipFree(q);
+  }
+};
+// the unit scale / zero shift of the training operators (TrainState::ones / zeros), c floats each
+hipError_t op_ones_zeros(OpScratch& sc, TrainState& T, int c) {
+  hipError_t e = sc.get(&T.ones, (size_t)c * sizeof(float));
+  if (e == hipSuccess) e = sc.get(&T.zeros, (size_t)c * sizeof(float), true);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(fill_kernel, dim3(4), dim3(256), 0, sc.s, T.ones, (size_t)c, 1.0f);   // as unet_train_create
+  return hipGetLastError();
+}
+int op_status(hipError_t e) {
+  if (e == hipSuccess) return UNET_OK;
+  g_opErr = hipGetErrorString(e);
+  return e == hipErrorInvalidValue ? UNET_ERR_INVALID_ARG : (e == hipErrorOutOfMemory ? UNET_ERR_NOMEM : UNET_ERR_HIP);
+}
+}  // namespace
+
+extern "C" {
+
+int unet_op_train_conv3x3_x3(int device, const uint16_t* xPlanes, const float* xF32, int scaled, int n, int hh, int ww,
+                             int cin, int cout, const float* wDev, int mode, int packer, int tileWidth, float* y, int ldo,
+                             int off, float* statPartialDev, int statCapRows, int* statRowsOut, float* invOut, int* pathOut,
+                             int* rangeOut, void* stream) {
+  static const int kWidths[] = {0, 16, 32, 28, 14, 228, 214, 332, 316, 308, 532, 628, 632, 728};
+  if (ldo == 0) ldo = cout;
+  if ((xPlanes == nullptr) == (xF32 == nullptr) || (scaled && !xF32) || !wDev || !y || n < 1 || hh < 1 || ww < 1 || cin < 64 ||
+      cin % 64 || cin > 1024 || cout < 64 || cout % 64 || cout > unet::X3Shape<32>::MAX_COUT || (mode != 0 && mode != 1) ||
+      (packer != 0 && packer != 1) || (packer == 1 && (reinterpret_cast<uintptr_t>(wDev) & 15)) ||
+      std::find(std::begin(kWidths), std::end(kWidths), tileWidth) == std::end(kWidths) || ldo % 64 || off < 0 || off % 64 ||
+      off + cout > ldo || (statPartialDev && (!statRowsOut || (size_t)statCapRows * 2 * cout > kPartialFloats)))
+    return UNET_ERR_INVALID_ARG;
+  // the epilogue writes its rows straight into the caller's buffer, so the room must be there before the structure and
+  // its grid are known: at most 256 blocks x 4 rows (run_conv_x3)
+  if (statRowsOut) *statRowsOut = 0;
+  if (statPartialDev && statCapRows < 256 * 4) {
+    *statRowsOut = 256 * 4;
+    return UNET_ERR_INVALID_ARG;
+  }
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  if (invOut) *invOut = 1.f;
+  const size_t elems = (size_t)n * hh * ww * cin;
+  OpScratch sc;
+  sc.s = s;
+  TrainState T;
+  OpRangeScope range;
+  X3Path path;
+  uint16_t *wt = nullptr, *wtOther = nullptr;
+  float *planes = nullptr, *inv = nullptr;
+  unsigned *key = nullptr, *start = nullptr;
+  unet::PackX3Desc* desc = nullptr;
+  int rows = 0;
+  hipError_t e = op_ones_zeros(sc, T, cout);
+  if (e == hipSuccess) e = sc.get(&wt, x3_conv_pack_halfs(cout, cin) * sizeof(uint16_t));
+  if (e == hipSuccess) e = sc.get(&key, 64, true);
+  if (e == hipSuccess) e = sc.get(&inv, 64, true);
+  if (e == hipSuccess && xF32) e = sc.get(&planes, elems * sizeof(float));
+  if (e == hipSuccess && !zero_page()) e = hipErrorOutOfMemory;
+  if (e == hipSuccess && packer == 1) {
+    // the table train_repack builds for this layer: its forward and its input-gradient operator, one launch; the one
+    // `mode` selects is used, the other goes to scratch
+    e = sc.get(&wtOther, x3_conv_pack_halfs(cout, cin) * sizeof(uint16_t));
+    std::vector<unet::PackX3Desc> d;
+    std::vector<unsigned> st{0};
+    if (mode == 0)
+      pack_x3_table_add(d, st, wDev, wt, wtOther, cout, cin);
+    else
+      pack_x3_table_add(d, st, wDev, wtOther, wt, cin, cout);
+    if (e == hipSuccess) e = sc.get(&desc, d.size() * sizeof(d[0]));
+    if (e == hipSuccess) e = hipMemcpy(desc, d.data(), d.size() * sizeof(d[0]), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = sc.get(&start, st.size() * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemcpy(start, st.data(), st.size() * sizeof(unsigned), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_pack_x3_lds_multi(desc, start, (int)d.size(), st.back(), s);
+  } else if (e == hipSuccess) {
+    launch_pack_x3(wDev, wt, cout, cin, mode, s);
+  }
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = range.arm();
+  if (e == hipSuccess && xF32) {
+    if (scaled) {
+      hipLaunchKernelGGL(unet::absmax_key_kernel, dim3(256), dim3(256), 0, s, xF32, elems, key);
+      split_to_planes(xF32, elems, planes, s, key, inv);
+    } else {
+      split_to_planes(xF32, elems, planes, s);
+    }
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess)
+    e = run_train_conv_x3_planes(&T, wt, cin, cout, xF32 ? planes : reinterpret_cast<const float*>(xPlanes), n, hh, ww, y, ldo,
+                                 off, mode ? "dgrad3x3_f16x3" : "conv3x3_f16x3", s, scaled ? inv : nullptr, statPartialDev,
+                                 statPartialDev ? &rows : nullptr, tileWidth, &path);
+  const hipError_t es = hipStreamSynchronize(s);   // also after a failed launch: the scratch is freed below
+  if (e == hipSuccess) e = es;
+  if (e == hipSuccess) e = range.read(rangeOut);
+  if (e == hipSuccess && scaled && invOut) e = hipMemcpy(invOut, inv, sizeof(float), hipMemcpyDeviceToHost);
+  T.ones = T.zeros = nullptr;   // owned by sc
+  path_to_ints(path, pathOut);
+  if (statPartialDev) *statRowsOut = rows;
+  return op_status(e);
+}
+
+int unet_op_upconv_bwd_x3(int device, const float* dY, int ldd, int offd, const uint16_t* inPlanes, const float* wDev, int n,
+                          int lh, int lw, int f, float* db, float* dW, float* dIn, float* invOut, int* structureOut,
+                          void* stream) {
+  const int cin = 2 * f, rowsG = 4 * f;
+  if (!dY || !inPlanes || !wDev || !db || !dW || !dIn || n < 1 || lh < 1 || lw < 1 || f < 64 || f % 64 || f > 512 ||
+      rowsG % 128 || cin % 128 || ldd % 4 || offd < 0 || offd % 4 || offd + f > ldd)
+    return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  if (structureOut) *structureOut = 0;
+  const size_t Pl = (size_t)n * lh * lw;
+  const size_t tiles = (size_t)(rowsG / 128) * (cin / 128);
+  const size_t slabFloats = wgrad_x3_splits(tiles, (Pl + 31) / 32) * (size_t)rowsG * cin;
+  OpScratch sc;
+  sc.s = s;
+  float *S = nullptr, *partial = nullptr, *inv = nullptr, *slab = nullptr;
+  unsigned* key = nullptr;
+  uint16_t* wt = nullptr;
+  int structure = 0;
+  hipError_t e = sc.get(&S, Pl * 4 * f * sizeof(float));
+  if (e == hipSuccess) e = sc.get(&partial, kPartialFloats * sizeof(float));
+  if (e == hipSuccess) e = sc.get(&slab, slabFloats * sizeof(float));
+  if (e == hipSuccess) e = sc.get(&wt, x3_upconv_dgrad_pack_halfs(cin, f) * sizeof(uint16_t));
+  if (e == hipSuccess) e = sc.get(&key, 64, true);
+  if (e == hipSuccess) e = sc.get(&inv, 64, true);
+  if (e == hipSuccess && !zero_page()) e = hipErrorOutOfMemory;
+  if (e == hipSuccess) {
+    launch_pack_upconv_dgrad_x3(wDev, wt, cin, f, s);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = run_up_bias_grad_x3(dY, ldd, offd, Pl * 4, f, partial, key, db, s);
+  if (e == hipSuccess) e = run_up_s2d_planes_x3(dY, ldd, offd, n, lh, lw, f, key, S, inv, s);
+  if (e == hipSuccess)
+    e = run_wgrad1_x3(S, rowsG, rowsG, reinterpret_cast<const float*>(inPlanes), cin, cin, (long)Pl, slab, slabFloats, dW, 1, f,
+                      inv, s);
+  if (e == hipSuccess)
+    e = run_gemm1x1_x3(wt, reinterpret_cast<const uint16_t*>(zero_page()), reinterpret_cast<const uint16_t*>(S),
+                       Pl * 4 * (size_t)f, (long)Pl, rowsG, cin, dIn, cin, 0, inv, "upconv_dgrad_f16x3", s, &structure);
+  const hipError_t es = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = es;
+  if (e == hipSuccess && invOut) e = hipMemcpy(invOut, inv, sizeof(float), hipMemcpyDeviceToHost);
+  if (structureOut) *structureOut = structure;
+  return op_status(e);
+}
+
+int unet_op_upconv_fwd_train_x3(int device, const uint16_t* x, size_t xLo, int n, int hh, int ww, int cin, const float* wDev,
+                                const float* biasDev, int cout, uint16_t* y, size_t yLo, int ldo, int coOff, int* pathOut,
+                                int* rangeOut, void* stream) {
+  if (ldo == 0) ldo = cout;
+  if (!x || !wDev || !biasDev || !y || n < 1 || hh < 1 || ww < 1 || cin < 64 || cin % 64 || cout < 64 || cout % 64 ||
+      cout > unet::UpconvX3Shape::MAX_COUT || xLo % 8 || yLo % 8 || ldo % 64 || coOff < 0 || coOff % 64 || coOff + cout > ldo)
+    return UNET_ERR_INVALID_ARG;
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  OpScratch sc;
+  sc.s = s;
+  TrainState T;
+  OpRangeScope range;
+  X3Path path;
+  uint16_t* wt = nullptr;
+  hipError_t e = op_ones_zeros(sc, T, cout);
+  if (e == hipSuccess) e = sc.get(&wt, x3_upconv_pack_halfs(cin, cout) * sizeof(uint16_t));
+  if (e == hipSuccess && !zero_page()) e = hipErrorOutOfMemory;
+  if (e == hipSuccess) {
+    launch_pack_upconv_x3(wDev, wt, cin, cout, s);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = range.arm();
+  if (e == hipSuccess) e = run_train_upconv_x3(&T, wt, biasDev, cin, cout, x, xLo, n, hh, ww, y, yLo, ldo, coOff, s, &path);
+  const hipError_t es = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = es;
+  if (e == hipSuccess) e = range.read(rangeOut);
+  T.ones = T.zeros = nullptr;   // owned by sc
+  path_to_ints(path, pathOut);
+  return op_status(e);
 }
 
 }  // extern "C"

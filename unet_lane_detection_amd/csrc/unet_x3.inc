@@ -1024,7 +1024,8 @@ hipError_t run_upconv_x3(const GemmOpX3& op, const uint16_t* zeros, const uint16
 // wt packed by pack_upconv_dgrad_x3_kernel; K % 64 == 0, nCols % 64 == 0
 hipError_t run_gemm1x1_x3(const uint16_t* wt, const uint16_t* zeros, const uint16_t* in, size_t inLo, long npix, int K,
                           int nCols, float* outF, int ldo, int coOff, const float* dynScale, const char* label,
-                          hipStream_t s) {
+                          hipStream_t s, int* structure = nullptr) {
+  // structure (test entry point): 2 = upconv_x3_r512.h, 1 = upconv_x3_ws.h, as X3Path::structure
   using S = unet::UpconvX3Shape;
   unet::UpconvX3Args a;
   a.in = in;
@@ -1052,9 +1053,12 @@ hipError_t run_gemm1x1_x3(const uint16_t* wt, const uint16_t* zeros, const uint1
   {
     hipError_t er = hipSuccess;
     if (launch_upconv_r512<1>(a, label, 2.0 * (double)npix * K * nCols, 4.0 * ((double)npix * K + (double)npix * nCols), s,
-                              &er))
+                              &er)) {
+      if (structure) *structure = 2;
       return er;
+    }
   }
+  if (structure) *structure = 1;
   auto kern = unet::upconv2x2_x3_ws_kernel<1>;
   hipError_t e = ensure_dyn_lds((const void*)kern, S::LDS_BYTES);
   if (e != hipSuccess) return e;
