@@ -363,23 +363,17 @@ int unet_op_head1x1(int device, const float* x_dev, int n, int h, int w, int c, 
                     float bias, float* logits_dev, void* stream);
 
 /* The same two operators in the split-operand tier (fp32 NHWC in and out; converted to / from fp16 hi + lo planes
- * internally).  cin, cout multiples of 64.  tile_width: 0 = automatic; 16 or 32 = force that pixel-tile shape of the
- * first kernel structure (csrc/conv_x3_ws.h); 28 (W % 28 == 0) or 14 (W == 14) = force the second structure
- * (csrc/conv_x3_r512.h; cout a multiple of 128; + 200 = its two-waves-along-the-pixels form even where cout is a
- * multiple of 256); 332 / 316 / 308 = the second structure's 7 x 32 / 14 x 16 / 28 x 8 pixel tiles (W a multiple of
- * 32 / 16 / 8, cout a multiple of 256); 532 = the 7 x 32 tile in the two-waves-along-the-pixels form (cout a multiple
- * of 128); 428 / 414 = csrc/conv_q8_r512.h (see unet_set_x3_cross_fp8); 628 / 632 = the third structure
- * (csrc/conv_x3_t448.h: 16 x 28 / 16 x 32 pixel tiles, W a multiple of 28 / 32, any cout that is a multiple of 64; the
- * network takes it by itself for the layers whose cout is 64 or 128); UNET_ERR_HIP if the forced structure does not
- * support the shape.
+ * internally).  cin, cout multiples of 64.  tile_width: 0 = the dispatch's own choice, else one of the forced forms of
+ * DESIGN.md section 4.15 ("The forced form"; csrc/unet_x3.inc, x3_decode_force); UNET_ERR_INVALID_ARG for any other value,
+ * UNET_ERR_HIP if the forced form does not support the shape.
  * y_pool_dev: optional (N,H/2,W/2,Cout) MaxPool2d(2,2) output (reference README.md:1429). */
 int unet_op_conv3x3_x3(int device, const float* x_dev, int n, int h, int w, int cin, const float* w_host,
                        const float* scale_host, const float* shift_host, int cout, int relu, int tile_width,
                        float* y_dev, float* y_pool_dev, void* stream);
 /* The network's last two layers as the split-operand tier runs them (reference README.md:1456-1457, :1447, :1481): a
  * 3x3 convolution to 64 channels + scale/shift (+ ReLU) with the 1x1 head (64 -> 1, bias) fused into its epilogue; the
- * 64-channel activation is never stored.  x (N,H,W,cin) fp32 -> logits (N,H,W).  tile_width 0 / 16 / 32: first
- * structure; 628 / 632: third structure. */
+ * 64-channel activation is never stored.  x (N,H,W,cin) fp32 -> logits (N,H,W).  tile_width: of the forced forms
+ *  only those with a fused-head instance, 0 / 16 / 32 / 628 / 632. */
 int unet_op_conv3x3_x3_head(int device, const float* x_dev, int n, int h, int w, int cin, const float* w_host,
                             const float* scale_host, const float* shift_host, int relu, int tile_width,
                             const float* head_w_host, float head_bias, float* logits_dev, void* stream);
@@ -488,6 +482,24 @@ int unet_op_upcat_conv3x3_x3(int device, const float* skip_dev, const float* x_d
  * class (0 = first row / column of the image, 1 = interior, 2 = last). */
 int unet_host_compose_upcat(const float* wt_host, const float* bt_host, const float* w3_host, int f, double* wp_out,
                             double* bias_out);
+/* Test hooks, host arithmetic only (no device is initialised): the plan the f16x3 dispatch makes (csrc/unet_x3.inc,
+ * x3_plan_conv / x3_plan_upconv; DESIGN.md, "f16x3 dispatch").  Everything the decision depends on is in the query, the
+ * A/B switches included, so the answer does not depend on the caller's environment.
+ * 3x3 convolution, query[22]: n, h, w, cin, cout, epilogue asked for (0 planes, 1 planes + pooled copy, 2 fused head,
+ *   3 fp32), tile_width, co_off, split-K scratch present, its size in floats, q-plane scratch present, fp8 fragments packed,
+ *   in_is_q, want_out_q, pool_src_q, pool_dst_q, BatchNorm statistics wanted, then the switches UNET_X3_FLAT, UNET_X3_R512,
+ *   UNET_X3_T448, UNET_X3_T448_C4 (1 = on, the default) and unet_set_x3_cross_fp8's mode.
+ *   plan_out[24]: the seven ints of path_out; grid; rows of fused statistics (0 = none); planes_to_q8 pass first; pooling
+ *   pass behind (0 none, 1 planes, 2 q8); split-K finish pass behind; the output's q plane written; valid (0: the forced
+ *   form does not fit or a q-plane input meets another form - everything else is then 0); N, H, imgH, tilesX, tilesY,
+ *   pixTiles, coTiles, coGroup, nChunks, kSplit as the kernel gets them.
+ * Transposed convolution, query[9]: n, h, w, cin, cout, co_off, want_out_q, unet_set_x3_upconv_r512's mode, 1 = the plain
+ *   GEMM of the backward pass on the same kernels (cin = K, cout = columns).  plan_out[16]: the first fourteen as above
+ *   (path waves = the (a,b) split), then pixTiles, coTiles.
+ * label_out (optional, label_cap >= 48): the profiler label of the plan's main kernel ("" where the caller names it).
+ * UNET_ERR_INVALID_ARG: a wrong array size, a non-positive shape or a tile_width outside the table. */
+int unet_host_plan_conv3x3_x3(const int* query, int n_query, int* plan_out, int n_plan, char* label_out, int label_cap);
+int unet_host_plan_upconv2x2_x3(const int* query, int n_query, int* plan_out, int n_plan, char* label_out, int label_cap);
 /* Process-wide switch for the composed decoder step in the f16x3 tier's forward (not the f16q8 tier, not training):
  * -1 = automatic (default) - the levels with f <= 128 on maps of width 28k with a work item for half of the CUs;
  * 0 = off: ConvTranspose2d + the 3x3 convolution as two kernels everywhere; 1 = wherever the shape rules allow.
@@ -515,7 +527,7 @@ int unet_set_x3_upconv_r512(int mode);
  * thread's forward computes); the first call after switching it on rebuilds the handle's operators with the extra weight
  * fragments (it synchronises the device: do not mix with HIP graphs captured from the same handle).  Returns the previous
  * setting.
- * unet_op_conv3x3_x3 runs the kernel directly with tile_width 428 (W % 28 == 0) / 414 (W == 14). */
+ * unet_op_conv3x3_x3 runs the kernel directly through the f16q8 forced forms of its tile_width. */
 int unet_set_x3_cross_fp8(int mode);
 
 /* Debug aid: during the next unet_train_forward_backward_* calls copy one internal buffer to dst_dev

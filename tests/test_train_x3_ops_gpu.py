@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import x3_model as M
+from x3_dispatch_queries import PATH, STAT_ROWS, VALID, ask, conv_query, switches_from_env
 from x3_gpu_helpers import ERR_HIP, ERR_INVALID_ARG, R512, T448, WS, GuardedF32, Planes, _p, path_str, seed_of, to_dev
 
 pytestmark = pytest.mark.gpu
@@ -63,6 +64,11 @@ def run_tconv(lib, w_dev, mode, packer, tw, shape, cout_op, *, planes=None, x32=
     stop_on_hip_error(lib, rc)
     assert rc == expect_rc, (rc, expect_rc, tw, shape, cout_op, mode)
     torch.cuda.synchronize()
+    if rc == 0:     # the host-side plan for the same query is what the launch reported
+        plan, _ = ask(lib, "conv", conv_query(n, h, wd, cin_op, cout_op, 3, tile_width=tw, co_off=off, stats=1 if stat else 0,
+                                              switches=switches_from_env()))
+        assert plan[VALID] == 1 and tuple(plan[PATH]) == tuple(path)[:7], (plan, tuple(path))
+        assert not stat or plan[STAT_ROWS] == rows.value, (plan, rows.value)
     return dict(out=out, path=tuple(path)[:7], inv=inv.value, rows=rows.value, stat=stat, range=rng.value)
 
 

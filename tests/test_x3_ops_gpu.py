@@ -19,6 +19,7 @@ import pytest
 import torch
 
 import x3_model as M
+from x3_dispatch_queries import PATH, VALID, ask, conv_query, switches_from_env
 from x3_gpu_helpers import (ERR_HIP, ERR_INVALID_ARG, R512, SENTINEL, T448, WS, Planes, _h, _p, path_str, seed_of,  # noqa: F401
                             to_dev)
 
@@ -98,6 +99,10 @@ def run_conv(lib, hi, lo, w, scale, shift, relu, tw, *, ldo=0, co_off=0, pool=Fa
         _h(head[0]) if head else None, head[1] if head else 0.0, thr, _p(logits), _p(probs), _p(mask), path, C.byref(rng), None)
     assert rc == expect_rc, (rc, tw, tuple(hi.shape), cout)
     torch.cuda.synchronize()
+    if rc == 0:     # the host-side plan for the same query is what the launch reported
+        plan, _ = ask(lib, "conv", conv_query(n, h, wd, cin, cout, 2 if head is not None else (1 if pool else 0), tile_width=tw,
+                                              co_off=co_off, split=1 if split_k else 0, switches=switches_from_env()))
+        assert plan[VALID] == 1 and tuple(plan[PATH]) == tuple(path)[:7], (plan, tuple(path))
     return dict(out=y, pool=yp, logits=logits, probs=probs, mask=mask, path=tuple(path)[:7], range=rng.value)
 
 

@@ -697,7 +697,7 @@ hipError_t run_train_conv_x3_planes(TrainState* T, const uint16_t* wt, int cin, 
                                     int hh, int ww, float* y, int ldo, int off, const char* label, hipStream_t s,
                                     const float* inv = nullptr, float* statPartial = nullptr, int* statRows = nullptr,
                                     int forceTw = 0, X3Path* path = nullptr) {
-  // forceTw / path: run_conv_x3's forced tile width and path report (the test entry point; the step passes neither)
+  // forceTw / path: the forced form and the path report of X3ConvOpts (the test entry point; the step passes neither)
   const size_t elems = (size_t)n * hh * ww * cin;
   GemmOpX3 op;   // borrowed pointers: never freed through this object
   op.taps = 9;
@@ -707,9 +707,16 @@ hipError_t run_train_conv_x3_planes(TrainState* T, const uint16_t* wt, int cin, 
   op.wt = const_cast<uint16_t*>(wt);
   op.scale = T->ones;
   op.shift = T->zeros;
-  const hipError_t e = run_conv_x3(op, reinterpret_cast<const uint16_t*>(zero_page()),
-                                   reinterpret_cast<const uint16_t*>(planes), elems, n, hh, ww, nullptr, 0, ldo, off, s,
-                                   nullptr, forceTw, y, label, inv, nullptr, statPartial, statRows, nullptr, nullptr, path);
+  const X3ConvIo io = x3_from(reinterpret_cast<const uint16_t*>(zero_page()), reinterpret_cast<const uint16_t*>(planes), elems,
+                              n, hh, ww).to(nullptr, 0, ldo, off);
+  X3ConvOpts o;
+  o.forceTw = forceTw;
+  o.outF = y;
+  o.label = label;
+  o.dynScale = inv;
+  o.statPartial = statPartial, o.statRows = statRows;
+  o.path = path;
+  const hipError_t e = run_conv_x3(op, io, o, s);
   op.wt = nullptr;
   op.scale = op.shift = nullptr;
   return e;
@@ -875,8 +882,8 @@ hipError_t run_train_upconv_x3(TrainState* T, const uint16_t* wt, const float* b
   op.wt = const_cast<uint16_t*>(wt);
   op.scale = T->ones;
   op.shift = const_cast<float*>(bias);
-  const hipError_t e = run_upconv_x3(op, reinterpret_cast<const uint16_t*>(zero_page()), in, inLo, n, h, w, out, outLo, ldo,
-                                     coOff, s, nullptr, path);
+  const hipError_t e = run_upconv_x3(op, x3_from(reinterpret_cast<const uint16_t*>(zero_page()), in, inLo, n, h, w)
+                                             .to(out, outLo, ldo, coOff), s, nullptr, path);
   op.wt = nullptr;
   op.scale = op.shift = nullptr;
   return e;
@@ -1296,9 +1303,9 @@ int train_forward_backward(unet_ctx* h, int n, int height, int width, const floa
       };
       if (!side) HIPCHK(h->err, up_wgrad(s));
       else if (train_side_mode() == 1 && (rc = side_up_wgrad())) return rc;
-      HIPCHK(h->err, run_gemm1x1_x3(U.x3Dgrad, reinterpret_cast<const uint16_t*>(zero_page()),
-                                    reinterpret_cast<const uint16_t*>(S), Pl * 4 * (size_t)f, (long)Pl, 4 * f, U.cin, gA,
-                                    U.cin, 0, inv, "upconv_dgrad_f16x3", s));
+      HIPCHK(h->err, run_gemm1x1_x3(U.x3Dgrad, x3_from(reinterpret_cast<const uint16_t*>(zero_page()), reinterpret_cast<const uint16_t*>(S),
+                                                       Pl * 4 * (size_t)f, n, lh, lw).to(nullptr, 0, U.cin),
+                                    4 * f, U.cin, gA, inv, "upconv_dgrad_f16x3", s));
       if (side && train_side_mode() != 1 && (rc = side_up_wgrad())) return rc;
       if (T->dbgStage == 200 + j)   // the fp32 form of S only exists for the snapshot
         hipLaunchKernelGGL(unet::space_to_depth_kernel, dim3(grid_for(Pl * 4 * (f / 4))), dim3(256), 0, s, ws + p.dCat[l],
@@ -1472,18 +1479,24 @@ int eval_unit(unet_ctx* h, ConvUnit& u, const float* in, const float* inPlanes, 
     op.wt = u.x3Fwd;
     op.scale = u.evScale;
     op.shift = u.evShift;
-    const uint16_t* zp = reinterpret_cast<const uint16_t*>(zero_page());
-    const uint16_t* ip = reinterpret_cast<const uint16_t*>(inPlanes);
-    hipError_t e;
+    X3ConvIo io = x3_from(reinterpret_cast<const uint16_t*>(zero_page()), reinterpret_cast<const uint16_t*>(inPlanes), P * u.cin,
+                          n, hh, ww);
+    X3ConvOpts co;
+    X3Fuse fz;
+    co.label = "eval_conv3x3_f16x3";
     if (o.planes) {
-      X3Fuse fz;
-      fz.pool = reinterpret_cast<uint16_t*>(o.pooled);
-      fz.poolLo = (P / 4) * (size_t)u.cout;
-      e = run_conv_x3(op, zp, ip, P * u.cin, n, hh, ww, reinterpret_cast<uint16_t*>(o.planes), P * (size_t)o.ldp, o.ldp,
-                      o.offp, s, o.pooled ? &fz : nullptr, 0, nullptr, o.pooled ? "eval_conv3x3_pool_f16x3" : "eval_conv3x3_f16x3");
+      io = io.to(reinterpret_cast<uint16_t*>(o.planes), P * (size_t)o.ldp, o.ldp, o.offp);
+      if (o.pooled) {
+        fz.pool = reinterpret_cast<uint16_t*>(o.pooled);
+        fz.poolLo = (P / 4) * (size_t)u.cout;
+        co.fuse = &fz;
+        co.label = "eval_conv3x3_pool_f16x3";
+      }
     } else {
-      e = run_conv_x3(op, zp, ip, P * u.cin, n, hh, ww, nullptr, 0, o.ld, o.off, s, nullptr, 0, o.f32, "eval_conv3x3_f16x3");
+      io = io.to(nullptr, 0, o.ld, o.off);
+      co.outF = o.f32;
     }
+    const hipError_t e = run_conv_x3(op, io, co, s);
     op.wt = nullptr;
     op.scale = op.shift = nullptr;
     HIPCHK(h->err, e);
@@ -2206,12 +2219,12 @@ int unet_op_train_conv3x3_x3(int device, const uint16_t* xPlanes, const float* x
                              int cin, int cout, const float* wDev, int mode, int packer, int tileWidth, float* y, int ldo,
                              int off, float* statPartialDev, int statCapRows, int* statRowsOut, float* invOut, int* pathOut,
                              int* rangeOut, void* stream) {
-  static const int kWidths[] = {0, 16, 32, 28, 14, 228, 214, 332, 316, 308, 532, 628, 632, 728};
+  X3Force force;   // (the f16q8 forms have no fp32 epilogue)
   if (ldo == 0) ldo = cout;
   if ((xPlanes == nullptr) == (xF32 == nullptr) || (scaled && !xF32) || !wDev || !y || n < 1 || hh < 1 || ww < 1 || cin < 64 ||
       cin % 64 || cin > 1024 || cout < 64 || cout % 64 || cout > unet::X3Shape<32>::MAX_COUT || (mode != 0 && mode != 1) ||
       (packer != 0 && packer != 1) || (packer == 1 && (reinterpret_cast<uintptr_t>(wDev) & 15)) ||
-      std::find(std::begin(kWidths), std::end(kWidths), tileWidth) == std::end(kWidths) || ldo % 64 || off < 0 || off % 64 ||
+      !x3_decode_force(tileWidth, &force) || force.family == kX3Q8 || ldo % 64 || off < 0 || off % 64 ||
       off + cout > ldo || (statPartialDev && (!statRowsOut || (size_t)statCapRows * 2 * cout > kPartialFloats)))
     return UNET_ERR_INVALID_ARG;
   // the epilogue writes its rows straight into the caller's buffer, so the room must be there before the structure and
@@ -2320,8 +2333,9 @@ int unet_op_upconv_bwd_x3(int device, const float* dY, int ldd, int offd, const 
     e = run_wgrad1_x3(S, rowsG, rowsG, reinterpret_cast<const float*>(inPlanes), cin, cin, (long)Pl, slab, slabFloats, dW, 1, f,
                       inv, s);
   if (e == hipSuccess)
-    e = run_gemm1x1_x3(wt, reinterpret_cast<const uint16_t*>(zero_page()), reinterpret_cast<const uint16_t*>(S),
-                       Pl * 4 * (size_t)f, (long)Pl, rowsG, cin, dIn, cin, 0, inv, "upconv_dgrad_f16x3", s, &structure);
+    e = run_gemm1x1_x3(wt, x3_from(reinterpret_cast<const uint16_t*>(zero_page()), reinterpret_cast<const uint16_t*>(S),
+                                   Pl * 4 * (size_t)f, n, lh, lw).to(nullptr, 0, cin),
+                       rowsG, cin, dIn, inv, "upconv_dgrad_f16x3", s, &structure);
   const hipError_t es = hipStreamSynchronize(s);
   if (e == hipSuccess) e = es;
   if (e == hipSuccess && invOut) e = hipMemcpy(invOut, inv, sizeof(float), hipMemcpyDeviceToHost);

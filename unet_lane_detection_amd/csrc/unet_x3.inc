@@ -299,23 +299,43 @@ int build_upconv_x3(std::string& err, GemmOpX3& op, const float* w, int cin, int
   return rc;
 }
 
-// Pixel-tile width of the persistent kernel for an H x W map: the shape that wastes fewer MFMAs on padding
-// n > 1 images whose height is not a multiple of the tile height are tiled as one tall image of n * h rows (the
-// kernel's FLAT instances), so only the last tile of the batch pads rows
-bool x3_flat_rows(int n, int h, int tw) {
-  static const bool on = [] {   // UNET_X3_FLAT=0: per-image tiles everywhere (A/B measurements)
-    const char* e = getenv("UNET_X3_FLAT");
-    return !(e && e[0] == '0');
+// ---- dispatch of the tier's 3x3 and transposed convolutions (DESIGN.md, section 4.15) ----
+// Which kernel runs, on which tiles and grid, is decided by x3_plan_conv / x3_plan_upconv: pure functions of integers.
+// run_conv_x3 / run_upconv_x3 fill the kernel arguments from the plan and launch it; forward_x3 asks the same functions
+// what a layer will do before it launches the layer's producer.
+
+// The A/B levers of the dispatch as a plan sees them.  x3_switches() reads them: the environment once per process, the
+// f16q8 switch per call.
+//   UNET_X3_FLAT=0     per-image tiles everywhere (default: n > 1 images whose height is no multiple of the tile height are
+//                      tiled as one tall image of n * h rows, the kernels' FLAT instances, so only the last tile pads rows)
+//   UNET_X3_R512=0     every layer stays off the second structure (conv_x3_r512.h)
+//   UNET_X3_T448=0     the 64- / 128-channel layers stay on the first two structures
+//   UNET_X3_T448_C4=0  the second structure instead of the third's 256-channel form where both apply (the third is 1.2 -
+//                      3.4 % faster per layer and has the pooled epilogue: profiles/r04/t448_c4_probe.txt)
+// f16q8 tier (conv_q8_r512.h): unet_set_x3_cross_fp8.  0 = off (the f16x3 tier as tested to 2e-4), 1 = the layers
+// that suit it (Cin % 64 == 0, Cout % 256 == 0, map width a multiple of 28 or 14, enough work items) form their two
+// cross terms on the fp8 matrix pipe
+struct X3Switches {
+  bool flat = true, r512 = true, t448 = true, t448c4 = true;
+  int crossFp8 = 0;
+};
+thread_local int g_x3CrossFp8 = 0;   // per calling thread: a caller's set / restore around its own forward cannot leak into another thread's
+X3Switches x3_switches() {
+  static const X3Switches env = [] {
+    auto on = [](const char* name) {
+      const char* e = getenv(name);
+      return !(e && e[0] == '0');
+    };
+    X3Switches s;
+    s.flat = on("UNET_X3_FLAT");
+    s.r512 = on("UNET_X3_R512");
+    s.t448 = on("UNET_X3_T448");
+    s.t448c4 = on("UNET_X3_T448_C4");
+    return s;
   }();
-  return on && n > 1 && h % (256 / tw) != 0;
-}
-int x3_tile_width(int h, int w, int n = 1) {
-  auto eff = [&](int tw) {
-    const int th = 256 / tw;
-    const double rows = x3_flat_rows(n, h, tw) ? (double)n * h / round_up(n * h, th) : (double)h / round_up(h, th);
-    return rows * w / (double)round_up(w, tw);
-  };
-  return eff(16) > eff(32) + 1e-9 ? 16 : 32;
+  X3Switches s = env;
+  s.crossFp8 = g_x3CrossFp8;
+  return s;
 }
 
 struct X3Fuse {
@@ -328,7 +348,7 @@ struct X3Fuse {
   uint8_t* mask = nullptr;
 };
 
-// Scratch of the split-K path (small batches): run_conv_x3 takes it when a layer has too few work items for the chip
+// Scratch of the split-K path (small batches): a layer with too few work items for the chip takes it
 constexpr size_t kSplitFloats = (size_t)256 * 256 * 64;
 struct X3SplitK {
   float* scratch = nullptr;   // kSplit x pixels x Cout partial sums
@@ -337,11 +357,12 @@ struct X3SplitK {
   const float* zerosF = nullptr;
 };
 
-// What run_conv_x3 / run_upconv_x3 launched (the plane-level test entry points report it; nothing reads it otherwise)
+enum { kX3Ws = 1, kX3R512 = 2, kX3T448 = 3, kX3Q8 = 4 };   // X3Path::structure
+// What a plan launches (the plane-level test entry points report it through path_out)
 struct X3Path {
   int structure = 0;   // 1 = conv_x3_ws.h / upconv_x3_ws.h, 2 = conv_x3_r512.h / upconv_x3_r512.h, 3 = conv_x3_t448.h, 4 = conv_q8_r512.h
   int tileW = 0;       // pixel-tile width
-  int epi = 0;         // the kernel's epilogue: 0 planes, 1 planes + fused 2x2 max-pool, 2 fused head, 3 fp32
+  int epi = 0;         // the kernel's epilogue: 0 planes, 1 planes + fused 2x2 max-pool, 2 fused head, 3 fp32, 4 (q8) hi + q planes
   int flat = 0;        // the batch tiled as one tall image
   int kSplit = 1;      // > 1: split-K partial sums + x3_splitk_finish_kernel
   int waves = 0;       // r512: waves along the pixels (1 / 2); t448: waves along the channels (1 / 2 / 4); upconv ws: abSplit
@@ -351,6 +372,7 @@ struct X3Path {
   }
 };
 
+// ---- the launches a plan can name: exactly the kernel instances the library carries ----
 template <int TW, int EPI, bool FLAT = false>
 hipError_t launch_conv_x3(const unet::ConvX3Args& a, int grid, hipStream_t s) {
   using S = unet::X3Shape<TW>;
@@ -359,6 +381,17 @@ hipError_t launch_conv_x3(const unet::ConvX3Args& a, int grid, hipStream_t s) {
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), (size_t)S::LDS_BYTES, s, a);
   return hipGetLastError();
+}
+template <int TW>
+hipError_t launch_conv_x3(const unet::ConvX3Args& a, int grid, int epi, bool flat, hipStream_t s) {
+  if (flat)
+    return epi == 0   ? launch_conv_x3<TW, 0, true>(a, grid, s)
+           : epi == 1 ? launch_conv_x3<TW, 1, true>(a, grid, s)
+                      : launch_conv_x3<TW, 3, true>(a, grid, s);
+  return epi == 0   ? launch_conv_x3<TW, 0>(a, grid, s)
+         : epi == 1 ? launch_conv_x3<TW, 1>(a, grid, s)
+         : epi == 2 ? launch_conv_x3<TW, 2>(a, grid, s)
+                    : launch_conv_x3<TW, 3>(a, grid, s);
 }
 
 // Second structure (conv_x3_r512.h): 224-pixel tiles of 8 x 28 or 16 x 14, one wave per SIMD
@@ -371,7 +404,6 @@ hipError_t launch_conv_r512(const unet::ConvX3Args& a, int grid, hipStream_t s) 
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), (size_t)S::LDS_BYTES, s, a);
   return hipGetLastError();
 }
-
 template <int TWX, int WPX>
 hipError_t launch_conv_r512(const unet::ConvX3Args& a, int grid, bool flat, bool f32out, hipStream_t s) {
   if (f32out) return flat ? launch_conv_r512<TWX, WPX, 3, true>(a, grid, s) : launch_conv_r512<TWX, WPX, 3, false>(a, grid, s);
@@ -404,28 +436,6 @@ hipError_t launch_conv_t448(const unet::ConvX3Args& a, int grid, int epi, bool f
        : epi == 1 ? launch_conv_t448<TWX, WCO, 1>(a, grid, s)
                   : launch_conv_t448<TWX, WCO, 3>(a, grid, s);
 }
-// UNET_X3_T448_C4=0: the second structure instead of the third's 256-channel form where both apply (A/B measurements;
-// the third is 1.2 - 3.4 % faster per layer and has the pooled epilogue: profiles/r04/t448_c4_probe.txt)
-bool x3_t448_c4_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("UNET_X3_T448_C4");
-    return e ? e[0] != '0' : true;
-  }();
-  return on;
-}
-// UNET_X3_T448=0 keeps the 64- / 128-channel layers on the first two structures (A/B measurements)
-bool x3_t448_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("UNET_X3_T448");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// f16q8 tier (conv_q8_r512.h): unet_set_x3_cross_fp8.  0 = off (the f16x3 tier as tested to 2e-4), 1 = the layers
-// that suit it (Cin % 64 == 0, Cout % 256 == 0, map width a multiple of 28 or 14, enough work items) form their two
-// cross terms on the fp8 matrix pipe
-thread_local int g_x3CrossFp8 = 0;   // per calling thread: a caller's set / restore around its own forward cannot leak into another thread's
 
 template <int TWX, int EPI, bool FLAT>
 hipError_t launch_conv_q8(const unet::ConvQ8Args& a, int grid, hipStream_t s) {
@@ -437,13 +447,38 @@ hipError_t launch_conv_q8(const unet::ConvQ8Args& a, int grid, hipStream_t s) {
   return hipGetLastError();
 }
 
-// which layers the second structure takes: UNET_X3_R512=0 keeps every layer on the first one (A/B measurements)
-bool x3_r512_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("UNET_X3_R512");
-    return !(e && e[0] == '0');
-  }();
-  return on;
+// The forced form of the test entry points' tile_width argument, decoded here and nowhere else (what each ABI integer
+// stands for: DESIGN.md, section 4.15, "The forced form")
+struct X3Force {
+  int family = 0;   // 0 = none, else X3Path::structure
+  int tileW = 0;
+  int waves = 0;    // 0 = the form's own choice
+};
+bool x3_decode_force(int code, X3Force* out) {
+  static const struct {
+    int code;
+    X3Force f;
+  } kForms[] = {{0, {0, 0, 0}},         {16, {kX3Ws, 16, 0}},     {32, {kX3Ws, 32, 0}},     {28, {kX3R512, 28, 0}},
+                {14, {kX3R512, 14, 0}}, {228, {kX3R512, 28, 2}},  {214, {kX3R512, 14, 2}},  {332, {kX3R512, 32, 1}},
+                {316, {kX3R512, 16, 1}}, {308, {kX3R512, 8, 1}},  {532, {kX3R512, 32, 2}},  {428, {kX3Q8, 28, 1}},
+                {414, {kX3Q8, 14, 1}},  {628, {kX3T448, 28, 0}},  {632, {kX3T448, 32, 0}},  {728, {kX3T448, 28, 4}}};
+  for (const auto& k : kForms)
+    if (k.code == code) {
+      if (out) *out = k.f;
+      return true;
+    }
+  return false;
+}
+
+// Pixel-tile width of the first structure for an H x W map: the shape that wastes fewer MFMAs on padding
+bool x3_flat_rows(int n, int h, int tw, bool flatOn) { return flatOn && n > 1 && h % (256 / tw) != 0; }
+int x3_tile_width(int h, int w, int n, bool flatOn) {
+  auto eff = [&](int tw) {
+    const int th = 256 / tw;
+    const double rows = x3_flat_rows(n, h, tw, flatOn) ? (double)n * h / round_up(n * h, th) : (double)h / round_up(h, th);
+    return rows * w / (double)round_up(w, tw);
+  };
+  return eff(16) > eff(32) + 1e-9 ? 16 : 32;
 }
 int x3_r512_tile_width(int w) {   // 0: no tile width of the second structure divides this map
   if (w % 28 == 0) return 28;
@@ -453,23 +488,239 @@ int x3_r512_tile_width(int w) {   // 0: no tile width of the second structure di
   if (w % 8 == 0) return 8;
   return 0;
 }
+inline int x3_grid(long items) { return (int)std::max<long>(8, std::min<long>(256, items / 8 * 8)); }
 
-// f16q8 tier: would run_conv_x3 take conv_q8_r512.h for this layer by itself (no forced tile width)?  The same conditions
-// as in run_conv_x3: the tier on, the fragments packed, a plain or pooled plane output, Cin % 64 == 0, Cout % 256 == 0, a
-// map width the 224 x 256 tiles divide, a work item for half of the CUs, and the 256-channel form preferred by the
-// balance heuristic (not the 14 x 14 layers at batch 256: accuracy margin, see there)
-bool x3_q8_auto(const GemmOpX3& op, int n, int h, int w, bool headFused, bool f32Out, bool pooled) {
-  if (g_x3CrossFp8 != 1 || !op.wq || f32Out || headFused || !x3_r512_enabled()) return false;
-  if (op.cin % 64 || op.cout % 256) return false;
-  const int twx = x3_r512_tile_width(w);
-  if (twx != 28 && twx != 14) return false;
-  const int thx = 224 / twx;
-  const bool flatR = n > 1 && h % thx != 0 && 2 * h >= thx;
-  const long tiles = flatR ? (long)((n * h + thx - 1) / thx) * (w / twx) : (long)n * ((h + thx - 1) / thx) * (w / twx);
-  auto balance = [](long items) { return (double)items / (double)((items + 255) / 256 * 256); };
-  const long i1 = tiles * (op.cout / 256), i2 = tiles * (op.cout / 128);
-  (void)pooled;
-  return balance(i1) >= 0.93 * balance(i2) && i1 >= 128;
+struct X3ConvQuery {
+  int n = 0, h = 0, w = 0, cin = 0, cout = 0;
+  int epi = 0;                // the epilogue asked for: 0 planes, 1 planes + pooled copy, 2 fused head, 3 fp32
+  X3Force force;
+  int coOff = 0;
+  bool splitScratch = false;  // split-K scratch handed over, splitFloats floats of it
+  size_t splitFloats = 0;
+  bool qScratch = false;      // f16q8: room for the input's q plane / the operator has its packed fp8 fragments
+  bool wq = false;
+  // f16q8, how the tensors pass between two convolutions of the tier (X3Q8Link)
+  bool inIsQ = false, wantOutQ = false, poolSrcQ = false, poolDstQ = false;
+  bool wantStats = false;     // fp32 epilogue: the caller takes fused BatchNorm partial sums if the structure has them
+  X3Switches sw;
+};
+struct X3ConvPlan {
+  bool valid = false;         // false: a forced form that does not fit the shape, or a q-plane input off the q8 form
+  X3Path path;
+  int N = 0, H = 0, imgH = 0, tilesX = 0, tilesY = 0, pixTiles = 0, coTiles = 0, coGroup = 0, nChunks = 0, kSplit = 1;
+  int grid = 0;
+  int statRows = 0;           // > 0: the epilogue writes that many rows of BatchNorm partial sums
+  bool toQ8Pass = false;      // planes_to_q8_kernel runs first
+  int poolPass = 0;           // 1: maxpool2x2_planes_kernel follows, 2: maxpool2x2_planes_q8_kernel
+  bool finishPass = false;    // x3_splitk_finish_kernel follows
+  bool outQ = false;          // the output's q plane is written in its lo plane's place
+  void tiles(int n, int h, int w, int tw, int th, bool flat) {
+    N = flat ? 1 : n;
+    H = flat ? n * h : h;
+    imgH = h;
+    tilesX = (w + tw - 1) / tw;
+    tilesY = (H + th - 1) / th;
+    pixTiles = N * tilesY * tilesX;
+  }
+};
+
+// Precedence: third structure, f16q8 form, second structure, split-K on the first structure, the first structure.  A
+// forced form never falls through to the first structure.
+X3ConvPlan x3_plan_conv(const X3ConvQuery& q) {
+  X3ConvPlan p;
+  const int n = q.n, h = q.h, w = q.w, cin = q.cin, cout = q.cout, epi = q.epi;
+  const X3Force& f = q.force;
+  const bool unforced = f.family == 0;
+  const bool stats = q.wantStats && epi == 3;
+  p.nChunks = cin / 32;
+  // ---- third structure (conv_x3_t448.h): forced (16-row tiles, 64 or 128 channels per block; 8-row tiles, 256 channels
+  //      per block), or by itself: the 64- / 128-channel form for the layers whose Cout is no multiple of 256 (the 224 x 224
+  //      and 112 x 112 levels), the 256-channel form for the others on maps of width 28k (56 x 56, 28 x 28; heights that
+  //      are no multiple of 8 as one tall image), wherever its tiles are filled to >= 90 % and there is a work item for at
+  //      least half of the CUs.  Plane, pooled and fp32 epilogues; the fused head with Cout = 64. ----
+  {
+    const bool forcedT = f.family == kX3T448;
+    const bool forcedC4 = forcedT && f.waves == 4;
+    const int twt = forcedT ? f.tileW : (w % 28 == 0 ? 28 : (w % 32 == 0 ? 32 : 0));
+    const bool c4 = forcedC4 || (!forcedT && cout % 256 == 0);
+    // waves along the channels: 4 (256 per block, 8-row tiles), 2 (128 per block where the 16 x 28 tile's 14 fragments
+    // per wave fit the registers), 1 (64 per block)
+    const int wco = c4 ? 4 : (twt == 28 && cout % 128 == 0 && epi != 2) ? 2 : 1;
+    const int tht = c4 ? 8 : 16;
+    const bool shapeT = twt != 0 && w % twt == 0 && cin % 32 == 0 && cout % (64 * wco) == 0 && (epi != 2 || cout == 64) &&
+                        (epi != 1 || (h % 2 == 0 && w % 2 == 0)) && !(c4 && (twt != 28 || epi == 2));
+    const bool flatT = c4 && n > 1 && h % tht != 0 && 2 * h >= tht;
+    const int tilesYT = flatT ? (n * h + tht - 1) / tht : (h + tht - 1) / tht;
+    const long itemsT = shapeT ? (long)(flatT ? 1 : n) * tilesYT * (w / twt) * (cout / (64 * wco)) : 0;
+    const bool fillT = flatT || 10 * h >= 9 * tht * tilesYT;
+    // (the 256-channel form steps aside for the f16q8 tier's own form)
+    const bool autoT = unforced && (c4 ? q.sw.t448c4 && q.sw.r512 : q.sw.t448) && itemsT >= 128 && fillT && !q.inIsQ &&
+                       !(c4 && q.sw.crossFp8 == 1 && q.qScratch);
+    if (shapeT && (forcedT || autoT)) {
+      const int coTiles = cout / (64 * wco);
+      int grid = x3_grid(itemsT);
+      if (stats)   // a block must keep ONE channel group for its per-channel sums: the grid a multiple of the groups' count
+        while (grid > 0 && grid % coTiles) grid -= 8;
+      if (grid > 0) {
+        p.tiles(n, h, w, twt, tht, flatT);
+        p.coTiles = p.coGroup = coTiles;
+        p.grid = grid;
+        p.statRows = stats ? grid * (4 / wco) : 0;
+        p.path.set(kX3T448, twt, epi, flatT, 1, wco, false);
+        p.valid = true;
+        return p;
+      }
+    }
+    if (forcedT) return p;
+  }
+  // ---- second structure and the f16q8 form on its tiles: forced, or by itself for every layer it supports once there
+  //      is a work item for at least half of the CUs ----
+  {
+    // tile width by the map's width: 28 (224, 112, 56, 28), 14, else 32 / 16 / 8 (the 640 x 640 configuration's 160-, 80-
+    // and 40-wide levels; 256-channel form only)
+    const bool forced = f.family == kX3R512;
+    const bool forcedW2 = forced && f.waves == 2;
+    const int twxRaw = forced ? f.tileW : x3_r512_tile_width(w);
+    const int twx = twxRaw ? twxRaw : 28;             // (no width fits: shapeOk below is false)
+    const bool narrowOnly = twx != 28 && twx != 14 && twx != 32;   // widths without the two-wave form
+    const bool narrow = twx != 28 && twx != 14;
+    const int thx = 224 / twx;
+    const bool flatR = n > 1 && h % thx != 0 && 2 * h >= thx;
+    const long tiles = flatR ? (long)((n * h + thx - 1) / thx) * (w / twx) : (long)n * ((h + thx - 1) / thx) * (w / twx);
+    // 256-channel block tiles (one wave per 64 channels) where Cout allows, unless the 128-channel form fills the
+    // chip's 256 CUs so much more evenly that it wins although its loop is ~7 % slower (the 14 x 14 layers at batch 256:
+    // 896 items = 3.5 per CU against 1792 = 7 per CU)
+    auto balance = [](long items) { return (double)items / (double)((items + 255) / 256 * 256); };
+    int wpx = 2;
+    if (cout % 256 == 0 && !forcedW2) {
+      const long i1 = tiles * (cout / 256), i2 = tiles * (cout / 128);
+      wpx = (forced || narrow || balance(i1) >= 0.93 * balance(i2)) ? 1 : 2;
+    }
+    const long items = tiles * (cout / (256 / wpx));
+    // a pooled layer of the two-wave form stays on the first structure's fused epilogue (measured at 112 x 112, batch
+    // 256: 2.15 ms fused against 2.04 + 0.42 ms with the separate pooling pass; at Cout >= 256 the second structure wins
+    // with the pass included: 1.95 against 2.12 ms, 1.72 against 2.13 ms)
+    const bool autoOk = unforced && q.sw.r512 && items >= 128 && !(epi == 1 && wpx == 2);
+    const bool shapeOk = twxRaw != 0 && w % twx == 0 && (twx != 14 || w == 14) && cin % 32 == 0 &&
+                         cout % (narrowOnly ? 256 : 128) == 0 && !(narrowOnly && wpx != 1);
+    const bool q8Forced = f.family == kX3Q8;
+    const int tq = q8Forced ? f.tileW : twx;
+    const bool q8Shape = q.qScratch && q.wq && epi != 3 && epi != 2 && cin % 64 == 0 && cout % 256 == 0 &&
+                         (tq == 28 ? w % 28 == 0 : w == 14);
+    // by itself: the tier on, and the layer one the second structure would run as 224 x 256 tiles (not where the balance
+    // rule picked the 128-channel form - the 14 x 14 layers at batch 256: with them the tier's logit error against the
+    // f16x3 tier reaches 1.0e-3 over 256 frames, without them 9.2e-4 (7.8e-4 against the reference's golden logits): the
+    // margin is kept)
+    const bool q8Auto = q.sw.crossFp8 == 1 && shapeOk && autoOk && wpx == 1 && !narrow;
+    if (q.inIsQ && !(q8Shape && q8Auto)) return p;   // the input has no lo plane
+    if (q8Shape && (q8Forced || q8Auto)) {
+      const int thq = 224 / tq;
+      const bool flatQ = n > 1 && h % thq != 0 && 2 * h >= thq;
+      p.tiles(n, h, w, tq, thq, flatQ);
+      p.coTiles = p.coGroup = cout / 256;
+      p.grid = x3_grid((long)p.pixTiles * p.coTiles);
+      p.toQ8Pass = !q.inIsQ;
+      p.outQ = q.wantOutQ && epi == 0 && q.coOff % 32 == 0;
+      if (epi == 1) p.poolPass = ((q.poolSrcQ || q.poolDstQ) && q.coOff % 32 == 0) ? 2 : 1;
+      p.path.set(kX3Q8, tq, p.outQ ? 4 : 0, flatQ, 1, 1, epi == 1);
+      p.valid = true;
+      return p;
+    }
+    if (q8Forced) return p;
+    if (epi != 2 && shapeOk && (forced || autoOk)) {
+      p.tiles(n, h, w, twx, thx, flatR);
+      p.coTiles = p.coGroup = cout / (256 / wpx);
+      p.grid = x3_grid(items);
+      p.statRows = stats ? p.grid * wpx : 0;
+      p.poolPass = epi == 1 ? 1 : 0;   // (this structure has no fused pooling epilogue)
+      p.path.set(kX3R512, twx, epi == 3 ? 3 : 0, flatR, 1, wpx, epi == 1);
+      p.valid = true;
+      return p;
+    }
+    if (forced) return p;
+  }
+  // ---- first structure (conv_x3_ws.h); the fused-head epilogue (224 x 224 only) has no FLAT instance ----
+  const int tw = f.family == kX3Ws ? f.tileW : x3_tile_width(h, w, n, q.sw.flat);
+  const bool flat = x3_flat_rows(n, h, tw, q.sw.flat) && epi != 2;
+  p.tiles(n, h, w, tw, 256 / tw, flat);
+  p.coTiles = cout / 64;
+  p.coGroup = 1;
+  for (int g : {8, 4, 2})
+    if (p.coTiles % g == 0) {
+      p.coGroup = g;
+      break;
+    }
+  // Split-K: with fewer work items than half of the CUs (single frames: a 14x14 map is one pixel tile), the input
+  // channels are divided over kSplit items per tile; the items write raw fp32 partial sums (EPI 3, unit scale) and
+  // x3_splitk_finish_kernel adds them, applies scale / shift / ReLU and writes the planes (+ the pooled copy).
+  const long items = (long)p.pixTiles * p.coTiles;
+  int kSplit = 1;
+  if (q.splitScratch && epi != 3 && epi != 2 && cout <= 1024) {
+    const int chunks = cin / 32;
+    while (items * kSplit * 2 <= 256 && (chunks / (kSplit * 2)) >= 2 && (chunks % (kSplit * 4)) == 0 &&
+           (size_t)(kSplit * 2) * (size_t)n * h * w * cout <= q.splitFloats)
+      kSplit *= 2;
+    if (items > 128) kSplit = 1;
+  }
+  p.kSplit = kSplit;
+  p.nChunks = cin / 32 / kSplit;   // even: chunks are consumed in pairs
+  p.grid = x3_grid(items * kSplit);
+  p.finishPass = kSplit > 1;
+  p.poolPass = kSplit > 1 && epi == 1 ? 1 : 0;
+  p.path.set(kX3Ws, tw, kSplit > 1 ? 0 : epi, flat, kSplit, 0, p.poolPass != 0);
+  p.valid = true;
+  return p;
+}
+
+// The profiler label of a plan's main kernel: one per template instance, so that bench.py's per-kernel figures line up
+// with rocprofv3's kernel names (bench.py:rocprof_name parses it)
+void x3_conv_label(const X3ConvPlan& p, char* buf, size_t cap) {
+  const X3Path& k = p.path;
+  const char* fl = k.flat ? "_flat" : "";
+  switch (k.structure) {
+    case kX3T448: snprintf(buf, cap, "conv3x3_t448_f16x3_t%d_c%d_e%d%s", k.tileW, k.waves, k.epi, fl); break;
+    case kX3Q8: snprintf(buf, cap, "conv3x3_q8_f16q8_t%d%s%s", k.tileW, p.outQ ? "_q" : "", fl); break;
+    case kX3R512: snprintf(buf, cap, "conv3x3_r512_f16x3_t%d_w%d_e%d%s", k.tileW, k.waves, k.epi, fl); break;
+    case kX3Ws:
+      if (k.kSplit > 1)
+        snprintf(buf, cap, "conv3x3_ws_f16x3_splitk");
+      else
+        snprintf(buf, cap, "conv3x3_ws_f16x3_tw%d_e%d%s", k.tileW, k.epi, fl);
+      break;
+    default: snprintf(buf, cap, "%s", ""); break;
+  }
+}
+
+hipError_t launch_conv_plan(const X3ConvPlan& p, const unet::ConvQ8Args& a, hipStream_t s) {
+  const X3Path& k = p.path;
+  const int grid = p.grid, tw = k.tileW;
+  const bool flat = k.flat != 0;
+  switch (k.structure) {
+    case kX3T448:
+      if (tw == 32) return launch_conv_t448<32, 1>(a, grid, k.epi, false, s);
+      return k.waves == 4   ? launch_conv_t448<28, 4>(a, grid, k.epi, flat, s)
+             : k.waves == 2 ? launch_conv_t448<28, 2>(a, grid, k.epi, false, s)
+                            : launch_conv_t448<28, 1>(a, grid, k.epi, false, s);
+    case kX3Q8:
+      if (tw == 14) return k.epi == 4 ? launch_conv_q8<14, 4, true>(a, grid, s) : launch_conv_q8<14, 0, true>(a, grid, s);
+      if (k.epi == 4) return flat ? launch_conv_q8<28, 4, true>(a, grid, s) : launch_conv_q8<28, 4, false>(a, grid, s);
+      return flat ? launch_conv_q8<28, 0, true>(a, grid, s) : launch_conv_q8<28, 0, false>(a, grid, s);
+    case kX3R512: {
+      const bool f32 = k.epi == 3, w1 = k.waves == 1;
+      switch (tw) {
+        case 28: return w1 ? launch_conv_r512<28, 1>(a, grid, flat, f32, s) : launch_conv_r512<28, 2>(a, grid, flat, f32, s);
+        case 14: return w1 ? launch_conv_r512<14, 1>(a, grid, flat, f32, s) : launch_conv_r512<14, 2>(a, grid, flat, f32, s);
+        case 32: return w1 ? launch_conv_r512<32, 1>(a, grid, flat, f32, s) : launch_conv_r512<32, 2>(a, grid, flat, f32, s);
+        case 16: return launch_conv_r512<16, 1>(a, grid, flat, f32, s);
+        default: return launch_conv_r512<8, 1>(a, grid, flat, f32, s);
+      }
+    }
+    case kX3Ws: {
+      const int epi = k.kSplit > 1 ? 3 : k.epi;   // split-K items write raw fp32 partial sums
+      return tw == 32 ? launch_conv_x3<32>(a, grid, epi, flat, s) : launch_conv_x3<16>(a, grid, epi, flat, s);
+    }
+    default: return hipErrorInvalidValue;
+  }
 }
 
 // f16q8 tier: how a tensor passes between two convolutions of the tier.  inIsQ: the input's lo-plane region already holds
@@ -484,440 +735,151 @@ struct X3Q8Link {
   bool poolSrcQ = false, poolDstQ = false, pooledQ = false, srcQDone = false;
 };
 
-// in: planes (N,H,W,op.cin) -> out planes with pixel stride ldo at channel offset coOff.  Exactly one of the fusions
-// in `fuse` (pool or head) may be requested; both are always possible for the shapes this tier accepts.
-hipError_t run_conv_x3(const GemmOpX3& op, const uint16_t* zeros, const uint16_t* in, size_t inLo, int n, int h, int w,
-                       uint16_t* out, size_t outLo, int ldo, int coOff, hipStream_t s, const X3Fuse* fuse = nullptr,
-                       int forceTw = 0, float* outF = nullptr, const char* label = nullptr,
-                       const float* dynScale = nullptr, const X3SplitK* splitK = nullptr, float* statPartial = nullptr,
-                       int* statRows = nullptr, uint8_t* qScratch = nullptr, X3Q8Link* q8Link = nullptr,
-                       X3Path* path = nullptr) {
-  // qScratch (f16q8 tier): room for the input's q plane (n * h * w * cin * 2 bytes); with it, op.wq and the tier switched
-  // on, a layer the second structure would run as 224 x 256 tiles runs on conv_q8_r512.h instead (forceTw 428 / 414
-  // force it)
-  // statPartial / statRows (training forward, fp32 output): if the layer runs on the second structure, its epilogue
-  // also produces the BatchNorm statistics' per-block sums (ConvX3Args::statPartial) and *statRows is their row count;
-  // otherwise *statRows = 0 and the caller runs its own statistics pass
-  if (statRows) *statRows = 0;
-  unet::ConvX3Args a;
-  a.statPartial = nullptr;
-  a.kSplit = 1;
-  a.chunksTotal = op.cin / 32;
-  a.splitStride = 0;
-  a.outF = outF;
-  a.dynScale = dynScale;
-  a.err = g_errWord ? g_errWord : op_err_word();
-  a.in = in;
-  a.inLo = inLo;
-  a.wt = op.wt;
-  a.zeros = zeros;
-  a.scale = op.scale;
-  a.shift = op.shift;
-  a.out = out;
-  a.outLo = outLo;
-  a.N = n;
-  a.H = h;
-  a.W = w;
-  a.Cin = op.cin;
-  a.Cout = op.cout;
-  a.ldo = ldo;
-  a.co_off = coOff;
-  const int tw = (forceTw == 16 || forceTw == 32) ? forceTw : x3_tile_width(h, w, n);
-  const int th = 256 / tw;
-  a.tilesX = (w + tw - 1) / tw;
-  a.tilesY = (h + th - 1) / th;
-  a.nChunks = op.cin / 32;
-  a.relu = op.relu;
-  a.pixTiles = n * a.tilesY * a.tilesX;
-  a.imgH = h;
-  // the fused-head epilogue (224 x 224 only) has no FLAT instance
-  const bool flat = x3_flat_rows(n, h, tw) && !(fuse && fuse->headW);
-  if (flat) {   // one tall image: see ConvX3Args::imgH
-    a.N = 1;
-    a.H = n * h;
-    a.tilesY = (n * h + th - 1) / th;
-    a.pixTiles = a.tilesY * a.tilesX;
+// The tensors of one convolution: planes (n,h,w,op.cin) in -> planes out with pixel stride ldo at channel offset coOff
+// (out may be null where the epilogue writes no planes: fused head, fp32 output)
+struct X3ConvIo {
+  const uint16_t* zeros = nullptr;   // >= 64 zero halfs
+  const uint16_t* in = nullptr;      // hi plane; the lo plane inLo halfs behind it
+  size_t inLo = 0;
+  int n = 0, h = 0, w = 0;
+  uint16_t* out = nullptr;
+  size_t outLo = 0;
+  int ldo = 0, coOff = 0;
+  X3ConvIo to(uint16_t* o, size_t oLo, int ld, int off = 0) const {
+    X3ConvIo r = *this;
+    r.out = o, r.outLo = oLo, r.ldo = ld, r.coOff = off;
+    return r;
   }
-  a.coTiles = op.cout / 64;
-  a.coGroup = 1;
-  for (int g : {8, 4, 2})
-    if (a.coTiles % g == 0) {
-      a.coGroup = g;
-      break;
-    }
-  a.pool = nullptr;
-  a.poolLo = 0;
-  a.headW = nullptr;
-  a.headB = a.headThr = 0.f;
-  a.logits = a.probs = nullptr;
-  a.mask = nullptr;
-  int epi = 0;
-  if (fuse && fuse->pool) {
-    a.pool = fuse->pool;
-    a.poolLo = fuse->poolLo;
-    epi = 1;
-  } else if (fuse && fuse->headW) {
-    a.headW = fuse->headW;
-    a.headB = fuse->headB;
-    a.headThr = fuse->headThr;
-    a.logits = fuse->logits;
-    a.probs = fuse->probs;
-    a.mask = fuse->mask;
-    epi = 2;
-  }
-  if (outF) epi = 3;   // fp32 output (training)
-  // ---- third structure (conv_x3_t448.h): forceTw 628 / 632 (16-row tiles, 64 or 128 channels per block) / 728 (8-row
-  //      tiles, 256 channels per block), or by itself: the 64- / 128-channel form for the layers whose Cout is no multiple
-  //      of 256 (the 224 x 224 and 112 x 112 levels), the 256-channel form for the others on maps of width 28k (56 x 56,
-  //      28 x 28; heights that are no multiple of 8 as one tall image), wherever its tiles are filled to >= 90 % and there
-  //      is a work item for at least half of the CUs.  Plane, pooled and fp32 epilogues; the fused head with Cout = 64. ----
-  {
-    const bool forcedT = forceTw == 628 || forceTw == 632 || forceTw == 728;
-    const bool forcedC4 = forceTw == 728;
-    const int twt = forcedT ? (forcedC4 ? 28 : forceTw - 600) : (w % 28 == 0 ? 28 : (w % 32 == 0 ? 32 : 0));
-    const bool c4 = forcedC4 || (!forcedT && op.cout % 256 == 0);
-    // waves along the channels: 4 (256 per block, 8-row tiles), 2 (128 per block where the 16 x 28 tile's 14 fragments
-    // per wave fit the registers), 1 (64 per block)
-    const int wco = c4 ? 4 : (twt == 28 && op.cout % 128 == 0 && epi != 2) ? 2 : 1;
-    const int tht = c4 ? 8 : 16;
-    const bool shapeT = twt != 0 && w % twt == 0 && op.cin % 32 == 0 && op.cout % (64 * wco) == 0 && (epi != 2 || op.cout == 64) &&
-                        (epi != 1 || (h % 2 == 0 && w % 2 == 0)) && !(c4 && (twt != 28 || epi == 2));
-    const bool flatT = c4 && n > 1 && h % tht != 0 && 2 * h >= tht;
-    const int tilesYT = flatT ? (n * h + tht - 1) / tht : (h + tht - 1) / tht;
-    const long itemsT = shapeT ? (long)(flatT ? 1 : n) * tilesYT * (w / twt) * (op.cout / (64 * wco)) : 0;
-    const bool fillT = flatT || 10 * h >= 9 * tht * tilesYT;
-    const bool autoT = forceTw == 0 && (c4 ? x3_t448_c4_enabled() && x3_r512_enabled() : x3_t448_enabled()) && itemsT >= 128 &&
-                       fillT && !(q8Link && q8Link->inIsQ) && !(c4 && g_x3CrossFp8 == 1 && qScratch);
-    if (shapeT && (forcedT || autoT)) {
-      unet::ConvX3Args b = a;
-      b.tilesX = w / twt;
-      b.tilesY = tilesYT;
-      b.N = n;
-      b.H = h;
-      b.imgH = h;
-      if (flatT) {
-        b.N = 1;
-        b.H = n * h;
-      }
-      b.pixTiles = b.N * b.tilesY * b.tilesX;
-      b.coTiles = op.cout / (64 * wco);
-      b.coGroup = b.coTiles;
-      int grid = (int)std::max<long>(8, std::min<long>(256, itemsT / 8 * 8));
-      if (outF && statPartial && statRows) {
-        // a block must keep ONE channel group for its per-channel sums: the grid a multiple of the groups' count
-        while (grid > 0 && grid % b.coTiles) grid -= 8;
-      }
-      static const char* const kLabelT[2][3][4] = {
-          {{"conv3x3_t448_f16x3_t28_c1_e0", "conv3x3_t448_f16x3_t28_c1_e1", "conv3x3_t448_f16x3_t28_c1_e2",
-            "conv3x3_t448_f16x3_t28_c1_e3"},
-           {"conv3x3_t448_f16x3_t28_c2_e0", "conv3x3_t448_f16x3_t28_c2_e1", "conv3x3_t448_f16x3_t28_c2_e2",
-            "conv3x3_t448_f16x3_t28_c2_e3"},
-           {"conv3x3_t448_f16x3_t28_c4_e0", "conv3x3_t448_f16x3_t28_c4_e1", "conv3x3_t448_f16x3_t28_c4_e2",
-            "conv3x3_t448_f16x3_t28_c4_e3"}},
-          {{"conv3x3_t448_f16x3_t32_c1_e0", "conv3x3_t448_f16x3_t32_c1_e1", "conv3x3_t448_f16x3_t32_c1_e2",
-            "conv3x3_t448_f16x3_t32_c1_e3"},
-           {"", "", "", ""},
-           {"", "", "", ""}}};
-      static const char* const kLabelTF[4] = {"conv3x3_t448_f16x3_t28_c4_e0_flat", "conv3x3_t448_f16x3_t28_c4_e1_flat", "",
-                                              "conv3x3_t448_f16x3_t28_c4_e3_flat"};
-      if (grid > 0) {
-        const double pxT = (double)n * h * w;
-        prof_begin(label ? label : (flatT ? kLabelTF[epi] : kLabelT[twt == 32][wco == 4 ? 2 : wco - 1][epi]),
-                   2.0 * pxT * 9 * op.cin * op.cout,
-                   4.0 * (pxT * op.cin + pxT * op.cout * (epi == 2 ? 0.0 : (epi == 1 ? 1.25 : 1.0)) + 9.0 * op.cin * op.cout), s);
-        if (outF && statPartial && statRows) {
-          const int rowsT = grid * (4 / wco);
-          const hipError_t em = hipMemsetAsync(statPartial, 0, (size_t)rowsT * 2 * op.cout * sizeof(float), s);
-          if (em != hipSuccess) return em;
-          b.statPartial = statPartial;
-          *statRows = rowsT;
-        }
-        hipError_t e;
-        if (twt == 28)
-          e = wco == 4   ? launch_conv_t448<28, 4>(b, grid, epi, flatT, s)
-              : wco == 2 ? launch_conv_t448<28, 2>(b, grid, epi, false, s)
-                         : launch_conv_t448<28, 1>(b, grid, epi, false, s);
-        else
-          e = launch_conv_t448<32, 1>(b, grid, epi, false, s);
-        prof_end(s);
-        if (e != hipSuccess) return e;
-        if (path) path->set(3, twt, epi, flatT, 1, wco, false);
-        return hipGetLastError();
-      }
-    }
-    if (forcedT) return hipErrorInvalidValue;
-  }
-  // ---- second structure: forceTw 28 / 14 (+ 200: two waves along the pixels even where Cout % 256 == 0), or by
-  //      itself for every layer it supports once there is a work item for at least half of the CUs ----
-  {
-    // tile width by the map's width: 28 (224, 112, 56, 28), 14, else 32 / 16 / 8 (the 640 x 640 configuration's 160-, 80-
-    // and 40-wide levels; 256-channel form only).  forceTw 300 + width forces one of the latter
-    // forceTw 532: the 7 x 32 tile in its two-wave form
-    const bool forcedN2 = forceTw == 532;
-    const int ftw = forcedN2 ? 32 : (forceTw >= 300 ? forceTw - 300 : (forceTw >= 200 ? forceTw - 200 : forceTw));
-    const bool forced = forcedN2 || (forceTw >= 300 ? (ftw == 32 || ftw == 16 || ftw == 8) : (ftw == 28 || ftw == 14));
-    const int twxRaw = forced ? ftw : x3_r512_tile_width(w);
-    const int twx = twxRaw ? twxRaw : 28;             // (no width fits: shapeOk below is false)
-    const bool narrowOnly = twx != 28 && twx != 14 && twx != 32;   // widths without the two-wave form
-    const bool narrow = twx != 28 && twx != 14;
-    const int thx = 224 / twx;
-    const bool flatR = n > 1 && h % thx != 0 && 2 * h >= thx;
-    const long tiles = flatR ? (long)((n * h + thx - 1) / thx) * (w / twx) : (long)n * ((h + thx - 1) / thx) * (w / twx);
-    // 256-channel block tiles (one wave per 64 channels) where Cout allows, unless the 128-channel form fills the
-    // chip's 256 CUs so much more evenly that it wins although its loop is ~7 % slower (the 14 x 14 layers at batch 256:
-    // 896 items = 3.5 per CU against 1792 = 7 per CU)
-    auto balance = [](long items) { return (double)items / (double)((items + 255) / 256 * 256); };
-    int wpx = 2;
-    if (op.cout % 256 == 0 && (forceTw < 200 || forceTw >= 300) && !forcedN2) {
-      const long i1 = tiles * (op.cout / 256), i2 = tiles * (op.cout / 128);
-      wpx = (forced || narrow || balance(i1) >= 0.93 * balance(i2)) ? 1 : 2;
-    }
-    const long items = tiles * (op.cout / (256 / wpx));
-    // a pooled layer of the two-wave form stays on the first structure's fused epilogue (measured at 112 x 112, batch
-    // 256: 2.15 ms fused against 2.04 + 0.42 ms with the separate pooling pass; at Cout >= 256 the second structure wins
-    // with the pass included: 1.95 against 2.12 ms, 1.72 against 2.13 ms)
-    const bool autoOk = forceTw == 0 && x3_r512_enabled() && items >= 128 && !(epi == 1 && wpx == 2);
-    const bool shapeOk = twxRaw != 0 && w % twx == 0 && (twx != 14 || w == 14) && op.cin % 32 == 0 &&
-                         op.cout % (narrowOnly ? 256 : 128) == 0 && !(narrowOnly && wpx != 1);
-    const bool q8Forced = forceTw == 428 || forceTw == 414;
-    const int q8Twx = q8Forced ? forceTw - 400 : twx;
-    const bool q8Shape = qScratch && op.wq && !outF && epi != 2 && op.cin % 64 == 0 && op.cout % 256 == 0 &&
-                         (q8Twx == 28 ? w % 28 == 0 : w == 14);
-    // (not where the balance heuristic above picked the 128-channel form - the 14 x 14 layers at batch 256: with them the
-    // tier's logit error against the f16x3 tier reaches 1.0e-3 over 256 frames, without them 9.2e-4 (7.8e-4 against the
-    // reference's golden logits): the margin is kept)
-    const bool q8Auto = forceTw == 0 && qScratch && x3_q8_auto(op, n, h, w, epi == 2, outF != nullptr, epi == 1) && shapeOk &&
-                        autoOk && wpx == 1 && !narrowOnly;
-    if (q8Link && q8Link->inIsQ && !(q8Shape && q8Auto)) return hipErrorInvalidValue;   // the input has no lo plane
-    if (q8Shape && (q8Forced || q8Auto)) {
-      const int tq = q8Twx, thq = 224 / tq;
-      const bool flatQ = n > 1 && h % thq != 0 && 2 * h >= thq;
-      unet::ConvQ8Args b;
-      static_cast<unet::ConvX3Args&>(b) = a;
-      b.tilesX = w / tq;
-      b.tilesY = (h + thq - 1) / thq;
-      b.N = n;
-      b.H = h;
-      if (flatQ) {
-        b.N = 1;
-        b.H = n * h;
-        b.tilesY = (n * h + thq - 1) / thq;
-      }
-      b.pixTiles = b.N * b.tilesY * b.tilesX;
-      b.coTiles = op.cout / 256;
-      b.coGroup = b.coTiles;
-      b.pool = nullptr;
-      b.wq = op.wq;
-      const size_t P = (size_t)n * h * w;
-      if (q8Link && q8Link->inIsQ) {
-        b.inLo = inLo;   // the producer wrote the q plane where the lo plane would be
-      } else {
-        // the q plane of the input: fp8(x_hi / 8) and fp8(256 x_lo) per 32 channels, from the two fp16 planes
-        prof_begin("planes_to_q8", 0.0, 6.0 * (double)P * op.cin, s);
-        hipLaunchKernelGGL(unet::planes_to_q8_kernel, dim3(grid_for(P * (op.cin / 16))), dim3(256), 0, s, in, inLo, P, op.cin,
-                           op.cin, qScratch);
-        prof_end(s);
-        b.inLo = (size_t)(reinterpret_cast<const uint16_t*>(qScratch) - in);   // halfs; the kernel adds it in bytes
-      }
-      const bool outQ = q8Link && q8Link->wantOutQ && epi == 0 && coOff % 32 == 0;
-      if (q8Link) q8Link->wroteQ = outQ;
-      const long itemsQ = (long)b.pixTiles * b.coTiles;
-      const int gridQ = (int)std::max<long>(8, std::min<long>(256, itemsQ / 8 * 8));
-      static const char* const kLabelQ[2][2][2] = {
-          {{"conv3x3_q8_f16q8_t28", "conv3x3_q8_f16q8_t28_flat"}, {"conv3x3_q8_f16q8_t14", "conv3x3_q8_f16q8_t14_flat"}},
-          {{"conv3x3_q8_f16q8_t28_q", "conv3x3_q8_f16q8_t28_q_flat"}, {"conv3x3_q8_f16q8_t14_q", "conv3x3_q8_f16q8_t14_q_flat"}}};
-      prof_begin(label ? label : kLabelQ[outQ ? 1 : 0][tq == 14][flatQ ? 1 : 0], 2.0 * (double)P * 9 * op.cin * op.cout,
-                 4.0 * ((double)P * op.cin + (double)P * op.cout + 9.0 * op.cin * op.cout), s);
-      hipError_t e;
-      if (outQ) {
-        if (tq == 28)
-          e = flatQ ? launch_conv_q8<28, 4, true>(b, gridQ, s) : launch_conv_q8<28, 4, false>(b, gridQ, s);
-        else
-          e = launch_conv_q8<14, 4, true>(b, gridQ, s);
-      } else if (tq == 28)
-        e = flatQ ? launch_conv_q8<28, 0, true>(b, gridQ, s) : launch_conv_q8<28, 0, false>(b, gridQ, s);
-      else
-        e = launch_conv_q8<14, 0, true>(b, gridQ, s);
-      prof_end(s);
-      if (e != hipSuccess) return e;
-      if (epi == 1) {
-        if (q8Link && (q8Link->poolSrcQ || q8Link->poolDstQ) && coOff % 32 == 0) {
-          prof_begin("maxpool2x2_planes_q8", 0.0, (double)P * op.cout * (4.0 + (q8Link->poolSrcQ ? 2.0 : 0.0) + 1.0), s);
-          hipLaunchKernelGGL(unet::maxpool2x2_planes_q8_kernel, dim3(grid_for(P / 4 * (op.cout / 32))), dim3(256), 0, s,
-                             out + coOff, outLo, n, h, w, op.cout, ldo, fuse->pool, fuse->poolLo, q8Link->poolSrcQ ? 1 : 0,
-                             q8Link->poolDstQ ? 1 : 0);
-          prof_end(s);
-          q8Link->pooledQ = q8Link->poolDstQ;
-          q8Link->srcQDone = q8Link->poolSrcQ;
-        } else {
-          prof_begin("maxpool2x2_planes_f16x3", 0.0, 4.0 * (double)P * op.cout * 1.25, s);
-          hipLaunchKernelGGL(unet::maxpool2x2_planes_kernel, dim3(grid_for(P / 4 * (op.cout / 2))), dim3(256), 0, s,
-                             reinterpret_cast<const uint32_t*>(out + coOff), outLo / 2, n, h, w, op.cout, ldo,
-                             reinterpret_cast<uint32_t*>(fuse->pool), fuse->poolLo / 2);
-          prof_end(s);
-        }
-      }
-      if (path) path->set(4, tq, outQ ? 4 : 0, flatQ, 1, 1, epi == 1);
-      return hipGetLastError();
-    }
-    if (q8Forced) return hipErrorInvalidValue;
-    if (epi != 2 && shapeOk && (forced || autoOk)) {
-      unet::ConvX3Args b = a;
-      b.tilesX = w / twx;
-      b.tilesY = (h + thx - 1) / thx;
-      b.N = n;
-      b.H = h;
-      if (flatR) {
-        b.N = 1;
-        b.H = n * h;
-        b.tilesY = (n * h + thx - 1) / thx;
-      }
-      b.pixTiles = b.N * b.tilesY * b.tilesX;
-      b.coTiles = op.cout / (256 / wpx);
-      b.coGroup = b.coTiles;
-      b.pool = nullptr;
-      const int grid = (int)std::max<long>(8, std::min<long>(256, items / 8 * 8));
-      static const char* const kLabelR[2][2][2][2] = {
-          {{{"conv3x3_r512_f16x3_t28_w1_e0", "conv3x3_r512_f16x3_t28_w1_e0_flat"},
-            {"conv3x3_r512_f16x3_t28_w1_e3", "conv3x3_r512_f16x3_t28_w1_e3_flat"}},
-           {{"conv3x3_r512_f16x3_t28_w2_e0", "conv3x3_r512_f16x3_t28_w2_e0_flat"},
-            {"conv3x3_r512_f16x3_t28_w2_e3", "conv3x3_r512_f16x3_t28_w2_e3_flat"}}},
-          {{{"conv3x3_r512_f16x3_t14_w1_e0", "conv3x3_r512_f16x3_t14_w1_e0_flat"},
-            {"conv3x3_r512_f16x3_t14_w1_e3", "conv3x3_r512_f16x3_t14_w1_e3_flat"}},
-           {{"conv3x3_r512_f16x3_t14_w2_e0", "conv3x3_r512_f16x3_t14_w2_e0_flat"},
-            {"conv3x3_r512_f16x3_t14_w2_e3", "conv3x3_r512_f16x3_t14_w2_e3_flat"}}}};
-      const double pxR = (double)n * h * w;
-      static const char* const kLabelN[3][2][2] = {
-          {{"conv3x3_r512_f16x3_t32_w1_e0", "conv3x3_r512_f16x3_t32_w1_e0_flat"},
-           {"conv3x3_r512_f16x3_t32_w1_e3", "conv3x3_r512_f16x3_t32_w1_e3_flat"}},
-          {{"conv3x3_r512_f16x3_t16_w1_e0", "conv3x3_r512_f16x3_t16_w1_e0_flat"},
-           {"conv3x3_r512_f16x3_t16_w1_e3", "conv3x3_r512_f16x3_t16_w1_e3_flat"}},
-          {{"conv3x3_r512_f16x3_t8_w1_e0", "conv3x3_r512_f16x3_t8_w1_e0_flat"},
-           {"conv3x3_r512_f16x3_t8_w1_e3", "conv3x3_r512_f16x3_t8_w1_e3_flat"}}};
-      static const char* const kLabelN2[2][2] = {{"conv3x3_r512_f16x3_t32_w2_e0", "conv3x3_r512_f16x3_t32_w2_e0_flat"},
-                                                 {"conv3x3_r512_f16x3_t32_w2_e3", "conv3x3_r512_f16x3_t32_w2_e3_flat"}};
-      const char* autoLabel = (twx == 32 && wpx == 2) ? kLabelN2[outF ? 1 : 0][flatR ? 1 : 0]
-                              : narrow              ? kLabelN[twx == 32 ? 0 : (twx == 16 ? 1 : 2)][outF ? 1 : 0][flatR ? 1 : 0]
-                                                    : kLabelR[twx == 14][wpx == 2][outF ? 1 : 0][flatR ? 1 : 0];
-      prof_begin(label ? label : autoLabel, 2.0 * pxR * 9 * op.cin * op.cout,
-                 4.0 * (pxR * op.cin + pxR * op.cout + 9.0 * op.cin * op.cout), s);
-      if (outF && statPartial && statRows) {
-        const hipError_t em = hipMemsetAsync(statPartial, 0, (size_t)grid * wpx * 2 * op.cout * sizeof(float), s);
-        if (em != hipSuccess) return em;
-        b.statPartial = statPartial;
-        *statRows = grid * wpx;
-      }
-      hipError_t e;
-      if (twx == 28)
-        e = wpx == 1 ? launch_conv_r512<28, 1>(b, grid, flatR, outF != nullptr, s)
-                     : launch_conv_r512<28, 2>(b, grid, flatR, outF != nullptr, s);
-      else if (twx == 14)
-        e = wpx == 1 ? launch_conv_r512<14, 1>(b, grid, flatR, outF != nullptr, s)
-                     : launch_conv_r512<14, 2>(b, grid, flatR, outF != nullptr, s);
-      else if (twx == 32)
-        e = wpx == 1 ? launch_conv_r512<32, 1>(b, grid, flatR, outF != nullptr, s)
-                     : launch_conv_r512<32, 2>(b, grid, flatR, outF != nullptr, s);
-      else if (twx == 16)
-        e = launch_conv_r512<16, 1>(b, grid, flatR, outF != nullptr, s);
-      else
-        e = launch_conv_r512<8, 1>(b, grid, flatR, outF != nullptr, s);
-      prof_end(s);
-      if (e != hipSuccess) return e;
-      if (epi == 1) {   // the pooled copy (this structure has no fused pooling epilogue yet)
-        const size_t P = (size_t)n * h * w;
-        prof_begin("maxpool2x2_planes_f16x3", 0.0, 4.0 * (double)P * op.cout * 1.25, s);
-        hipLaunchKernelGGL(unet::maxpool2x2_planes_kernel, dim3(grid_for(P / 4 * (op.cout / 2))), dim3(256), 0, s,
-                           reinterpret_cast<const uint32_t*>(out + coOff), outLo / 2, n, h, w, op.cout, ldo,
-                           reinterpret_cast<uint32_t*>(fuse->pool), fuse->poolLo / 2);
-        prof_end(s);
-      }
-      if (path) path->set(2, twx, outF ? 3 : 0, flatR, 1, wpx, epi == 1);
-      return hipGetLastError();
-    }
-    if (forced) return hipErrorInvalidValue;
-  }
-  // Split-K: with fewer work items than half of the CUs (single frames: a 14x14 map is one pixel tile), the input
-  // channels are divided over kSplit items per tile; the items write raw fp32 partial sums (EPI 3, unit scale) and
-  // x3_splitk_finish_kernel adds them, applies scale / shift / ReLU and writes the planes (+ the pooled copy).
-  int kSplit = 1;
-  if (splitK && splitK->scratch && !outF && epi != 2 && op.cout <= 1024) {
-    const long items = (long)a.pixTiles * a.coTiles;
-    while (items * kSplit * 2 <= 256 && (a.chunksTotal / (kSplit * 2)) >= 2 && (a.chunksTotal % (kSplit * 4)) == 0 &&
-           (size_t)(kSplit * 2) * (size_t)n * h * w * op.cout <= splitK->floats)
-      kSplit *= 2;
-    if (items > 128) kSplit = 1;
-  }
-  if (kSplit > 1) {
-    const size_t P = (size_t)n * h * w;
-    unet::ConvX3Args b = a;
-    b.kSplit = kSplit;
-    b.nChunks = a.chunksTotal / kSplit;   // even: chunks are consumed in pairs
-    b.splitStride = P * op.cout;
-    b.outF = splitK->scratch;
-    b.scale = splitK->ones;
-    b.shift = splitK->zerosF;
-    b.relu = 0;
-    b.ldo = op.cout;
-    b.co_off = 0;
-    b.pool = nullptr;
-    const long workS = (long)a.pixTiles * a.coTiles * kSplit;
-    const int gridS = (int)std::max<long>(8, std::min<long>(256, workS / 8 * 8));
-    prof_begin(label ? label : "conv3x3_ws_f16x3_splitk", 2.0 * (double)P * 9 * op.cin * op.cout,
-               4.0 * ((double)P * op.cin + (double)kSplit * P * op.cout + 9.0 * op.cin * op.cout), s);
-    hipError_t es = flat ? (tw == 32 ? launch_conv_x3<32, 3, true>(b, gridS, s) : launch_conv_x3<16, 3, true>(b, gridS, s))
-                         : (tw == 32 ? launch_conv_x3<32, 3>(b, gridS, s) : launch_conv_x3<16, 3>(b, gridS, s));
-    prof_end(s);
-    if (es != hipSuccess) return es;
-    prof_begin("splitk_finish_f16x3", 0.0, 4.0 * (double)(kSplit + 1) * P * op.cout, s);
-    hipLaunchKernelGGL(unet::x3_splitk_finish_kernel, dim3(grid_for(P * (op.cout / 4))), dim3(256), 0, s,
-                       (const float*)splitK->scratch, kSplit, P, op.cout, (const float*)op.scale, (const float*)op.shift,
-                       op.relu, reinterpret_cast<uint32_t*>(out), outLo / 2, ldo, coOff, a.err);
-    if (epi == 1)   // the pooled copy the fused epilogue would have written (of the channels at coOff, as above)
-      hipLaunchKernelGGL(unet::maxpool2x2_planes_kernel, dim3(grid_for(P / 4 * (op.cout / 2))), dim3(256), 0, s,
-                         reinterpret_cast<const uint32_t*>(out + coOff), outLo / 2, n, h, w, op.cout, ldo,
-                         reinterpret_cast<uint32_t*>(fuse->pool), fuse->poolLo / 2);
-    prof_end(s);
-    if (path) path->set(1, tw, 0, flat, kSplit, 0, epi == 1);
-    return hipGetLastError();
-  }
-  const long work = (long)a.pixTiles * a.coTiles;
-  const int grid = (int)std::max<long>(8, std::min<long>(256, work / 8 * 8));
-  const double px = (double)n * h * w;
-  // algorithmic (direct-convolution) flops; the kernel executes 3x that many fp16 MFMA flops
-  // one label per template instance, so that bench.py's per-kernel figures line up with rocprofv3's kernel names
-  static const char* const kLabel[2][2][4] = {
-      {{"conv3x3_ws_f16x3_tw32_e0", "conv3x3_ws_f16x3_tw32_e1", "conv3x3_ws_f16x3_tw32_e2", "conv3x3_ws_f16x3_tw32_e3"},
-       {"conv3x3_ws_f16x3_tw16_e0", "conv3x3_ws_f16x3_tw16_e1", "conv3x3_ws_f16x3_tw16_e2", "conv3x3_ws_f16x3_tw16_e3"}},
-      {{"conv3x3_ws_f16x3_tw32_e0_flat", "conv3x3_ws_f16x3_tw32_e1_flat", "conv3x3_ws_f16x3_tw32_e2_flat",
-        "conv3x3_ws_f16x3_tw32_e3_flat"},
-       {"conv3x3_ws_f16x3_tw16_e0_flat", "conv3x3_ws_f16x3_tw16_e1_flat", "conv3x3_ws_f16x3_tw16_e2_flat",
-        "conv3x3_ws_f16x3_tw16_e3_flat"}}};
-  prof_begin(label ? label : kLabel[flat ? 1 : 0][tw == 16][epi], 2.0 * px * 9 * op.cin * op.cout,
-             4.0 * (px * op.cin + px * op.cout + 9.0 * op.cin * op.cout), s);
-  hipError_t e;
-  if (flat) {
-    if (tw == 32)
-      e = epi == 0 ? launch_conv_x3<32, 0, true>(a, grid, s)
-          : epi == 1 ? launch_conv_x3<32, 1, true>(a, grid, s)
-                     : launch_conv_x3<32, 3, true>(a, grid, s);
-    else
-      e = epi == 0 ? launch_conv_x3<16, 0, true>(a, grid, s)
-          : epi == 1 ? launch_conv_x3<16, 1, true>(a, grid, s)
-                     : launch_conv_x3<16, 3, true>(a, grid, s);
-  } else if (tw == 32)
-    e = epi == 0   ? launch_conv_x3<32, 0>(a, grid, s)
-        : epi == 1 ? launch_conv_x3<32, 1>(a, grid, s)
-        : epi == 2 ? launch_conv_x3<32, 2>(a, grid, s)
-                   : launch_conv_x3<32, 3>(a, grid, s);
-  else
-    e = epi == 0   ? launch_conv_x3<16, 0>(a, grid, s)
-        : epi == 1 ? launch_conv_x3<16, 1>(a, grid, s)
-        : epi == 2 ? launch_conv_x3<16, 2>(a, grid, s)
-                   : launch_conv_x3<16, 3>(a, grid, s);
-  prof_end(s);
-  if (path) path->set(1, tw, epi, flat, 1, 0, false);
-  return e;
+};
+inline X3ConvIo x3_from(const uint16_t* zeros, const uint16_t* in, size_t inLo, int n, int h, int w) {
+  X3ConvIo io;
+  io.zeros = zeros, io.in = in, io.inLo = inLo, io.n = n, io.h = h, io.w = w;
+  return io;
 }
+struct X3ConvOpts {
+  const X3Fuse* fuse = nullptr;       // exactly one of its fusions (pool or head) may be requested
+  int forceTw = 0;                    // the test entry points' tile_width (x3_decode_force)
+  float* outF = nullptr;              // fp32 output (training) at pixel stride ldo, channel offset coOff
+  const float* dynScale = nullptr;
+  const char* label = nullptr;        // profiler label instead of the plan's own
+  const X3SplitK* splitK = nullptr;
+  // training forward, fp32 output: where the structure that runs fuses the BatchNorm statistics' per-block sums
+  // (ConvX3Args::statPartial) *statRows is their row count; otherwise 0 and the caller runs its own statistics pass
+  float* statPartial = nullptr;
+  int* statRows = nullptr;
+  uint8_t* qScratch = nullptr;        // f16q8 tier: room for the input's q plane (n * h * w * cin * 2 bytes)
+  X3Q8Link* q8Link = nullptr;
+  X3Path* path = nullptr;             // what ran (test entry points)
+};
+
+X3ConvQuery x3_conv_query(const GemmOpX3& op, const X3ConvIo& io, const X3ConvOpts& o) {
+  X3ConvQuery q;
+  q.n = io.n, q.h = io.h, q.w = io.w, q.cin = op.cin, q.cout = op.cout;
+  q.epi = o.outF ? 3 : (o.fuse && o.fuse->pool) ? 1 : (o.fuse && o.fuse->headW) ? 2 : 0;
+  q.coOff = io.coOff;
+  q.splitScratch = o.splitK && o.splitK->scratch;
+  q.splitFloats = o.splitK ? o.splitK->floats : 0;
+  q.qScratch = o.qScratch != nullptr;
+  q.wq = op.wq != nullptr;
+  if (o.q8Link) q.inIsQ = o.q8Link->inIsQ, q.wantOutQ = o.q8Link->wantOutQ, q.poolSrcQ = o.q8Link->poolSrcQ, q.poolDstQ = o.q8Link->poolDstQ;
+  q.wantStats = o.outF && o.statPartial && o.statRows;
+  q.sw = x3_switches();
+  return q;
+}
+
+// One 3x3 convolution of the tier: plan, fill the kernel's arguments from the plan, launch (+ the passes the plan names)
+hipError_t run_conv_x3(const GemmOpX3& op, const X3ConvIo& io, const X3ConvOpts& o, hipStream_t s) {
+  if (o.statRows) *o.statRows = 0;
+  X3ConvQuery q = x3_conv_query(op, io, o);
+  if (!x3_decode_force(o.forceTw, &q.force)) return hipErrorInvalidValue;
+  const X3ConvPlan p = x3_plan_conv(q);
+  if (!p.valid) return hipErrorInvalidValue;
+  const X3Path& k = p.path;
+  const int n = io.n, h = io.h, w = io.w;
+  const size_t P = (size_t)n * h * w;
+  const bool split = p.kSplit > 1;
+  unet::ConvQ8Args a{};   // (pool, head, statistics: null unless the plan's epilogue takes them)
+  a.in = io.in, a.inLo = io.inLo, a.zeros = io.zeros;
+  a.wt = op.wt, a.wq = op.wq;
+  a.out = io.out, a.outLo = io.outLo;
+  a.N = p.N, a.H = p.H, a.W = w, a.imgH = p.imgH, a.Cin = op.cin, a.Cout = op.cout;
+  a.tilesX = p.tilesX, a.tilesY = p.tilesY, a.pixTiles = p.pixTiles;
+  a.coTiles = p.coTiles, a.coGroup = p.coGroup, a.nChunks = p.nChunks;
+  a.kSplit = p.kSplit, a.chunksTotal = op.cin / 32;
+  a.dynScale = o.dynScale;
+  a.err = g_errWord ? g_errWord : op_err_word();
+  if (split) {   // raw fp32 partial sums into the scratch, unscaled: the finish pass applies scale / shift / ReLU
+    a.scale = o.splitK->ones, a.shift = o.splitK->zerosF, a.relu = 0;
+    a.outF = o.splitK->scratch, a.ldo = op.cout, a.co_off = 0, a.splitStride = P * op.cout;
+  } else {
+    a.scale = op.scale, a.shift = op.shift, a.relu = op.relu;
+    a.outF = o.outF, a.ldo = io.ldo, a.co_off = io.coOff;
+  }
+  if (k.epi == 1) a.pool = o.fuse->pool, a.poolLo = o.fuse->poolLo;
+  if (k.epi == 2) {
+    const X3Fuse& z = *o.fuse;
+    a.headW = z.headW, a.headB = z.headB, a.headThr = z.headThr, a.logits = z.logits, a.probs = z.probs, a.mask = z.mask;
+  }
+  if (p.toQ8Pass) {
+    // the q plane of the input: fp8(x_hi / 8) and fp8(256 x_lo) per 32 channels, from the two fp16 planes
+    prof_begin("planes_to_q8", 0.0, 6.0 * (double)P * op.cin, s);
+    hipLaunchKernelGGL(unet::planes_to_q8_kernel, dim3(grid_for(P * (op.cin / 16))), dim3(256), 0, s, io.in, io.inLo, P, op.cin,
+                       op.cin, o.qScratch);
+    prof_end(s);
+    a.inLo = (size_t)(reinterpret_cast<const uint16_t*>(o.qScratch) - io.in);   // halfs; the kernel adds it in bytes
+  }
+  if (p.statRows) {
+    const hipError_t em = hipMemsetAsync(o.statPartial, 0, (size_t)p.statRows * 2 * op.cout * sizeof(float), s);
+    if (em != hipSuccess) return em;
+    a.statPartial = o.statPartial;
+    *o.statRows = p.statRows;
+  }
+  // algorithmic (direct-convolution) flops; the kernels execute 3x that many fp16 MFMA flops.  The label is only spelt
+  // out while a profiler listens: the unprofiled launch path does no string work
+  char autoLabel[48];
+  const char* label = o.label ? o.label : "";
+  if (!o.label && g_prof && g_prof->on) {
+    x3_conv_label(p, autoLabel, sizeof(autoLabel));
+    label = autoLabel;
+  }
+  const double px = (double)P;
+  const double outShare = split ? (double)p.kSplit : k.structure != kX3T448 ? 1.0 : k.epi == 2 ? 0.0 : k.epi == 1 ? 1.25 : 1.0;
+  prof_begin(label, 2.0 * px * 9 * op.cin * op.cout, 4.0 * (px * op.cin + outShare * px * op.cout + 9.0 * op.cin * op.cout), s);
+  const hipError_t e = launch_conv_plan(p, a, s);
+  prof_end(s);
+  if (e != hipSuccess) return e;
+  auto pool_pass = [&]() {   // the pooled copy a fused epilogue would have written (of the channels at coOff)
+    hipLaunchKernelGGL(unet::maxpool2x2_planes_kernel, dim3(grid_for(P / 4 * (op.cout / 2))), dim3(256), 0, s,
+                       reinterpret_cast<const uint32_t*>(io.out + io.coOff), io.outLo / 2, n, h, w, op.cout, io.ldo,
+                       reinterpret_cast<uint32_t*>(o.fuse->pool), o.fuse->poolLo / 2);
+  };
+  if (p.finishPass) {
+    prof_begin("splitk_finish_f16x3", 0.0, 4.0 * (double)(p.kSplit + 1) * P * op.cout, s);
+    hipLaunchKernelGGL(unet::x3_splitk_finish_kernel, dim3(grid_for(P * (op.cout / 4))), dim3(256), 0, s,
+                       (const float*)o.splitK->scratch, p.kSplit, P, op.cout, (const float*)op.scale, (const float*)op.shift,
+                       op.relu, reinterpret_cast<uint32_t*>(io.out), io.outLo / 2, io.ldo, io.coOff, a.err);
+    if (p.poolPass) pool_pass();
+    prof_end(s);
+  } else if (p.poolPass == 2) {
+    X3Q8Link& lk = *o.q8Link;
+    prof_begin("maxpool2x2_planes_q8", 0.0, (double)P * op.cout * (4.0 + (lk.poolSrcQ ? 2.0 : 0.0) + 1.0), s);
+    hipLaunchKernelGGL(unet::maxpool2x2_planes_q8_kernel, dim3(grid_for(P / 4 * (op.cout / 32))), dim3(256), 0, s,
+                       io.out + io.coOff, io.outLo, n, h, w, op.cout, io.ldo, o.fuse->pool, o.fuse->poolLo, lk.poolSrcQ ? 1 : 0,
+                       lk.poolDstQ ? 1 : 0);
+    prof_end(s);
+    lk.pooledQ = lk.poolDstQ;
+    lk.srcQDone = lk.poolSrcQ;
+  } else if (p.poolPass == 1) {
+    prof_begin("maxpool2x2_planes_f16x3", 0.0, 4.0 * (double)P * op.cout * 1.25, s);
+    pool_pass();
+    prof_end(s);
+  }
+  if (o.q8Link && k.structure == kX3Q8) o.q8Link->wroteQ = p.outQ;
+  if (o.path) *o.path = k;
+  return hipGetLastError();
+}
+
+// ---- the transposed convolution and the plain GEMM on its kernels ----
 
 // which launches the one-wave-per-SIMD structure (upconv_x3_r512.h) takes (unet_set_x3_upconv_r512): -1 = automatic
 // (shapes it supports with a work item for at least half of the CUs; UNET_X3_UPCONV_R512=0 in the environment: never),
@@ -932,142 +894,106 @@ int x3_upconv_r512_mode() {
   const int m = g_x3UpconvR512;
   return m < 0 ? (envOff ? 0 : -1) : m;
 }
-// would a ConvTranspose2d of this shape run on upconv_x3_r512.h (run_upconv_x3's own choice)?
-bool x3_upconv_r512_auto(const GemmOpX3& op, int n, int h, int w) {
-  const long npix = (long)n * h * w;
-  const long work = (npix + 223) / 224 * (op.cout / 64);
-  const bool abSplit = (npix + 127) / 128 * (op.cout / 64) <= 64;
-  const int mode = x3_upconv_r512_mode();
-  return !(mode == 0 || op.cin % 128 != 0 || w < 4 || (mode < 0 && (work < 128 || abSplit)));
+
+struct X3UpconvQuery {
+  long npix = 0;          // input pixels
+  int w = 0;              // map width (ConvTranspose2d; a plain GEMM passes gemm = true instead)
+  int cin = 0, cout = 0;  // GEMM: K and the column count
+  bool gemm = false;      // MODE 1: a channel tile is 256 columns
+  int coOff = 0;
+  bool wantOutQ = false;  // f16q8: the output's q plane in its lo plane's place (second structure only)
+  int mode = -1;          // x3_upconv_r512_mode()
+};
+struct X3UpconvPlan {
+  bool valid = false;     // false: a q plane was asked of a launch the second structure does not take
+  X3Path path;
+  int coTiles = 0, pixTiles = 0, abSplit = 1, grid = 0;
+  bool outQ = false;
+};
+X3UpconvPlan x3_plan_upconv(const X3UpconvQuery& q) {
+  X3UpconvPlan p;
+  p.coTiles = q.gemm ? (q.cout + 255) / 256 : q.cout / 64;
+  const int tilesW = (int)((q.npix + unet::UpconvX3Shape::TP - 1) / unet::UpconvX3Shape::TP);
+  const int tilesR = (int)((q.npix + unet::UpconvX3RShape::TP - 1) / unet::UpconvX3RShape::TP);
+  const int abSplit = !q.gemm && (long)tilesW * p.coTiles <= 64 ? 4 : 1;   // small batches: one item per (a,b)
+  const long workR = (long)tilesR * p.coTiles;
+  const bool r512 = !(q.mode == 0 || q.cin % 128 != 0 || (!q.gemm && q.w < 4) || (q.mode < 0 && (workR < 128 || abSplit != 1)));
+  if (q.wantOutQ && !(r512 && q.coOff % 32 == 0 && !q.gemm)) return p;   // the consumer has been told
+  p.valid = true;
+  p.outQ = q.wantOutQ;
+  p.pixTiles = r512 ? tilesR : tilesW;
+  p.abSplit = r512 ? 1 : abSplit;
+  p.grid = x3_grid(r512 ? workR : (long)tilesW * p.coTiles * abSplit);
+  p.path.set(r512 ? kX3R512 : kX3Ws, 0, 0, false, 1, p.abSplit, false);
+  return p;
 }
-// the same arguments on 224-pixel tiles; false: the shape or the work count does not suit it
-template <int MODE, bool OUTQ = false>
-bool launch_upconv_r512(unet::UpconvX3Args a, const char* label, double flops, double bytes, hipStream_t s, hipError_t* err) {
-  using R = unet::UpconvX3RShape;
-  const int pixTiles = (int)((a.npix + R::TP - 1) / R::TP);
-  const long work = (long)pixTiles * a.coTiles;
-  const int mode = x3_upconv_r512_mode();
-  if (mode == 0 || a.Cin % 128 != 0 || (MODE == 0 && a.w < 4) || (mode < 0 && (work < 128 || a.abSplit != 1))) return false;
-  a.abSplit = 1;
-  a.pixTiles = pixTiles;
-  auto kern = unet::upconv2x2_x3_r512_kernel<MODE, OUTQ>;
-  *err = ensure_dyn_lds((const void*)kern, R::LDS_BYTES);
-  if (*err != hipSuccess) return true;
-  const int grid = (int)std::max<long>(8, std::min<long>(256, work / 8 * 8));
-  prof_begin(label, flops, bytes, s);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), (size_t)R::LDS_BYTES, s, a);
-  prof_end(s);
-  *err = hipGetLastError();
-  return true;
+const char* x3_upconv_label(const X3UpconvPlan& p) {
+  return p.path.structure == kX3Ws ? "upconv2x2_ws_f16x3" : p.outQ ? "upconv2x2_r512_f16x3_q" : "upconv2x2_r512_f16x3";
 }
 
-// q8Link (f16q8 tier): wantOutQ - write the output's q plane in its lo plane's place (only asked for where
-// x3_upconv_r512_auto holds; an error otherwise, because the consumer has been told)
-hipError_t run_upconv_x3(const GemmOpX3& op, const uint16_t* zeros, const uint16_t* in, size_t inLo, int n, int h, int w,
-                         uint16_t* out, size_t outLo, int ldo, int coOff, hipStream_t s, X3Q8Link* q8Link = nullptr,
-                         X3Path* path = nullptr) {
-  using S = unet::UpconvX3Shape;
-  unet::UpconvX3Args a;
-  a.in = in;
-  a.inLo = inLo;
-  a.wt = op.wt;
-  a.zeros = zeros;
-  a.scale = op.scale;
-  a.bias = op.shift;
-  a.out = out;
-  a.outLo = outLo;
-  a.npix = (long)n * h * w;
-  a.h = h;
-  a.w = w;
-  a.Cin = op.cin;
-  a.Cout = op.cout;
-  a.ldo = ldo;
-  a.co_off = coOff;
-  a.nChunks = op.cin / 32;
-  a.coTiles = op.cout / 64;
-  a.pixTiles = (int)((a.npix + S::TP - 1) / S::TP);
-  a.outF = nullptr;
-  a.dynScale = nullptr;
+// One launch on the plan's kernel; MODE 0: ConvTranspose2d, MODE 1: the plain GEMM.  The fill both share: `a` arrives with
+// what differs between the two (scale / bias / out / h / w / err, or outF / dynScale)
+template <int MODE>
+hipError_t launch_upconv_plan(const X3UpconvPlan& p, unet::UpconvX3Args a, const uint16_t* wt, const X3ConvIo& io, long npix,
+                              int cin, int cout, const char* label, hipStream_t s) {
+  a.in = io.in, a.inLo = io.inLo, a.zeros = io.zeros, a.wt = wt;
+  a.npix = npix, a.Cin = cin, a.Cout = cout, a.ldo = io.ldo, a.co_off = io.coOff;
+  a.nChunks = cin / 32, a.coTiles = p.coTiles, a.pixTiles = p.pixTiles, a.abSplit = p.abSplit;
+  const double px = (double)npix, cols = MODE == 0 ? 4.0 * cout : (double)cout;
+  const bool r512 = p.path.structure == kX3R512;
+  void (*kern)(const unet::UpconvX3Args);
+  if (!r512)
+    kern = unet::upconv2x2_x3_ws_kernel<MODE>;
+  else if constexpr (MODE == 0)
+    kern = p.outQ ? unet::upconv2x2_x3_r512_kernel<0, true> : unet::upconv2x2_x3_r512_kernel<0>;
+  else
+    kern = unet::upconv2x2_x3_r512_kernel<1>;
+  const int lds = r512 ? unet::UpconvX3RShape::LDS_BYTES : unet::UpconvX3Shape::LDS_BYTES;
+  const hipError_t e = ensure_dyn_lds((const void*)kern, lds);
+  if (e != hipSuccess) return e;
+  prof_begin(label, 2.0 * px * cin * cols, 4.0 * (px * cin + px * cols), s);
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(r512 ? 256 : 512), (size_t)lds, s, a);
+  prof_end(s);
+  return hipGetLastError();
+}
+
+// in: planes (n,h,w,op.cin) -> out planes (n,2h,2w) with pixel stride ldo at channel offset coOff.
+// q8Link (f16q8 tier): wantOutQ - write the output's q plane in its lo plane's place (an error where the second structure
+// does not take the launch, because the consumer has been told)
+X3UpconvQuery x3_upconv_query(const GemmOpX3& op, const X3ConvIo& io, bool wantOutQ) {
+  X3UpconvQuery q;
+  q.npix = (long)io.n * io.h * io.w, q.w = io.w, q.cin = op.cin, q.cout = op.cout, q.coOff = io.coOff;
+  q.wantOutQ = wantOutQ;
+  q.mode = x3_upconv_r512_mode();
+  return q;
+}
+hipError_t run_upconv_x3(const GemmOpX3& op, const X3ConvIo& io, hipStream_t s, X3Q8Link* q8Link = nullptr, X3Path* path = nullptr) {
+  const X3UpconvQuery q = x3_upconv_query(op, io, q8Link && q8Link->wantOutQ);
+  const X3UpconvPlan p = x3_plan_upconv(q);
+  if (!p.valid) return hipErrorInvalidValue;
+  unet::UpconvX3Args a{};
+  a.scale = op.scale, a.bias = op.shift, a.out = io.out, a.outLo = io.outLo, a.h = io.h, a.w = io.w;
   a.err = g_errWord ? g_errWord : op_err_word();
-  a.abSplit = (long)a.pixTiles * a.coTiles <= 64 ? 4 : 1;   // small batches: one item per (a,b)
-  {
-    hipError_t er = hipSuccess;
-    const double pxr = (double)a.npix;
-    if (q8Link && q8Link->wantOutQ) {
-      if (coOff % 32 == 0 && launch_upconv_r512<0, true>(a, "upconv2x2_r512_f16x3_q", 2.0 * pxr * op.cin * 4.0 * op.cout,
-                                                         4.0 * (pxr * op.cin + 4.0 * pxr * op.cout), s, &er)) {
-        q8Link->wroteQ = er == hipSuccess;
-        return er;
-      }
-      return hipErrorInvalidValue;
-    }
-    if (launch_upconv_r512<0>(a, "upconv2x2_r512_f16x3", 2.0 * pxr * op.cin * 4.0 * op.cout,
-                              4.0 * (pxr * op.cin + 4.0 * pxr * op.cout), s, &er)) {
-      if (path) path->set(2, 0, 0, false, 1, 1, false);
-      return er;
-    }
-  }
-  if (path) path->set(1, 0, 0, false, 1, a.abSplit, false);
-  auto kern = unet::upconv2x2_x3_ws_kernel<0>;
-  hipError_t e = ensure_dyn_lds((const void*)kern, S::LDS_BYTES);
-  if (e != hipSuccess) return e;
-  const long work = (long)a.pixTiles * a.coTiles * a.abSplit;
-  const int grid = (int)std::max<long>(8, std::min<long>(256, work / 8 * 8));
-  const double px = (double)a.npix;
-  prof_begin("upconv2x2_ws_f16x3", 2.0 * px * op.cin * 4.0 * op.cout, 4.0 * (px * op.cin + 4.0 * px * op.cout), s);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), (size_t)S::LDS_BYTES, s, a);
-  prof_end(s);
-  return hipGetLastError();
+  const hipError_t e = launch_upconv_plan<0>(p, a, op.wt, io, q.npix, op.cin, op.cout, x3_upconv_label(p), s);
+  if (q8Link && p.outQ) q8Link->wroteQ = e == hipSuccess;
+  if (path) *path = p.path;
+  return e;
 }
 
-// Plain GEMM on planes through the same kernel (MODE 1): outF[p][coOff + n] = dyn * sum_k in[p][k] W[k][n], n < nCols;
-// wt packed by pack_upconv_dgrad_x3_kernel; K % 64 == 0, nCols % 64 == 0
-hipError_t run_gemm1x1_x3(const uint16_t* wt, const uint16_t* zeros, const uint16_t* in, size_t inLo, long npix, int K,
-                          int nCols, float* outF, int ldo, int coOff, const float* dynScale, const char* label,
-                          hipStream_t s, int* structure = nullptr) {
-  // structure (test entry point): 2 = upconv_x3_r512.h, 1 = upconv_x3_ws.h, as X3Path::structure
-  using S = unet::UpconvX3Shape;
-  unet::UpconvX3Args a;
-  a.in = in;
-  a.inLo = inLo;
-  a.wt = wt;
-  a.zeros = zeros;
-  a.scale = nullptr;
-  a.bias = nullptr;
-  a.out = nullptr;
-  a.outLo = 0;
-  a.npix = npix;
-  a.h = 1;
-  a.w = 1;
-  a.Cin = K;
-  a.Cout = nCols;
-  a.ldo = ldo;
-  a.co_off = coOff;
-  a.nChunks = K / 32;
-  a.coTiles = (nCols + 255) / 256;
-  a.pixTiles = (int)((npix + S::TP - 1) / S::TP);
-  a.outF = outF;
-  a.dynScale = dynScale;
-  a.err = nullptr;
-  a.abSplit = 1;
-  {
-    hipError_t er = hipSuccess;
-    if (launch_upconv_r512<1>(a, label, 2.0 * (double)npix * K * nCols, 4.0 * ((double)npix * K + (double)npix * nCols), s,
-                              &er)) {
-      if (structure) *structure = 2;
-      return er;
-    }
-  }
-  if (structure) *structure = 1;
-  auto kern = unet::upconv2x2_x3_ws_kernel<1>;
-  hipError_t e = ensure_dyn_lds((const void*)kern, S::LDS_BYTES);
-  if (e != hipSuccess) return e;
-  const long work = (long)a.pixTiles * a.coTiles;
-  const int grid = (int)std::max<long>(8, std::min<long>(256, work / 8 * 8));
-  prof_begin(label, 2.0 * (double)npix * K * nCols, 4.0 * ((double)npix * K + (double)npix * nCols), s);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), (size_t)S::LDS_BYTES, s, a);
-  prof_end(s);
-  return hipGetLastError();
+// Plain GEMM on planes through the same kernels (MODE 1): outF[p][coOff + n] = dyn * sum_k in[p][k] W[k][n], n < nCols, for
+// the npix = io.n * io.h * io.w pixels of `io` (only its input side, ldo and coOff are read); wt packed by
+// pack_upconv_dgrad_x3_kernel; K % 64 == 0, nCols % 64 == 0.  structure (test entry point): as X3Path::structure
+hipError_t run_gemm1x1_x3(const uint16_t* wt, const X3ConvIo& io, int K, int nCols, float* outF, const float* dynScale,
+                          const char* label, hipStream_t s, int* structure = nullptr) {
+  X3UpconvQuery q;
+  q.npix = (long)io.n * io.h * io.w, q.cin = K, q.cout = nCols, q.coOff = io.coOff;
+  q.gemm = true;
+  q.mode = x3_upconv_r512_mode();
+  const X3UpconvPlan p = x3_plan_upconv(q);
+  unet::UpconvX3Args a{};
+  a.outF = outF, a.dynScale = dynScale, a.h = a.w = 1;
+  if (structure) *structure = p.path.structure;
+  return launch_upconv_plan<1>(p, a, wt, io, q.npix, K, nCols, label, s);
 }
 
 // ---- the decoder's composed first convolution (conv_x3_dec.h) ----
@@ -1525,6 +1451,24 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
   const WsTensor* cur = nullptr;
   int ch = height, cw = width;
   X3Q8Link lk1, lk2;
+  // a layer as the forward launches it: its tensors by workspace slot; the forward's split-K and q-plane scratch
+  auto io_of = [&](const WsTensor& in, int hh, int ww, const WsTensor& out, int ldo, int coOff) {
+    return x3_from(X->zeros, U(in), in.elems, n, hh, ww).to(U(out), out.elems, ldo, coOff);
+  };
+  auto opts_of = [&](X3Q8Link* lk, const X3Fuse* fuse) {
+    X3ConvOpts o;
+    o.fuse = fuse;
+    o.splitK = &sk;
+    o.qScratch = qs;
+    o.q8Link = lk;
+    return o;
+  };
+  // the look-ahead of the f16q8 tier: will that launch run on conv_q8_r512.h (x3_plan_conv's own answer for the same
+  // epilogue and scratch)?  Its producer then writes a q plane in the lo plane's place
+  auto lands_on_q8 = [&](const GemmOpX3& op, const X3ConvIo& io, const X3Fuse* fuse) {
+    const X3ConvPlan pl = x3_plan_conv(x3_conv_query(op, io, opts_of(nullptr, fuse)));
+    return qs && pl.valid && pl.path.structure == kX3Q8;
+  };
   // f16q8 tier, decided per level before anything is overwritten: catQ - the concat buffer's lo plane becomes its q plane
   // (skip half: by the encoder's pooling pass, in place; upper half: by the transposed convolution) because the
   // decoder's first convolution, its only other reader, is of the tier; poolQ - the same for the pooled tensor and
@@ -1532,6 +1476,12 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
   std::vector<char> catQ(c.depth, 0), poolQ(c.depth, 0);
   for (int l = 0; l < c.depth; ++l) {
     const int f = c.features[l];
+    // the block's second convolution: pooled, into the skip half of the concat buffer
+    X3Fuse fz;
+    fz.pool = U(p.pool[l]);
+    fz.poolLo = p.pool[l].elems;
+    const X3ConvIo conv2Io = io_of(p.tmpA, ch, cw, p.cat[l], 2 * f, 0);
+    const bool conv2OnQ8 = lands_on_q8(X->enc[2 * l + 1], conv2Io, &fz);
     if (l == 0) {
       unet::ConvFirstX3Args fa;
       fa.frames = input;
@@ -1569,25 +1519,21 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
       // first writes tmpA's q plane in the lo plane's place (X3Q8Link) and no conversion pass is needed
       lk1 = X3Q8Link();
       lk1.inIsQ = poolQ[l - 1];
-      lk1.wantOutQ = qs && x3_q8_auto(X->enc[2 * l + 1], n, ch, cw, false, false, true);
-      HIPCHK(h->err, run_conv_x3(X->enc[2 * l], X->zeros, U(*cur), cur->elems, n, ch, cw, U(p.tmpA), p.tmpA.elems, f, 0, s,
-                                 nullptr, 0, nullptr, nullptr, nullptr, &sk, nullptr, nullptr, qs, &lk1));
+      lk1.wantOutQ = conv2OnQ8;
+      HIPCHK(h->err, run_conv_x3(X->enc[2 * l], io_of(*cur, ch, cw, p.tmpA, f, 0), opts_of(&lk1, nullptr), s));
     }
-    X3Fuse fz;
-    fz.pool = U(p.pool[l]);
-    fz.poolLo = p.pool[l].elems;
     lk2 = X3Q8Link();
     lk2.inIsQ = l > 0 && lk1.wroteQ;
-    if (qs && x3_q8_auto(X->enc[2 * l + 1], n, ch, cw, false, false, true)) {
+    if (conv2OnQ8) {
       const int jd = c.depth - 1 - l;
       const GemmOpX3& nextConv1 = l + 1 < c.depth ? X->enc[2 * (l + 1)] : X->bott[0];
-      catQ[l] = x3_q8_auto(X->dec[2 * jd], n, ch, cw, false, false, false) && x3_upconv_r512_auto(X->up[jd], n, ch / 2, cw / 2);
-      poolQ[l] = x3_q8_auto(nextConv1, n, ch / 2, cw / 2, false, false, false);
+      catQ[l] = lands_on_q8(X->dec[2 * jd], io_of(p.cat[l], ch, cw, p.tmpA, f, 0), nullptr) &&
+                x3_plan_upconv(x3_upconv_query(X->up[jd], io_of(p.tmpB, ch / 2, cw / 2, p.cat[l], 2 * f, f), true)).valid;
+      poolQ[l] = lands_on_q8(nextConv1, io_of(p.pool[l], ch / 2, cw / 2, p.tmpA, 2 * f, 0), nullptr);
       lk2.poolSrcQ = catQ[l];
       lk2.poolDstQ = poolQ[l];
     }
-    HIPCHK(h->err, run_conv_x3(X->enc[2 * l + 1], X->zeros, U(p.tmpA), p.tmpA.elems, n, ch, cw, U(p.cat[l]),
-                               p.cat[l].elems, 2 * f, 0, s, &fz, 0, nullptr, nullptr, nullptr, &sk, nullptr, nullptr, qs, &lk2));
+    HIPCHK(h->err, run_conv_x3(X->enc[2 * l + 1], conv2Io, opts_of(&lk2, &fz), s));
     if (lk2.srcQDone != (bool)catQ[l] || lk2.pooledQ != (bool)poolQ[l]) {
       h->err = "f16q8: a pooling pass did not hand its q planes on as planned";
       return UNET_ERR_STATE;
@@ -1599,13 +1545,12 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
   const int fb = 2 * c.features[c.depth - 1];
   lk1 = X3Q8Link();
   lk1.inIsQ = poolQ[c.depth - 1];
-  lk1.wantOutQ = qs && x3_q8_auto(X->bott[1], n, ch, cw, false, false, false);
-  HIPCHK(h->err, run_conv_x3(X->bott[0], X->zeros, U(*cur), cur->elems, n, ch, cw, U(p.tmpA), p.tmpA.elems, fb, 0, s, nullptr,
-                             0, nullptr, nullptr, nullptr, &sk, nullptr, nullptr, qs, &lk1));
+  const X3ConvIo bott2Io = io_of(p.tmpA, ch, cw, p.tmpB, fb, 0);
+  lk1.wantOutQ = lands_on_q8(X->bott[1], bott2Io, nullptr);
+  HIPCHK(h->err, run_conv_x3(X->bott[0], io_of(*cur, ch, cw, p.tmpA, fb, 0), opts_of(&lk1, nullptr), s));
   lk2 = X3Q8Link();
   lk2.inIsQ = lk1.wroteQ;
-  HIPCHK(h->err, run_conv_x3(X->bott[1], X->zeros, U(p.tmpA), p.tmpA.elems, n, ch, cw, U(p.tmpB), p.tmpB.elems, fb, 0, s,
-                             nullptr, 0, nullptr, nullptr, nullptr, &sk, nullptr, nullptr, qs, &lk2));
+  HIPCHK(h->err, run_conv_x3(X->bott[1], bott2Io, opts_of(&lk2, nullptr), s));
   cur = &p.tmpB;
   bool headFused = false;
   for (int j = 0; j < c.depth; ++j) {
@@ -1626,19 +1571,19 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
     ch *= 2;
     cw *= 2;
     lk1 = X3Q8Link();
+    const X3ConvIo conv2Io = io_of(p.tmpA, ch, cw, p.tmpB, f, 0);
     if (!composed) {
       X3Q8Link lku;
       lku.wantOutQ = catQ[l];
-      HIPCHK(h->err, run_upconv_x3(X->up[j], X->zeros, U(*cur), cur->elems, n, ch / 2, cw / 2, U(p.cat[l]), p.cat[l].elems,
-                                   2 * f, f, s, &lku));
+      HIPCHK(h->err, run_upconv_x3(X->up[j], io_of(*cur, ch / 2, cw / 2, p.cat[l], 2 * f, f), s, &lku));
       lk1.inIsQ = catQ[l];
-      lk1.wantOutQ = qs && x3_q8_auto(X->dec[2 * j + 1], n, ch, cw, headNext, false, false);
-      HIPCHK(h->err, run_conv_x3(X->dec[2 * j], X->zeros, U(p.cat[l]), p.cat[l].elems, n, ch, cw, U(p.tmpA), p.tmpA.elems, f, 0,
-                                 s, nullptr, 0, nullptr, nullptr, nullptr, &sk, nullptr, nullptr, qs, &lk1));
+      // (the fused-head launch below is handed no q-plane scratch: it never takes a q plane)
+      lk1.wantOutQ = !headNext && lands_on_q8(X->dec[2 * j + 1], conv2Io, nullptr);
+      HIPCHK(h->err, run_conv_x3(X->dec[2 * j], io_of(p.cat[l], ch, cw, p.tmpA, f, 0), opts_of(&lk1, nullptr), s));
     }
     lk2 = X3Q8Link();
     lk2.inIsQ = lk1.wroteQ;
-    if (j == c.depth - 1 && f == 64) {
+    if (headNext) {
       // last DoubleConv: its only consumer is the 1x1 head, fused into the epilogue (the activation is never written)
       X3Fuse fz;
       fz.headW = X->headW;
@@ -1647,11 +1592,12 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
       fz.logits = logits;
       fz.probs = probs;
       fz.mask = mask;
-      HIPCHK(h->err, run_conv_x3(X->dec[2 * j + 1], X->zeros, U(p.tmpA), p.tmpA.elems, n, ch, cw, U(p.tmpB), p.tmpB.elems, f, 0, s, &fz));
+      X3ConvOpts oh;
+      oh.fuse = &fz;
+      HIPCHK(h->err, run_conv_x3(X->dec[2 * j + 1], conv2Io, oh, s));
       headFused = true;
     } else {
-      HIPCHK(h->err, run_conv_x3(X->dec[2 * j + 1], X->zeros, U(p.tmpA), p.tmpA.elems, n, ch, cw, U(p.tmpB), p.tmpB.elems, f, 0, s,
-                                 nullptr, 0, nullptr, nullptr, nullptr, &sk, nullptr, nullptr, qs, &lk2));
+      HIPCHK(h->err, run_conv_x3(X->dec[2 * j + 1], conv2Io, opts_of(&lk2, nullptr), s));
     }
     cur = &p.tmpB;
   }
@@ -1727,16 +1673,14 @@ int unet_forward_f32_x3(unet_handle_t h, const float* image, int n, int height, 
 int unet_op_conv3x3_x3(int device, const float* x, int n, int hh, int ww, int cin, const float* wHost,
                        const float* scale, const float* shift, int cout, int relu, int tileWidth, float* y,
                        float* yPool, void* stream) {
+  X3Force force;
   if (!x || !wHost || !scale || !shift || !y || cin % 64 || cout % 64 || cout > unet::X3Shape<32>::MAX_COUT ||
-      (tileWidth != 0 && tileWidth != 16 && tileWidth != 32 && tileWidth != 28 && tileWidth != 14 && tileWidth != 228 &&
-       tileWidth != 214 && tileWidth != 332 && tileWidth != 316 && tileWidth != 308 && tileWidth != 428 &&
-       tileWidth != 414 && tileWidth != 532 && tileWidth != 628 && tileWidth != 632 && tileWidth != 728) ||
-      (yPool && (hh % 2 || ww % 2)))
+      !x3_decode_force(tileWidth, &force) || (yPool && (hh % 2 || ww % 2)))
     return UNET_ERR_INVALID_ARG;
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   GemmOpX3 op;
-  const bool q8 = tileWidth == 428 || tileWidth == 414;
+  const bool q8 = force.family == kX3Q8;
   int rc = build_conv_x3(g_opErr, op, wHost, cout, cin, scale, shift, relu, false, nullptr, nullptr, q8);
   const size_t px = (size_t)n * hh * ww;
   const size_t ein = px * cin, eout = px * cout, epool = (px / 4) * cout;
@@ -1759,8 +1703,11 @@ int unet_op_conv3x3_x3(int device, const float* x, int n, int hh, int ww, int ci
       X3Fuse fz;
       fz.pool = ppool;
       fz.poolLo = epool;
-      e = run_conv_x3(op, zeros, pin, ein, n, hh, ww, pout, eout, cout, 0, s, yPool ? &fz : nullptr, tileWidth, nullptr, nullptr,
-                      nullptr, nullptr, nullptr, nullptr, reinterpret_cast<uint8_t*>(qsc));
+      X3ConvOpts o;
+      o.fuse = yPool ? &fz : nullptr;
+      o.forceTw = tileWidth;
+      o.qScratch = reinterpret_cast<uint8_t*>(qsc);
+      e = run_conv_x3(op, x3_from(zeros, pin, ein, n, hh, ww).to(pout, eout, cout), o, s);
     }
     if (e == hipSuccess) {
       hipLaunchKernelGGL(unet::merge_planes_kernel, dim3(grid_for(eout / 2)), dim3(256), 0, s,
@@ -1787,8 +1734,10 @@ int unet_op_conv3x3_x3(int device, const float* x, int n, int hh, int ww, int ci
 int unet_op_conv3x3_x3_head(int device, const float* x, int n, int hh, int ww, int cin, const float* wHost,
                             const float* scale, const float* shift, int relu, int tileWidth, const float* headW,
                             float headB, float* logits, void* stream) {
-  if (!x || !wHost || !scale || !shift || !headW || !logits || cin % 64 ||
-      (tileWidth != 0 && tileWidth != 16 && tileWidth != 32 && tileWidth != 628 && tileWidth != 632))
+  // (the fused head exists on the first structure and on the third's 16-row tiles)
+  X3Force force;
+  if (!x || !wHost || !scale || !shift || !headW || !logits || cin % 64 || !x3_decode_force(tileWidth, &force) ||
+      !(force.family == 0 || force.family == kX3Ws || (force.family == kX3T448 && force.waves != 4)))
     return UNET_ERR_INVALID_ARG;
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
@@ -1817,7 +1766,10 @@ int unet_op_conv3x3_x3_head(int device, const float* x, int n, int hh, int ww, i
       fz.headB = headB;
       fz.headThr = 0.f;
       fz.logits = logits;
-      e = run_conv_x3(op, zeros, pin, ein, n, hh, ww, nullptr, 0, 64, 0, s, &fz, tileWidth);
+      X3ConvOpts o;
+      o.fuse = &fz;
+      o.forceTw = tileWidth;
+      e = run_conv_x3(op, x3_from(zeros, pin, ein, n, hh, ww).to(nullptr, 0, 64), o, s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) {
@@ -1892,6 +1844,52 @@ int unet_host_compose_upcat(const float* wt, const float* bt, const float* w3, i
   return UNET_OK;
 }
 
+// Test hooks (host arithmetic only, no device): the plan the dispatch makes for a query given as integers, the switches
+// included (include/unet_hip.h lists both layouts)
+int unet_host_plan_conv3x3_x3(const int* query, int nQuery, int* planOut, int nPlan, char* labelOut, int labelCap) {
+  if (!query || nQuery != 22 || !planOut || nPlan != 24 || (labelOut && labelCap < 48)) return UNET_ERR_INVALID_ARG;
+  X3ConvQuery q;
+  q.n = query[0], q.h = query[1], q.w = query[2], q.cin = query[3], q.cout = query[4], q.epi = query[5];
+  if (q.n < 1 || q.h < 1 || q.w < 1 || q.cin < 32 || q.cout < 64 || q.epi < 0 || q.epi > 3 || query[9] < 0 ||
+      !x3_decode_force(query[6], &q.force))
+    return UNET_ERR_INVALID_ARG;
+  q.coOff = query[7], q.splitScratch = query[8] != 0, q.splitFloats = (size_t)query[9];
+  q.qScratch = query[10] != 0, q.wq = query[11] != 0;
+  q.inIsQ = query[12] != 0, q.wantOutQ = query[13] != 0, q.poolSrcQ = query[14] != 0, q.poolDstQ = query[15] != 0;
+  q.wantStats = query[16] != 0;
+  q.sw.flat = query[17] != 0, q.sw.r512 = query[18] != 0, q.sw.t448 = query[19] != 0, q.sw.t448c4 = query[20] != 0;
+  q.sw.crossFp8 = query[21];
+  const X3ConvPlan p = x3_plan_conv(q);
+  path_to_ints(p.path, planOut);
+  const int rest[17] = {p.grid,   p.statRows, p.toQ8Pass ? 1 : 0, p.poolPass, p.finishPass ? 1 : 0, p.outQ ? 1 : 0,
+                        p.valid ? 1 : 0, p.N,  p.H,  p.imgH,     p.tilesX,   p.tilesY, p.pixTiles, p.coTiles, p.coGroup,
+                        p.nChunks, p.kSplit};
+  std::copy(rest, rest + 17, planOut + 7);
+  if (!p.valid) std::fill(planOut, planOut + 24, 0);
+  if (labelOut) {
+    labelOut[0] = 0;
+    if (p.valid) x3_conv_label(p, labelOut, (size_t)labelCap);
+  }
+  return UNET_OK;
+}
+
+int unet_host_plan_upconv2x2_x3(const int* query, int nQuery, int* planOut, int nPlan, char* labelOut, int labelCap) {
+  if (!query || nQuery != 9 || !planOut || nPlan != 16 || (labelOut && labelCap < 48)) return UNET_ERR_INVALID_ARG;
+  X3UpconvQuery q;
+  if (query[0] < 1 || query[1] < 1 || query[2] < 1 || query[3] < 64 || query[4] < 64) return UNET_ERR_INVALID_ARG;
+  q.npix = (long)query[0] * query[1] * query[2], q.w = query[2], q.cin = query[3], q.cout = query[4];
+  q.coOff = query[5], q.wantOutQ = query[6] != 0;
+  q.mode = query[7] < 0 ? -1 : (query[7] > 1 ? 1 : query[7]);
+  q.gemm = query[8] != 0;
+  const X3UpconvPlan p = x3_plan_upconv(q);
+  path_to_ints(p.path, planOut);
+  const int rest[9] = {p.grid, 0, 0, 0, 0, p.outQ ? 1 : 0, p.valid ? 1 : 0, p.pixTiles, p.coTiles};
+  std::copy(rest, rest + 9, planOut + 7);
+  if (!p.valid) std::fill(planOut, planOut + 16, 0);
+  if (labelOut) snprintf(labelOut, (size_t)labelCap, "%s", p.valid && !q.gemm ? x3_upconv_label(p) : "");
+  return UNET_OK;
+}
+
 int unet_set_x3_compose(int mode) {
   const int prev = x3_compose_mode();
   x3_compose_mode() = mode < 0 ? -1 : (mode > 1 ? 1 : mode);
@@ -1929,7 +1927,7 @@ int unet_op_upconv2x2_x3(int device, const float* x, int n, int hh, int ww, int 
     if (e == hipSuccess) {
       hipLaunchKernelGGL(unet::split_planes_kernel, dim3(grid_for(ein / 2)), dim3(256), 0, s, x, ein / 2,
                          reinterpret_cast<uint32_t*>(pin), reinterpret_cast<uint32_t*>(pin + ein));
-      e = run_upconv_x3(op, zeros, pin, ein, n, hh, ww, pout, eout, cout, 0, s);
+      e = run_upconv_x3(op, x3_from(zeros, pin, ein, n, hh, ww).to(pout, eout, cout), s);
     }
     if (e == hipSuccess) {
       hipLaunchKernelGGL(unet::merge_planes_kernel, dim3(grid_for(eout / 2)), dim3(256), 0, s,
@@ -1956,10 +1954,10 @@ int unet_op_conv3x3_x3_planes(int device, const uint16_t* x, size_t xLo, int n, 
                               const float* outAct, int splitK, uint16_t* y, size_t yLo, int ldo, int coOff, uint16_t* pool,
                               size_t poolLo, const float* headW, float headB, float headThr, float* logits, float* probs,
                               uint8_t* mask, int* pathOut, int* rangeOut, void* stream) {
-  static const int kWidths[] = {0, 16, 32, 28, 14, 228, 214, 332, 316, 308, 532, 628, 632, 728};
+  X3Force force;   // (the f16q8 forms have no plane-level entry point)
   if (ldo == 0) ldo = cout;
   if (!x || !wHost || !scale || !shift || n < 1 || hh < 1 || ww < 1 || cin < 64 || cin % 64 || cout < 64 || cout % 64 ||
-      cout > unet::X3Shape<32>::MAX_COUT || std::find(std::begin(kWidths), std::end(kWidths), tileWidth) == std::end(kWidths) ||
+      cout > unet::X3Shape<32>::MAX_COUT || !x3_decode_force(tileWidth, &force) || force.family == kX3Q8 ||
       xLo % 8 || yLo % 8 || poolLo % 8 || ldo % 64 || coOff < 0 || coOff % 64 || coOff + cout > ldo ||
       (pool && (headW || hh % 2 || ww % 2)) || (headW ? (cout != 64 || !(logits || probs || mask)) : !y))
     return UNET_ERR_INVALID_ARG;
@@ -2007,8 +2005,12 @@ int unet_op_conv3x3_x3_planes(int device, const uint16_t* x, size_t xLo, int n, 
       sk.floats = kSplitFloats;
       sk.ones = ones;
       sk.zerosF = reinterpret_cast<const float*>(zeros);
-      e = run_conv_x3(op, zeros, x, xLo, n, hh, ww, y, yLo, ldo, coOff, s, (pool || headW) ? &fz : nullptr, tileWidth, nullptr,
-                      nullptr, nullptr, splitK ? &sk : nullptr, nullptr, nullptr, nullptr, nullptr, &path);
+      X3ConvOpts o;
+      o.fuse = (pool || headW) ? &fz : nullptr;
+      o.forceTw = tileWidth;
+      o.splitK = splitK ? &sk : nullptr;
+      o.path = &path;
+      e = run_conv_x3(op, x3_from(zeros, x, xLo, n, hh, ww).to(y, yLo, ldo, coOff), o, s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess) e = range.read(rangeOut);
@@ -2044,7 +2046,7 @@ int unet_op_upconv2x2_x3_planes(int device, const uint16_t* x, size_t xLo, int n
     hipError_t e = hipMalloc((void**)&zeros, 4096);
     if (e == hipSuccess) e = hipMemset(zeros, 0, 4096);
     if (e == hipSuccess) e = range.arm();
-    if (e == hipSuccess) e = run_upconv_x3(op, zeros, x, xLo, n, hh, ww, y, yLo, ldo, coOff, s, nullptr, &path);
+    if (e == hipSuccess) e = run_upconv_x3(op, x3_from(zeros, x, xLo, n, hh, ww).to(y, yLo, ldo, coOff), s, nullptr, &path);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess) e = range.read(rangeOut);
     if (e != hipSuccess) {
