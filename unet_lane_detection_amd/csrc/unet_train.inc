@@ -61,6 +61,68 @@ struct TrainPlan {
   size_t total = 0;
 };
 
+// Weight gradients beside the chain (train_side_mode): nothing in the backward pass waits for a dW, so the f16x3 weight-
+// gradient kernels run on a second stream of lower priority, each forked behind its unit's input-gradient convolution,
+// and the HBM-bound passes of the NEXT unit (BatchNorm backward, pooling backward, space-to-depth) run under them
+// instead of leaving the matrix pipes idle.  A slot is a set of buffers the side stream reads: the dZ planes alternate
+// between two (slots 0 and 1: a unit's planes are rewritten two units later, behind wait_slot), the transposed
+// convolutions' space-to-depth planes are the third.  The split-K slab belongs to the side stream while anything is
+// pending there (join before every main-stream use).  join() is the only place that clears the flags.
+struct SideStream {
+  static constexpr int kUpSlot = 2;
+  hipStream_t stream = nullptr;
+  hipEvent_t evFork = nullptr, evJoin = nullptr, evSlot[3] = {nullptr, nullptr, nullptr};
+  bool busy[3] = {false, false, false}, any = false;
+  int nextUnit = 0;   // conv units of this backward pass forked so far
+  int unit_slot() { return nextUnit++ & 1; }
+  hipError_t init() {
+    if (stream) return hipSuccess;
+    int lo = 0, hi = 0;
+    hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);   // lo = least urgent
+    if (e != hipSuccess) return e;
+    int prio = lo;   // UNET_TRAIN_SIDE_PRIO=n|h: the caller's / the highest priority (A/B measurements)
+    if (const char* pe = getenv("UNET_TRAIN_SIDE_PRIO")) prio = pe[0] == 'h' ? hi : (pe[0] == 'n' ? 0 : lo);
+    if ((e = hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, prio)) != hipSuccess) return e;
+    for (hipEvent_t* ev : {&evFork, &evJoin, &evSlot[0], &evSlot[1], &evSlot[2]})
+      if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return e;
+    return hipSuccess;
+  }
+  // whatever the side stream last ran on this slot's buffers happens before what is queued on s next
+  hipError_t wait_slot(int slot, hipStream_t s) { return busy[slot] ? hipStreamWaitEvent(s, evSlot[slot], 0) : hipSuccess; }
+  // launch(stream) on the side stream, behind everything queued on s so far; the slot is busy until the next join
+  template <class F>
+  hipError_t fork(int slot, hipStream_t s, F&& launch) {
+    hipError_t e = hipEventRecord(evFork, s);
+    if (e == hipSuccess) e = hipStreamWaitEvent(stream, evFork, 0);
+    if (e != hipSuccess) return e;
+    any = true;   // from here on something may be queued there: an error below still needs the join
+    if ((e = launch(stream)) == hipSuccess && (e = hipEventRecord(evSlot[slot], stream)) == hipSuccess) busy[slot] = true;
+    return e;
+  }
+  // everything queued on the side stream so far happens before whatever is queued on s next
+  hipError_t join(hipStream_t s) {
+    if (!any) return hipSuccess;
+    hipError_t e = hipEventRecord(evJoin, stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(s, evJoin, 0);
+    any = busy[0] = busy[1] = busy[2] = false;
+    return e;
+  }
+  void destroy() {
+    if (stream) {
+      hipStreamSynchronize(stream);
+      hipStreamDestroy(stream);
+    }
+    for (hipEvent_t ev : {evFork, evJoin, evSlot[0], evSlot[1], evSlot[2]})
+      if (ev) hipEventDestroy(ev);
+  }
+};
+// joins the side stream into s when the backward pass is left, on whichever return: a no-op after the pass's own final join
+struct SideJoinOnExit {
+  SideStream& side;
+  hipStream_t s;
+  ~SideJoinOnExit() { side.join(s); }
+};
+
 }  // namespace
 
 #include "validate_kernels.h"
@@ -94,19 +156,17 @@ struct TrainState {
   float* lossCoef = nullptr; // 2 floats (device) for the Dice gradient
   hipStream_t commStream = nullptr;   // data-parallel overlap: see unet_train_set_comm_stream
   hipEvent_t lateGradsReady = nullptr;
-  // Weight gradients beside the chain (train_side_mode): nothing in the backward pass waits for a dW, so the f16x3 weight-
-  // gradient kernels run on a second stream of lower priority, each forked behind its unit's input-gradient convolution,
-  // and the HBM-bound passes of the NEXT unit (BatchNorm backward, pooling backward, space-to-depth) run under them
-  // instead of leaving the matrix pipes idle.  The dZ planes alternate between two buffers (a unit's planes are
-  // rewritten two units later, behind evSide[]); the split-K slab belongs to the side stream while anything is pending
-  // there (side_join before every main-stream use).
-  hipStream_t side = nullptr;
-  hipEvent_t evFork = nullptr, evJoin = nullptr, evSide[2] = {nullptr, nullptr}, evSideUp = nullptr;
-  bool sideBusy[2] = {false, false}, sideUpBusy = false, sideAny = false;
-  int bwdIdx = 0;
-  unsigned* gzKeys = nullptr; // 8 order keys per conv unit, zeroed every step: [0..4] the maxima behind bn_bwd_scale_exponent,
+  SideStream side;            // the weight gradients' stream (train_side_mode)
+  std::vector<ConvUnit*> units;   // every conv unit in dbgId order: enc, bott, dec (fixed once attached)
+  unsigned* gzKeys = nullptr; // 8 order keys per unit, zeroed every step: [0..4] the maxima behind bn_bwd_scale_exponent,
                               // [7] max |dZ| (fp16 range scaling of dZ when it is split by a separate pass)
-  float* gzInv = nullptr;     // per conv unit: 2^-k undoing that scaling
+  float* gzInv = nullptr;     // per unit: 2^-k undoing that scaling
+  // the tables' layout: the conv units by dbgId, then the transposed convolutions by decoder step
+  size_t scaled_units() const { return units.size() + up.size(); }
+  unsigned* unit_keys(const ConvUnit& u) const { return gzKeys ? gzKeys + 8 * u.dbgId : nullptr; }
+  unsigned* up_keys(int j) const { return gzKeys + 8 * (units.size() + j); }
+  float* unit_inv(const ConvUnit& u) const { return gzInv + u.dbgId; }
+  float* up_inv(int j) const { return gzInv + units.size() + j; }
   // Eval-mode forward (unet_train_eval_*): per-unit folded scale / shift, rewritten by one launch at the start of every
   // eval pass from the live gamma / beta / running statistics; apart from the step's own scale / shift / mean / invstd,
   // which a later backward pass reads
@@ -250,8 +310,7 @@ int train_repack(unet_ctx* h, hipStream_t s) {
         }
       }
     };
-    for (auto* vec : {&T->enc, &T->bott, &T->dec})
-      for (auto& u : *vec) unit(u);
+    for (ConvUnit* u : T->units) unit(*u);
     for (auto& u : T->up)
       for (int t = 0; t < 2; ++t) {
         d[t].push_back(make_pack(u.fwd, T->params + u.offW, 2, u.cout, u.cin, u.cout));
@@ -290,15 +349,13 @@ int train_repack(unet_ctx* h, hipStream_t s) {
   // block per (64-channel tile, 32-channel chunk) with the tile's weights through LDS (float4 loads: every tensor starts
   // on a 16-byte boundary of the parameter buffer, else the gathering kernel per operator)
   bool viaLds = (reinterpret_cast<uintptr_t>(T->params) & 15) == 0;
-  for (auto* vec : {&T->enc, &T->bott, &T->dec})
-    for (auto& u : *vec)
-      if ((u.x3Fwd || u.x3Dgrad) && u.offW % 4 != 0) viaLds = false;
+  for (const ConvUnit* u : T->units)
+    if ((u->x3Fwd || u->x3Dgrad) && u->offW % 4 != 0) viaLds = false;
   if (viaLds) {
     if (!T->packX3Descs) {
       std::vector<unet::PackX3Desc> d;
       std::vector<unsigned> start{0};
-      for (auto* vec : {&T->enc, &T->bott, &T->dec})
-        for (auto& u : *vec) pack_x3_table_add(d, start, T->params + u.offW, u.x3Fwd, u.x3Dgrad, u.cout, u.cin);
+      for (const ConvUnit* u : T->units) pack_x3_table_add(d, start, T->params + u->offW, u->x3Fwd, u->x3Dgrad, u->cout, u->cin);
       T->nPackX3 = (int)d.size();
       T->packX3Blocks = start.back();
       if (T->nPackX3) {
@@ -310,11 +367,10 @@ int train_repack(unet_ctx* h, hipStream_t s) {
     }
     if (T->nPackX3) HIPCHK(h->err, launch_pack_x3_lds_multi(T->packX3Descs, T->packX3Start, T->nPackX3, T->packX3Blocks, s));
   } else {
-    for (auto* vec : {&T->enc, &T->bott, &T->dec})
-      for (auto& u : *vec) {
-        if (u.x3Fwd) launch_pack_x3(T->params + u.offW, u.x3Fwd, u.cout, u.cin, 0, s);
-        if (u.x3Dgrad) launch_pack_x3(T->params + u.offW, u.x3Dgrad, u.cin, u.cout, 1, s);
-      }
+    for (const ConvUnit* u : T->units) {
+      if (u->x3Fwd) launch_pack_x3(T->params + u->offW, u->x3Fwd, u->cout, u->cin, 0, s);
+      if (u->x3Dgrad) launch_pack_x3(T->params + u->offW, u->x3Dgrad, u->cin, u->cout, 1, s);
+    }
   }
   for (auto& u : T->up) {
     if (u.x3Fwd) launch_pack_upconv_x3(T->params + u.offW, u.x3Fwd, u.cin, u.cout, s);
@@ -691,6 +747,20 @@ void split_to_planes(const float* x, size_t elems, float* planes, hipStream_t s,
   prof_end(s);
 }
 
+// An operator of the f16x3 tier over packs and epilogue arrays that live elsewhere (a unit's x3Fwd / x3Dgrad, the
+// parameter buffer, TrainState::ones / zeros): GemmOpX3 frees nothing on its own, so the copy is simply dropped.
+GemmOpX3 x3_borrowed(int taps, int cin, int cout, int relu, const uint16_t* wt, const float* scale, const float* shift) {
+  GemmOpX3 op;
+  op.taps = taps;
+  op.cin = cin;
+  op.cout = cout;
+  op.relu = relu;
+  op.wt = const_cast<uint16_t*>(wt);
+  op.scale = const_cast<float*>(scale);
+  op.shift = const_cast<float*>(shift);
+  return op;
+}
+
 // y (fp32, pixel stride ldo, channel offset off) = conv3x3(planes of a dense (n,hh,ww,cin) tensor, packed hi/lo
 // weights); inv: the device scalar split_to_planes left for a scaled input, or null
 hipError_t run_train_conv_x3_planes(TrainState* T, const uint16_t* wt, int cin, int cout, const float* planes, int n,
@@ -699,14 +769,7 @@ hipError_t run_train_conv_x3_planes(TrainState* T, const uint16_t* wt, int cin, 
                                     int forceTw = 0, X3Path* path = nullptr) {
   // forceTw / path: the forced form and the path report of X3ConvOpts (the test entry point; the step passes neither)
   const size_t elems = (size_t)n * hh * ww * cin;
-  GemmOpX3 op;   // borrowed pointers: never freed through this object
-  op.taps = 9;
-  op.cin = cin;
-  op.cout = cout;
-  op.relu = 0;
-  op.wt = const_cast<uint16_t*>(wt);
-  op.scale = T->ones;
-  op.shift = T->zeros;
+  const GemmOpX3 op = x3_borrowed(9, cin, cout, 0, wt, T->ones, T->zeros);
   const X3ConvIo io = x3_from(reinterpret_cast<const uint16_t*>(zero_page()), reinterpret_cast<const uint16_t*>(planes), elems,
                               n, hh, ww).to(nullptr, 0, ldo, off);
   X3ConvOpts o;
@@ -716,10 +779,7 @@ hipError_t run_train_conv_x3_planes(TrainState* T, const uint16_t* wt, int cin, 
   o.dynScale = inv;
   o.statPartial = statPartial, o.statRows = statRows;
   o.path = path;
-  const hipError_t e = run_conv_x3(op, io, o, s);
-  op.wt = nullptr;
-  op.scale = op.shift = nullptr;
-  return e;
+  return run_conv_x3(op, io, o, s);
 }
 
 hipError_t run_train_conv_x3(TrainState* T, const uint16_t* wt, int cin, int cout, const float* x, int n, int hh, int ww,
@@ -843,31 +903,26 @@ int train_side_mode() {
 // or a debug snapshot is being taken
 bool side_on(const TrainState* T) { return train_side_mode() > 0 && !(g_prof && g_prof->on) && T->dbgStage < 0; }
 
-hipError_t side_init(TrainState* T) {
-  if (T->side) return hipSuccess;
-  int lo = 0, hi = 0;
-  hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);   // lo = least urgent
-  if (e != hipSuccess) return e;
-  int prio = lo;   // UNET_TRAIN_SIDE_PRIO=n|h: the caller's / the highest priority (A/B measurements)
-  if (const char* pe = getenv("UNET_TRAIN_SIDE_PRIO")) prio = pe[0] == 'h' ? hi : (pe[0] == 'n' ? 0 : lo);
-  if ((e = hipStreamCreateWithPriority(&T->side, hipStreamNonBlocking, prio)) != hipSuccess) return e;
-  for (hipEvent_t* ev : {&T->evFork, &T->evJoin, &T->evSide[0], &T->evSide[1], &T->evSideUp})
-    if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return e;
-  return hipSuccess;
-}
-// everything queued on the side stream so far happens before whatever is queued on s next
-hipError_t side_join(TrainState* T, hipStream_t s) {
-  if (!T->sideAny) return hipSuccess;
-  hipError_t e = hipEventRecord(T->evJoin, T->side);
-  if (e == hipSuccess) e = hipStreamWaitEvent(s, T->evJoin, 0);
-  T->sideAny = T->sideBusy[0] = T->sideBusy[1] = T->sideUpBusy = false;
-  return e;
-}
-// the side stream's next launch waits for everything queued on s so far
-hipError_t side_fork(TrainState* T, hipStream_t s) {
-  hipError_t e = hipEventRecord(T->evFork, s);
-  if (e == hipSuccess) e = hipStreamWaitEvent(T->side, T->evFork, 0);
-  return e;
+// One backward operator with a weight gradient, a conv unit or a transposed convolution: producer() on s writes what
+// both gradients read (into the buffers of `slot`), dgrad() on s is the input gradient, wgrad(stream) the weight gradient:
+// beside the chain on the side stream - forked before the input gradient in mode 1, behind it in mode 2 - or, with
+// slot < 0, in line on s between the two, where it takes the split-K slab back from the side stream first.
+template <class Producer, class Wgrad, class Dgrad>
+int backward_with_wgrad(unet_ctx* h, hipStream_t s, int slot, Producer&& producer, Wgrad&& wgrad, Dgrad&& dgrad) {
+  SideStream& side = h->train->side;
+  int rc;
+  if (slot >= 0) {
+    HIPCHK(h->err, side.init());
+    HIPCHK(h->err, side.wait_slot(slot, s));   // the weight gradient that last read these buffers must be through
+  } else {
+    HIPCHK(h->err, side.join(s));
+  }
+  if ((rc = producer())) return rc;
+  if (slot < 0) HIPCHK(h->err, wgrad(s));
+  else if (train_side_mode() == 1) HIPCHK(h->err, side.fork(slot, s, wgrad));
+  if ((rc = dgrad())) return rc;
+  if (slot >= 0 && train_side_mode() != 1) HIPCHK(h->err, side.fork(slot, s, wgrad));
+  return UNET_OK;
 }
 
 // ConvTranspose2d(2f -> f) of the training forward on planes: planes (n,h,w,cin) in, planes out with pixel stride ldo at
@@ -875,18 +930,9 @@ hipError_t side_fork(TrainState* T, hipStream_t s) {
 hipError_t run_train_upconv_x3(TrainState* T, const uint16_t* wt, const float* bias, int cin, int cout, const uint16_t* in,
                                size_t inLo, int n, int h, int w, uint16_t* out, size_t outLo, int ldo, int coOff,
                                hipStream_t s, X3Path* path = nullptr) {
-  GemmOpX3 op;   // borrowed pointers
-  op.taps = 1;
-  op.cin = cin;
-  op.cout = cout;
-  op.wt = const_cast<uint16_t*>(wt);
-  op.scale = T->ones;
-  op.shift = const_cast<float*>(bias);
-  const hipError_t e = run_upconv_x3(op, x3_from(reinterpret_cast<const uint16_t*>(zero_page()), in, inLo, n, h, w)
-                                             .to(out, outLo, ldo, coOff), s, nullptr, path);
-  op.wt = nullptr;
-  op.scale = op.shift = nullptr;
-  return e;
+  const GemmOpX3 op = x3_borrowed(1, cin, cout, 0, wt, T->ones, bias);
+  return run_upconv_x3(op, x3_from(reinterpret_cast<const uint16_t*>(zero_page()), in, inLo, n, h, w).to(out, outLo, ldo, coOff), s,
+                       nullptr, path);
 }
 
 // ConvTranspose2d backward, f16x3: the bias gradient is the column sum of the gradient slice dY (P hi-res pixels, pixel
@@ -924,6 +970,14 @@ struct ActOut {
   const float *headW = nullptr, *headB = nullptr;   // the last unit (64 channels): the 1x1 head in the same pass
   float* logits = nullptr;
 };
+// a dense activation of ld channels as fp32 and / or planes (either may be null)
+ActOut act_out(float* f32, float* planes, int ld) {
+  ActOut o;
+  o.f32 = f32;
+  o.planes = planes;
+  o.ld = o.ldp = ld;
+  return o;
+}
 
 // conv (raw) -> batch statistics -> a = relu(bn(z)).  inPlanes: the input already in operand form (planes mode),
 // else `in` is fp32 and is split into `planes` scratch when the unit runs on the split-operand kernel
@@ -963,9 +1017,9 @@ int unit_forward(unet_ctx* h, ConvUnit& u, const float* in, const float* inPlane
                      u.invstd, T->bn + u.offRM, T->bn + u.offRV);
   prof_end(s);
   prof_begin("bn_apply_relu", 0.0, (4.0 + (o.f32 ? 4.0 : 0.0) + (o.planes ? 4.0 : 0.0)) * P * u.cout, s);
-  if (o.pooled && hh % 2 == 0 && ww % 2 == 0) {
+  if (o.pooled) {
     // the pooling rides in the same pass (measured, batch 64: bn_apply_relu + maxpool2x2 over the four levels 1.31 ->
-    // 0.98 ms; same bits)
+    // 0.98 ms; same bits).  Only the walk asks for it, in front of a pooling: check_shape has made that map even.
     hipLaunchKernelGGL(unet::bn_apply_relu_pool_kernel, dim3(grid_for((P / 4) * (u.cout / 4))), dim3(256), 0, s, z, u.scale,
                        u.shift, n, hh, ww, u.cout, o.f32, o.ld, o.off, reinterpret_cast<uint32_t*>(o.planes),
                        P * (size_t)o.ldp / 2, o.ldp, o.offp, reinterpret_cast<uint32_t*>(o.pooled),
@@ -1005,401 +1059,65 @@ int unit_backward(unet_ctx* h, ConvUnit& u, const float* dA, int ldd, int offd, 
     h->err = "training plan inconsistent: a unit outside the split-operand path was handed an input in planes";
     return UNET_ERR_STATE;
   }
-  unsigned* keys = T->gzKeys ? T->gzKeys + 8 * u.dbgId : nullptr;
-  float* gzPlanes = ws + p.gzPlanes;
-  const bool side = fusedPlanes && side_on(T);
-  int sideIdx = 0;
-  if (side) {
-    HIPCHK(h->err, side_init(T));
-    sideIdx = T->bwdIdx++ & 1;
-    if (sideIdx) gzPlanes = ws + p.gzPlanes2;
-    // the weight gradient that read these planes two units ago must be through before they are rewritten
-    if (T->sideBusy[sideIdx]) HIPCHK(h->err, hipStreamWaitEvent(s, T->evSide[sideIdx], 0));
-  } else {
-    HIPCHK(h->err, side_join(T, s));   // this unit's weight gradient takes the slab on s
-  }
+  unsigned* keys = T->unit_keys(u);
+  float* inv = T->unit_inv(u);
+  // on the side stream the dZ planes alternate between two buffers, one per slot
+  const int slot = fusedPlanes && side_on(T) ? T->side.unit_slot() : -1;
+  float* gzPlanes = ws + (slot == 1 ? p.gzPlanes2 : p.gzPlanes);
   float* gzF32 = (!fusedPlanes || T->dbgStage == 300 + u.dbgId) ? gZ : nullptr;
-  prof_begin("bn_relu_bwd", 0.0, 4.0 * P * u.cout * 5, s);
-  if (partialRows <= 0)
-    hipLaunchKernelGGL(unet::bn_bwd_partial_kernel, dim3(nb), dim3(256), 0, s, dA, ldd, offd, z, u.scale, u.shift,
-                       u.mean, u.invstd, P, u.cout, partial, fusedPlanes ? keys : (unsigned*)nullptr, r1p, r1c);
-  hipLaunchKernelGGL(unet::reduce2_finalize_kernel, dim3((u.cout + unet::FIN_CH - 1) / unet::FIN_CH), dim3(256), 0, s, partial, nb, u.cout,
-                     T->grads + u.offB, T->grads + u.offG, fusedPlanes ? keys : (unsigned*)nullptr, (const float*)u.scale);
-  hipLaunchKernelGGL(unet::bn_bwd_apply_kernel, dim3(grid_for(P * (u.cout / 4))), dim3(256), 0, s, dA, ldd, offd, z,
-                     u.scale, u.shift, u.mean, u.invstd, T->grads + u.offB, T->grads + u.offG, (float)(1.0 / (double)P),
-                     P, u.cout, gzF32, (keys && !fusedPlanes) ? keys + 7 : (unsigned*)nullptr,
-                     (const unsigned*)(fusedPlanes ? keys : nullptr),
-                     fusedPlanes ? reinterpret_cast<uint32_t*>(gzPlanes) : (uint32_t*)nullptr, P * (size_t)u.cout / 2,
-                     fusedPlanes ? T->gzInv + u.dbgId : (float*)nullptr, r1p, r1c);
-  prof_end(s);
-  HIPCHK(h->err, hipGetLastError());
-  if (T->dbgStage == 300 + u.dbgId) hipMemcpyAsync(T->dbgDst, gZ, std::min(T->dbgMax, P * u.cout) * 4, hipMemcpyDeviceToDevice, s);
-  if (T->dbgStage == 400 + u.dbgId) hipMemcpyAsync(T->dbgDst, z, std::min(T->dbgMax, P * u.cout) * 4, hipMemcpyDeviceToDevice, s);
-  if (T->dbgStage == 500 + u.dbgId) hipMemcpyAsync(T->dbgDst, u.scale, std::min<size_t>(T->dbgMax, 4 * round_up(u.cout, 64)) * 4, hipMemcpyDeviceToDevice, s);
-  if (x3Path) {
+  auto producer = [&]() -> int {
+    prof_begin("bn_relu_bwd", 0.0, 4.0 * P * u.cout * 5, s);
+    if (partialRows <= 0)
+      hipLaunchKernelGGL(unet::bn_bwd_partial_kernel, dim3(nb), dim3(256), 0, s, dA, ldd, offd, z, u.scale, u.shift,
+                         u.mean, u.invstd, P, u.cout, partial, fusedPlanes ? keys : (unsigned*)nullptr, r1p, r1c);
+    hipLaunchKernelGGL(unet::reduce2_finalize_kernel, dim3((u.cout + unet::FIN_CH - 1) / unet::FIN_CH), dim3(256), 0, s, partial, nb, u.cout,
+                       T->grads + u.offB, T->grads + u.offG, fusedPlanes ? keys : (unsigned*)nullptr, (const float*)u.scale);
+    hipLaunchKernelGGL(unet::bn_bwd_apply_kernel, dim3(grid_for(P * (u.cout / 4))), dim3(256), 0, s, dA, ldd, offd, z,
+                       u.scale, u.shift, u.mean, u.invstd, T->grads + u.offB, T->grads + u.offG, (float)(1.0 / (double)P),
+                       P, u.cout, gzF32, (keys && !fusedPlanes) ? keys + 7 : (unsigned*)nullptr,
+                       (const unsigned*)(fusedPlanes ? keys : nullptr),
+                       fusedPlanes ? reinterpret_cast<uint32_t*>(gzPlanes) : (uint32_t*)nullptr, P * (size_t)u.cout / 2,
+                       fusedPlanes ? inv : (float*)nullptr, r1p, r1c);
+    prof_end(s);
+    HIPCHK(h->err, hipGetLastError());
+    if (T->dbgStage == 300 + u.dbgId) hipMemcpyAsync(T->dbgDst, gZ, std::min(T->dbgMax, P * u.cout) * 4, hipMemcpyDeviceToDevice, s);
+    if (T->dbgStage == 400 + u.dbgId) hipMemcpyAsync(T->dbgDst, z, std::min(T->dbgMax, P * u.cout) * 4, hipMemcpyDeviceToDevice, s);
+    if (T->dbgStage == 500 + u.dbgId) hipMemcpyAsync(T->dbgDst, u.scale, std::min<size_t>(T->dbgMax, 4 * round_up(u.cout, 64)) * 4, hipMemcpyDeviceToDevice, s);
     // f16x3: dZ in operand form (scaled into the fp16 range) serves the weight gradient and the input gradient
-    if (!fusedPlanes) split_to_planes(gZ, P * u.cout, gzPlanes, s, keys + 7, T->gzInv + u.dbgId);
-    auto side_wgrad = [&]() -> int {
-      HIPCHK(h->err, side_fork(T, s));
-      HIPCHK(h->err, run_wgrad_x3(gzPlanes, xPlanesIn, u.cout, u.cin, n, hh, ww, ws + p.slab, p.slabFloats,
-                                  T->grads + u.offW, T->gzInv + u.dbgId, T->side));
-      HIPCHK(h->err, hipEventRecord(T->evSide[sideIdx], T->side));
-      T->sideBusy[sideIdx] = T->sideAny = true;
-      return UNET_OK;
-    };
-    if (side) {
-      if (train_side_mode() == 1) {
-        const int rcw = side_wgrad();
-        if (rcw) return rcw;
-      }
-    } else if (wgradX3) {
-      if (!xPlanesIn) split_to_planes(x, P * u.cin, ws + p.xPlanes, s);
-      HIPCHK(h->err, run_wgrad_x3(gzPlanes, xPlanesIn ? xPlanesIn : ws + p.xPlanes, u.cout, u.cin, n, hh, ww,
-                                  ws + p.slab, p.slabFloats, T->grads + u.offW, T->gzInv + u.dbgId, s));
-    } else {
-      HIPCHK(h->err, run_wgrad(gZ, u.cout, x, ldx, u.cin, 9, n, hh, ww, ws + p.slab, p.slabFloats, T->grads + u.offW, 0,
-                               0, s, ws + p.s2d, p.s2dFloats));
-    }
-    if (u.needDgrad && dIn)
-      HIPCHK(h->err, run_train_conv_x3_planes(T, u.x3Dgrad, u.cout, u.cin, gzPlanes, n, hh, ww, dIn, ldIn, offIn,
-                                              "dgrad3x3_f16x3", s, T->gzInv + u.dbgId));
-    if (side && train_side_mode() != 1) return side_wgrad();
+    if (x3Path && !fusedPlanes) split_to_planes(gZ, P * u.cout, gzPlanes, s, keys + 7, inv);
     return UNET_OK;
-  }
-  // (p.s2d is free here: only the upconv backward uses it, and never inside a conv unit)
-  HIPCHK(h->err, run_wgrad(gZ, u.cout, x, ldx, u.cin, 9, n, hh, ww, ws + p.slab, p.slabFloats, T->grads + u.offW, 0,
-                           0, s, ws + p.s2d, p.s2dFloats));
-  if (u.needDgrad && dIn) HIPCHK(h->err, run_gemm_op(u.dgrad, gZ, n, hh, ww, dIn, ldIn, offIn, s));
-  return UNET_OK;
+  };
+  auto wgrad = [&](hipStream_t st) -> hipError_t {
+    if (!wgradX3)   // (p.s2d is free here: only the upconv backward uses it, and never inside a conv unit)
+      return run_wgrad(gZ, u.cout, x, ldx, u.cin, 9, n, hh, ww, ws + p.slab, p.slabFloats, T->grads + u.offW, 0, 0, st,
+                       ws + p.s2d, p.s2dFloats);
+    if (!xPlanesIn) split_to_planes(x, P * u.cin, ws + p.xPlanes, st);
+    return run_wgrad_x3(gzPlanes, xPlanesIn ? xPlanesIn : ws + p.xPlanes, u.cout, u.cin, n, hh, ww, ws + p.slab,
+                        p.slabFloats, T->grads + u.offW, inv, st);
+  };
+  auto dgrad = [&]() -> int {
+    if (!u.needDgrad || !dIn) return UNET_OK;
+    if (x3Path)
+      HIPCHK(h->err, run_train_conv_x3_planes(T, u.x3Dgrad, u.cout, u.cin, gzPlanes, n, hh, ww, dIn, ldIn, offIn,
+                                              "dgrad3x3_f16x3", s, inv));
+    else
+      HIPCHK(h->err, run_gemm_op(u.dgrad, gZ, n, hh, ww, dIn, ldIn, offIn, s));
+    return UNET_OK;
+  };
+  return backward_with_wgrad(h, s, slot, producer, wgrad, dgrad);
 }
 
-int train_forward_backward(unet_ctx* h, int n, int height, int width, const float* targets, float* lossDev,
-                           float* logitsOut, hipStream_t s, const TrainPlan& p) {
-  TrainState* T = h->train;
-  const unet_config& c = h->cfg;
-  const int D = c.depth;
-  LaunchScope scope(h);
-  float* ws = reinterpret_cast<float*>(T->ws);
-  float* partial = ws + p.partial;
-  float* planes = ws + p.xPlanes;
-  int rc;
-  if (T->packedX3 != (train_x3_enabled() ? 1 : 0) && (rc = train_repack(h, s))) return rc;   // unet_set_train_x3 since
-
-  // ------------------------------- forward (train mode) -------------------------------
-  const bool PM = p.planes;
-  auto f32Out = [](float* ptr, int ld, int off) {
-    ActOut o;
-    o.f32 = ptr;
-    o.ld = ld;
-    o.off = off;
-    return o;
-  };
-  auto planesOut = [](float* ptr, int ldp, int offp) {
-    ActOut o;
-    o.planes = ptr;
-    o.ldp = ldp;
-    o.offp = offp;
-    return o;
-  };
-  const float* cur = ws + p.x0;   // fp32 activation, or planes where PM says so
-  int ch = height, cw = width;
-  for (int l = 0; l < D; ++l) {
-    const int f = c.features[l];
-    const bool inP = PM && l > 0;   // the pooled input is in planes
-    if ((rc = unit_forward(h, T->enc[2 * l], inP ? nullptr : cur, inP ? cur : nullptr, n, ch, cw, ws + p.encZ1[l],
-                           PM ? planesOut(ws + p.encA1[l], f, 0) : f32Out(ws + p.encA1[l], f, 0), partial, planes, s)))
-      return rc;
-    ActOut skip = f32Out(ws + p.cat[l], 2 * f, 0);   // skip half of the concat buffer (fp32: pooling, its backward)
-    const bool poolFused = PM && ch % 2 == 0 && cw % 2 == 0 && train_pool_fused();
-    if (PM) {
-      skip.planes = ws + p.catP[l];
-      skip.ldp = 2 * f;
-      if (poolFused) skip.pooled = ws + p.pool[l];
-    }
-    if ((rc = unit_forward(h, T->enc[2 * l + 1], PM ? nullptr : ws + p.encA1[l], PM ? ws + p.encA1[l] : nullptr, n, ch, cw,
-                           ws + p.encZ2[l], skip, partial, planes, s)))
-      return rc;
-    if (poolFused) {
-      // pooled planes already written by the unit's BatchNorm pass
-    } else if (PM) {
-      const size_t total = (size_t)n * (ch / 2) * (cw / 2) * (f / 4);
-      prof_begin("maxpool2x2", 0.0, 4.0 * total * 4 * 5, s);
-      hipLaunchKernelGGL(unet::maxpool2x2_to_planes_kernel, dim3(grid_for(total)), dim3(256), 0, s, ws + p.cat[l], n, ch,
-                         cw, f, 2 * f, reinterpret_cast<uint32_t*>(ws + p.pool[l]), total * 2);
-      prof_end(s);
-      HIPCHK(h->err, hipGetLastError());
-    } else {
-      HIPCHK(h->err, run_maxpool(ws + p.cat[l], ws + p.pool[l], n, ch, cw, f, 2 * f, s));
-    }
-    cur = ws + p.pool[l];
-    ch /= 2;
-    cw /= 2;
-  }
-  const int fb = 2 * c.features[D - 1];
-  if ((rc = unit_forward(h, T->bott[0], PM ? nullptr : cur, PM ? cur : nullptr, n, ch, cw, ws + p.botZ1,
-                         PM ? planesOut(ws + p.botA1, fb, 0) : f32Out(ws + p.botA1, fb, 0), partial, planes, s)))
-    return rc;
-  // the output of a unit that feeds a transposed convolution: fp32 (its backward GEMMs) and, in planes mode, planes
-  auto upInOut = [&](float* f32, int j, int chn) {
-    ActOut o = f32Out(f32, chn, 0);
-    if (PM && j < D && T->up[j].x3Fwd) {
-      o.planes = ws + p.upInP[j];
-      o.ldp = chn;
-      // the fp32 copy is only read by the exact-fp32 GEMMs of the transposed convolution's backward
-      if (T->up[j].x3Dgrad && train_x3_wgrad_enabled() && T->dbgStage < 0) o.f32 = nullptr;
-    }
-    return o;
-  };
-  if ((rc = unit_forward(h, T->bott[1], PM ? nullptr : ws + p.botA1, PM ? ws + p.botA1 : nullptr, n, ch, cw, ws + p.botZ2,
-                         upInOut(ws + p.botA2, 0, fb), partial, planes, s)))
-    return rc;
-  cur = ws + p.botA2;
-  for (int j = 0; j < D; ++j) {
-    const int l = D - 1 - j;
-    const int f = c.features[l];
-    const bool upX3 = PM && T->up[j].x3Fwd;
-    if (upX3) {   // planes in, planes out: straight into the upper channel half of the concat buffer's operand form
-      const size_t Pin = (size_t)n * ch * cw;
-      uint16_t* outHi = reinterpret_cast<uint16_t*>(ws + p.catP[l]);
-      HIPCHK(h->err, run_train_upconv_x3(T, T->up[j].x3Fwd, T->params + T->up[j].offB, 2 * f, f,
-                                         reinterpret_cast<const uint16_t*>(ws + p.upInP[j]), Pin * 2 * f, n, ch, cw, outHi,
-                                         Pin * 4 * 2 * f, 2 * f, f, s));
-    } else {
-      HIPCHK(h->err, run_gemm_op(T->up[j].fwd, cur, n, ch, cw, ws + p.cat[l], 2 * f, f, s));
-    }
-    ch *= 2;
-    cw *= 2;
-    if (PM && !upX3) {   // upper half of the concat buffer -> operand form
-      const size_t Pl = (size_t)n * ch * cw;
-      prof_begin("split_planes", 0.0, 8.0 * Pl * f, s);
-      hipLaunchKernelGGL(unet::split_planes_strided_kernel, dim3(grid_for(Pl * (f / 4))), dim3(256), 0, s, ws + p.cat[l],
-                         2 * f, f, Pl, f, reinterpret_cast<uint32_t*>(ws + p.catP[l]), Pl * (size_t)(2 * f) / 2, 2 * f, f);
-      prof_end(s);
-      HIPCHK(h->err, hipGetLastError());
-    }
-    if ((rc = unit_forward(h, T->dec[2 * j], PM ? nullptr : ws + p.cat[l], PM ? ws + p.catP[l] : nullptr, n, ch, cw,
-                           ws + p.decZ1[l], PM ? planesOut(ws + p.decA1[l], f, 0) : f32Out(ws + p.decA1[l], f, 0), partial,
-                           planes, s)))
-      return rc;
-    ActOut lastOut = upInOut(ws + p.decA2[l], j + 1, f);
-    const bool headHere = j == D - 1 && f == 64 && train_pool_fused();   // (the same A/B switch as the pooling fusions)
-    if (headHere) {
-      lastOut.headW = T->params + T->offHeadW;
-      lastOut.headB = T->params + T->offHeadB;
-      lastOut.logits = ws + p.logits;
-    }
-    if ((rc = unit_forward(h, T->dec[2 * j + 1], PM ? nullptr : ws + p.decA1[l], PM ? ws + p.decA1[l] : nullptr, n, ch, cw,
-                           ws + p.decZ2[l], lastOut, partial, planes, s)))
-      return rc;
-    cur = ws + p.decA2[l];
-  }
-  const size_t P0 = (size_t)n * height * width;
-  const int f0 = c.features[0];
-  if (!(D > 0 && f0 == 64 && train_pool_fused()))
-    HIPCHK(h->err, run_head(cur, T->params + T->offHeadW, 0.f, P0, f0, ws + p.logits, nullptr, nullptr, 0.f, s,
-                            T->params + T->offHeadB));
-  if (logitsOut)
-    HIPCHK(h->err, hipMemcpyAsync(logitsOut, ws + p.logits, P0 * sizeof(float), hipMemcpyDeviceToDevice, s));
-
-  // ------------------------------- loss (a12) -------------------------------
-  if (T->lossMode == 2) {
-    // the reduction scratch holds kRedBlocks * 2 * 4096 floats, far beyond loss_scratch_bytes of any batch
-    const unet::LossParams lp{T->bceW, T->focalW, T->diceW, T->posWeight, T->focalAlpha, T->focalGamma, T->diceSmooth};
-    prof_begin("focal_loss_grad", 0.0, 20.0 * P0, s);
-    const hipError_t e = unet::launch_loss_grad(ws + p.logits, targets, P0, lp, partial, lossDev, ws + p.dlogits, s);
-    prof_end(s);
-    HIPCHK(h->err, e);
-  } else if (T->lossMode == 1) {
-    const int nb = red_blocks(P0);
-    prof_begin("bce_dice_loss_grad", 0.0, 20.0 * P0, s);
-    hipLaunchKernelGGL(unet::bce_dice_partial_kernel, dim3(nb), dim3(256), 0, s, ws + p.logits, targets, P0,
-                       T->posWeight, partial);
-    hipLaunchKernelGGL(unet::bce_dice_finalize_kernel, dim3(1), dim3(1), 0, s, partial, nb, (double)P0, T->bceW,
-                       T->diceW, T->diceSmooth, lossDev, T->lossCoef);
-    hipLaunchKernelGGL(unet::bce_dice_grad_kernel, dim3(grid_for(P0)), dim3(256), 0, s, ws + p.logits, targets, P0,
-                       (float)((double)T->bceW / (double)P0), T->diceW, T->posWeight, T->lossCoef, ws + p.dlogits);
-    prof_end(s);
-    HIPCHK(h->err, hipGetLastError());
-  } else {
-    const int nb = red_blocks(P0);
-    prof_begin("bce_loss_grad", 0.0, 12.0 * P0, s);
-    hipLaunchKernelGGL(unet::bce_loss_grad_kernel, dim3(nb), dim3(256), 0, s, ws + p.logits, targets, P0,
-                       (float)(1.0 / (double)P0), ws + p.dlogits, partial);
-    hipLaunchKernelGGL(unet::scalar_sum_finalize_kernel, dim3(1), dim3(1), 0, s, partial, nb, 1.0 / (double)P0,
-                       lossDev);
-    prof_end(s);
-    HIPCHK(h->err, hipGetLastError());
-  }
-
-  // ------------------------------- backward -------------------------------
-  T->bwdIdx = 0;
-  HIPCHK(h->err, hipMemsetAsync(T->gzKeys, 0, 8 * (T->enc.size() + T->bott.size() + T->dec.size() + T->up.size()) * sizeof(unsigned), s));
-  float* gA = ws + p.gA;
-  float* gB = ws + p.gB;
-  float* gZ = ws + p.gZ;
-  // The gradient w.r.t. the last unit's activation is dlogits[p] * w_head[c]: its BatchNorm backward forms that product
-  // itself instead of reading a P0 x f0 buffer written here (3 x 4 bytes per element less; same bits).  A debug snapshot
-  // keeps the buffer.
-  const bool headRank1 = T->dbgStage < 0;
-  {  // head: dW, db; dA (dense f0) into gA unless headRank1
-    const int nb = red_blocks(P0);
-    prof_begin("head_bwd", 0.0, 4.0 * P0 * ((headRank1 ? 1 : 2) * f0 + 1), s);
-    hipLaunchKernelGGL(unet::head_bwd_kernel, dim3(nb), dim3(256), 0, s, ws + p.dlogits, cur,
-                       T->params + T->offHeadW, P0, f0, headRank1 ? (float*)nullptr : gA, partial);
-    hipLaunchKernelGGL(unet::reduce2_finalize_kernel, dim3((f0 + unet::FIN_CH - 1) / unet::FIN_CH), dim3(256), 0, s, partial, nb, f0,
-                       T->grads + T->offHeadW, gB /* per-channel copies of sum(dl); column 0 is db */);
-    prof_end(s);
-    HIPCHK(h->err, hipMemcpyAsync(T->grads + T->offHeadB, gB, sizeof(float), hipMemcpyDeviceToDevice, s));
-  }
-  // decoder, shallowest level first (reverse of the forward order)
-  ch = height;
-  cw = width;
-  for (int j = D - 1; j >= 0; --j) {
-    const int l = D - 1 - j;
-    const int f = c.features[l];
-    // conv2: dA in gA (dense f) -> input gradient (w.r.t. decA1) into gB
-    const bool r1 = headRank1 && j == D - 1;
-    if ((rc = unit_backward(h, T->dec[2 * j + 1], gA, f, 0, ws + p.decZ2[l], ws + p.decA1[l], f, n, ch, cw, gZ, gB, f,
-                            0, p, s, PM ? ws + p.decA1[l] : nullptr, r1 ? ws + p.dlogits : nullptr,
-                            r1 ? T->params + T->offHeadW : nullptr)))
-      return rc;
-    // conv1: dA in gB -> gradient w.r.t. the concat buffer (2f channels) into dCat[l]
-    if ((rc = unit_backward(h, T->dec[2 * j], gB, f, 0, ws + p.decZ1[l], ws + p.cat[l], 2 * f, n, ch, cw, gZ,
-                            ws + p.dCat[l], 2 * f, 0, p, s, PM ? ws + p.catP[l] : nullptr)))
-      return rc;
-    // ConvTranspose2d backward on the upper channel half of dCat[l]
-    UpUnit& U = T->up[j];
-    const int lh = ch / 2, lw = cw / 2;
-    const size_t Pl = (size_t)n * lh * lw;
-    float* S = ws + p.s2d;
-    const float* upIn = (j == 0) ? ws + p.botA2 : ws + p.decA2[l + 1];
-    const bool upBwdX3 = PM && U.x3Dgrad && T->up[j].x3Fwd && train_x3_wgrad_enabled();
-    if (upBwdX3) {
-      // f16x3: the bias gradient is the column sum of the gradient slice itself; the same pass takes max |.|, the
-      // space-to-depth pass writes the scaled operand planes, both GEMMs run on the fp16 pipe
-      const size_t nUnits = T->enc.size() + T->bott.size() + T->dec.size();
-      unsigned* key = T->gzKeys + 8 * (nUnits + j);
-      float* inv = T->gzInv + nUnits + j;
-      HIPCHK(h->err, run_up_bias_grad_x3(ws + p.dCat[l], 2 * f, f, Pl * 4, f, partial, key, T->grads + U.offB, s));
-      const bool side = side_on(T);
-      if (side) {
-        HIPCHK(h->err, side_init(T));
-        // the previous level's weight gradient reads S on the side stream
-        if (T->sideUpBusy) HIPCHK(h->err, hipStreamWaitEvent(s, T->evSideUp, 0));
-      } else {
-        HIPCHK(h->err, side_join(T, s));
-      }
-      HIPCHK(h->err, run_up_s2d_planes_x3(ws + p.dCat[l], 2 * f, f, n, lh, lw, f, key, S, inv, s));
-      auto up_wgrad = [&](hipStream_t ws_) {
-        return run_wgrad1_x3(S, 4 * f, 4 * f, ws + p.upInP[j], U.cin, U.cin, (long)Pl, ws + p.slab, p.slabFloats,
-                             T->grads + U.offW, 1, f, inv, ws_);
-      };
-      auto side_up_wgrad = [&]() -> int {
-        HIPCHK(h->err, side_fork(T, s));
-        HIPCHK(h->err, up_wgrad(T->side));
-        HIPCHK(h->err, hipEventRecord(T->evSideUp, T->side));
-        T->sideUpBusy = T->sideAny = true;
-        return UNET_OK;
-      };
-      if (!side) HIPCHK(h->err, up_wgrad(s));
-      else if (train_side_mode() == 1 && (rc = side_up_wgrad())) return rc;
-      HIPCHK(h->err, run_gemm1x1_x3(U.x3Dgrad, x3_from(reinterpret_cast<const uint16_t*>(zero_page()), reinterpret_cast<const uint16_t*>(S),
-                                                       Pl * 4 * (size_t)f, n, lh, lw).to(nullptr, 0, U.cin),
-                                    4 * f, U.cin, gA, inv, "upconv_dgrad_f16x3", s));
-      if (side && train_side_mode() != 1 && (rc = side_up_wgrad())) return rc;
-      if (T->dbgStage == 200 + j)   // the fp32 form of S only exists for the snapshot
-        hipLaunchKernelGGL(unet::space_to_depth_kernel, dim3(grid_for(Pl * 4 * (f / 4))), dim3(256), 0, s, ws + p.dCat[l],
-                           2 * f, f, n, lh, lw, f, S);
-    } else {
-      HIPCHK(h->err, side_join(T, s));   // S and the slab are used on s below
-      prof_begin("space_to_depth", 0.0, 8.0 * Pl * 4 * f, s);
-      hipLaunchKernelGGL(unet::space_to_depth_kernel, dim3(grid_for(Pl * 4 * (f / 4))), dim3(256), 0, s, ws + p.dCat[l],
-                         2 * f, f, n, lh, lw, f, S);
-      prof_end(s);
-      {
-        const int nb = red_blocks(Pl);
-        prof_begin("bias_grad", 0.0, 4.0 * Pl * 4 * f, s);
-        hipLaunchKernelGGL(unet::colsum_partial_kernel, dim3(nb), dim3(256), 0, s, S, 4 * f, 0, Pl, 4 * f, partial,
-                           (unsigned*)nullptr);
-        hipLaunchKernelGGL(unet::colsum_finalize_kernel, dim3((f + unet::FIN_CH - 1) / unet::FIN_CH), dim3(256), 0, s, partial, nb, 4 * f, f,
-                           T->grads + U.offB);
-        prof_end(s);
-      }
-      HIPCHK(h->err, hipGetLastError());
-      HIPCHK(h->err, run_wgrad(S, 4 * f, upIn, U.cin, U.cin, 1, n, lh, lw, ws + p.slab, p.slabFloats,
-                               T->grads + U.offW, 1, f, s));
-      HIPCHK(h->err, run_gemm_op(U.dgrad, S, n, lh, lw, gA, U.cin, 0, s));  // gradient w.r.t. the upconv input
-    }
-    if (T->dbgStage == 100 + j) hipMemcpyAsync(T->dbgDst, gA, std::min(T->dbgMax, Pl * U.cin) * 4, hipMemcpyDeviceToDevice, s);
-    if (T->dbgStage == 200 + j) hipMemcpyAsync(T->dbgDst, S, std::min(T->dbgMax, Pl * 4 * f) * 4, hipMemcpyDeviceToDevice, s);
-    ch = lh;
-    cw = lw;
-  }
-  // bottleneck (gA holds the gradient w.r.t. botA2)
-  {
-    const int fl = c.features[D - 1];
-    if ((rc = unit_backward(h, T->bott[1], gA, fb, 0, ws + p.botZ2, ws + p.botA1, fb, n, ch, cw, gZ, gB, fb, 0, p, s,
-                            PM ? ws + p.botA1 : nullptr)))
-      return rc;
-    // gradient w.r.t. pool[D-1] into gA (dense fl channels)
-    if ((rc = unit_backward(h, T->bott[0], gB, fb, 0, ws + p.botZ1, ws + p.pool[D - 1], fl, n, ch, cw, gZ, gA, fl, 0,
-                            p, s, PM ? ws + p.pool[D - 1] : nullptr)))
-      return rc;
-  }
-  // Every gradient of the decoder, the bottleneck and the head is final now: they are the tail of the flat buffer
-  // (unet_train_grad_split).  A data-parallel caller's communication stream may start reducing that tail while the
-  // encoder's backward still runs.
-  if (T->commStream) {
-    HIPCHK(h->err, side_join(T, s));   // ... once the side stream's weight gradients are in
-    if (!T->lateGradsReady) HIPCHK(h->err, hipEventCreateWithFlags(&T->lateGradsReady, hipEventDisableTiming));
-    HIPCHK(h->err, hipEventRecord(T->lateGradsReady, s));
-    HIPCHK(h->err, hipStreamWaitEvent(T->commStream, T->lateGradsReady, 0));
-  }
-  // encoder, deepest level first; gA = gradient w.r.t. pool[l]
-  for (int l = D - 1; l >= 0; --l) {
-    const int f = c.features[l];
-    ch *= 2;
-    cw *= 2;
-    const size_t P = (size_t)n * ch * cw;
-    // dA(conv2 output) = skip half of dCat[l] + unpooled gA   -> gB (dense f)
-    // ... with the first pass of that unit's BatchNorm backward in the same kernel (UNET_TRAIN_POOL_FUSED=0: separately)
-    int poolRows = 0;
-    if (train_pool_fused() && ch % 2 == 0 && cw % 2 == 0 && T->dbgStage < 0) {
-      ConvUnit& u2 = T->enc[2 * l + 1];
-      poolRows = red_blocks(P / 4);
-      prof_begin("maxpool_bwd_add_bnstat", 0.0, 4.0 * P * f * 4.25, s);
-      hipLaunchKernelGGL(unet::maxpool_bwd_add_bnstat_kernel, dim3(poolRows), dim3(256), 0, s, ws + p.cat[l], 2 * f,
-                         ws + p.dCat[l], 2 * f, 0, gA, n, ch, cw, f, gB, ws + p.encZ2[l], u2.mean, u2.invstd, partial,
-                         T->gzKeys ? T->gzKeys + 8 * u2.dbgId : (unsigned*)nullptr);
-      prof_end(s);
-    } else {
-      prof_begin("maxpool_bwd_add", 0.0, 4.0 * P * f * 3.25, s);
-      hipLaunchKernelGGL(unet::maxpool_bwd_add_kernel, dim3(grid_for((P / 4) * (f / 4))), dim3(256), 0, s, ws + p.cat[l],
-                         2 * f, ws + p.dCat[l], 2 * f, 0, gA, n, ch, cw, f, gB);
-      prof_end(s);
-    }
-    HIPCHK(h->err, hipGetLastError());
-    if ((rc = unit_backward(h, T->enc[2 * l + 1], gB, f, 0, ws + p.encZ2[l], ws + p.encA1[l], f, n, ch, cw, gZ, gA, f,
-                            0, p, s, PM ? ws + p.encA1[l] : nullptr, nullptr, nullptr, poolRows)))
-      return rc;
-    const float* xin = (l == 0) ? ws + p.x0 : ws + p.pool[l - 1];
-    const int ldx = (l == 0) ? 4 : c.features[l - 1];
-    if ((rc = unit_backward(h, T->enc[2 * l], gA, f, 0, ws + p.encZ1[l], xin, ldx, n, ch, cw, gZ,
-                            (l == 0) ? nullptr : gB, ldx, 0, p, s, (PM && l > 0) ? xin : nullptr)))
-      return rc;
-    if (l > 0) std::swap(gA, gB);  // the input gradient (w.r.t. pool[l-1]) is now in gA
-  }
-  HIPCHK(h->err, side_join(T, s));   // the caller's stream owns every gradient again
-  return h->async_error();
-}
-
-int train_prologue(unet_ctx* h, const void* in, const float* targets, float* loss, int n, int height, int width,
-                   TrainPlan& plan) {
-  if (!h || !in || !targets || !loss) return UNET_ERR_INVALID_ARG;
+// What a pass over the attached state needs before its first launch, for either pass: the attached state ...
+int pass_state(unet_ctx* h) {
+  if (!h) return UNET_ERR_INVALID_ARG;
   if (!h->train || !h->train->packed) {
     h->err = "unet_train_attach has not been called";
     return UNET_ERR_STATE;
   }
+  return UNET_OK;
+}
+// ... and a legal shape, its plan and a workspace that holds it
+int pass_workspace(unet_ctx* h, int n, int height, int width, TrainPlan& plan) {
   int rc = check_shape(h, n, height, width);
   if (rc) return rc;
   HIPCHK(h->err, hipSetDevice(h->cfg.device));
@@ -1422,6 +1140,20 @@ int train_prologue(unet_ctx* h, const void* in, const float* targets, float* los
   return UNET_OK;
 }
 
+int train_prologue(unet_ctx* h, const void* in, const float* targets, float* loss, int n, int height, int width,
+                   TrainPlan& plan) {
+  if (!h || !in || !targets || !loss) return UNET_ERR_INVALID_ARG;
+  const int rc = pass_state(h);
+  return rc ? rc : pass_workspace(h, n, height, width, plan);
+}
+
+int eval_prologue(unet_ctx* h, const void* in, float* logits, int n, int height, int width, TrainPlan& plan) {
+  const int rc = pass_state(h);
+  if (rc) return rc;
+  if (!in || !logits) return UNET_ERR_INVALID_ARG;
+  return pass_workspace(h, n, height, width, plan);
+}
+
 // ---- eval-mode forward on the attached parameters (reference README.md:2089-2099: model.eval(); no_grad) --------
 //
 // The same operand packs and the same dispatch as unit_forward, with BatchNorm in eval form: one launch folds gamma,
@@ -1437,19 +1169,17 @@ int eval_init(unet_ctx* h) {
   TrainState* T = h->train;
   if (T->evalArena) return UNET_OK;
   size_t floats = 0;
-  for (auto* vec : {&T->enc, &T->bott, &T->dec})
-    for (auto& u : *vec) floats += 2 * (size_t)round_up(u.cout, 128);
+  for (const ConvUnit* u : T->units) floats += 2 * (size_t)round_up(u->cout, 128);
   HIPCHK(h->err, hipMalloc((void**)&T->evalArena, floats * sizeof(float)));
   std::vector<unet::BnFoldDesc> d;
   float* sp = T->evalArena;
-  for (auto* vec : {&T->enc, &T->bott, &T->dec})
-    for (auto& u : *vec) {
-      const int cp = round_up(u.cout, 128);
-      u.evScale = sp;
-      u.evShift = sp + cp;
-      sp += 2 * cp;
-      d.push_back({T->params + u.offG, T->params + u.offB, T->bn + u.offRM, T->bn + u.offRV, u.evScale, u.evShift, u.cout, cp});
-    }
+  for (ConvUnit* u : T->units) {
+    const int cp = round_up(u->cout, 128);
+    u->evScale = sp;
+    u->evShift = sp + cp;
+    sp += 2 * cp;
+    d.push_back({T->params + u->offG, T->params + u->offB, T->bn + u->offRM, T->bn + u->offRV, u->evScale, u->evShift, u->cout, cp});
+  }
   T->nEvalUnits = (int)d.size();
   HIPCHK(h->err, hipMalloc((void**)&T->evalDescs, d.size() * sizeof(unet::BnFoldDesc)));
   HIPCHK(h->err, hipMemcpy(T->evalDescs, d.data(), d.size() * sizeof(unet::BnFoldDesc), hipMemcpyHostToDevice));
@@ -1471,14 +1201,7 @@ int eval_unit(unet_ctx* h, ConvUnit& u, const float* in, const float* inPlanes, 
       split_to_planes(in, P * u.cin, planes, s);
       inPlanes = planes;
     }
-    GemmOpX3 op;   // borrowed pointers: never freed through this object
-    op.taps = 9;
-    op.cin = u.cin;
-    op.cout = u.cout;
-    op.relu = 1;
-    op.wt = u.x3Fwd;
-    op.scale = u.evScale;
-    op.shift = u.evShift;
+    const GemmOpX3 op = x3_borrowed(9, u.cin, u.cout, 1, u.x3Fwd, u.evScale, u.evShift);
     X3ConvIo io = x3_from(reinterpret_cast<const uint16_t*>(zero_page()), reinterpret_cast<const uint16_t*>(inPlanes), P * u.cin,
                           n, hh, ww);
     X3ConvOpts co;
@@ -1496,10 +1219,7 @@ int eval_unit(unet_ctx* h, ConvUnit& u, const float* in, const float* inPlanes, 
       io = io.to(nullptr, 0, o.ld, o.off);
       co.outF = o.f32;
     }
-    const hipError_t e = run_conv_x3(op, io, co, s);
-    op.wt = nullptr;
-    op.scale = op.shift = nullptr;
-    HIPCHK(h->err, e);
+    HIPCHK(h->err, run_conv_x3(op, io, co, s));
     return UNET_OK;
   }
   if (o.planes) {
@@ -1530,64 +1250,80 @@ int eval_unit(unet_ctx* h, ConvUnit& u, const float* in, const float* inPlanes, 
   return UNET_OK;
 }
 
-int train_eval_forward(unet_ctx* h, int n, int height, int width, float* logitsOut, hipStream_t s, const TrainPlan& p) {
+// unet_set_train_x3 since the last repack: the packs follow the switch
+int repack_if_switched(unet_ctx* h, hipStream_t s) {
+  return h->train->packedX3 != (train_x3_enabled() ? 1 : 0) ? train_repack(h, s) : UNET_OK;
+}
+
+// The forward traversal of the network, once for both passes: the training step (unit_forward: batch statistics, everything
+// the backward pass reads is kept) and the eval pass (eval_unit: folded running statistics, nothing kept).  The rules that
+// differ between the two stand side by side in the lambdas at the top; the loops, the level arithmetic, the workspace
+// offsets, the transposed convolutions' dispatch and the strided split below them exist once.  Logits to `logits`.
+enum class Pass { Train, Eval };
+
+int forward_walk(unet_ctx* h, Pass pass, int n, int height, int width, float* logits, hipStream_t s, const TrainPlan& p) {
   TrainState* T = h->train;
   const unet_config& c = h->cfg;
   const int D = c.depth;
-  LaunchScope scope(h);
+  const bool train = pass == Pass::Train, PM = p.planes;
   float* ws = reinterpret_cast<float*>(T->ws);
-  float* planes = ws + p.xPlanes;
   int rc;
-  if (T->packedX3 != (train_x3_enabled() ? 1 : 0) && (rc = train_repack(h, s))) return rc;   // unet_set_train_x3 since
-  if ((rc = eval_init(h))) return rc;
-  prof_begin("eval_bn_fold", 0.0, 24.0 * T->B, s);
-  const hipError_t ef = unet::launch_bn_eval_fold(T->evalDescs, T->nEvalUnits, kBnEps, s);
-  prof_end(s);
-  HIPCHK(h->err, ef);
-
-  const bool PM = p.planes;
-  auto actOut = [&](float* ptr, int ld, bool asPlanes) {
-    ActOut o;
-    if (asPlanes) {
-      o.planes = ptr;
-      o.ldp = ld;
-    } else {
-      o.f32 = ptr;
-      o.ld = ld;
-    }
+  // one conv unit; `in` is planes where inP says so
+  auto unit = [&](ConvUnit& u, const float* in, bool inP, int hh, int ww, float* z, const ActOut& o) {
+    const float *f32 = inP ? nullptr : in, *pl = inP ? in : nullptr;
+    return train ? unit_forward(h, u, f32, pl, n, hh, ww, z, o, ws + p.partial, ws + p.xPlanes, s)
+                 : eval_unit(h, u, f32, pl, n, hh, ww, z, o, ws + p.xPlanes, s);
+  };
+  // an activation only 3x3 convolutions read (either pass): planes in planes mode, else fp32
+  auto inner = [&](float* buf, int ld) { return PM ? act_out(nullptr, buf, ld) : act_out(buf, nullptr, ld); };
+  // pooling: inside the unit that writes the skip (train: its BatchNorm pass, unless UNET_TRAIN_POOL_FUSED=0; eval: the
+  // convolution's epilogue), else as a pass over the fp32 skip.  The maps are even: check_shape, at every level above
+  // the bottleneck
+  const bool poolInUnit = PM && (!train || train_pool_fused());
+  // the skip half of the concat buffer: train keeps fp32 (its pooling's backward reads it) beside the planes of planes
+  // mode; eval writes planes or fp32, never both
+  auto skipOut = [&](int l, int f) {
+    ActOut o = act_out(train || !PM ? ws + p.cat[l] : nullptr, PM ? ws + p.catP[l] : nullptr, 2 * f);
+    if (poolInUnit) o.pooled = ws + p.pool[l];
     return o;
   };
+  // the output of the unit in front of decoder step j (j == D: the last unit, which feeds the head in fp32): planes where
+  // the transposed convolution runs on the split-operand kernel.  Eval then writes no fp32; train keeps fp32 unless nobody
+  // reads it (only the exact-fp32 GEMMs of the transposed convolution's backward do, and a debug snapshot)
+  auto upInOut = [&](float* buf, int j, int chn) {
+    const bool asP = PM && j < D && T->up[j].x3Fwd;
+    const bool f32 = !asP || (train && !(T->up[j].x3Dgrad && train_x3_wgrad_enabled() && T->dbgStage < 0));
+    return act_out(f32 ? buf : nullptr, asP ? ws + p.upInP[j] : nullptr, chn);
+  };
+  // the 1x1 head: train lets it ride in the last unit's BatchNorm pass (64 channels; the same A/B switch as the pooling
+  // fusions), eval always launches it
+  const bool headInUnit = train && c.features[0] == 64 && train_pool_fused();
+
   const float* cur = ws + p.x0;   // fp32 activation, or planes where PM says so
   int ch = height, cw = width;
   for (int l = 0; l < D; ++l) {
     const int f = c.features[l];
-    const bool inP = PM && l > 0;
-    if ((rc = eval_unit(h, T->enc[2 * l], inP ? nullptr : cur, inP ? cur : nullptr, n, ch, cw, ws + p.encZ1[l],
-                        actOut(ws + p.encA1[l], f, PM), planes, s)))
-      return rc;
-    // the skip half of the concat buffer; in planes mode with the pooled planes from the same epilogue
-    ActOut skip = actOut(PM ? ws + p.catP[l] : ws + p.cat[l], 2 * f, PM);
-    if (PM) skip.pooled = ws + p.pool[l];
-    if ((rc = eval_unit(h, T->enc[2 * l + 1], PM ? nullptr : ws + p.encA1[l], PM ? ws + p.encA1[l] : nullptr, n, ch, cw,
-                        ws + p.encZ2[l], skip, planes, s)))
-      return rc;
-    if (!PM) HIPCHK(h->err, run_maxpool(ws + p.cat[l], ws + p.pool[l], n, ch, cw, f, 2 * f, s));
+    if ((rc = unit(T->enc[2 * l], cur, PM && l > 0, ch, cw, ws + p.encZ1[l], inner(ws + p.encA1[l], f)))) return rc;
+    if ((rc = unit(T->enc[2 * l + 1], ws + p.encA1[l], PM, ch, cw, ws + p.encZ2[l], skipOut(l, f)))) return rc;
+    if (poolInUnit) {
+      // pooled planes already written by the unit
+    } else if (PM) {
+      const size_t total = (size_t)n * (ch / 2) * (cw / 2) * (f / 4);
+      prof_begin("maxpool2x2", 0.0, 4.0 * total * 4 * 5, s);
+      hipLaunchKernelGGL(unet::maxpool2x2_to_planes_kernel, dim3(grid_for(total)), dim3(256), 0, s, ws + p.cat[l], n, ch,
+                         cw, f, 2 * f, reinterpret_cast<uint32_t*>(ws + p.pool[l]), total * 2);
+      prof_end(s);
+      HIPCHK(h->err, hipGetLastError());
+    } else {
+      HIPCHK(h->err, run_maxpool(ws + p.cat[l], ws + p.pool[l], n, ch, cw, f, 2 * f, s));
+    }
     cur = ws + p.pool[l];
     ch /= 2;
     cw /= 2;
   }
   const int fb = 2 * c.features[D - 1];
-  if ((rc = eval_unit(h, T->bott[0], PM ? nullptr : cur, PM ? cur : nullptr, n, ch, cw, ws + p.botZ1,
-                      actOut(ws + p.botA1, fb, PM), planes, s)))
-    return rc;
-  // the output of a unit that feeds a transposed convolution: planes where that runs on the split-operand kernel
-  auto upInOut = [&](float* f32, int j, int chn) {
-    const bool asP = PM && j < D && T->up[j].x3Fwd;
-    return actOut(asP ? ws + p.upInP[j] : f32, chn, asP);
-  };
-  if ((rc = eval_unit(h, T->bott[1], PM ? nullptr : ws + p.botA1, PM ? ws + p.botA1 : nullptr, n, ch, cw, ws + p.botZ2,
-                      upInOut(ws + p.botA2, 0, fb), planes, s)))
-    return rc;
+  if ((rc = unit(T->bott[0], cur, PM, ch, cw, ws + p.botZ1, inner(ws + p.botA1, fb)))) return rc;
+  if ((rc = unit(T->bott[1], ws + p.botA1, PM, ch, cw, ws + p.botZ2, upInOut(ws + p.botA2, 0, fb)))) return rc;
   cur = ws + p.botA2;
   for (int j = 0; j < D; ++j) {
     const int l = D - 1 - j;
@@ -1611,30 +1347,266 @@ int train_eval_forward(unet_ctx* h, int n, int height, int width, float* logitsO
       prof_end(s);
       HIPCHK(h->err, hipGetLastError());
     }
-    if ((rc = eval_unit(h, T->dec[2 * j], PM ? nullptr : ws + p.cat[l], PM ? ws + p.catP[l] : nullptr, n, ch, cw,
-                        ws + p.decZ1[l], actOut(ws + p.decA1[l], f, PM), planes, s)))
+    if ((rc = unit(T->dec[2 * j], PM ? ws + p.catP[l] : ws + p.cat[l], PM, ch, cw, ws + p.decZ1[l], inner(ws + p.decA1[l], f))))
       return rc;
-    // the last unit feeds the 1x1 head: fp32
-    const ActOut lastOut = j == D - 1 ? actOut(ws + p.decA2[l], f, false) : upInOut(ws + p.decA2[l], j + 1, f);
-    if ((rc = eval_unit(h, T->dec[2 * j + 1], PM ? nullptr : ws + p.decA1[l], PM ? ws + p.decA1[l] : nullptr, n, ch, cw,
-                        ws + p.decZ2[l], lastOut, planes, s)))
-      return rc;
+    ActOut last = upInOut(ws + p.decA2[l], j + 1, f);
+    if (headInUnit && j == D - 1) {
+      last.headW = T->params + T->offHeadW;
+      last.headB = T->params + T->offHeadB;
+      last.logits = logits;
+    }
+    if ((rc = unit(T->dec[2 * j + 1], ws + p.decA1[l], PM, ch, cw, ws + p.decZ2[l], last))) return rc;
     cur = ws + p.decA2[l];
   }
-  HIPCHK(h->err, run_head(cur, T->params + T->offHeadW, 0.f, (size_t)n * height * width, c.features[0], logitsOut, nullptr,
-                          nullptr, 0.f, s, T->params + T->offHeadB));
+  if (!headInUnit)
+    HIPCHK(h->err, run_head(cur, T->params + T->offHeadW, 0.f, (size_t)n * height * width, c.features[0], logits, nullptr,
+                            nullptr, 0.f, s, T->params + T->offHeadB));
+  return UNET_OK;
+}
+
+// the loss of lossMode over P0 logits: its terms to lossDev, its logit gradient to the workspace's dlogits
+int run_loss_grad(unet_ctx* h, const float* targets, size_t P0, float* lossDev, hipStream_t s, const TrainPlan& p) {
+  TrainState* T = h->train;
+  float* ws = reinterpret_cast<float*>(T->ws);
+  float* partial = ws + p.partial;
+  if (T->lossMode == 2) {
+    // the reduction scratch holds kRedBlocks * 2 * 4096 floats, far beyond loss_scratch_bytes of any batch
+    const unet::LossParams lp{T->bceW, T->focalW, T->diceW, T->posWeight, T->focalAlpha, T->focalGamma, T->diceSmooth};
+    prof_begin("focal_loss_grad", 0.0, 20.0 * P0, s);
+    const hipError_t e = unet::launch_loss_grad(ws + p.logits, targets, P0, lp, partial, lossDev, ws + p.dlogits, s);
+    prof_end(s);
+    HIPCHK(h->err, e);
+  } else if (T->lossMode == 1) {
+    const int nb = red_blocks(P0);
+    prof_begin("bce_dice_loss_grad", 0.0, 20.0 * P0, s);
+    hipLaunchKernelGGL(unet::bce_dice_partial_kernel, dim3(nb), dim3(256), 0, s, ws + p.logits, targets, P0,
+                       T->posWeight, partial);
+    hipLaunchKernelGGL(unet::bce_dice_finalize_kernel, dim3(1), dim3(1), 0, s, partial, nb, (double)P0, T->bceW,
+                       T->diceW, T->diceSmooth, lossDev, T->lossCoef);
+    hipLaunchKernelGGL(unet::bce_dice_grad_kernel, dim3(grid_for(P0)), dim3(256), 0, s, ws + p.logits, targets, P0,
+                       (float)((double)T->bceW / (double)P0), T->diceW, T->posWeight, T->lossCoef, ws + p.dlogits);
+    prof_end(s);
+    HIPCHK(h->err, hipGetLastError());
+  } else {
+    const int nb = red_blocks(P0);
+    prof_begin("bce_loss_grad", 0.0, 12.0 * P0, s);
+    hipLaunchKernelGGL(unet::bce_loss_grad_kernel, dim3(nb), dim3(256), 0, s, ws + p.logits, targets, P0,
+                       (float)(1.0 / (double)P0), ws + p.dlogits, partial);
+    hipLaunchKernelGGL(unet::scalar_sum_finalize_kernel, dim3(1), dim3(1), 0, s, partial, nb, 1.0 / (double)P0,
+                       lossDev);
+    prof_end(s);
+    HIPCHK(h->err, hipGetLastError());
+  }
+  return UNET_OK;
+}
+
+// ConvTranspose2d backward of decoder step j, on the upper channel half of dCat[l] (n x ch x cw pixels): db, dW, and the
+// gradient w.r.t. the transposed convolution's input (botA2 / decA2[l + 1]) into gA
+int upconv_backward(unet_ctx* h, int j, int n, int ch, int cw, float* gA, hipStream_t s, const TrainPlan& p) {
+  TrainState* T = h->train;
+  const int l = h->cfg.depth - 1 - j;
+  const int f = h->cfg.features[l];
+  float* ws = reinterpret_cast<float*>(T->ws);
+  float* partial = ws + p.partial;
+  UpUnit& U = T->up[j];
+  const int lh = ch / 2, lw = cw / 2;
+  const size_t Pl = (size_t)n * lh * lw;
+  float* S = ws + p.s2d;
+  const float* dY = ws + p.dCat[l];
+  if (p.planes && U.x3Dgrad && U.x3Fwd && train_x3_wgrad_enabled()) {
+    // f16x3: the bias gradient is the column sum of the gradient slice itself; the same pass takes max |.|, the
+    // space-to-depth pass writes the scaled operand planes, both GEMMs run on the fp16 pipe
+    unsigned* key = T->up_keys(j);
+    float* inv = T->up_inv(j);
+    HIPCHK(h->err, run_up_bias_grad_x3(dY, 2 * f, f, Pl * 4, f, partial, key, T->grads + U.offB, s));
+    // (the slot: the previous level's weight gradient reads S on the side stream)
+    const int rc = backward_with_wgrad(
+        h, s, side_on(T) ? SideStream::kUpSlot : -1,
+        [&]() -> int {
+          HIPCHK(h->err, run_up_s2d_planes_x3(dY, 2 * f, f, n, lh, lw, f, key, S, inv, s));
+          return UNET_OK;
+        },
+        [&](hipStream_t st) {
+          return run_wgrad1_x3(S, 4 * f, 4 * f, ws + p.upInP[j], U.cin, U.cin, (long)Pl, ws + p.slab, p.slabFloats,
+                               T->grads + U.offW, 1, f, inv, st);
+        },
+        [&]() -> int {
+          HIPCHK(h->err, run_gemm1x1_x3(U.x3Dgrad, x3_from(reinterpret_cast<const uint16_t*>(zero_page()), reinterpret_cast<const uint16_t*>(S),
+                                                           Pl * 4 * (size_t)f, n, lh, lw).to(nullptr, 0, U.cin),
+                                        4 * f, U.cin, gA, inv, "upconv_dgrad_f16x3", s));
+          return UNET_OK;
+        });
+    if (rc) return rc;
+    if (T->dbgStage == 200 + j)   // the fp32 form of S only exists for the snapshot
+      hipLaunchKernelGGL(unet::space_to_depth_kernel, dim3(grid_for(Pl * 4 * (f / 4))), dim3(256), 0, s, dY, 2 * f, f, n, lh,
+                         lw, f, S);
+  } else {
+    const float* upIn = (j == 0) ? ws + p.botA2 : ws + p.decA2[l + 1];
+    HIPCHK(h->err, T->side.join(s));   // S and the slab are used on s below
+    prof_begin("space_to_depth", 0.0, 8.0 * Pl * 4 * f, s);
+    hipLaunchKernelGGL(unet::space_to_depth_kernel, dim3(grid_for(Pl * 4 * (f / 4))), dim3(256), 0, s, dY, 2 * f, f, n, lh,
+                       lw, f, S);
+    prof_end(s);
+    {
+      const int nb = red_blocks(Pl);
+      prof_begin("bias_grad", 0.0, 4.0 * Pl * 4 * f, s);
+      hipLaunchKernelGGL(unet::colsum_partial_kernel, dim3(nb), dim3(256), 0, s, S, 4 * f, 0, Pl, 4 * f, partial,
+                         (unsigned*)nullptr);
+      hipLaunchKernelGGL(unet::colsum_finalize_kernel, dim3((f + unet::FIN_CH - 1) / unet::FIN_CH), dim3(256), 0, s, partial, nb, 4 * f, f,
+                         T->grads + U.offB);
+      prof_end(s);
+    }
+    HIPCHK(h->err, hipGetLastError());
+    HIPCHK(h->err, run_wgrad(S, 4 * f, upIn, U.cin, U.cin, 1, n, lh, lw, ws + p.slab, p.slabFloats,
+                             T->grads + U.offW, 1, f, s));
+    HIPCHK(h->err, run_gemm_op(U.dgrad, S, n, lh, lw, gA, U.cin, 0, s));  // gradient w.r.t. the upconv input
+  }
+  if (T->dbgStage == 100 + j) hipMemcpyAsync(T->dbgDst, gA, std::min(T->dbgMax, Pl * U.cin) * 4, hipMemcpyDeviceToDevice, s);
+  if (T->dbgStage == 200 + j) hipMemcpyAsync(T->dbgDst, S, std::min(T->dbgMax, Pl * 4 * f) * 4, hipMemcpyDeviceToDevice, s);
+  return UNET_OK;
+}
+
+// Backward of the head, the decoder (shallowest level first: the reverse of the forward order) and the bottleneck; leaves
+// the gradient w.r.t. pool[D-1] in the workspace's gA
+int backward_decoder(unet_ctx* h, int n, int height, int width, hipStream_t s, const TrainPlan& p) {
+  TrainState* T = h->train;
+  const unet_config& c = h->cfg;
+  const int D = c.depth, f0 = c.features[0];
+  const bool PM = p.planes;
+  float* ws = reinterpret_cast<float*>(T->ws);
+  float *gA = ws + p.gA, *gB = ws + p.gB, *gZ = ws + p.gZ;
+  const size_t P0 = (size_t)n * height * width;
+  int rc;
+  // The gradient w.r.t. the last unit's activation is dlogits[p] * w_head[c]: its BatchNorm backward forms that product
+  // itself instead of reading a P0 x f0 buffer written here (3 x 4 bytes per element less; same bits).  A debug snapshot
+  // keeps the buffer.
+  const bool headRank1 = T->dbgStage < 0;
+  {  // head: dW, db; dA (dense f0) into gA unless headRank1
+    const int nb = red_blocks(P0);
+    prof_begin("head_bwd", 0.0, 4.0 * P0 * ((headRank1 ? 1 : 2) * f0 + 1), s);
+    hipLaunchKernelGGL(unet::head_bwd_kernel, dim3(nb), dim3(256), 0, s, ws + p.dlogits, ws + p.decA2[0],
+                       T->params + T->offHeadW, P0, f0, headRank1 ? (float*)nullptr : gA, ws + p.partial);
+    hipLaunchKernelGGL(unet::reduce2_finalize_kernel, dim3((f0 + unet::FIN_CH - 1) / unet::FIN_CH), dim3(256), 0, s, ws + p.partial, nb, f0,
+                       T->grads + T->offHeadW, gB /* per-channel copies of sum(dl); column 0 is db */);
+    prof_end(s);
+    HIPCHK(h->err, hipMemcpyAsync(T->grads + T->offHeadB, gB, sizeof(float), hipMemcpyDeviceToDevice, s));
+  }
+  int ch = height, cw = width;
+  for (int j = D - 1; j >= 0; --j) {
+    const int l = D - 1 - j;
+    const int f = c.features[l];
+    // conv2: dA in gA (dense f) -> input gradient (w.r.t. decA1) into gB
+    const bool r1 = headRank1 && j == D - 1;
+    if ((rc = unit_backward(h, T->dec[2 * j + 1], gA, f, 0, ws + p.decZ2[l], ws + p.decA1[l], f, n, ch, cw, gZ, gB, f,
+                            0, p, s, PM ? ws + p.decA1[l] : nullptr, r1 ? ws + p.dlogits : nullptr,
+                            r1 ? T->params + T->offHeadW : nullptr)))
+      return rc;
+    // conv1: dA in gB -> gradient w.r.t. the concat buffer (2f channels) into dCat[l]
+    if ((rc = unit_backward(h, T->dec[2 * j], gB, f, 0, ws + p.decZ1[l], ws + p.cat[l], 2 * f, n, ch, cw, gZ,
+                            ws + p.dCat[l], 2 * f, 0, p, s, PM ? ws + p.catP[l] : nullptr)))
+      return rc;
+    if ((rc = upconv_backward(h, j, n, ch, cw, gA, s, p))) return rc;
+    ch /= 2;
+    cw /= 2;
+  }
+  // bottleneck (gA holds the gradient w.r.t. botA2)
+  const int fl = c.features[D - 1], fb = 2 * fl;
+  if ((rc = unit_backward(h, T->bott[1], gA, fb, 0, ws + p.botZ2, ws + p.botA1, fb, n, ch, cw, gZ, gB, fb, 0, p, s,
+                          PM ? ws + p.botA1 : nullptr)))
+    return rc;
+  // gradient w.r.t. pool[D-1] into gA (dense fl channels)
+  return unit_backward(h, T->bott[0], gB, fb, 0, ws + p.botZ1, ws + p.pool[D - 1], fl, n, ch, cw, gZ, gA, fl, 0, p, s,
+                       PM ? ws + p.pool[D - 1] : nullptr);
+}
+
+// Backward of the encoder, deepest level first; gA = gradient w.r.t. pool[l]
+int backward_encoder(unet_ctx* h, int n, int height, int width, hipStream_t s, const TrainPlan& p) {
+  TrainState* T = h->train;
+  const unet_config& c = h->cfg;
+  const int D = c.depth;
+  const bool PM = p.planes;
+  float* ws = reinterpret_cast<float*>(T->ws);
+  float *gA = ws + p.gA, *gB = ws + p.gB, *gZ = ws + p.gZ;
+  int rc;
+  for (int l = D - 1; l >= 0; --l) {
+    const int f = c.features[l];
+    const int ch = height >> l, cw = width >> l;   // even: check_shape (a pooling follows this level)
+    const size_t P = (size_t)n * ch * cw;
+    // dA(conv2 output) = skip half of dCat[l] + unpooled gA   -> gB (dense f)
+    // ... with the first pass of that unit's BatchNorm backward in the same kernel (UNET_TRAIN_POOL_FUSED=0: separately)
+    int poolRows = 0;
+    if (train_pool_fused() && T->dbgStage < 0) {
+      ConvUnit& u2 = T->enc[2 * l + 1];
+      poolRows = red_blocks(P / 4);
+      prof_begin("maxpool_bwd_add_bnstat", 0.0, 4.0 * P * f * 4.25, s);
+      hipLaunchKernelGGL(unet::maxpool_bwd_add_bnstat_kernel, dim3(poolRows), dim3(256), 0, s, ws + p.cat[l], 2 * f,
+                         ws + p.dCat[l], 2 * f, 0, gA, n, ch, cw, f, gB, ws + p.encZ2[l], u2.mean, u2.invstd, ws + p.partial,
+                         T->unit_keys(u2));
+      prof_end(s);
+    } else {
+      prof_begin("maxpool_bwd_add", 0.0, 4.0 * P * f * 3.25, s);
+      hipLaunchKernelGGL(unet::maxpool_bwd_add_kernel, dim3(grid_for((P / 4) * (f / 4))), dim3(256), 0, s, ws + p.cat[l],
+                         2 * f, ws + p.dCat[l], 2 * f, 0, gA, n, ch, cw, f, gB);
+      prof_end(s);
+    }
+    HIPCHK(h->err, hipGetLastError());
+    if ((rc = unit_backward(h, T->enc[2 * l + 1], gB, f, 0, ws + p.encZ2[l], ws + p.encA1[l], f, n, ch, cw, gZ, gA, f,
+                            0, p, s, PM ? ws + p.encA1[l] : nullptr, nullptr, nullptr, poolRows)))
+      return rc;
+    const float* xin = (l == 0) ? ws + p.x0 : ws + p.pool[l - 1];
+    const int ldx = (l == 0) ? 4 : c.features[l - 1];
+    if ((rc = unit_backward(h, T->enc[2 * l], gA, f, 0, ws + p.encZ1[l], xin, ldx, n, ch, cw, gZ,
+                            (l == 0) ? nullptr : gB, ldx, 0, p, s, (PM && l > 0) ? xin : nullptr)))
+      return rc;
+    if (l > 0) std::swap(gA, gB);  // the input gradient (w.r.t. pool[l-1]) is now in gA
+  }
+  return UNET_OK;
+}
+
+int train_forward_backward(unet_ctx* h, int n, int height, int width, const float* targets, float* lossDev,
+                           float* logitsOut, hipStream_t s, const TrainPlan& p) {
+  TrainState* T = h->train;
+  LaunchScope scope(h);
+  float* ws = reinterpret_cast<float*>(T->ws);
+  const size_t P0 = (size_t)n * height * width;
+  int rc;
+  if ((rc = repack_if_switched(h, s))) return rc;
+  if ((rc = forward_walk(h, Pass::Train, n, height, width, ws + p.logits, s, p))) return rc;
+  if (logitsOut)
+    HIPCHK(h->err, hipMemcpyAsync(logitsOut, ws + p.logits, P0 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if ((rc = run_loss_grad(h, targets, P0, lossDev, s, p))) return rc;
+  // backward.  Whatever return ends it, the caller's stream has been joined with the side stream and no slot is left
+  // busy: a caller that reuses the workspace, the gradients or the slab after an error meets no weight gradient in flight
+  SideJoinOnExit joinOnExit{T->side, s};
+  T->side.nextUnit = 0;
+  HIPCHK(h->err, hipMemsetAsync(T->gzKeys, 0, 8 * T->scaled_units() * sizeof(unsigned), s));
+  if ((rc = backward_decoder(h, n, height, width, s, p))) return rc;
+  // Every gradient of the decoder, the bottleneck and the head is final now: they are the tail of the flat buffer
+  // (unet_train_grad_split).  A data-parallel caller's communication stream may start reducing that tail while the
+  // encoder's backward still runs.
+  if (T->commStream) {
+    HIPCHK(h->err, T->side.join(s));   // ... once the side stream's weight gradients are in
+    if (!T->lateGradsReady) HIPCHK(h->err, hipEventCreateWithFlags(&T->lateGradsReady, hipEventDisableTiming));
+    HIPCHK(h->err, hipEventRecord(T->lateGradsReady, s));
+    HIPCHK(h->err, hipStreamWaitEvent(T->commStream, T->lateGradsReady, 0));
+  }
+  if ((rc = backward_encoder(h, n, height, width, s, p))) return rc;
+  HIPCHK(h->err, T->side.join(s));   // the caller's stream owns every gradient again
   return h->async_error();
 }
 
-int eval_prologue(unet_ctx* h, const void* in, float* logits, int n, int height, int width, TrainPlan& plan) {
-  if (!h) return UNET_ERR_INVALID_ARG;
-  if (!h->train || !h->train->packed) {
-    h->err = "unet_train_attach has not been called";
-    return UNET_ERR_STATE;
-  }
-  if (!in || !logits) return UNET_ERR_INVALID_ARG;
-  // (train_prologue only checks its targets / loss pointers for null: an eval pass has neither)
-  return train_prologue(h, in, logits, logits, n, height, width, plan);
+int train_eval_forward(unet_ctx* h, int n, int height, int width, float* logitsOut, hipStream_t s, const TrainPlan& p) {
+  TrainState* T = h->train;
+  LaunchScope scope(h);
+  int rc;
+  if ((rc = repack_if_switched(h, s))) return rc;
+  if ((rc = eval_init(h))) return rc;
+  prof_begin("eval_bn_fold", 0.0, 24.0 * T->B, s);
+  const hipError_t ef = unet::launch_bn_eval_fold(T->evalDescs, T->nEvalUnits, kBnEps, s);
+  prof_end(s);
+  HIPCHK(h->err, ef);
+  if ((rc = forward_walk(h, Pass::Eval, n, height, width, logitsOut, s, p))) return rc;
+  return h->async_error();
 }
 
 }  // namespace
@@ -1642,16 +1614,15 @@ int eval_prologue(unet_ctx* h, const void* in, float* logits, int n, int height,
 static void train_free(unet_ctx* h) {
   TrainState* T = h->train;
   if (!T) return;
-  for (auto* vec : {&T->enc, &T->bott, &T->dec})
-    for (auto& u : *vec) {
-      u.fwd.scale = u.fwd.shift = nullptr;  // shared ones/zeros arrays, freed below
-      u.dgrad.scale = u.dgrad.shift = nullptr;
-      u.fwd.free_dev();
-      u.dgrad.free_dev();
-      if (u.x3Fwd) hipFree(u.x3Fwd);
-      if (u.x3Dgrad) hipFree(u.x3Dgrad);
-      u.x3Fwd = u.x3Dgrad = nullptr;
-    }
+  for (ConvUnit* u : T->units) {
+    u->fwd.scale = u->fwd.shift = nullptr;  // shared ones/zeros arrays, freed below
+    u->dgrad.scale = u->dgrad.shift = nullptr;
+    u->fwd.free_dev();
+    u->dgrad.free_dev();
+    if (u->x3Fwd) hipFree(u->x3Fwd);
+    if (u->x3Dgrad) hipFree(u->x3Dgrad);
+    u->x3Fwd = u->x3Dgrad = nullptr;
+  }
   for (auto& u : T->up) {
     u.fwd.scale = nullptr;
     u.dgrad.scale = u.dgrad.shift = nullptr;
@@ -1668,12 +1639,7 @@ static void train_free(unet_ctx* h) {
   if (T->evalArena) hipFree(T->evalArena);
   if (T->evalDescs) hipFree(T->evalDescs);
   if (T->lateGradsReady) hipEventDestroy(T->lateGradsReady);
-  if (T->side) {
-    hipStreamSynchronize(T->side);
-    hipStreamDestroy(T->side);
-  }
-  for (hipEvent_t ev : {T->evFork, T->evJoin, T->evSide[0], T->evSide[1], T->evSideUp})
-    if (ev) hipEventDestroy(ev);
+  T->side.destroy();
   if (T->gzKeys) hipFree(T->gzKeys);
   if (T->gzInv) hipFree(T->gzInv);
   if (T->packDescs) hipFree(T->packDescs);
@@ -1791,43 +1757,43 @@ int unet_train_attach(unet_handle_t h, float* params, float* grads, float* expAv
     T->dec.push_back(makeUnit(p, 0, 1, 2 * f, f, l, true));
     T->dec.push_back(makeUnit(p, 3, 4, f, f, l, true));
   }
-  {
-    int id = 0;
-    for (auto* vec : {&T->enc, &T->bott, &T->dec})
-      for (auto& u : *vec) u.dbgId = id++;
-  }
+  for (auto* vec : {&T->enc, &T->bott, &T->dec})   // the one place that fixes the order of TrainState::units
+    for (auto& u : *vec) {
+      u.dbgId = (int)T->units.size();
+      T->units.push_back(&u);
+    }
   T->offHeadW = off("output.weight");
   T->offHeadB = off("output.bias");
 
   int rc;
   HIPCHK(h->err, hipMalloc((void**)&T->statArena, (size_t)statFloats * sizeof(float)));
   float* sp = T->statArena;
-  for (auto* vec : {&T->enc, &T->bott, &T->dec})
-    for (auto& u : *vec) {
-      const int cp = round_up(u.cout, 64);
-      u.scale = sp;
-      u.shift = sp + cp;
-      u.mean = sp + 2 * cp;
-      u.invstd = sp + 3 * cp;
-      sp += 4 * cp;
-      // the first layer reads the 4-channel packed input: GEMM K = 4 with a zero weight row for the pad channel
-      const int kFwd = u.cin;
-      if ((rc = alloc_gemm(h->err, u.fwd, 9, kFwd, u.cout, u.cout, round_up(u.cout, 16)))) return rc;
-      u.fwd.name = "conv3x3_igemm_f32";
-      u.fwd.nameWino = "conv3x3_wino_f32";
-      maxN = std::max(maxN, u.fwd.nTotal);
-      if (u.needDgrad) {
-        if ((rc = alloc_gemm(h->err, u.dgrad, 9, u.cout, u.cin, u.cin, round_up(u.cin, 16)))) return rc;
-        u.dgrad.name = "dgrad3x3_igemm_f32";
-        u.dgrad.nameWino = "dgrad3x3_wino_f32";
-        maxN = std::max(maxN, u.dgrad.nTotal);
-      }
-      if (u.cin % 64 == 0 && u.cout % 64 == 0 && u.cin <= 1024 && u.cout <= 1024) {
-        const size_t halfs = x3_conv_pack_halfs(u.cout, u.cin);   // the same count for both operators
-        HIPCHK(h->err, hipMalloc((void**)&u.x3Fwd, halfs * sizeof(uint16_t)));
-        if (u.needDgrad) HIPCHK(h->err, hipMalloc((void**)&u.x3Dgrad, halfs * sizeof(uint16_t)));
-      }
+  for (ConvUnit* unit : T->units) {
+    ConvUnit& u = *unit;
+    const int cp = round_up(u.cout, 64);
+    u.scale = sp;
+    u.shift = sp + cp;
+    u.mean = sp + 2 * cp;
+    u.invstd = sp + 3 * cp;
+    sp += 4 * cp;
+    // the first layer reads the 4-channel packed input: GEMM K = 4 with a zero weight row for the pad channel
+    const int kFwd = u.cin;
+    if ((rc = alloc_gemm(h->err, u.fwd, 9, kFwd, u.cout, u.cout, round_up(u.cout, 16)))) return rc;
+    u.fwd.name = "conv3x3_igemm_f32";
+    u.fwd.nameWino = "conv3x3_wino_f32";
+    maxN = std::max(maxN, u.fwd.nTotal);
+    if (u.needDgrad) {
+      if ((rc = alloc_gemm(h->err, u.dgrad, 9, u.cout, u.cin, u.cin, round_up(u.cin, 16)))) return rc;
+      u.dgrad.name = "dgrad3x3_igemm_f32";
+      u.dgrad.nameWino = "dgrad3x3_wino_f32";
+      maxN = std::max(maxN, u.dgrad.nTotal);
     }
+    if (u.cin % 64 == 0 && u.cout % 64 == 0 && u.cin <= 1024 && u.cout <= 1024) {
+      const size_t halfs = x3_conv_pack_halfs(u.cout, u.cin);   // the same count for both operators
+      HIPCHK(h->err, hipMalloc((void**)&u.x3Fwd, halfs * sizeof(uint16_t)));
+      if (u.needDgrad) HIPCHK(h->err, hipMalloc((void**)&u.x3Dgrad, halfs * sizeof(uint16_t)));
+    }
+  }
   for (auto& U : T->up) {
     const int cp = round_up(U.cout, 16);
     if ((rc = alloc_gemm(h->err, U.fwd, 1, U.cin, 4 * cp, U.cout, cp))) return rc;
@@ -1845,25 +1811,19 @@ int unet_train_attach(unet_handle_t h, float* params, float* grads, float* expAv
   HIPCHK(h->err, hipMalloc((void**)&T->zeros, (size_t)maxN * sizeof(float)));
   hipLaunchKernelGGL(fill_kernel, dim3(4), dim3(256), 0, 0, T->ones, (size_t)maxN, 1.0f);
   hipLaunchKernelGGL(fill_kernel, dim3(4), dim3(256), 0, 0, T->zeros, (size_t)maxN, 0.0f);
-  for (auto* vec : {&T->enc, &T->bott, &T->dec})
-    for (auto& u : *vec) {
-      u.fwd.scale = T->ones;
-      u.fwd.shift = T->zeros;
-      u.dgrad.scale = T->ones;
-      u.dgrad.shift = T->zeros;
-    }
+  for (ConvUnit* u : T->units) {
+    u->fwd.scale = u->dgrad.scale = T->ones;
+    u->fwd.shift = u->dgrad.shift = T->zeros;
+  }
   for (auto& U : T->up) {
     U.fwd.scale = T->ones;
     U.dgrad.scale = T->ones;
     U.dgrad.shift = T->zeros;
   }
   HIPCHK(h->err, hipMalloc((void**)&T->lossCoef, 2 * sizeof(float)));
-  {
-    const size_t nu = T->enc.size() + T->bott.size() + T->dec.size() + T->up.size();   // the up units' keys / inverse scales follow the conv units'
-    HIPCHK(h->err, hipMalloc((void**)&T->gzKeys, 8 * nu * sizeof(unsigned)));
-    HIPCHK(h->err, hipMalloc((void**)&T->gzInv, nu * sizeof(float)));
-    HIPCHK(h->err, hipMemset(T->gzKeys, 0, 8 * nu * sizeof(unsigned)));
-  }
+  HIPCHK(h->err, hipMalloc((void**)&T->gzKeys, 8 * T->scaled_units() * sizeof(unsigned)));
+  HIPCHK(h->err, hipMalloc((void**)&T->gzInv, T->scaled_units() * sizeof(float)));
+  HIPCHK(h->err, hipMemset(T->gzKeys, 0, 8 * T->scaled_units() * sizeof(unsigned)));
   rc = train_repack(h, 0);
   if (rc) return rc;
   HIPCHK(h->err, hipDeviceSynchronize());

@@ -7,7 +7,7 @@
 
 namespace {
 
-struct GemmOpX3 {
+struct GemmOpX3 {   // no destructor: an owner calls free_dev(), a copy over borrowed pointers is simply dropped
   int taps = 9, cin = 0, cout = 0, relu = 0;
   uint16_t* wt = nullptr;     // packed hi/lo fragments (conv_x3_ws.h / upconv_x3_ws.h)
   float* scale = nullptr;     // per channel: folded BN scale (1 for the upconv) / the weights' power-of-two pre-scale
