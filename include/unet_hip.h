@@ -10,7 +10,8 @@
  *
  * Conventions
  *   - every function returns UNET_OK (0) or a non-zero unet_status code;
- *     unet_last_error() gives the text of the last failure on that handle
+ *     unet_last_error() gives the text of the last failure on that handle,
+ *     unet_op_last_error() that of the calling thread's last failed call without one
  *     (reference: `exit(ret)` on init failure, rknn_executor.py:16-18);
  *   - `*_dev` pointers are caller-owned DEVICE pointers on the handle's HIP
  *     device; `*_host` pointers are host memory;
@@ -283,6 +284,10 @@ int unet_mask_positive_counts(int device, const uint8_t* masks_dev, int n, size_
                               unsigned long long* counts_dev, void* stream);
 
 const char* unet_last_error(unet_handle_t h);
+/* The same for the entry points that take a device ordinal instead of a handle (unet_op_*, the loss, metric and camera
+ * helpers, unet_augment_u8): the text of the last failure of such a call on the calling thread ("" if there was none).
+ * Every non-zero status of such a call sets it, a refusal by the argument checks included; it is not cleared on success. */
+const char* unet_op_last_error(void);
 const char* unet_version(void);
 
 /* Asynchronous kernel-side conditions, kept in a per-handle error block the kernels write to.
@@ -337,7 +342,11 @@ int unet_set_bf16_persistent(int mode);
 
 /* ---- single operators, for parity tests against the oracle (tests/test_ops_gpu.py) ----
  * All tensors are dense NHWC float32 device buffers.  Weights are passed in
- * PyTorch layout on the HOST and packed internally (slow path, test only). */
+ * PyTorch layout on the HOST and packed internally (slow path, test only).
+ * These and the other unet_op_* entry points below take a device ordinal, own their device scratch for the length of the
+ * call (everything is freed on every return path), wait for `stream` before they return (all but unet_op_loss_grad,
+ * which the training step's helper runs behind and which only enqueues) and leave the text of a failure for
+ * unet_op_last_error(). */
 
 /* y = relu?(conv3x3(x, w) * scale + shift), pad 1, stride 1 (reference README.md:1452-1457).
  * x (N,H,W,Cin) -> y (N,H,W,Cout); w_host (Cout,Cin,3,3); scale/shift host (Cout). */

@@ -132,3 +132,34 @@ def test_train_x3_entry_points_check_arguments_first(lib):
     # the 3x3 weight gradient: channel counts multiples of 64, even heights
     assert lib.unet_op_wgrad3x3_x3(0, q, q, 1, 7, 8, 64, 64, q, 0, None) == 1
     assert lib.unet_op_wgrad3x3_x3(0, q, q, 1, 8, 8, 96, 64, q, 0, None) == 1
+
+
+def test_op_last_error_names_the_failing_call(lib):
+    """a handle-less entry point that fails leaves its text for unet_op_last_error, per thread: a device ordinal the
+    runtime refuses (no device is touched, with or without GPUs) in one entry point of each of three files"""
+    import threading
+    buf = (C.c_uint16 * 64)()
+    f = (C.c_float * 64)()
+    p, q = C.cast(buf, C.c_void_p), C.cast(f, C.c_void_p)
+    seen = {}
+
+    def other():   # a thread that has made no failing call
+        seen["other"] = lib.unet_op_last_error()
+    t = threading.Thread(target=other)
+    bad = 1 << 20
+    calls = {
+        "unet_op_maxpool2x2": lambda: lib.unet_op_maxpool2x2(bad, q, 1, 2, 2, 4, q, None),
+        "unet_op_maxpool2x2_bf16": lambda: lib.unet_op_maxpool2x2_bf16(bad, p, 1, 2, 2, 8, 0, p, None),
+        "unet_op_split_planes_x3": lambda: lib.unet_op_split_planes_x3(bad, q, 4, p, 4, None, None),
+    }
+    for name, call in calls.items():
+        assert call() == 4, name                       # UNET_ERR_HIP
+        msg = lib.unet_op_last_error()
+        assert msg and b"hipSetDevice" in msg, (name, msg)
+    assert lib.unet_op_maxpool2x2(0, q, 1, 3, 2, 4, q, None) == 1      # a refusal by the argument checks replaces the text
+    assert lib.unet_op_last_error().startswith(b"invalid argument")
+    t.start()
+    t.join()
+    assert seen["other"] == b""
+    with pytest.raises(_lib.UnetError, match="hipSetDevice"):   # _lib.check appends the text when there is no handle
+        _lib.check(calls["unet_op_maxpool2x2"](), "unet_op_maxpool2x2")

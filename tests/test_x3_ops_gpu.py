@@ -484,6 +484,8 @@ def first_case(n, h, w, cout, gen, scaled):
                          ids=["11x37", "8x32-ldo256", "21x70"])
 @pytest.mark.parametrize("scaled", [False, True], ids=["plain", "out_act"])
 def test_conv_first(lib, u8, shape, scaled):
+    """the entry point launches through run_first_x3 (csrc/unet_x3.inc), the function forward_x3 calls for the network's
+    first layer: its argument fill, its u8 / fp32 switch and its profiler label are the ones under test here"""
     n, h, w, cout, ldo = shape
     gen = torch.Generator().manual_seed(h * 100 + w)
     frames, x32, wt, scale, shift, oa, m = first_case(n, h, w, cout, gen, scaled)

@@ -169,6 +169,7 @@ SIGNATURES = {
     "unet_debug_set_error_block": (C.c_int, [C.c_void_p, C.c_int, C.c_uint]),
     "unet_debug_act_scale": (C.c_float, [C.c_float, C.c_float]),
     "unet_last_error": (C.c_char_p, [C.c_void_p]),
+    "unet_op_last_error": (C.c_char_p, []),
     "unet_version": (C.c_char_p, []),
     "unet_set_winograd": (C.c_int, [C.c_int]),
     "unet_set_bf16_persistent": (C.c_int, [C.c_int]),
@@ -232,8 +233,7 @@ class UnetError(RuntimeError):
 
 def check(code, where, handle=None):
     if code != 0:
-        detail = ""
-        if handle:
-            msg = load().unet_last_error(handle)
-            detail = msg.decode() if msg else ""
+        # without a handle: the calling thread's last failure in a handle-less entry point (unet_op_*, metrics, camera)
+        msg = load().unet_last_error(handle) if handle else load().unet_op_last_error()
+        detail = msg.decode() if msg else ""
         raise UnetError(code, where, detail)

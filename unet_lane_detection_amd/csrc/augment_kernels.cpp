@@ -15,6 +15,12 @@
 
 #include "../../include/unet_hip.h"
 
+#include <string>
+
+namespace unet {
+int op_fail(int status, const std::string& text);   // unet_hip.cpp: the text behind unet_op_last_error
+}
+
 // The model rounds every floating-point operation on its own (numpy has no fused multiply-add); so does this file.
 #pragma clang fp contract(off)
 
@@ -247,16 +253,18 @@ size_t unet_augment_param_bytes(void) { return sizeof(unet::AugmentParams); }
 int unet_augment_u8(int device, const uint8_t* imagesDev, const uint8_t* masksDev, int nSource, int height, int width,
                     const void* paramsDev, int nOut, int maskThreshold, uint8_t* imagesOutDev, float* targetsOutDev,
                     void* stream) {
-  if (!imagesDev || !paramsDev || !imagesOutDev || (masksDev == nullptr) != (targetsOutDev == nullptr)) return UNET_ERR_INVALID_ARG;
-  if (nOut <= 0 || nSource <= 0) return UNET_ERR_INVALID_ARG;
+  if (!imagesDev || !paramsDev || !imagesOutDev || (masksDev == nullptr) != (targetsOutDev == nullptr) ||
+      nOut <= 0 || nSource <= 0)
+    return unet::op_fail(UNET_ERR_INVALID_ARG, "invalid argument: refused by the entry point's checks");
   if (height < unet::AUG_MIN_SIDE || width < unet::AUG_MIN_SIDE || height > unet::AUG_MAX_SIDE || width > unet::AUG_MAX_SIDE)
-    return UNET_ERR_SHAPE;
-  if (hipSetDevice(device) != hipSuccess) return UNET_ERR_HIP;
-  const hipError_t e = unet::launch_augment(imagesDev, masksDev, nSource, height, width,
+    return unet::op_fail(UNET_ERR_SHAPE, "height and width must lie between AUG_MIN_SIDE and AUG_MAX_SIDE");
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
+  e = unet::launch_augment(imagesDev, masksDev, nSource, height, width,
                                             static_cast<const unet::AugmentParams*>(paramsDev), nOut, maskThreshold,
                                             imagesOutDev, targetsOutDev, (hipStream_t)stream);
-  if (e == hipErrorInvalidValue) return UNET_ERR_INVALID_ARG;
-  return e == hipSuccess ? UNET_OK : UNET_ERR_HIP;
+  if (e == hipSuccess) return UNET_OK;
+  return unet::op_fail(e == hipErrorInvalidValue ? UNET_ERR_INVALID_ARG : UNET_ERR_HIP, hipGetErrorString(e));
 }
 
 }  // extern "C"

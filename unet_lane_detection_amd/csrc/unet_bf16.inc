@@ -633,15 +633,14 @@ struct Bf16Net {
   uint16_t* zeros = nullptr;
   uint16_t* firstWt = nullptr;   // conv_first_bf16x3.h packing of the first convolution (3 input channels)
   std::vector<GemmOpBf> enc, bott, up, dec;
-  char* ws = nullptr;
-  size_t wsBytes = 0;
+  GrowBuf ws;
 };
 
 static void bf16_free(unet_ctx* h) {
   if (!h->bf) return;
   for (auto* v : {&h->bf->enc, &h->bf->bott, &h->bf->up, &h->bf->dec})
     for (auto& op : *v) op.free_dev();
-  if (h->bf->ws) hipFree(h->bf->ws);
+  h->bf->ws.release();
   if (h->bf->zeros) hipFree(h->bf->zeros);
   if (h->bf->firstWt) hipFree(h->bf->firstWt);
   delete h->bf;
@@ -748,23 +747,11 @@ int unet_forward_u8_bf16(unet_handle_t h, const uint8_t* frames, int n, int heig
   Bf16Net* B = h->bf;
   const unet_config& c = h->cfg;
   const WsPlanBf p = plan_ws_bf(c, n, height, width);
-  if (p.total > B->wsBytes) {
-    if (B->ws) {
-      HIPCHK(h->err, hipDeviceSynchronize());
-      hipFree(B->ws);
-      B->ws = nullptr;
-      B->wsBytes = 0;
-    }
-    if (hipMalloc((void**)&B->ws, p.total) != hipSuccess) {
-      h->err = "bf16 workspace allocation failed";
-      return UNET_ERR_NOMEM;
-    }
-    B->wsBytes = p.total;
-  }
+  if ((rc = B->ws.reserve(h->err, p.total, "bf16 workspace"))) return rc;
   hipStream_t s = (hipStream_t)stream;
   LaunchScope scope(h);
   const size_t npix = (size_t)n * height * width;
-  float* x0 = reinterpret_cast<float*>(B->ws + p.x0);
+  float* x0 = reinterpret_cast<float*>(B->ws.p + p.x0);
   static const bool firstOk = [] { const char* e = getenv("UNET_BF16_FIRST"); return !(e && e[0] == '0'); }();
   const bool firstFused = firstOk && B->firstWt && height % 8 == 0;
   if (!firstFused) {
@@ -773,7 +760,7 @@ int unet_forward_u8_bf16(unet_handle_t h, const uint8_t* frames, int n, int heig
                        c.input_std[2]);
     HIPCHK(h->err, hipGetLastError());
   }
-  auto U = [&](size_t off) { return reinterpret_cast<uint16_t*>(B->ws + off); };
+  auto U = [&](size_t off) { return reinterpret_cast<uint16_t*>(B->ws.p + off); };
   uint16_t* tmpA = U(p.tmpA);
   uint16_t* tmpB = U(p.tmpB);
   const uint16_t* cur = nullptr;
@@ -837,39 +824,25 @@ int unet_forward_u8_bf16(unet_handle_t h, const uint8_t* frames, int n, int heig
 
 namespace {
 
-// Device scratch of one test operator call, freed on every exit path
-struct BfOpScratch {
-  GemmOp f;
-  GemmOpBf op;
-  uint16_t* zeros = nullptr;
-  uint16_t* wtFirst = nullptr;
-  uint16_t* act = nullptr;
-  float* x0 = nullptr;
-  float* headW = nullptr;
-  ~BfOpScratch() {
-    op.free_dev();
-    f.free_dev();
-    for (uint16_t* q : {zeros, wtFirst, act})
-      if (q) hipFree(q);
-    if (x0) hipFree(x0);
-    if (headW) hipFree(headW);
-  }
-  // the network's zero page (bf16_build): the out-of-image halo source of the wave-specialised / one-wave-per-SIMD kernels
-  hipError_t alloc_zeros() {
-    hipError_t e = hipMalloc((void**)&zeros, 8192 * sizeof(uint16_t));
-    return e == hipSuccess ? hipMemset(zeros, 0, 8192 * sizeof(uint16_t)) : e;
-  }
-};
-
 void clear_path(int* path) {
   if (path) path[0] = path[1] = path[2] = 0;
 }
 
-int op_finish(hipError_t e, hipStream_t s) {
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) {
-    g_opErr = hipGetErrorString(e);
-    return UNET_ERR_HIP;
+// The operator of one test call as bf16_build makes it: the fp32 operator of the layer (taps 9: build_conv3x3 with
+// scale / shift; taps 1: build_upconv with `shift` as the bias), the tier's zero page, the tier's packing.  A forced
+// kernel that does not take the shape is refused here, after the allocations.
+int bf_op_build(OpScratch& sc, GemmOp& f, GemmOpBf& op, int taps, const float* w, int cin, int cout, const float* scale,
+                const float* shift, int relu, int n, int hh, int ww, int kernel) {
+  int rc = taps == 9 ? build_conv3x3(g_opErr, f, w, cout, cin, scale, shift, relu ? 1 : 0)
+                     : build_upconv(g_opErr, f, w, cin, cout, shift);
+  if (rc) return rc;
+  uint16_t* zeros = nullptr;
+  const hipError_t e = sc.zero_page(&zeros, 8192 * sizeof(uint16_t));
+  if (e != hipSuccess) return op_done(e, sc.s, kOpNoSync);
+  if ((rc = taps == 9 ? pack_conv_bf(g_opErr, op, f, w, zeros) : pack_upconv_bf(g_opErr, op, f, w, zeros))) return rc;
+  if (bf_kernel_for(op, n, hh, ww, kernel) == BF_NONE) {
+    g_opErr = "the forced bf16 kernel does not take this shape";
+    return UNET_ERR_INVALID_ARG;
   }
   return UNET_OK;
 }
@@ -886,18 +859,14 @@ int unet_op_conv3x3_bf16(int device, const uint16_t* x, int n, int hh, int ww, i
   if (!x || !wHost || !scale || !shift || !y || n < 1 || hh < 1 || ww < 1 || cin < 32 || cin % 32 || cout < 32 ||
       cout % 32 || kernel < 0 || kernel > 3 || ldo % 32 || coOff < 0 || coOff % 32 || coOff + cout > ldo ||
       (yPool && (hh % 2 || ww % 2)))
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  BfOpScratch t;
-  int rc = build_conv3x3(g_opErr, t.f, wHost, cout, cin, scale, shift, relu ? 1 : 0);
+  OpScratch sc(s);
+  OpGuard<GemmOp> f;
+  OpGuard<GemmOpBf> t;
+  const int rc = bf_op_build(sc, f.op, t.op, 9, wHost, cin, cout, scale, shift, relu, n, hh, ww, kernel);
   if (rc) return rc;
-  HIPCHK(g_opErr, t.alloc_zeros());
-  if ((rc = pack_conv_bf(g_opErr, t.op, t.f, wHost, t.zeros))) return rc;
-  if (bf_kernel_for(t.op, n, hh, ww, kernel) == BF_NONE) {
-    g_opErr = "the forced bf16 kernel does not take this shape";
-    return UNET_ERR_INVALID_ARG;
-  }
   BfFuse fz;
   fz.pool = yPool;
   bool pooled = false;
@@ -907,7 +876,7 @@ int unet_op_conv3x3_bf16(int device, const uint16_t* x, int n, int hh, int ww, i
     pathOut[0] = ran;
     pathOut[1] = pooled ? 1 : 0;
   }
-  return op_finish(e, s);
+  return op_done(e, s);
 }
 
 int unet_op_conv3x3_bf16_head(int device, const uint16_t* x, int n, int hh, int ww, int cin, const float* wHost,
@@ -917,24 +886,21 @@ int unet_op_conv3x3_bf16_head(int device, const uint16_t* x, int n, int hh, int 
   clear_path(pathOut);
   if (!x || !wHost || !scale || !shift || !headWHost || n < 1 || hh < 1 || ww < 1 || cin < 32 || cin % 32 ||
       cout < 32 || cout % 32 || kernel < 0 || kernel > 3)
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  BfOpScratch t;
-  int rc = build_conv3x3(g_opErr, t.f, wHost, cout, cin, scale, shift, relu ? 1 : 0);
+  OpScratch sc(s);
+  OpGuard<GemmOp> f;
+  OpGuard<GemmOpBf> t;
+  const int rc = bf_op_build(sc, f.op, t.op, 9, wHost, cin, cout, scale, shift, relu, n, hh, ww, kernel);
   if (rc) return rc;
-  HIPCHK(g_opErr, t.alloc_zeros());
-  if ((rc = pack_conv_bf(g_opErr, t.op, t.f, wHost, t.zeros))) return rc;
-  if (bf_kernel_for(t.op, n, hh, ww, kernel) == BF_NONE) {
-    g_opErr = "the forced bf16 kernel does not take this shape";
-    return UNET_ERR_INVALID_ARG;
-  }
   const size_t npix = (size_t)n * hh * ww;
-  HIPCHK(g_opErr, hipMalloc((void**)&t.headW, cout * sizeof(float)));
-  HIPCHK(g_opErr, hipMemcpy(t.headW, headWHost, cout * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(g_opErr, hipMalloc((void**)&t.act, npix * cout * sizeof(uint16_t)));
   BfFuse fz;
-  fz.headW = t.headW;
+  uint16_t* act = nullptr;
+  float* headW = nullptr;
+  hipError_t e = sc.upload(&headW, headWHost, (size_t)cout);
+  if (e == hipSuccess) e = sc.get(&act, npix * cout * sizeof(uint16_t));
+  fz.headW = headW;
   fz.headB = headB;
   fz.headThr = thr;
   fz.logits = logits;
@@ -942,14 +908,14 @@ int unet_op_conv3x3_bf16_head(int device, const uint16_t* x, int n, int hh, int 
   fz.mask = mask;
   bool headFused = false;
   int ran = BF_NONE;
-  hipError_t e = run_gemm_bf(t.op, x, n, hh, ww, t.act, cout, 0, s, &fz, nullptr, &headFused, kernel, &ran);
+  if (e == hipSuccess) e = run_gemm_bf(t.op, x, n, hh, ww, act, cout, 0, s, &fz, nullptr, &headFused, kernel, &ran);
   // as the forward: the unfused head reads the stored activation
-  if (e == hipSuccess && !headFused) e = run_head_bf(t.act, t.headW, headB, npix, cout, logits, probs, mask, thr, s);
+  if (e == hipSuccess && !headFused) e = run_head_bf(act, headW, headB, npix, cout, logits, probs, mask, thr, s);
   if (pathOut) {
     pathOut[0] = ran;
     pathOut[2] = headFused ? 1 : 0;
   }
-  return op_finish(e, s);
+  return op_done(e, s);
 }
 
 int unet_op_upconv2x2_bf16(int device, const uint16_t* x, int n, int hh, int ww, int cin, const float* wHost,
@@ -959,22 +925,18 @@ int unet_op_upconv2x2_bf16(int device, const uint16_t* x, int n, int hh, int ww,
   if (ldo == 0) ldo = cout;
   if (!x || !wHost || !bias || !y || n < 1 || hh < 1 || ww < 1 || cin < 32 || cin % 32 || cout < 32 || cout % 32 ||
       kernel < 0 || kernel > 3 || ldo % 32 || coOff < 0 || coOff % 32 || coOff + cout > ldo)
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  BfOpScratch t;
-  int rc = build_upconv(g_opErr, t.f, wHost, cin, cout, bias);
+  OpScratch sc(s);
+  OpGuard<GemmOp> f;
+  OpGuard<GemmOpBf> t;
+  const int rc = bf_op_build(sc, f.op, t.op, 1, wHost, cin, cout, nullptr, bias, 0, n, hh, ww, kernel);
   if (rc) return rc;
-  HIPCHK(g_opErr, t.alloc_zeros());
-  if ((rc = pack_upconv_bf(g_opErr, t.op, t.f, wHost, t.zeros))) return rc;
-  if (bf_kernel_for(t.op, n, hh, ww, kernel) == BF_NONE) {
-    g_opErr = "the forced bf16 kernel does not take this shape";
-    return UNET_ERR_INVALID_ARG;
-  }
   int ran = BF_NONE;
   hipError_t e = run_gemm_bf(t.op, x, n, hh, ww, y, ldo, coOff, s, nullptr, nullptr, nullptr, kernel, &ran);
   if (pathOut) pathOut[0] = ran;
-  return op_finish(e, s);
+  return op_done(e, s);
 }
 
 int unet_op_conv_first_bf16(int device, const uint8_t* frames, int n, int hh, int ww, const float* wHost,
@@ -983,7 +945,7 @@ int unet_op_conv_first_bf16(int device, const uint8_t* frames, int n, int hh, in
   clear_path(pathOut);
   if (!frames || !wHost || !scale || !shift || !meanHost || !stdHost || !y || n < 1 || hh < 1 || ww < 1 ||
       cout < 32 || cout % 32 || kernel < 0 || kernel > 2)
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   // the forward's choice (unet_forward_u8_bf16): conv_first_bf16x3.h where H % 8 == 0 and Cout % 64 == 0, else the fp32
   // kernel with a bf16 store
   static const bool firstOk = [] { const char* e = getenv("UNET_BF16_FIRST"); return !(e && e[0] == '0'); }();
@@ -995,44 +957,52 @@ int unet_op_conv_first_bf16(int device, const uint8_t* frames, int n, int hh, in
   const int k = kernel ? kernel : (firstOk && fusedOk ? 1 : 2);
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  BfOpScratch t;
-  int rc = build_conv3x3(g_opErr, t.f, wHost, cout, 3, scale, shift, relu ? 1 : 0);
+  OpScratch sc(s);
+  OpGuard<GemmOp> f;
+  int rc = build_conv3x3(g_opErr, f.op, wHost, cout, 3, scale, shift, relu ? 1 : 0);
   if (rc) return rc;
   hipError_t e;
   if (k == 1) {
-    if ((rc = pack_first_bf16x3(g_opErr, &t.wtFirst, wHost, cout))) return rc;
-    e = run_first_bf16x3(frames, t.wtFirst, t.f.scale, t.f.shift, y, n, hh, ww, cout, t.f.relu, meanHost, stdHost, s);
+    uint16_t* wtFirst = nullptr;
+    rc = pack_first_bf16x3(g_opErr, &wtFirst, wHost, cout);
+    sc.adopt(wtFirst);
+    if (rc) return rc;
+    e = run_first_bf16x3(frames, wtFirst, f.op.scale, f.op.shift, y, n, hh, ww, cout, f.op.relu, meanHost, stdHost, s);
   } else {
     const size_t npix = (size_t)n * hh * ww;
-    HIPCHK(g_opErr, hipMalloc((void**)&t.x0, npix * 4 * sizeof(float)));
-    hipLaunchKernelGGL(unet::pack_u8_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, frames, t.x0, npix, meanHost[0],
-                       meanHost[1], meanHost[2], stdHost[0], stdHost[1], stdHost[2]);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = run_gemm_op(t.f, t.x0, n, hh, ww, reinterpret_cast<float*>(y), cout, 0, s, 1);
+    float* x0 = nullptr;
+    e = sc.get(&x0, npix * 4 * sizeof(float));
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(unet::pack_u8_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, frames, x0, npix, meanHost[0],
+                         meanHost[1], meanHost[2], stdHost[0], stdHost[1], stdHost[2]);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = run_gemm_op(f.op, x0, n, hh, ww, reinterpret_cast<float*>(y), cout, 0, s, 1);
   }
   if (pathOut) pathOut[0] = k;
-  return op_finish(e, s);
+  return op_done(e, s);
 }
 
 int unet_op_maxpool2x2_bf16(int device, const uint16_t* x, int n, int hh, int ww, int c, int ldi, uint16_t* y,
                             void* stream) {
   if (ldi == 0) ldi = c;
   if (!x || !y || n < 1 || hh < 2 || ww < 2 || hh % 2 || ww % 2 || c < 8 || c % 8 || ldi % 8 || ldi < c)
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  return op_finish(run_maxpool_bf(x, y, n, hh, ww, c, ldi, s), s);
+  return op_done(run_maxpool_bf(x, y, n, hh, ww, c, ldi, s), s);
 }
 
 int unet_op_head1x1_bf16(int device, const uint16_t* x, int n, int hh, int ww, int c, const float* wHost, float bias,
                          float thr, float* logits, float* probs, uint8_t* mask, void* stream) {
-  if (!x || !wHost || n < 1 || hh < 1 || ww < 1 || c < 8 || c % 8) return UNET_ERR_INVALID_ARG;
+  if (!x || !wHost || n < 1 || hh < 1 || ww < 1 || c < 8 || c % 8) return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  BfOpScratch t;
-  HIPCHK(g_opErr, hipMalloc((void**)&t.headW, c * sizeof(float)));
-  HIPCHK(g_opErr, hipMemcpy(t.headW, wHost, c * sizeof(float), hipMemcpyHostToDevice));
-  return op_finish(run_head_bf(x, t.headW, bias, (size_t)n * hh * ww, c, logits, probs, mask, thr, s), s);
+  OpScratch sc(s);
+  float* headW = nullptr;
+  hipError_t e = sc.upload(&headW, wHost, (size_t)c);
+  if (e == hipSuccess) e = run_head_bf(x, headW, bias, (size_t)n * hh * ww, c, logits, probs, mask, thr, s);
+  return op_done(e, s);
 }
 
 }  // extern "C"

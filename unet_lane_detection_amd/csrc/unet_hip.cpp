@@ -64,6 +64,32 @@ constexpr float kBnEps = 1e-5f;  // nn.BatchNorm2d default (reference README.md:
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// A device buffer that only grows (workspaces, the f16q8 q plane).  Growing waits for the device first: launches still
+// in flight may read the old block.  `what` names the buffer in the error text.
+struct GrowBuf {
+  char* p = nullptr;
+  size_t bytes = 0;
+  int reserve(std::string& err, size_t need, const char* what) {
+    if (need <= bytes) return UNET_OK;
+    if (p) {
+      HIPCHK(err, hipDeviceSynchronize());
+      release();
+    }
+    if (hipMalloc((void**)&p, need) != hipSuccess) {
+      p = nullptr;
+      err = std::string(what) + " allocation of " + std::to_string(need) + " bytes failed";
+      return UNET_ERR_NOMEM;
+    }
+    bytes = need;
+    return UNET_OK;
+  }
+  void release() {
+    if (p) hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+};
+
 // ------------------------------------------------------------------------------------------
 // Optional per-launch timing: a hipEvent pair around every kernel launch, recorded on the stream
 // the kernel runs on.  Used by bench.py for the live roofline numbers; off by default.
@@ -540,9 +566,7 @@ struct unet_ctx {
   float* headW = nullptr;
   float headB = 0.f;
 
-  // workspace
-  char* ws = nullptr;
-  size_t wsBytes = 0;
+  GrowBuf ws;   // workspace
 
   std::string err;
   Profiler prof;
@@ -599,9 +623,7 @@ struct unet_ctx {
       for (auto& op : *v) op.free_dev();
     if (headW) hipFree(headW);
     headW = nullptr;
-    if (ws) hipFree(ws);
-    ws = nullptr;
-    wsBytes = 0;
+    ws.release();
   }
 };
 
@@ -684,18 +706,24 @@ WsPlan plan_ws(const unet_config& c, int n, int h, int w) {
   return p;
 }
 
-int fold_bn_and_build(unet_ctx* h, GemmOp& op, const std::string& prefix, int convIdx, int bnIdx, int cin, int cout) {
-  auto& P = h->params;
-  const auto& w = P[prefix + "." + std::to_string(convIdx) + ".weight"];
-  const std::string bn = prefix + "." + std::to_string(bnIdx) + ".";
+// eval BatchNorm (x - mean) / sqrt(var + eps) * gamma + beta (reference README.md:1453) of the module named `bn`
+// ("....1.") as a scale and shift per channel; every tier folds through here, so they agree to the bit
+void fold_bn(std::map<std::string, std::vector<float>>& P, const std::string& bn, int c, std::vector<float>& sc,
+             std::vector<float>& sh) {
   const auto &g = P[bn + "weight"], &b = P[bn + "bias"], &m = P[bn + "running_mean"], &v = P[bn + "running_var"];
-  std::vector<float> sc(cout), sh(cout);
-  for (int i = 0; i < cout; ++i) {
-    // eval BatchNorm: (x - mean) / sqrt(var + eps) * gamma + beta (reference README.md:1453)
+  sc.resize(c);
+  sh.resize(c);
+  for (int i = 0; i < c; ++i) {
     const float inv = 1.0f / std::sqrt(v[i] + kBnEps);
     sc[i] = g[i] * inv;
     sh[i] = b[i] - m[i] * sc[i];
   }
+}
+
+int fold_bn_and_build(unet_ctx* h, GemmOp& op, const std::string& prefix, int convIdx, int bnIdx, int cin, int cout) {
+  const auto& w = h->params[prefix + "." + std::to_string(convIdx) + ".weight"];
+  std::vector<float> sc, sh;
+  fold_bn(h->params, prefix + "." + std::to_string(bnIdx) + ".", cout, sc, sh);
   return build_conv3x3(h->err, op, w.data(), cout, cin, sc.data(), sh.data(), 1);
 }
 
@@ -703,7 +731,7 @@ int forward_common(unet_ctx* h, int n, int height, int width, float* logits, flo
                    float thr, hipStream_t s, const WsPlan& p) {
   const unet_config& c = h->cfg;
   LaunchScope scope(h);
-  float* ws = reinterpret_cast<float*>(h->ws);
+  float* ws = reinterpret_cast<float*>(h->ws.p);
   const float* cur = ws + p.x0;
   int ch = height, cw = width;
   float* tmpA = ws + p.tmpA;
@@ -884,20 +912,9 @@ int unet_reserve(unet_handle_t h, int n, int height, int width) {
   int rc = check_shape(h, n, height, width);
   if (rc) return rc;
   const size_t need = plan_ws(h->cfg, n, height, width).total * sizeof(float);
-  if (need <= h->wsBytes) return UNET_OK;
+  if (need <= h->ws.bytes) return UNET_OK;
   HIPCHK(h->err, hipSetDevice(h->cfg.device));
-  if (h->ws) {
-    HIPCHK(h->err, hipDeviceSynchronize());
-    hipFree(h->ws);
-    h->ws = nullptr;
-    h->wsBytes = 0;
-  }
-  if (hipMalloc((void**)&h->ws, need) != hipSuccess) {
-    h->err = "workspace allocation of " + std::to_string(need) + " bytes failed";
-    return UNET_ERR_NOMEM;
-  }
-  h->wsBytes = need;
-  return UNET_OK;
+  return h->ws.reserve(h->err, need, "workspace");
 }
 
 static int forward_prologue(unet_handle_t h, const void* in, int n, int height, int width) {
@@ -925,7 +942,7 @@ int unet_forward_u8(unet_handle_t h, const uint8_t* frames, int n, int height, i
   const size_t npix = (size_t)n * height * width;
   const unet_config& c = h->cfg;
   hipLaunchKernelGGL(unet::pack_u8_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, frames,
-                     reinterpret_cast<float*>(h->ws) + p.x0, npix, c.input_mean[0], c.input_mean[1], c.input_mean[2],
+                     reinterpret_cast<float*>(h->ws.p) + p.x0, npix, c.input_mean[0], c.input_mean[1], c.input_mean[2],
                      c.input_std[0], c.input_std[1], c.input_std[2]);
   HIPCHK(h->err, hipGetLastError());
   return forward_common(h, n, height, width, logits, probs, mask, thr, s, p);
@@ -939,7 +956,7 @@ int unet_forward_f32(unet_handle_t h, const float* image, int n, int height, int
   const WsPlan p = plan_ws(h->cfg, n, height, width);
   const size_t npix = (size_t)n * height * width;
   hipLaunchKernelGGL(unet::pack_nchw_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, image,
-                     reinterpret_cast<float*>(h->ws) + p.x0, n, (size_t)height * width, h->cfg.in_channels);
+                     reinterpret_cast<float*>(h->ws.p) + p.x0, n, (size_t)height * width, h->cfg.in_channels);
   HIPCHK(h->err, hipGetLastError());
   return forward_common(h, n, height, width, logits, probs, mask, thr, s, p);
 }
@@ -1024,45 +1041,172 @@ int unet_debug_set_error_block(unet_handle_t h, int word, unsigned value) {
   return UNET_OK;
 }
 
+}  // extern "C"
+
 // ---- single operators (test entry points) -------------------------------------------------
+//
+// The handle-less entry points of all four files (unet_op_*, the loss, metric and camera helpers) share what follows:
+// g_opErr is the text of the calling thread's last failure (unet_op_last_error), OpScratch owns the device memory of one
+// call, OpGuard the operator built for it, and op_done is the one exit that turns the launches' hipError_t into a status.
 
 static thread_local std::string g_opErr;
 
+// for the handle-less entry points of the other translation units (augment_kernels.cpp); not exported
+namespace unet {
+__attribute__((visibility("hidden"))) int op_fail(int status, const std::string& text) {
+  g_opErr = text;
+  return status;
+}
+}  // namespace unet
+// what an entry point returns for arguments its own checks refuse (before any device work)
+static int op_bad_args() { return unet::op_fail(UNET_ERR_INVALID_ARG, "invalid argument: refused by the entry point's checks"); }
+
+namespace {
+
+// Every device allocation of one call, freed when it returns, on every path.  Zeroing, where asked, is on the call's stream.
+struct OpScratch {
+  hipStream_t s;
+  std::vector<void*> all;
+  explicit OpScratch(hipStream_t stream) : s(stream) {}
+  OpScratch(const OpScratch&) = delete;
+  OpScratch& operator=(const OpScratch&) = delete;
+  ~OpScratch() {
+    for (void* q : all) hipFree(q);
+  }
+  template <class T>
+  hipError_t get(T** p, size_t bytes, bool zero = false) {
+    bytes = std::max<size_t>(bytes, 64);
+    hipError_t e = hipMalloc((void**)p, bytes);
+    if (e != hipSuccess) return e;
+    all.push_back(*p);
+    return zero ? hipMemsetAsync(*p, 0, bytes, s) : hipSuccess;
+  }
+  // `count` host elements, copied before the call returns to the caller's launches
+  template <class T>
+  hipError_t upload(T** p, const T* host, size_t count) {
+    hipError_t e = get(p, count * sizeof(T));
+    return e == hipSuccess ? hipMemcpy(*p, host, count * sizeof(T), hipMemcpyHostToDevice) : e;
+  }
+  // a buffer that one of the tiers' own pack functions allocated for this call
+  void adopt(void* p) {
+    if (p) all.push_back(p);
+  }
+  // the zero page the kernels read for an out-of-image halo (x3_build: 4096 bytes; bf16_build: 8192 elements)
+  hipError_t zero_page(uint16_t** p, size_t bytes = 4096) { return get(p, bytes, true); }
+};
+
+// The operator a call builds (GemmOp, GemmOpBf, GemmOpX3, DecOpX3): its device arrays are released on every exit
+template <class Op>
+struct OpGuard {
+  Op op;
+  OpGuard() = default;
+  OpGuard(const OpGuard&) = delete;
+  ~OpGuard() { op.free_dev(); }
+};
+
+// fp32 dense tensor -> fp16 hi / lo planes (lo plane `elems` halfs behind the hi plane, together the bytes of the fp32
+// tensor).  absmaxKey / inv: for tensors far below the fp16 range (gradients): scaled by the power of two that
+// brings the maximum to ~2^13, its inverse left in *inv.
+void split_to_planes(const float* x, size_t elems, void* planes, hipStream_t s, const unsigned* absmaxKey = nullptr,
+                     float* inv = nullptr) {
+  uint16_t* hi = reinterpret_cast<uint16_t*>(planes);
+  prof_begin("split_planes", 0.0, 8.0 * elems, s);
+  if (absmaxKey)
+    hipLaunchKernelGGL(unet::split_planes_scaled_kernel, dim3(grid_for(elems / 2)), dim3(256), 0, s, x, elems / 2,
+                       reinterpret_cast<uint32_t*>(hi), reinterpret_cast<uint32_t*>(hi + elems), absmaxKey, inv);
+  else
+    hipLaunchKernelGGL(unet::split_planes_kernel, dim3(grid_for(elems / 2)), dim3(256), 0, s, x, elems / 2,
+                       reinterpret_cast<uint32_t*>(hi), reinterpret_cast<uint32_t*>(hi + elems));
+  prof_end(s);
+}
+// ... and back: planes laid out the same way -> fp32 dense tensor
+void merge_from_planes(const void* planes, size_t elems, float* y, hipStream_t s) {
+  const uint16_t* hi = reinterpret_cast<const uint16_t*>(planes);
+  hipLaunchKernelGGL(unet::merge_planes_kernel, dim3(grid_for(elems / 2)), dim3(256), 0, s,
+                     reinterpret_cast<const uint32_t*>(hi), reinterpret_cast<const uint32_t*>(hi + elems), elems / 2, y);
+}
+
+// The plane-level test entry points (unet_op_*_x3_planes) watch the range with a word of their own: for the scope's
+// lifetime the calling thread's launches report into it instead of the per-device word of the other entry points
+struct OpRangeScope {
+  unsigned* dev = nullptr;
+  unsigned* prev = nullptr;
+  bool armed = false;
+  hipError_t arm() {
+    hipError_t e = hipMalloc((void**)&dev, 2 * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemset(dev, 0, 2 * sizeof(unsigned));
+    if (e != hipSuccess) return e;
+    prev = g_errWord;
+    g_errWord = dev;
+    armed = true;
+    return hipSuccess;
+  }
+  // after the stream has been synchronised: did a kernel of the call set word 1?
+  hipError_t read(int* rangeOut) {
+    unsigned host[2] = {0, 0};
+    const hipError_t e = hipMemcpy(host, dev, sizeof(host), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rangeOut) *rangeOut = host[1] != 0 ? 1 : 0;
+    return e;
+  }
+  ~OpRangeScope() {
+    if (armed) g_errWord = prev;
+    if (dev) hipFree(dev);
+  }
+};
+
+// The one exit of a handle-less entry point.  `e`: what the call's allocations and launches returned.  The stream is
+// synchronised (also after a failure: the scratch is freed when the caller returns) unless kOpNoSync says that the entry
+// point is asynchronous; then an armed `range` is read into *rangeOut.  A failure leaves its text in g_opErr and is
+// UNET_ERR_HIP, or with kOpMapCodes UNET_ERR_INVALID_ARG / UNET_ERR_NOMEM for the runtime's codes of those names.
+enum : unsigned { kOpNoSync = 1, kOpMapCodes = 2 };
+int op_done(hipError_t e, hipStream_t s, unsigned flags = 0, OpRangeScope* range = nullptr, int* rangeOut = nullptr) {
+  if (!(flags & kOpNoSync)) {
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+  }
+  if (e == hipSuccess && range) e = range->read(rangeOut);
+  if (e == hipSuccess) return UNET_OK;
+  g_opErr = hipGetErrorString(e);
+  if (flags & kOpMapCodes) {
+    if (e == hipErrorInvalidValue) return UNET_ERR_INVALID_ARG;
+    if (e == hipErrorOutOfMemory) return UNET_ERR_NOMEM;
+  }
+  return UNET_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* unet_op_last_error(void) { return g_opErr.c_str(); }
+
 int unet_op_conv3x3(int device, const float* x, int n, int h, int w, int cin, const float* wHost,
                     const float* scale, const float* shift, int cout, int relu, float* y, void* stream) {
-  if (!x || !wHost || !scale || !shift || !y || cin % 4 || cout % 4) return UNET_ERR_INVALID_ARG;
+  if (!x || !wHost || !scale || !shift || !y || cin % 4 || cout % 4) return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
-  GemmOp op;
-  int rc = build_conv3x3(g_opErr, op, wHost, cout, cin, scale, shift, relu);
-  if (!rc) {
-    hipError_t e = run_gemm_op(op, x, n, h, w, y, cout, 0, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) rc = UNET_ERR_HIP;
-  }
-  op.free_dev();
-  return rc;
+  hipStream_t s = (hipStream_t)stream;
+  OpGuard<GemmOp> g;
+  const int rc = build_conv3x3(g_opErr, g.op, wHost, cout, cin, scale, shift, relu);
+  return rc ? rc : op_done(run_gemm_op(g.op, x, n, h, w, y, cout, 0, s), s);
 }
 
 int unet_op_upconv2x2(int device, const float* x, int n, int h, int w, int cin, const float* wHost,
                       const float* bias, int cout, float* y, void* stream) {
-  if (!x || !wHost || !bias || !y || cin % 4 || cout % 4) return UNET_ERR_INVALID_ARG;
+  if (!x || !wHost || !bias || !y || cin % 4 || cout % 4) return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
-  GemmOp op;
-  int rc = build_upconv(g_opErr, op, wHost, cin, cout, bias);
-  if (!rc) {
-    hipError_t e = run_gemm_op(op, x, n, h, w, y, cout, 0, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) rc = UNET_ERR_HIP;
-  }
-  op.free_dev();
-  return rc;
+  hipStream_t s = (hipStream_t)stream;
+  OpGuard<GemmOp> g;
+  const int rc = build_upconv(g_opErr, g.op, wHost, cin, cout, bias);
+  return rc ? rc : op_done(run_gemm_op(g.op, x, n, h, w, y, cout, 0, s), s);
 }
 
 int unet_op_conv1x1(int device, const float* x, int n, int h, int w, int cin, const float* wHost, int cout, float* y,
                     void* stream) {
-  if (!x || !wHost || !y || cin % 4 || cout % 4) return UNET_ERR_INVALID_ARG;
+  if (!x || !wHost || !y || cin % 4 || cout % 4) return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
-  GemmOp op;
+  hipStream_t s = (hipStream_t)stream;
+  OpGuard<GemmOp> g;
+  GemmOp& op = g.op;
   op.taps = 1;
   op.plain = 1;
   op.cinReal = cin;
@@ -1078,34 +1222,26 @@ int unet_op_conv1x1(int device, const float* x, int n, int h, int w, int cin, co
   int rc = upload(g_opErr, &op.wt, packed);
   if (!rc) rc = upload(g_opErr, &op.scale, sc);
   if (!rc) rc = upload(g_opErr, &op.shift, sh);
-  if (!rc) {
-    hipError_t e = run_gemm_op(op, x, n, h, w, y, cout, 0, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) rc = UNET_ERR_HIP;
-  }
-  op.free_dev();
-  return rc;
+  return rc ? rc : op_done(run_gemm_op(op, x, n, h, w, y, cout, 0, s), s);
 }
 
 int unet_op_maxpool2x2(int device, const float* x, int n, int h, int w, int c, float* y, void* stream) {
-  if (!x || !y || c % 4 || h % 2 || w % 2) return UNET_ERR_INVALID_ARG;
+  if (!x || !y || c % 4 || h % 2 || w % 2) return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
-  HIPCHK(g_opErr, run_maxpool(x, y, n, h, w, c, c, (hipStream_t)stream));
-  HIPCHK(g_opErr, hipStreamSynchronize((hipStream_t)stream));
-  return UNET_OK;
+  hipStream_t s = (hipStream_t)stream;
+  return op_done(run_maxpool(x, y, n, h, w, c, c, s), s);
 }
 
 int unet_op_head1x1(int device, const float* x, int n, int h, int w, int c, const float* wHost, float bias,
                     float* logits, void* stream) {
-  if (!x || !wHost || !logits || c % 4) return UNET_ERR_INVALID_ARG;
+  if (!x || !wHost || !logits || c % 4) return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  OpScratch sc(s);
   float* wd = nullptr;
-  HIPCHK(g_opErr, hipMalloc((void**)&wd, c * sizeof(float)));
-  HIPCHK(g_opErr, hipMemcpy(wd, wHost, c * sizeof(float), hipMemcpyHostToDevice));
-  hipError_t e = run_head(x, wd, bias, (size_t)n * h * w, c, logits, nullptr, nullptr, 0.f, (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  hipFree(wd);
-  return e == hipSuccess ? UNET_OK : UNET_ERR_HIP;
+  hipError_t e = sc.upload(&wd, wHost, (size_t)c);
+  if (e == hipSuccess) e = run_head(x, wd, bias, (size_t)n * h * w, c, logits, nullptr, nullptr, 0.f, s);
+  return op_done(e, s);
 }
 
 }  // extern "C"
@@ -1123,7 +1259,7 @@ int unet_ipm_prestage_u8(int device, const uint8_t* img, int height, int width, 
                          void* stream) {
   if (!img || !minv || !outRgb || height <= 0 || width <= 0 || step < 3 * width || warpW <= 0 || warpH <= 0 ||
       outW <= 0 || outH <= 0)
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   unet::CameraArgs a;
   a.img = img;
@@ -1141,20 +1277,18 @@ int unet_ipm_prestage_u8(int device, const uint8_t* img, int height, int width, 
   a.out_h = outH;
   hipLaunchKernelGGL(unet::ipm_prestage_kernel, dim3((unsigned)(((size_t)outW * outH + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, a);
-  HIPCHK(g_opErr, hipGetLastError());
-  return UNET_OK;
+  return op_done(hipGetLastError(), (hipStream_t)stream, kOpNoSync);
 }
 
 int unet_resize_u8(int device, const uint8_t* src, int height, int width, int channels, int outW, int outH,
                    uint8_t* dst, void* stream) {
-  if (!src || !dst || height <= 0 || width <= 0 || channels <= 0 || outW <= 0 || outH <= 0) return UNET_ERR_INVALID_ARG;
+  if (!src || !dst || height <= 0 || width <= 0 || channels <= 0 || outW <= 0 || outH <= 0) return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   const size_t total = (size_t)outW * outH * channels;
   hipLaunchKernelGGL(unet::resize_u8_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, src, height,
                      width, channels, 1.0 / ((double)outW / (double)width), 1.0 / ((double)outH / (double)height), outW,
                      outH, dst);
-  HIPCHK(g_opErr, hipGetLastError());
-  return UNET_OK;
+  return op_done(hipGetLastError(), (hipStream_t)stream, kOpNoSync);
 }
 
 }  // extern "C"

@@ -44,8 +44,7 @@ struct unet_i8_ctx {
   int headWzp = 0, headXzp = 0, headBias = 0;
   float headMult = 0.f;
   std::map<std::string, I8Tensor> tensors;   // by name, incl. "im2col"
-  char* ws = nullptr;
-  size_t wsBytes = 0;
+  GrowBuf ws;
   int wsN = 0, wsH = 0, wsW = 0;
   std::string err;
   void free_all() {
@@ -54,10 +53,8 @@ struct unet_i8_ctx {
     first.free_dev();
     if (lut) hipFree(lut);
     if (headW) hipFree(headW);
-    if (ws) hipFree(ws);
+    ws.release();
     lut = headW = nullptr;
-    ws = nullptr;
-    wsBytes = 0;
   }
 };
 
@@ -210,7 +207,7 @@ int i8_build_upconv(unet_i8_ctx* h, I8Unit& u, const std::string& key, int cinRe
                        wzc, bc, mc);
 }
 
-void i8_plan(unet_i8_ctx* h, int n, int height, int width) {
+int i8_plan(unet_i8_ctx* h, int n, int height, int width) {
   h->tensors.clear();
   size_t off = 0;
   auto add = [&](const std::string& name, int c, int level, bool feedsUpconv = false) {
@@ -241,18 +238,10 @@ void i8_plan(unet_i8_ctx* h, int n, int height, int width) {
   h->wsN = n;
   h->wsH = height;
   h->wsW = width;
-  if (off > h->wsBytes) {
-    if (h->ws) {
-      hipDeviceSynchronize();
-      hipFree(h->ws);
-      h->ws = nullptr;
-      h->wsBytes = 0;
-    }
-    if (hipMalloc((void**)&h->ws, off) == hipSuccess) {
-      h->wsBytes = off;
-      hipMemset(h->ws, 0, off);   // padded channels are never written; they are multiplied by zero either way
-    }
-  }
+  if (off <= h->ws.bytes) return UNET_OK;
+  const int rc = h->ws.reserve(h->err, off, "int8 workspace");
+  if (!rc) hipMemset(h->ws.p, 0, off);   // padded channels are never written; they are multiplied by zero either way
+  return rc;
 }
 
 // scratch page of the current device for the lanes of conv_i8_lw_kernel that have nothing to store
@@ -459,17 +448,14 @@ int unet_i8_forward_u8(unet_i8_handle_t h, const uint8_t* frames, int n, int hei
     return UNET_ERR_SHAPE;
   }
   HIPCHK(h->err, hipSetDevice(h->device));
-  if (n != h->wsN || height != h->wsH || width != h->wsW || !h->ws) {
-    i8_plan(h, n, height, width);
-    if (!h->ws) {
-      h->err = "int8 workspace allocation failed";
-      return UNET_ERR_NOMEM;
-    }
+  if (n != h->wsN || height != h->wsH || width != h->wsW || !h->ws.p) {
+    const int rc = i8_plan(h, n, height, width);
+    if (rc) return rc;
   }
   hipStream_t s = (hipStream_t)stream;
   const int d = h->depth;
   auto T = [&](const std::string& name) -> const I8Tensor& { return h->tensors.at(name); };
-  auto P = [&](const I8Tensor& t) { return reinterpret_cast<int8_t*>(h->ws + t.off); };
+  auto P = [&](const I8Tensor& t) { return reinterpret_cast<int8_t*>(h->ws.p + t.off); };
   const size_t npix = (size_t)n * height * width;
   hipLaunchKernelGGL(unet::im2col27_i8_kernel, dim3(grid_for(npix)), dim3(256), 0, s, frames, h->lut, n, height, width, h->zin,
                      P(T("im2col")));
@@ -516,7 +502,7 @@ int unet_i8_forward_u8(unet_i8_handle_t h, const uint8_t* frames, int n, int hei
 // Copy one activation tensor of the last forward call to the host as dense NHWC int8 with its real channels
 // (parity tests): name = "im2col", "enc<l>.a", "cat<l>", "cat<l>.pool", "bott.a", "bott.b", "dec<j>.a", "dec<j>.b".
 int unet_i8_read_tensor(unet_i8_handle_t h, const char* name, int8_t* dstHost, size_t capBytes, int* channels) {
-  if (!h || !name || !dstHost || !h->ws) return UNET_ERR_INVALID_ARG;
+  if (!h || !name || !dstHost || !h->ws.p) return UNET_ERR_INVALID_ARG;
   auto it = h->tensors.find(name);
   if (it == h->tensors.end()) return UNET_ERR_UNKNOWN_PARAM;
   HIPCHK(h->err, hipSetDevice(h->device));
@@ -525,7 +511,7 @@ int unet_i8_read_tensor(unet_i8_handle_t h, const char* name, int8_t* dstHost, s
   const size_t px = (size_t)h->wsN * (h->wsH >> t.level) * (h->wsW >> t.level);
   if (capBytes < px * t.c) return UNET_ERR_INVALID_ARG;
   if (channels) *channels = t.c;
-  HIPCHK(h->err, hipMemcpy2D(dstHost, t.c, h->ws + t.off, t.ld, t.c, px, hipMemcpyDeviceToHost));
+  HIPCHK(h->err, hipMemcpy2D(dstHost, t.c, h->ws.p + t.off, t.ld, t.c, px, hipMemcpyDeviceToHost));
   return UNET_OK;
 }
 
@@ -548,14 +534,14 @@ int unet_forward_u8_ranges(unet_handle_t h, const uint8_t* frames, int n, int he
   if (!h || !frames || !rangesHost) return UNET_ERR_INVALID_ARG;
   const int nt = unet_num_range_tensors(h);
   HIPCHK(h->err, hipSetDevice(h->cfg.device));
-  unsigned* keys = nullptr;
-  HIPCHK(h->err, hipMalloc((void**)&keys, (size_t)nt * 2 * sizeof(unsigned)));
   std::vector<unsigned> init((size_t)nt * 2);
   for (int i = 0; i < nt; ++i) {
     init[2 * i] = 0xFFFFFFFFu;
     init[2 * i + 1] = 0u;
   }
-  hipMemcpy(keys, init.data(), init.size() * sizeof(unsigned), hipMemcpyHostToDevice);
+  OpScratch sc((hipStream_t)stream);
+  unsigned* keys = nullptr;
+  HIPCHK(h->err, sc.upload(&keys, init.data(), init.size()));
   h->rangeKeys = keys;
   // direct kernels only: the Winograd kernel fuses the pool and the algorithms agree to 3e-5 anyway; ranges are
   // taken on the tensors the forward materialises
@@ -573,7 +559,6 @@ int unet_forward_u8_ranges(unet_handle_t h, const uint8_t* frames, int n, int he
       rangesHost[i] = f;
     }
   }
-  hipFree(keys);
   return rc ? rc : rc2;
 }
 

@@ -138,8 +138,7 @@ struct TrainState {
   size_t offHeadW = 0, offHeadB = 0;
   float *ones = nullptr, *zeros = nullptr;
   float* statArena = nullptr;
-  char* ws = nullptr;
-  size_t wsBytes = 0;
+  GrowBuf ws;
   bool packed = false;
   PackArgs* packDescs = nullptr;   // device table of every packed operand (train_repack)
   unsigned* packStart = nullptr;   // first block of each table entry, nPack + 1 entries
@@ -731,22 +730,6 @@ bool train_x3_enabled() {
   return g_trainX3 == 1;
 }
 
-// fp32 dense tensor -> fp16 hi / lo planes (lo plane `elems` halfs behind the hi plane, together the bytes of the fp32
-// tensor).  absmaxKey / inv: for tensors far below the fp16 range (gradients): scaled by the power of two that
-// brings the maximum to ~2^13, its inverse left in *inv.
-void split_to_planes(const float* x, size_t elems, float* planes, hipStream_t s, const unsigned* absmaxKey = nullptr,
-                     float* inv = nullptr) {
-  uint16_t* hi = reinterpret_cast<uint16_t*>(planes);
-  prof_begin("split_planes", 0.0, 8.0 * elems, s);
-  if (absmaxKey)
-    hipLaunchKernelGGL(unet::split_planes_scaled_kernel, dim3(grid_for(elems / 2)), dim3(256), 0, s, x, elems / 2,
-                       reinterpret_cast<uint32_t*>(hi), reinterpret_cast<uint32_t*>(hi + elems), absmaxKey, inv);
-  else
-    hipLaunchKernelGGL(unet::split_planes_kernel, dim3(grid_for(elems / 2)), dim3(256), 0, s, x, elems / 2,
-                       reinterpret_cast<uint32_t*>(hi), reinterpret_cast<uint32_t*>(hi + elems));
-  prof_end(s);
-}
-
 // An operator of the f16x3 tier over packs and epilogue arrays that live elsewhere (a unit's x3Fwd / x3Dgrad, the
 // parameter buffer, TrainState::ones / zeros): GemmOpX3 frees nothing on its own, so the copy is simply dropped.
 GemmOpX3 x3_borrowed(int taps, int cin, int cout, int relu, const uint16_t* wt, const float* scale, const float* shift) {
@@ -1046,7 +1029,7 @@ int unit_backward(unet_ctx* h, ConvUnit& u, const float* dA, int ldd, int offd, 
   // `partial`) and the two maxima in the unit's keys (maxpool_bwd_add_bnstat_kernel)
   // r1p / r1c: dA is the outer product r1p[pixel] * r1c[channel] (the unit under the 1x1 head) and is never stored
   TrainState* T = h->train;
-  float* ws = reinterpret_cast<float*>(T->ws);
+  float* ws = reinterpret_cast<float*>(T->ws.p);
   float* partial = ws + p.partial;
   const size_t P = (size_t)n * hh * ww;
   const int nb = partialRows > 0 ? partialRows : red_blocks(P);
@@ -1122,22 +1105,7 @@ int pass_workspace(unet_ctx* h, int n, int height, int width, TrainPlan& plan) {
   if (rc) return rc;
   HIPCHK(h->err, hipSetDevice(h->cfg.device));
   plan = plan_train(h->cfg, n, height, width);
-  TrainState* T = h->train;
-  const size_t need = plan.total * sizeof(float);
-  if (need > T->wsBytes) {
-    if (T->ws) {
-      HIPCHK(h->err, hipDeviceSynchronize());
-      hipFree(T->ws);
-      T->ws = nullptr;
-      T->wsBytes = 0;
-    }
-    if (hipMalloc((void**)&T->ws, need) != hipSuccess) {
-      h->err = "training workspace allocation of " + std::to_string(need) + " bytes failed";
-      return UNET_ERR_NOMEM;
-    }
-    T->wsBytes = need;
-  }
-  return UNET_OK;
+  return h->train->ws.reserve(h->err, plan.total * sizeof(float), "training workspace");
 }
 
 int train_prologue(unet_ctx* h, const void* in, const float* targets, float* loss, int n, int height, int width,
@@ -1266,7 +1234,7 @@ int forward_walk(unet_ctx* h, Pass pass, int n, int height, int width, float* lo
   const unet_config& c = h->cfg;
   const int D = c.depth;
   const bool train = pass == Pass::Train, PM = p.planes;
-  float* ws = reinterpret_cast<float*>(T->ws);
+  float* ws = reinterpret_cast<float*>(T->ws.p);
   int rc;
   // one conv unit; `in` is planes where inP says so
   auto unit = [&](ConvUnit& u, const float* in, bool inP, int hh, int ww, float* z, const ActOut& o) {
@@ -1367,7 +1335,7 @@ int forward_walk(unet_ctx* h, Pass pass, int n, int height, int width, float* lo
 // the loss of lossMode over P0 logits: its terms to lossDev, its logit gradient to the workspace's dlogits
 int run_loss_grad(unet_ctx* h, const float* targets, size_t P0, float* lossDev, hipStream_t s, const TrainPlan& p) {
   TrainState* T = h->train;
-  float* ws = reinterpret_cast<float*>(T->ws);
+  float* ws = reinterpret_cast<float*>(T->ws.p);
   float* partial = ws + p.partial;
   if (T->lossMode == 2) {
     // the reduction scratch holds kRedBlocks * 2 * 4096 floats, far beyond loss_scratch_bytes of any batch
@@ -1406,7 +1374,7 @@ int upconv_backward(unet_ctx* h, int j, int n, int ch, int cw, float* gA, hipStr
   TrainState* T = h->train;
   const int l = h->cfg.depth - 1 - j;
   const int f = h->cfg.features[l];
-  float* ws = reinterpret_cast<float*>(T->ws);
+  float* ws = reinterpret_cast<float*>(T->ws.p);
   float* partial = ws + p.partial;
   UpUnit& U = T->up[j];
   const int lh = ch / 2, lw = cw / 2;
@@ -1473,7 +1441,7 @@ int backward_decoder(unet_ctx* h, int n, int height, int width, hipStream_t s, c
   const unet_config& c = h->cfg;
   const int D = c.depth, f0 = c.features[0];
   const bool PM = p.planes;
-  float* ws = reinterpret_cast<float*>(T->ws);
+  float* ws = reinterpret_cast<float*>(T->ws.p);
   float *gA = ws + p.gA, *gB = ws + p.gB, *gZ = ws + p.gZ;
   const size_t P0 = (size_t)n * height * width;
   int rc;
@@ -1525,7 +1493,7 @@ int backward_encoder(unet_ctx* h, int n, int height, int width, hipStream_t s, c
   const unet_config& c = h->cfg;
   const int D = c.depth;
   const bool PM = p.planes;
-  float* ws = reinterpret_cast<float*>(T->ws);
+  float* ws = reinterpret_cast<float*>(T->ws.p);
   float *gA = ws + p.gA, *gB = ws + p.gB, *gZ = ws + p.gZ;
   int rc;
   for (int l = D - 1; l >= 0; --l) {
@@ -1567,7 +1535,7 @@ int train_forward_backward(unet_ctx* h, int n, int height, int width, const floa
                            float* logitsOut, hipStream_t s, const TrainPlan& p) {
   TrainState* T = h->train;
   LaunchScope scope(h);
-  float* ws = reinterpret_cast<float*>(T->ws);
+  float* ws = reinterpret_cast<float*>(T->ws.p);
   const size_t P0 = (size_t)n * height * width;
   int rc;
   if ((rc = repack_if_switched(h, s))) return rc;
@@ -1646,7 +1614,7 @@ static void train_free(unet_ctx* h) {
   if (T->packX3Descs) hipFree(T->packX3Descs);
   if (T->packX3Start) hipFree(T->packX3Start);
   if (T->packStart) hipFree(T->packStart);
-  if (T->ws) hipFree(T->ws);
+  T->ws.release();
   delete T;
   h->train = nullptr;
 }
@@ -1929,7 +1897,7 @@ int unet_train_forward_backward_u8(unet_handle_t h, const uint8_t* frames, const
   const size_t npix = (size_t)n * height * width;
   const unet_config& c = h->cfg;
   hipLaunchKernelGGL(unet::pack_u8_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, frames,
-                     reinterpret_cast<float*>(h->train->ws) + p.x0, npix, c.input_mean[0], c.input_mean[1],
+                     reinterpret_cast<float*>(h->train->ws.p) + p.x0, npix, c.input_mean[0], c.input_mean[1],
                      c.input_mean[2], c.input_std[0], c.input_std[1], c.input_std[2]);
   HIPCHK(h->err, hipGetLastError());
   return train_forward_backward(h, n, height, width, targets, lossDev, logitsDev, s, p);
@@ -1943,7 +1911,7 @@ int unet_train_forward_backward_f32(unet_handle_t h, const float* image, const f
   hipStream_t s = (hipStream_t)stream;
   const size_t npix = (size_t)n * height * width;
   hipLaunchKernelGGL(unet::pack_nchw_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, image,
-                     reinterpret_cast<float*>(h->train->ws) + p.x0, n, (size_t)height * width, h->cfg.in_channels);
+                     reinterpret_cast<float*>(h->train->ws.p) + p.x0, n, (size_t)height * width, h->cfg.in_channels);
   HIPCHK(h->err, hipGetLastError());
   return train_forward_backward(h, n, height, width, targets, lossDev, logitsDev, s, p);
 }
@@ -1980,7 +1948,7 @@ int unet_train_eval_u8(unet_handle_t h, const uint8_t* frames, int n, int height
   const size_t npix = (size_t)n * height * width;
   const unet_config& c = h->cfg;
   hipLaunchKernelGGL(unet::pack_u8_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, frames,
-                     reinterpret_cast<float*>(h->train->ws) + p.x0, npix, c.input_mean[0], c.input_mean[1],
+                     reinterpret_cast<float*>(h->train->ws.p) + p.x0, npix, c.input_mean[0], c.input_mean[1],
                      c.input_mean[2], c.input_std[0], c.input_std[1], c.input_std[2]);
   HIPCHK(h->err, hipGetLastError());
   return train_eval_forward(h, n, height, width, logitsDev, s, p);
@@ -1994,7 +1962,7 @@ int unet_train_eval_f32(unet_handle_t h, const float* image, int n, int height, 
   hipStream_t s = (hipStream_t)stream;
   const size_t npix = (size_t)n * height * width;
   hipLaunchKernelGGL(unet::pack_nchw_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, image,
-                     reinterpret_cast<float*>(h->train->ws) + p.x0, n, (size_t)height * width, h->cfg.in_channels);
+                     reinterpret_cast<float*>(h->train->ws.p) + p.x0, n, (size_t)height * width, h->cfg.in_channels);
   HIPCHK(h->err, hipGetLastError());
   return train_eval_forward(h, n, height, width, logitsDev, s, p);
 }
@@ -2004,7 +1972,7 @@ int unet_train_eval_f32(unet_handle_t h, const float* image, int n, int height, 
 int unet_seg_metrics_accumulate(int device, const float* logitsDev, const void* targetsDev, int targetsAreU8,
                                 size_t numel, float thresholdLogit, int lossMode, float bceWeight, float diceWeight,
                                 float posWeight, float smooth, double* accDev, void* stream) {
-  if (!logitsDev || !targetsDev || !accDev || numel == 0 || (lossMode != 0 && lossMode != 1)) return UNET_ERR_INVALID_ARG;
+  if (!logitsDev || !targetsDev || !accDev || numel == 0 || (lossMode != 0 && lossMode != 1)) return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = std::min<unsigned>(grid_for(numel), 1024);
@@ -2013,8 +1981,7 @@ int unet_seg_metrics_accumulate(int device, const float* logitsDev, const void* 
   const hipError_t e = unet::launch_seg_metrics(logitsDev, targetsDev, targetsAreU8 != 0, numel, thresholdLogit, lossMode,
                                                   bceWeight, diceWeight, posWeight, smooth, partial, nb, accDev, s);
   HIPCHK(g_opErr, hipFreeAsync(partial, s));
-  HIPCHK(g_opErr, e);
-  return UNET_OK;
+  return op_done(e, s, kOpNoSync);
 }
 
 // The same reduction with the loss given as a structure; mode 2 runs the general loss (loss_kernels.h) and adds the
@@ -2022,13 +1989,13 @@ int unet_seg_metrics_accumulate(int device, const float* logitsDev, const void* 
 int unet_seg_metrics_accumulate_cfg(int device, const float* logitsDev, const void* targetsDev, int targetsAreU8,
                                     size_t numel, float thresholdLogit, const unet_loss_config* cfg, double* accDev,
                                     void* stream) {
-  if (!cfg) return UNET_ERR_INVALID_ARG;
+  if (!cfg) return op_bad_args();
   if (cfg->mode == 0 || cfg->mode == 1)
     return unet_seg_metrics_accumulate(device, logitsDev, targetsDev, targetsAreU8, numel, thresholdLogit, cfg->mode,
                                        cfg->bce_weight, cfg->dice_weight, cfg->pos_weight, cfg->smooth, accDev, stream);
   const unet::LossParams lp = loss_params_of(*cfg);
   if (!logitsDev || !targetsDev || !accDev || numel == 0 || cfg->mode != 2 || !unet::loss_params_valid(lp))
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   void* scratch = nullptr;
@@ -2036,40 +2003,38 @@ int unet_seg_metrics_accumulate_cfg(int device, const float* logitsDev, const vo
   const hipError_t e = unet::launch_seg_metrics_cfg(logitsDev, targetsDev, targetsAreU8 != 0, numel, thresholdLogit, lp,
                                                       scratch, accDev, s);
   HIPCHK(g_opErr, hipFreeAsync(scratch, s));
-  HIPCHK(g_opErr, e);
-  return UNET_OK;
+  return op_done(e, s, kOpNoSync);
 }
 
 // Test entry: the general loss and its logit gradient through launch_loss_grad, the helper the training step calls.
 int unet_op_loss_grad(int device, const float* logitsDev, const float* targetsDev, size_t numel,
                       const unet_loss_config* cfg, float* lossTermsDev, float* dlogitsDev, void* stream) {
   if (!logitsDev || !targetsDev || !cfg || !lossTermsDev || !dlogitsDev || numel == 0 || cfg->mode != 2)
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   const unet::LossParams lp = loss_params_of(*cfg);
-  if (!unet::loss_params_valid(lp)) return UNET_ERR_INVALID_ARG;
+  if (!unet::loss_params_valid(lp)) return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   void* scratch = nullptr;
   HIPCHK(g_opErr, hipMallocAsync(&scratch, unet::loss_scratch_bytes(numel), s));
   const hipError_t e = unet::launch_loss_grad(logitsDev, targetsDev, numel, lp, scratch, lossTermsDev, dlogitsDev, s);
   HIPCHK(g_opErr, hipFreeAsync(scratch, s));
-  HIPCHK(g_opErr, e);
-  return UNET_OK;
+  return op_done(e, s, kOpNoSync);
 }
 
 // Positive pixels per mask (reference README.md:2514-2530, :2544-2553): see include/unet_hip.h.
 int unet_mask_positive_counts(int device, const uint8_t* masksDev, int n, size_t pixelsPerImage, int threshold,
                               unsigned long long* countsDev, void* stream) {
-  if (!masksDev || !countsDev || n <= 0 || pixelsPerImage == 0) return UNET_ERR_INVALID_ARG;
+  if (!masksDev || !countsDev || n <= 0 || pixelsPerImage == 0) return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
-  HIPCHK(g_opErr, unet::launch_mask_positive_counts(masksDev, n, pixelsPerImage, threshold, countsDev, (hipStream_t)stream));
-  return UNET_OK;
+  hipStream_t s = (hipStream_t)stream;
+  return op_done(unet::launch_mask_positive_counts(masksDev, n, pixelsPerImage, threshold, countsDev, s), s, kOpNoSync);
 }
 
 // Dice metric of the validation loop (reference README.md:2115-2120) on device buffers; out_dev holds 4 floats.
 int unet_dice_metric(int device, const float* logitsDev, const float* targetsDev, size_t numel, float thresholdLogit,
                      float smooth, float* outDev, void* stream) {
-  if (!logitsDev || !targetsDev || !outDev || numel == 0) return UNET_ERR_INVALID_ARG;
+  if (!logitsDev || !targetsDev || !outDev || numel == 0) return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = std::min<unsigned>(grid_for(numel), 1024);
@@ -2078,45 +2043,45 @@ int unet_dice_metric(int device, const float* logitsDev, const float* targetsDev
   hipLaunchKernelGGL(unet::dice_metric_partial_kernel, dim3(nb), dim3(256), 0, s, logitsDev, targetsDev, numel,
                      thresholdLogit, partial);
   hipLaunchKernelGGL(unet::dice_metric_finalize_kernel, dim3(1), dim3(64), 0, s, partial, (int)nb, smooth, outDev);
-  HIPCHK(g_opErr, hipGetLastError());
+  const hipError_t e = hipGetLastError();
   HIPCHK(g_opErr, hipFreeAsync(partial, s));
-  return UNET_OK;
+  return op_done(e, s, kOpNoSync);
 }
 
 // Test entry: dW of a 3x3 convolution.  dz (N,H,W,Cout) and x (N,H,W,Cin) dense device buffers -> dw_dev (Cout,Cin,3,3).
 int unet_op_wgrad3x3(int device, const float* dz, const float* x, int n, int hh, int ww, int cin, int cout,
                      float* dwDev, void* stream) {
-  if (!dz || !x || !dwDev || cin % 4 || cout % 4) return UNET_ERR_INVALID_ARG;
+  if (!dz || !x || !dwDev || cin % 4 || cout % 4) return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   const size_t tiles = (size_t)(round_up(cout, 64) / 64) * (round_up(cin, 64) / 64);
   const size_t splits = std::max<size_t>(1, 1536 / tiles);
   const size_t slabFloats = splits * 9 * (size_t)round_up(cout, 64) * round_up(cin, 64);
+  hipStream_t s = (hipStream_t)stream;
+  OpScratch sc(s);
   float* slab = nullptr;
-  HIPCHK(g_opErr, hipMalloc((void**)&slab, slabFloats * sizeof(float)));
-  hipError_t e = run_wgrad(dz, cout, x, cin, cin, 9, n, hh, ww, slab, slabFloats, dwDev, 0, 0, (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  hipFree(slab);
-  return e == hipSuccess ? UNET_OK : UNET_ERR_HIP;
+  hipError_t e = sc.get(&slab, slabFloats * sizeof(float));
+  if (e == hipSuccess) e = run_wgrad(dz, cout, x, cin, cin, 9, n, hh, ww, slab, slabFloats, dwDev, 0, 0, s);
+  return op_done(e, s);
 }
 
 // Test entry: the same weight gradient through the split-operand kernel (wgrad_x3_ws.h).  scaled != 0: dz is first
 // scaled into the fp16 range by the power of two derived from its maximum, as the training step does for gradients.
 int unet_op_wgrad3x3_x3(int device, const float* dz, const float* x, int n, int hh, int ww, int cin, int cout,
                         float* dwDev, int scaled, void* stream) {
-  if (!dz || !x || !dwDev || cin % 64 || cout % 64 || hh % 2) return UNET_ERR_INVALID_ARG;
+  if (!dz || !x || !dwDev || cin % 64 || cout % 64 || hh % 2) return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   const size_t px = (size_t)n * hh * ww;
   const size_t tiles = (size_t)(cout / 64) * (cin / 64);
   const size_t slabFloats = wgrad_x3_splits(tiles, std::max<size_t>(1, px / 32)) * 9 * (size_t)cout * cin;
+  OpScratch sc(s);
   float *slab = nullptr, *dzP = nullptr, *xP = nullptr, *inv = nullptr;
   unsigned* key = nullptr;
-  hipError_t e = hipMalloc((void**)&slab, slabFloats * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&dzP, px * cout * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&xP, px * cin * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&inv, 64);
-  if (e == hipSuccess) e = hipMalloc((void**)&key, 64);
-  if (e == hipSuccess) e = hipMemsetAsync(key, 0, 64, s);
+  hipError_t e = sc.get(&slab, slabFloats * sizeof(float));
+  if (e == hipSuccess) e = sc.get(&dzP, px * cout * sizeof(float));
+  if (e == hipSuccess) e = sc.get(&xP, px * cin * sizeof(float));
+  if (e == hipSuccess) e = sc.get(&inv, 64);
+  if (e == hipSuccess) e = sc.get(&key, 64, true);
   if (e == hipSuccess) {
     if (scaled) {
       hipLaunchKernelGGL(unet::absmax_key_kernel, dim3(256), dim3(256), 0, s, dz, px * cout, key);
@@ -2127,14 +2092,7 @@ int unet_op_wgrad3x3_x3(int device, const float* dz, const float* x, int n, int 
     split_to_planes(x, px * cin, xP, s);
     e = run_wgrad_x3(dzP, xP, cout, cin, n, hh, ww, slab, slabFloats, dwDev, scaled ? inv : nullptr, s);
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  hipFree(slab);
-  hipFree(dzP);
-  hipFree(xP);
-  hipFree(inv);
-  hipFree(key);
-  if (e != hipSuccess) g_opErr = e;
-  return e == hipSuccess ? UNET_OK : UNET_ERR_HIP;
+  return op_done(e, s);
 }
 
 // ---- test entry points of the training step's MFMA operators (include/unet_hip.h, "The training step's f16x3 operators"):
@@ -2144,20 +2102,6 @@ int unet_op_wgrad3x3_x3(int device, const float* dz, const float* x, int n, int 
 }  // extern "C"
 
 namespace {
-struct OpScratch {   // device allocations of one call, freed when it returns; cleared, where asked, on the call's stream
-  std::vector<void*> all;
-  hipStream_t s = nullptr;
-  template <class T>
-  hipError_t get(T** p, size_t bytes, bool zero = false) {
-    hipError_t e = hipMalloc((void**)p, std::max<size_t>(bytes, 64));
-    if (e != hipSuccess) return e;
-    all.push_back(*p);
-    return zero ? hipMemsetAsync(*p, 0, std::max<size_t>(bytes, 64), s) : hipSuccess;
-  }
-  ~OpScratch() {
-    for (void* q : all) hipFree(q);
-  }
-};
 // the unit scale / zero shift of the training operators (TrainState::ones / zeros), c floats each
 hipError_t op_ones_zeros(OpScratch& sc, TrainState& T, int c) {
   hipError_t e = sc.get(&T.ones, (size_t)c * sizeof(float));
@@ -2165,11 +2109,6 @@ hipError_t op_ones_zeros(OpScratch& sc, TrainState& T, int c) {
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fill_kernel, dim3(4), dim3(256), 0, sc.s, T.ones, (size_t)c, 1.0f);   // as unet_train_create
   return hipGetLastError();
-}
-int op_status(hipError_t e) {
-  if (e == hipSuccess) return UNET_OK;
-  g_opErr = hipGetErrorString(e);
-  return e == hipErrorInvalidValue ? UNET_ERR_INVALID_ARG : (e == hipErrorOutOfMemory ? UNET_ERR_NOMEM : UNET_ERR_HIP);
 }
 }  // namespace
 
@@ -2186,20 +2125,19 @@ int unet_op_train_conv3x3_x3(int device, const uint16_t* xPlanes, const float* x
       (packer != 0 && packer != 1) || (packer == 1 && (reinterpret_cast<uintptr_t>(wDev) & 15)) ||
       !x3_decode_force(tileWidth, &force) || force.family == kX3Q8 || ldo % 64 || off < 0 || off % 64 ||
       off + cout > ldo || (statPartialDev && (!statRowsOut || (size_t)statCapRows * 2 * cout > kPartialFloats)))
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   // the epilogue writes its rows straight into the caller's buffer, so the room must be there before the structure and
   // its grid are known: at most 256 blocks x 4 rows (run_conv_x3)
   if (statRowsOut) *statRowsOut = 0;
   if (statPartialDev && statCapRows < 256 * 4) {
     *statRowsOut = 256 * 4;
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   }
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   if (invOut) *invOut = 1.f;
   const size_t elems = (size_t)n * hh * ww * cin;
-  OpScratch sc;
-  sc.s = s;
+  OpScratch sc(s);
   TrainState T;
   OpRangeScope range;
   X3Path path;
@@ -2224,10 +2162,8 @@ int unet_op_train_conv3x3_x3(int device, const uint16_t* xPlanes, const float* x
       pack_x3_table_add(d, st, wDev, wt, wtOther, cout, cin);
     else
       pack_x3_table_add(d, st, wDev, wtOther, wt, cin, cout);
-    if (e == hipSuccess) e = sc.get(&desc, d.size() * sizeof(d[0]));
-    if (e == hipSuccess) e = hipMemcpy(desc, d.data(), d.size() * sizeof(d[0]), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = sc.get(&start, st.size() * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemcpy(start, st.data(), st.size() * sizeof(unsigned), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = sc.upload(&desc, d.data(), d.size());
+    if (e == hipSuccess) e = sc.upload(&start, st.data(), st.size());
     if (e == hipSuccess) e = launch_pack_x3_lds_multi(desc, start, (int)d.size(), st.back(), s);
   } else if (e == hipSuccess) {
     launch_pack_x3(wDev, wt, cout, cin, mode, s);
@@ -2247,14 +2183,12 @@ int unet_op_train_conv3x3_x3(int device, const uint16_t* xPlanes, const float* x
     e = run_train_conv_x3_planes(&T, wt, cin, cout, xF32 ? planes : reinterpret_cast<const float*>(xPlanes), n, hh, ww, y, ldo,
                                  off, mode ? "dgrad3x3_f16x3" : "conv3x3_f16x3", s, scaled ? inv : nullptr, statPartialDev,
                                  statPartialDev ? &rows : nullptr, tileWidth, &path);
-  const hipError_t es = hipStreamSynchronize(s);   // also after a failed launch: the scratch is freed below
-  if (e == hipSuccess) e = es;
-  if (e == hipSuccess) e = range.read(rangeOut);
-  if (e == hipSuccess && scaled && invOut) e = hipMemcpy(invOut, inv, sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && scaled && invOut) e = hipMemcpyAsync(invOut, inv, sizeof(float), hipMemcpyDeviceToHost, s);
+  const int st = op_done(e, s, kOpMapCodes, &range, rangeOut);
   T.ones = T.zeros = nullptr;   // owned by sc
   path_to_ints(path, pathOut);
   if (statPartialDev) *statRowsOut = rows;
-  return op_status(e);
+  return st;
 }
 
 int unet_op_upconv_bwd_x3(int device, const float* dY, int ldd, int offd, const uint16_t* inPlanes, const float* wDev, int n,
@@ -2263,15 +2197,14 @@ int unet_op_upconv_bwd_x3(int device, const float* dY, int ldd, int offd, const 
   const int cin = 2 * f, rowsG = 4 * f;
   if (!dY || !inPlanes || !wDev || !db || !dW || !dIn || n < 1 || lh < 1 || lw < 1 || f < 64 || f % 64 || f > 512 ||
       rowsG % 128 || cin % 128 || ldd % 4 || offd < 0 || offd % 4 || offd + f > ldd)
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   if (structureOut) *structureOut = 0;
   const size_t Pl = (size_t)n * lh * lw;
   const size_t tiles = (size_t)(rowsG / 128) * (cin / 128);
   const size_t slabFloats = wgrad_x3_splits(tiles, (Pl + 31) / 32) * (size_t)rowsG * cin;
-  OpScratch sc;
-  sc.s = s;
+  OpScratch sc(s);
   float *S = nullptr, *partial = nullptr, *inv = nullptr, *slab = nullptr;
   unsigned* key = nullptr;
   uint16_t* wt = nullptr;
@@ -2296,11 +2229,9 @@ int unet_op_upconv_bwd_x3(int device, const float* dY, int ldd, int offd, const 
     e = run_gemm1x1_x3(wt, x3_from(reinterpret_cast<const uint16_t*>(zero_page()), reinterpret_cast<const uint16_t*>(S),
                                    Pl * 4 * (size_t)f, n, lh, lw).to(nullptr, 0, cin),
                        rowsG, cin, dIn, inv, "upconv_dgrad_f16x3", s, &structure);
-  const hipError_t es = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = es;
-  if (e == hipSuccess && invOut) e = hipMemcpy(invOut, inv, sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && invOut) e = hipMemcpyAsync(invOut, inv, sizeof(float), hipMemcpyDeviceToHost, s);
   if (structureOut) *structureOut = structure;
-  return op_status(e);
+  return op_done(e, s, kOpMapCodes);
 }
 
 int unet_op_upconv_fwd_train_x3(int device, const uint16_t* x, size_t xLo, int n, int hh, int ww, int cin, const float* wDev,
@@ -2309,11 +2240,10 @@ int unet_op_upconv_fwd_train_x3(int device, const uint16_t* x, size_t xLo, int n
   if (ldo == 0) ldo = cout;
   if (!x || !wDev || !biasDev || !y || n < 1 || hh < 1 || ww < 1 || cin < 64 || cin % 64 || cout < 64 || cout % 64 ||
       cout > unet::UpconvX3Shape::MAX_COUT || xLo % 8 || yLo % 8 || ldo % 64 || coOff < 0 || coOff % 64 || coOff + cout > ldo)
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  OpScratch sc;
-  sc.s = s;
+  OpScratch sc(s);
   TrainState T;
   OpRangeScope range;
   X3Path path;
@@ -2327,12 +2257,10 @@ int unet_op_upconv_fwd_train_x3(int device, const uint16_t* x, size_t xLo, int n
   }
   if (e == hipSuccess) e = range.arm();
   if (e == hipSuccess) e = run_train_upconv_x3(&T, wt, biasDev, cin, cout, x, xLo, n, hh, ww, y, yLo, ldo, coOff, s, &path);
-  const hipError_t es = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = es;
-  if (e == hipSuccess) e = range.read(rangeOut);
+  const int st = op_done(e, s, kOpMapCodes, &range, rangeOut);
   T.ones = T.zeros = nullptr;   // owned by sc
   path_to_ints(path, pathOut);
-  return op_status(e);
+  return st;
 }
 
 }  // extern "C"

@@ -1205,6 +1205,43 @@ bool run_upcat_x3(const DecOpX3& op, const uint16_t* zeros, const uint16_t* skip
   return true;
 }
 
+// First convolution on conv_first_x3.h: uint8 (N,H,W,3) frames (u8) or an fp32 NCHW image -> planes (N,H,W,op.cout) with
+// pixel stride ldo; op from build_conv_x3(first = true).  mean / stdv: the input normalisation, null = none
+hipError_t run_first_x3(const GemmOpX3& op, const void* input, bool u8, int n, int h, int w, uint16_t* out, size_t outLo,
+                        int ldo, const float* mean, const float* stdv, hipStream_t s) {
+  unet::ConvFirstX3Args fa;
+  fa.frames = input;
+  fa.wt = op.wt;
+  fa.scale = op.scale;
+  fa.shift = op.shift;
+  fa.out = out;
+  fa.outLo = outLo;
+  fa.N = n;
+  fa.H = h;
+  fa.W = w;
+  fa.Cout = op.cout;
+  fa.ldo = ldo;
+  fa.tilesX = (w + 31) / 32;
+  fa.tilesY = (h + 7) / 8;
+  fa.relu = op.relu;
+  fa.m0 = mean ? mean[0] : 0.f;
+  fa.m1 = mean ? mean[1] : 0.f;
+  fa.m2 = mean ? mean[2] : 0.f;
+  fa.s0 = stdv ? stdv[0] : 1.f;
+  fa.s1 = stdv ? stdv[1] : 1.f;
+  fa.s2 = stdv ? stdv[2] : 1.f;
+  fa.err = g_errWord;
+  const double px = (double)n * h * w;
+  prof_begin("conv3x3_first_f16x3", 2.0 * px * 27 * op.cout, px * (u8 ? 3 : 12) + 4.0 * px * op.cout, s);
+  const dim3 grid((unsigned)(fa.tilesX * fa.tilesY * n));
+  if (u8)
+    hipLaunchKernelGGL(unet::conv_first_x3_kernel<true>, grid, dim3(256), 0, s, fa);
+  else
+    hipLaunchKernelGGL(unet::conv_first_x3_kernel<false>, grid, dim3(256), 0, s, fa);
+  prof_end(s);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 struct X3Net {
@@ -1214,11 +1251,9 @@ struct X3Net {
   float* headW = nullptr;        // head weights with the last activation's scale divided out
   std::vector<GemmOpX3> enc, bott, up, dec;
   std::vector<DecOpX3> comp;     // per decoder step j: the composed up + dec[2 j] operator (conv_x3_dec.h), where built
-  char* ws = nullptr;
-  size_t wsBytes = 0;
+  GrowBuf ws;
   bool hasQ8 = false;            // the operators carry their fp8 cross-term fragments (f16q8 tier)
-  uint8_t* qbuf = nullptr;       // q plane of the layer input being consumed (f16q8 tier)
-  size_t qbufBytes = 0;
+  GrowBuf qbuf;                  // q plane of the layer input being consumed (f16q8 tier)
 };
 
 static void x3_free(unet_ctx* h) {
@@ -1226,8 +1261,8 @@ static void x3_free(unet_ctx* h) {
   for (auto* v : {&h->x3->enc, &h->x3->bott, &h->x3->up, &h->x3->dec})
     for (auto& op : *v) op.free_dev();
   for (auto& op : h->x3->comp) op.free_dev();
-  if (h->x3->ws) hipFree(h->x3->ws);
-  if (h->x3->qbuf) hipFree(h->x3->qbuf);
+  h->x3->ws.release();
+  h->x3->qbuf.release();
   if (h->x3->zeros) hipFree(h->x3->zeros);
   if (h->x3->ones) hipFree(h->x3->ones);
   if (h->x3->splitScratch) hipFree(h->x3->splitScratch);
@@ -1278,14 +1313,9 @@ int x3_build(unet_ctx* h) {
                   const ActScale* in, ActScale* out) -> int {
     const auto& w = P[prefix + "." + std::to_string(convIdx) + ".weight"];
     const std::string bn = prefix + "." + std::to_string(bnIdx) + ".";
-    const auto &g = P[bn + "weight"], &b = P[bn + "bias"], &m = P[bn + "running_mean"], &v = P[bn + "running_var"];
-    std::vector<float> sc(cout), sh(cout);
-    for (int i = 0; i < cout; ++i) {   // eval BatchNorm folded exactly as the fp32 tier does (fold_bn_and_build)
-      const float inv = 1.0f / std::sqrt(v[i] + kBnEps);
-      sc[i] = g[i] * inv;
-      sh[i] = b[i] - m[i] * sc[i];
-    }
-    *out = act_from_bn(g.data(), b.data(), cout);
+    std::vector<float> sc, sh;
+    fold_bn(P, bn, cout, sc, sh);
+    *out = act_from_bn(P[bn + "weight"].data(), P[bn + "bias"].data(), cout);
     return build_conv_x3(h->err, o, w.data(), cout, cin, sc.data(), sh.data(), 1, first, useAct ? in : nullptr,
                          useAct ? out : nullptr, withQ8);
   };
@@ -1325,14 +1355,8 @@ int x3_build(unet_ctx* h) {
     if ((rc = conv(X->dec[2 * j], pd, 0, 1, 2 * f, f, false, &cat, &tmp))) return rc;
     if (f % 64 == 0 && f <= 128) {
       // the same step composed (conv_x3_dec.h): x = the transposed convolution's input, scale `cur`
-      const std::string bn = pd + ".1.";
-      const auto &g = P[bn + "weight"], &b = P[bn + "bias"], &m = P[bn + "running_mean"], &v = P[bn + "running_var"];
-      std::vector<float> sc(f), sh(f);
-      for (int i = 0; i < f; ++i) {
-        const float inv = 1.0f / std::sqrt(v[i] + kBnEps);
-        sc[i] = g[i] * inv;
-        sh[i] = b[i] - m[i] * sc[i];
-      }
+      std::vector<float> sc, sh;
+      fold_bn(P, pd + ".1.", f, sc, sh);
       if ((rc = build_upcat_x3(h->err, X->comp[j], P[pu + ".weight"].data(), P[pu + ".bias"].data(), P[pd + ".0.weight"].data(),
                                f, sc.data(), sh.data(), 1, useAct ? &skip[l] : nullptr, useAct ? &cur : nullptr,
                                useAct ? &tmp : nullptr)))
@@ -1412,36 +1436,12 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
       const size_t cinMax = l < c.depth ? 2 * (size_t)c.features[l] : 2 * (size_t)c.features[c.depth - 1];
       need = std::max(need, px * cinMax * 2);
     }
-    if (need > X->qbufBytes) {
-      if (X->qbuf) {
-        HIPCHK(h->err, hipDeviceSynchronize());
-        hipFree(X->qbuf);
-        X->qbuf = nullptr;
-        X->qbufBytes = 0;
-      }
-      if (hipMalloc((void**)&X->qbuf, need) != hipSuccess) {
-        h->err = "f16q8 q-plane allocation of " + std::to_string(need) + " bytes failed";
-        return UNET_ERR_NOMEM;
-      }
-      X->qbufBytes = need;
-    }
-    qs = X->qbuf;
+    if ((rc = X->qbuf.reserve(h->err, need, "f16q8 q-plane"))) return rc;
+    qs = reinterpret_cast<uint8_t*>(X->qbuf.p);
   }
-  if (p.total > X->wsBytes) {
-    if (X->ws) {
-      HIPCHK(h->err, hipDeviceSynchronize());
-      hipFree(X->ws);
-      X->ws = nullptr;
-      X->wsBytes = 0;
-    }
-    if (hipMalloc((void**)&X->ws, p.total) != hipSuccess) {
-      h->err = "f16x3 workspace allocation of " + std::to_string(p.total) + " bytes failed";
-      return UNET_ERR_NOMEM;
-    }
-    X->wsBytes = p.total;
-  }
+  if ((rc = X->ws.reserve(h->err, p.total, "f16x3 workspace"))) return rc;
   LaunchScope scope(h);
-  auto U = [&](const WsTensor& t) { return reinterpret_cast<uint16_t*>(X->ws + t.off); };
+  auto U = [&](const WsTensor& t) { return reinterpret_cast<uint16_t*>(X->ws.p + t.off); };
   X3SplitK sk;
   sk.scratch = X->splitScratch;
   sk.floats = kSplitFloats;
@@ -1483,37 +1483,7 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
     const X3ConvIo conv2Io = io_of(p.tmpA, ch, cw, p.cat[l], 2 * f, 0);
     const bool conv2OnQ8 = lands_on_q8(X->enc[2 * l + 1], conv2Io, &fz);
     if (l == 0) {
-      unet::ConvFirstX3Args fa;
-      fa.frames = input;
-      fa.wt = X->enc[0].wt;
-      fa.scale = X->enc[0].scale;
-      fa.shift = X->enc[0].shift;
-      fa.out = U(p.tmpA);
-      fa.outLo = p.tmpA.elems;
-      fa.N = n;
-      fa.H = ch;
-      fa.W = cw;
-      fa.Cout = f;
-      fa.ldo = f;
-      fa.tilesX = (cw + 31) / 32;
-      fa.tilesY = (ch + 7) / 8;
-      fa.relu = 1;
-      fa.m0 = c.input_mean[0];
-      fa.m1 = c.input_mean[1];
-      fa.m2 = c.input_mean[2];
-      fa.s0 = c.input_std[0];
-      fa.s1 = c.input_std[1];
-      fa.s2 = c.input_std[2];
-      fa.err = g_errWord;
-      const double px = (double)npix;
-      prof_begin("conv3x3_first_f16x3", 2.0 * px * 27 * f, px * (u8 ? 3 : 12) + 4.0 * px * f, s);
-      const dim3 grid((unsigned)(fa.tilesX * fa.tilesY * n));
-      if (u8)
-        hipLaunchKernelGGL(unet::conv_first_x3_kernel<true>, grid, dim3(256), 0, s, fa);
-      else
-        hipLaunchKernelGGL(unet::conv_first_x3_kernel<false>, grid, dim3(256), 0, s, fa);
-      prof_end(s);
-      HIPCHK(h->err, hipGetLastError());
+      HIPCHK(h->err, run_first_x3(X->enc[0], input, u8, n, ch, cw, U(p.tmpA), p.tmpA.elems, f, c.input_mean, c.input_std, s));
     } else {
       // f16q8 tier: tmpA has one consumer, the block's second convolution; where that one runs on conv_q8_r512.h the
       // first writes tmpA's q plane in the lo plane's place (X3Q8Link) and no conversion pass is needed
@@ -1613,34 +1583,6 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
   return h->async_error();
 }
 
-// The plane-level test entry points (unet_op_*_x3_planes) watch the range with a word of their own: for the scope's
-// lifetime the calling thread's launches report into it instead of the per-device word of the other entry points
-struct OpRangeScope {
-  unsigned* dev = nullptr;
-  unsigned* prev = nullptr;
-  bool armed = false;
-  hipError_t arm() {
-    hipError_t e = hipMalloc((void**)&dev, 2 * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemset(dev, 0, 2 * sizeof(unsigned));
-    if (e != hipSuccess) return e;
-    prev = g_errWord;
-    g_errWord = dev;
-    armed = true;
-    return hipSuccess;
-  }
-  // after the stream has been synchronised: did a kernel of the call set word 1?
-  hipError_t read(int* rangeOut) {
-    unsigned host[2] = {0, 0};
-    const hipError_t e = hipMemcpy(host, dev, sizeof(host), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rangeOut) *rangeOut = host[1] != 0 ? 1 : 0;
-    return e;
-  }
-  ~OpRangeScope() {
-    if (armed) g_errWord = prev;
-    if (dev) hipFree(dev);
-  }
-};
-
 ActScale act_from_host(const float* act, int c) {
   ActScale a;
   a.act.assign(act, act + c);
@@ -1676,56 +1618,39 @@ int unet_op_conv3x3_x3(int device, const float* x, int n, int hh, int ww, int ci
   X3Force force;
   if (!x || !wHost || !scale || !shift || !y || cin % 64 || cout % 64 || cout > unet::X3Shape<32>::MAX_COUT ||
       !x3_decode_force(tileWidth, &force) || (yPool && (hh % 2 || ww % 2)))
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  GemmOpX3 op;
+  OpScratch sc(s);
+  OpGuard<GemmOpX3> g;
   const bool q8 = force.family == kX3Q8;
-  int rc = build_conv_x3(g_opErr, op, wHost, cout, cin, scale, shift, relu, false, nullptr, nullptr, q8);
+  const int rc = build_conv_x3(g_opErr, g.op, wHost, cout, cin, scale, shift, relu, false, nullptr, nullptr, q8);
+  if (rc) return rc;
   const size_t px = (size_t)n * hh * ww;
   const size_t ein = px * cin, eout = px * cout, epool = (px / 4) * cout;
   uint16_t *zeros = nullptr, *pin = nullptr, *pout = nullptr, *ppool = nullptr, *qsc = nullptr;
-  auto cleanup = [&]() {
-    op.free_dev();
-    for (uint16_t* q : {zeros, pin, pout, ppool, qsc})
-      if (q) hipFree(q);
-  };
-  if (!rc) {
-    hipError_t e = hipMalloc((void**)&zeros, 4096);
-    if (e == hipSuccess) e = hipMemset(zeros, 0, 4096);
-    if (e == hipSuccess) e = hipMalloc((void**)&pin, 2 * ein * 2);
-    if (e == hipSuccess) e = hipMalloc((void**)&pout, 2 * eout * 2);
-    if (e == hipSuccess && yPool) e = hipMalloc((void**)&ppool, 2 * epool * 2);
-    if (e == hipSuccess && q8) e = hipMalloc((void**)&qsc, ein * 2);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(unet::split_planes_kernel, dim3(grid_for(ein / 2)), dim3(256), 0, s, x, ein / 2,
-                         reinterpret_cast<uint32_t*>(pin), reinterpret_cast<uint32_t*>(pin + ein));
-      X3Fuse fz;
-      fz.pool = ppool;
-      fz.poolLo = epool;
-      X3ConvOpts o;
-      o.fuse = yPool ? &fz : nullptr;
-      o.forceTw = tileWidth;
-      o.qScratch = reinterpret_cast<uint8_t*>(qsc);
-      e = run_conv_x3(op, x3_from(zeros, pin, ein, n, hh, ww).to(pout, eout, cout), o, s);
-    }
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(unet::merge_planes_kernel, dim3(grid_for(eout / 2)), dim3(256), 0, s,
-                         reinterpret_cast<const uint32_t*>(pout), reinterpret_cast<const uint32_t*>(pout + eout), eout / 2, y);
-      if (yPool)
-        hipLaunchKernelGGL(unet::merge_planes_kernel, dim3(grid_for(epool / 2)), dim3(256), 0, s,
-                           reinterpret_cast<const uint32_t*>(ppool), reinterpret_cast<const uint32_t*>(ppool + epool),
-                           epool / 2, yPool);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-      g_opErr = hipGetErrorString(e);
-      rc = UNET_ERR_HIP;
-    }
+  hipError_t e = sc.zero_page(&zeros);
+  if (e == hipSuccess) e = sc.get(&pin, 2 * ein * sizeof(uint16_t));
+  if (e == hipSuccess) e = sc.get(&pout, 2 * eout * sizeof(uint16_t));
+  if (e == hipSuccess && yPool) e = sc.get(&ppool, 2 * epool * sizeof(uint16_t));
+  if (e == hipSuccess && q8) e = sc.get(&qsc, ein * sizeof(uint16_t));
+  if (e == hipSuccess) {
+    split_to_planes(x, ein, pin, s);
+    X3Fuse fz;
+    fz.pool = ppool;
+    fz.poolLo = epool;
+    X3ConvOpts o;
+    o.fuse = yPool ? &fz : nullptr;
+    o.forceTw = tileWidth;
+    o.qScratch = reinterpret_cast<uint8_t*>(qsc);
+    e = run_conv_x3(g.op, x3_from(zeros, pin, ein, n, hh, ww).to(pout, eout, cout), o, s);
   }
-  cleanup();
-  return rc;
+  if (e == hipSuccess) {
+    merge_from_planes(pout, eout, y, s);
+    if (yPool) merge_from_planes(ppool, epool, yPool, s);
+    e = hipGetLastError();
+  }
+  return op_done(e, s);
 }
 
 // Test entry point: the 64-channel 3x3 convolution with the 1x1 head fused into its epilogue (the network's last two
@@ -1738,47 +1663,32 @@ int unet_op_conv3x3_x3_head(int device, const float* x, int n, int hh, int ww, i
   X3Force force;
   if (!x || !wHost || !scale || !shift || !headW || !logits || cin % 64 || !x3_decode_force(tileWidth, &force) ||
       !(force.family == 0 || force.family == kX3Ws || (force.family == kX3T448 && force.waves != 4)))
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  GemmOpX3 op;
-  int rc = build_conv_x3(g_opErr, op, wHost, 64, cin, scale, shift, relu, false, nullptr, nullptr, false);
+  OpScratch sc(s);
+  OpGuard<GemmOpX3> g;
+  const int rc = build_conv_x3(g_opErr, g.op, wHost, 64, cin, scale, shift, relu, false, nullptr, nullptr, false);
+  if (rc) return rc;
   const size_t px = (size_t)n * hh * ww, ein = px * cin;
   uint16_t *zeros = nullptr, *pin = nullptr;
   float* hwDev = nullptr;
-  auto cleanup = [&]() {
-    op.free_dev();
-    if (zeros) hipFree(zeros);
-    if (pin) hipFree(pin);
-    if (hwDev) hipFree(hwDev);
-  };
-  if (!rc) {
-    hipError_t e = hipMalloc((void**)&zeros, 4096);
-    if (e == hipSuccess) e = hipMemset(zeros, 0, 4096);
-    if (e == hipSuccess) e = hipMalloc((void**)&pin, 2 * ein * 2);
-    if (e == hipSuccess) e = hipMalloc((void**)&hwDev, 64 * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(hwDev, headW, 64 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(unet::split_planes_kernel, dim3(grid_for(ein / 2)), dim3(256), 0, s, x, ein / 2,
-                         reinterpret_cast<uint32_t*>(pin), reinterpret_cast<uint32_t*>(pin + ein));
-      X3Fuse fz;
-      fz.headW = hwDev;
-      fz.headB = headB;
-      fz.headThr = 0.f;
-      fz.logits = logits;
-      X3ConvOpts o;
-      o.fuse = &fz;
-      o.forceTw = tileWidth;
-      e = run_conv_x3(op, x3_from(zeros, pin, ein, n, hh, ww).to(nullptr, 0, 64), o, s);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-      g_opErr = hipGetErrorString(e);
-      rc = UNET_ERR_HIP;
-    }
+  hipError_t e = sc.zero_page(&zeros);
+  if (e == hipSuccess) e = sc.get(&pin, 2 * ein * sizeof(uint16_t));
+  if (e == hipSuccess) e = sc.upload(&hwDev, headW, 64);
+  if (e == hipSuccess) {
+    split_to_planes(x, ein, pin, s);
+    X3Fuse fz;
+    fz.headW = hwDev;
+    fz.headB = headB;
+    fz.headThr = 0.f;
+    fz.logits = logits;
+    X3ConvOpts o;
+    o.fuse = &fz;
+    o.forceTw = tileWidth;
+    e = run_conv_x3(g.op, x3_from(zeros, pin, ein, n, hh, ww).to(nullptr, 0, 64), o, s);
   }
-  cleanup();
-  return rc;
+  return op_done(e, s);
 }
 
 // Test hook (host arithmetic only, no device): the power-of-two activation scale the f16x3 tier picks for a BatchNorm
@@ -1792,51 +1702,36 @@ int unet_op_upcat_conv3x3_x3(int device, const float* skip, const float* x, int 
                              const float* bt, const float* w3, const float* scale, const float* shift, int relu, float* y,
                              void* stream) {
   if (!skip || !x || !wt || !bt || !w3 || !scale || !shift || !y || n < 1 || f % 64 || f > 128 || ww % 28 || hh % 2 || hh < 2)
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  DecOpX3 op;
-  int rc = build_upcat_x3(g_opErr, op, wt, bt, w3, f, scale, shift, relu, nullptr, nullptr, nullptr);
+  OpScratch sc(s);
+  OpGuard<DecOpX3> g;
+  const int rc = build_upcat_x3(g_opErr, g.op, wt, bt, w3, f, scale, shift, relu, nullptr, nullptr, nullptr);
+  if (rc) return rc;
   const size_t px = (size_t)n * hh * ww;
   const size_t es = px * f, ex = px / 4 * 2 * f, eo = px * f;
   uint16_t *zeros = nullptr, *ps = nullptr, *pxl = nullptr, *po = nullptr;
-  auto cleanup = [&]() {
-    op.free_dev();
-    for (uint16_t* q : {zeros, ps, pxl, po})
-      if (q) hipFree(q);
-  };
-  if (!rc) {
-    hipError_t e = hipMalloc((void**)&zeros, 4096);
-    if (e == hipSuccess) e = hipMemset(zeros, 0, 4096);
-    if (e == hipSuccess) e = hipMalloc((void**)&ps, 2 * es * 2);
-    if (e == hipSuccess) e = hipMalloc((void**)&pxl, 2 * ex * 2);
-    if (e == hipSuccess) e = hipMalloc((void**)&po, 2 * eo * 2);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(unet::split_planes_kernel, dim3(grid_for(es / 2)), dim3(256), 0, s, skip, es / 2,
-                         reinterpret_cast<uint32_t*>(ps), reinterpret_cast<uint32_t*>(ps + es));
-      hipLaunchKernelGGL(unet::split_planes_kernel, dim3(grid_for(ex / 2)), dim3(256), 0, s, x, ex / 2,
-                         reinterpret_cast<uint32_t*>(pxl), reinterpret_cast<uint32_t*>(pxl + ex));
-      if (!run_upcat_x3(op, zeros, ps, es, f, pxl, ex, n, hh, ww, po, eo, f, true, s, &e) && e == hipSuccess)
-        e = hipErrorInvalidValue;
-    }
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(unet::merge_planes_kernel, dim3(grid_for(eo / 2)), dim3(256), 0, s,
-                         reinterpret_cast<const uint32_t*>(po), reinterpret_cast<const uint32_t*>(po + eo), eo / 2, y);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-      g_opErr = hipGetErrorString(e);
-      rc = UNET_ERR_HIP;
-    }
+  hipError_t e = sc.zero_page(&zeros);
+  if (e == hipSuccess) e = sc.get(&ps, 2 * es * sizeof(uint16_t));
+  if (e == hipSuccess) e = sc.get(&pxl, 2 * ex * sizeof(uint16_t));
+  if (e == hipSuccess) e = sc.get(&po, 2 * eo * sizeof(uint16_t));
+  if (e == hipSuccess) {
+    split_to_planes(skip, es, ps, s);
+    split_to_planes(x, ex, pxl, s);
+    if (!run_upcat_x3(g.op, zeros, ps, es, f, pxl, ex, n, hh, ww, po, eo, f, true, s, &e) && e == hipSuccess)
+      e = hipErrorInvalidValue;
   }
-  cleanup();
-  return rc;
+  if (e == hipSuccess) {
+    merge_from_planes(po, eo, y, s);
+    e = hipGetLastError();
+  }
+  return op_done(e, s);
 }
 
 // Test hook (host arithmetic only, no device): the float64 composition the operator above is built from (compose_upcat)
 int unet_host_compose_upcat(const float* wt, const float* bt, const float* w3, int f, double* wp, double* bias) {
-  if (!wt || !bt || !w3 || !wp || !bias || f < 1) return UNET_ERR_INVALID_ARG;
+  if (!wt || !bt || !w3 || !wp || !bias || f < 1) return op_bad_args();
   std::vector<double> a, b;
   compose_upcat(wt, bt, w3, f, a, b);
   std::copy(a.begin(), a.end(), wp);
@@ -1847,12 +1742,12 @@ int unet_host_compose_upcat(const float* wt, const float* bt, const float* w3, i
 // Test hooks (host arithmetic only, no device): the plan the dispatch makes for a query given as integers, the switches
 // included (include/unet_hip.h lists both layouts)
 int unet_host_plan_conv3x3_x3(const int* query, int nQuery, int* planOut, int nPlan, char* labelOut, int labelCap) {
-  if (!query || nQuery != 22 || !planOut || nPlan != 24 || (labelOut && labelCap < 48)) return UNET_ERR_INVALID_ARG;
+  if (!query || nQuery != 22 || !planOut || nPlan != 24 || (labelOut && labelCap < 48)) return op_bad_args();
   X3ConvQuery q;
   q.n = query[0], q.h = query[1], q.w = query[2], q.cin = query[3], q.cout = query[4], q.epi = query[5];
   if (q.n < 1 || q.h < 1 || q.w < 1 || q.cin < 32 || q.cout < 64 || q.epi < 0 || q.epi > 3 || query[9] < 0 ||
       !x3_decode_force(query[6], &q.force))
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   q.coOff = query[7], q.splitScratch = query[8] != 0, q.splitFloats = (size_t)query[9];
   q.qScratch = query[10] != 0, q.wq = query[11] != 0;
   q.inIsQ = query[12] != 0, q.wantOutQ = query[13] != 0, q.poolSrcQ = query[14] != 0, q.poolDstQ = query[15] != 0;
@@ -1874,9 +1769,9 @@ int unet_host_plan_conv3x3_x3(const int* query, int nQuery, int* planOut, int nP
 }
 
 int unet_host_plan_upconv2x2_x3(const int* query, int nQuery, int* planOut, int nPlan, char* labelOut, int labelCap) {
-  if (!query || nQuery != 9 || !planOut || nPlan != 16 || (labelOut && labelCap < 48)) return UNET_ERR_INVALID_ARG;
+  if (!query || nQuery != 9 || !planOut || nPlan != 16 || (labelOut && labelCap < 48)) return op_bad_args();
   X3UpconvQuery q;
-  if (query[0] < 1 || query[1] < 1 || query[2] < 1 || query[3] < 64 || query[4] < 64) return UNET_ERR_INVALID_ARG;
+  if (query[0] < 1 || query[1] < 1 || query[2] < 1 || query[3] < 64 || query[4] < 64) return op_bad_args();
   q.npix = (long)query[0] * query[1] * query[2], q.w = query[2], q.cin = query[3], q.cout = query[4];
   q.coOff = query[5], q.wantOutQ = query[6] != 0;
   q.mode = query[7] < 0 ? -1 : (query[7] > 1 ? 1 : query[7]);
@@ -1911,39 +1806,28 @@ int unet_set_x3_upconv_r512(int mode) {
 int unet_op_upconv2x2_x3(int device, const float* x, int n, int hh, int ww, int cin, const float* wHost,
                          const float* bias, int cout, float* y, void* stream) {
   if (!x || !wHost || !bias || !y || cin % 64 || cout % 64 || cout > unet::UpconvX3Shape::MAX_COUT)
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  GemmOpX3 op;
-  int rc = build_upconv_x3(g_opErr, op, wHost, cin, cout, bias);
+  OpScratch sc(s);
+  OpGuard<GemmOpX3> g;
+  const int rc = build_upconv_x3(g_opErr, g.op, wHost, cin, cout, bias);
+  if (rc) return rc;
   const size_t px = (size_t)n * hh * ww;
   const size_t ein = px * cin, eout = 4 * px * cout;
   uint16_t *zeros = nullptr, *pin = nullptr, *pout = nullptr;
-  if (!rc) {
-    hipError_t e = hipMalloc((void**)&zeros, 4096);
-    if (e == hipSuccess) e = hipMemset(zeros, 0, 4096);
-    if (e == hipSuccess) e = hipMalloc((void**)&pin, 2 * ein * 2);
-    if (e == hipSuccess) e = hipMalloc((void**)&pout, 2 * eout * 2);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(unet::split_planes_kernel, dim3(grid_for(ein / 2)), dim3(256), 0, s, x, ein / 2,
-                         reinterpret_cast<uint32_t*>(pin), reinterpret_cast<uint32_t*>(pin + ein));
-      e = run_upconv_x3(op, x3_from(zeros, pin, ein, n, hh, ww).to(pout, eout, cout), s);
-    }
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(unet::merge_planes_kernel, dim3(grid_for(eout / 2)), dim3(256), 0, s,
-                         reinterpret_cast<const uint32_t*>(pout), reinterpret_cast<const uint32_t*>(pout + eout), eout / 2, y);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-      g_opErr = hipGetErrorString(e);
-      rc = UNET_ERR_HIP;
-    }
+  hipError_t e = sc.zero_page(&zeros);
+  if (e == hipSuccess) e = sc.get(&pin, 2 * ein * sizeof(uint16_t));
+  if (e == hipSuccess) e = sc.get(&pout, 2 * eout * sizeof(uint16_t));
+  if (e == hipSuccess) {
+    split_to_planes(x, ein, pin, s);
+    e = run_upconv_x3(g.op, x3_from(zeros, pin, ein, n, hh, ww).to(pout, eout, cout), s);
   }
-  op.free_dev();
-  for (uint16_t* q : {zeros, pin, pout})
-    if (q) hipFree(q);
-  return rc;
+  if (e == hipSuccess) {
+    merge_from_planes(pout, eout, y, s);
+    e = hipGetLastError();
+  }
+  return op_done(e, s);
 }
 
 // ---- plane-level test entry points: caller-owned fp16 hi / lo planes in and out, the network's own packing, dispatch
@@ -1960,70 +1844,58 @@ int unet_op_conv3x3_x3_planes(int device, const uint16_t* x, size_t xLo, int n, 
       cout > unet::X3Shape<32>::MAX_COUT || !x3_decode_force(tileWidth, &force) || force.family == kX3Q8 ||
       xLo % 8 || yLo % 8 || poolLo % 8 || ldo % 64 || coOff < 0 || coOff % 64 || coOff + cout > ldo ||
       (pool && (headW || hh % 2 || ww % 2)) || (headW ? (cout != 64 || !(logits || probs || mask)) : !y))
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  GemmOpX3 op;
+  path_to_ints(X3Path(), pathOut);
+  OpScratch sc(s);
+  OpGuard<GemmOpX3> g;
   ActScale ia, oa;
   if (inAct) ia = act_from_host(inAct, cin);
   if (outAct) oa = act_from_host(outAct, cout);
-  int rc = build_conv_x3(g_opErr, op, wHost, cout, cin, scale, shift, relu, false, inAct ? &ia : nullptr,
-                         outAct ? &oa : nullptr, false);
+  const int rc = build_conv_x3(g_opErr, g.op, wHost, cout, cin, scale, shift, relu, false, inAct ? &ia : nullptr,
+                               outAct ? &oa : nullptr, false);
+  if (rc) return rc;
   uint16_t* zeros = nullptr;
   float *ones = nullptr, *scratch = nullptr, *hwDev = nullptr;
   OpRangeScope range;
   X3Path path;
-  if (!rc) {
-    hipError_t e = hipMalloc((void**)&zeros, 4096);
-    if (e == hipSuccess) e = hipMemset(zeros, 0, 4096);
-    if (e == hipSuccess && splitK) {   // as x3_build / forward_x3 set the X3SplitK up
-      const std::vector<float> one(1024, 1.f);
-      e = hipMalloc((void**)&ones, 4096);
-      if (e == hipSuccess) e = hipMemcpy(ones, one.data(), 4096, hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMalloc((void**)&scratch, kSplitFloats * sizeof(float));
-    }
-    if (e == hipSuccess && headW) {
-      e = hipMalloc((void**)&hwDev, 64 * sizeof(float));
-      if (e == hipSuccess) e = hipMemcpy(hwDev, headW, 64 * sizeof(float), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = range.arm();
-    if (e == hipSuccess) {
-      X3Fuse fz;
-      if (pool) {
-        fz.pool = pool;
-        fz.poolLo = poolLo;
-      } else if (headW) {
-        fz.headW = hwDev;
-        fz.headB = headB;
-        fz.headThr = headThr;
-        fz.logits = logits;
-        fz.probs = probs;
-        fz.mask = mask;
-      }
-      X3SplitK sk;
-      sk.scratch = scratch;
-      sk.floats = kSplitFloats;
-      sk.ones = ones;
-      sk.zerosF = reinterpret_cast<const float*>(zeros);
-      X3ConvOpts o;
-      o.fuse = (pool || headW) ? &fz : nullptr;
-      o.forceTw = tileWidth;
-      o.splitK = splitK ? &sk : nullptr;
-      o.path = &path;
-      e = run_conv_x3(op, x3_from(zeros, x, xLo, n, hh, ww).to(y, yLo, ldo, coOff), o, s);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = range.read(rangeOut);
-    if (e != hipSuccess) {
-      g_opErr = hipGetErrorString(e);
-      rc = UNET_ERR_HIP;
-    }
+  hipError_t e = sc.zero_page(&zeros);
+  if (e == hipSuccess && splitK) {   // as x3_build / forward_x3 set the X3SplitK up
+    const std::vector<float> one(1024, 1.f);
+    e = sc.upload(&ones, one.data(), one.size());
+    if (e == hipSuccess) e = sc.get(&scratch, kSplitFloats * sizeof(float));
   }
+  if (e == hipSuccess && headW) e = sc.upload(&hwDev, headW, 64);
+  if (e == hipSuccess) e = range.arm();
+  if (e == hipSuccess) {
+    X3Fuse fz;
+    if (pool) {
+      fz.pool = pool;
+      fz.poolLo = poolLo;
+    } else if (headW) {
+      fz.headW = hwDev;
+      fz.headB = headB;
+      fz.headThr = headThr;
+      fz.logits = logits;
+      fz.probs = probs;
+      fz.mask = mask;
+    }
+    X3SplitK sk;
+    sk.scratch = scratch;
+    sk.floats = kSplitFloats;
+    sk.ones = ones;
+    sk.zerosF = reinterpret_cast<const float*>(zeros);
+    X3ConvOpts o;
+    o.fuse = (pool || headW) ? &fz : nullptr;
+    o.forceTw = tileWidth;
+    o.splitK = splitK ? &sk : nullptr;
+    o.path = &path;
+    e = run_conv_x3(g.op, x3_from(zeros, x, xLo, n, hh, ww).to(y, yLo, ldo, coOff), o, s);
+  }
+  const int st = op_done(e, s, 0, &range, rangeOut);
   path_to_ints(path, pathOut);
-  op.free_dev();
-  for (void* q : {(void*)zeros, (void*)ones, (void*)scratch, (void*)hwDev})
-    if (q) hipFree(q);
-  return rc;
+  return st;
 }
 
 int unet_op_upconv2x2_x3_planes(int device, const uint16_t* x, size_t xLo, int n, int hh, int ww, int cin, const float* wHost,
@@ -2032,32 +1904,25 @@ int unet_op_upconv2x2_x3_planes(int device, const uint16_t* x, size_t xLo, int n
   if (ldo == 0) ldo = cout;
   if (!x || !wHost || !bias || !y || n < 1 || hh < 1 || ww < 1 || cin < 64 || cin % 64 || cout < 64 || cout % 64 ||
       cout > unet::UpconvX3Shape::MAX_COUT || xLo % 8 || yLo % 8 || ldo % 64 || coOff < 0 || coOff % 64 || coOff + cout > ldo)
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  GemmOpX3 op;
+  path_to_ints(X3Path(), pathOut);
+  OpScratch sc(s);
+  OpGuard<GemmOpX3> g;
   ActScale ia;
   if (inAct) ia = act_from_host(inAct, cin);
-  int rc = build_upconv_x3(g_opErr, op, wHost, cin, cout, bias, inAct ? &ia : nullptr, nullptr);
+  const int rc = build_upconv_x3(g_opErr, g.op, wHost, cin, cout, bias, inAct ? &ia : nullptr, nullptr);
+  if (rc) return rc;
   uint16_t* zeros = nullptr;
   OpRangeScope range;
   X3Path path;
-  if (!rc) {
-    hipError_t e = hipMalloc((void**)&zeros, 4096);
-    if (e == hipSuccess) e = hipMemset(zeros, 0, 4096);
-    if (e == hipSuccess) e = range.arm();
-    if (e == hipSuccess) e = run_upconv_x3(op, x3_from(zeros, x, xLo, n, hh, ww).to(y, yLo, ldo, coOff), s, nullptr, &path);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = range.read(rangeOut);
-    if (e != hipSuccess) {
-      g_opErr = hipGetErrorString(e);
-      rc = UNET_ERR_HIP;
-    }
-  }
+  hipError_t e = sc.zero_page(&zeros);
+  if (e == hipSuccess) e = range.arm();
+  if (e == hipSuccess) e = run_upconv_x3(g.op, x3_from(zeros, x, xLo, n, hh, ww).to(y, yLo, ldo, coOff), s, nullptr, &path);
+  const int st = op_done(e, s, 0, &range, rangeOut);
   path_to_ints(path, pathOut);
-  op.free_dev();
-  if (zeros) hipFree(zeros);
-  return rc;
+  return st;
 }
 
 int unet_op_conv_first_x3_planes(int device, const void* input, int isU8, int n, int hh, int ww, const float* wHost,
@@ -2067,108 +1932,63 @@ int unet_op_conv_first_x3_planes(int device, const void* input, int isU8, int n,
   if (ldo == 0) ldo = cout;
   if (!input || !wHost || !scale || !shift || !y || (isU8 && (!mean || !stdv)) || n < 1 || hh < 1 || ww < 1 || cout < 64 ||
       cout % 64 || yLo % 8 || ldo % 64 || cout > ldo)
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
-  GemmOpX3 op;
+  OpGuard<GemmOpX3> g;
   ActScale oa;
   if (outAct) oa = act_from_host(outAct, cout);
-  int rc = build_conv_x3(g_opErr, op, wHost, cout, 3, scale, shift, relu, true, nullptr, outAct ? &oa : nullptr, false);
+  const int rc = build_conv_x3(g_opErr, g.op, wHost, cout, 3, scale, shift, relu, true, nullptr, outAct ? &oa : nullptr, false);
+  if (rc) return rc;
   OpRangeScope range;
-  if (!rc) {
-    hipError_t e = range.arm();
-    if (e == hipSuccess) {
-      unet::ConvFirstX3Args fa;   // as forward_x3 fills it
-      fa.frames = input;
-      fa.wt = op.wt;
-      fa.scale = op.scale;
-      fa.shift = op.shift;
-      fa.out = y;
-      fa.outLo = yLo;
-      fa.N = n;
-      fa.H = hh;
-      fa.W = ww;
-      fa.Cout = cout;
-      fa.ldo = ldo;
-      fa.tilesX = (ww + 31) / 32;
-      fa.tilesY = (hh + 7) / 8;
-      fa.relu = relu;
-      fa.m0 = mean ? mean[0] : 0.f;
-      fa.m1 = mean ? mean[1] : 0.f;
-      fa.m2 = mean ? mean[2] : 0.f;
-      fa.s0 = stdv ? stdv[0] : 1.f;
-      fa.s1 = stdv ? stdv[1] : 1.f;
-      fa.s2 = stdv ? stdv[2] : 1.f;
-      fa.err = g_errWord;
-      const dim3 grid((unsigned)(fa.tilesX * fa.tilesY * n));
-      if (isU8)
-        hipLaunchKernelGGL(unet::conv_first_x3_kernel<true>, grid, dim3(256), 0, s, fa);
-      else
-        hipLaunchKernelGGL(unet::conv_first_x3_kernel<false>, grid, dim3(256), 0, s, fa);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = range.read(rangeOut);
-    if (e != hipSuccess) {
-      g_opErr = hipGetErrorString(e);
-      rc = UNET_ERR_HIP;
-    }
-  }
-  op.free_dev();
-  return rc;
+  hipError_t e = range.arm();
+  if (e == hipSuccess) e = run_first_x3(g.op, input, isU8 != 0, n, hh, ww, y, yLo, ldo, mean, stdv, s);
+  return op_done(e, s, 0, &range, rangeOut);
 }
 
 int unet_op_maxpool2x2_x3_planes(int device, const uint16_t* x, size_t xLo, int n, int hh, int ww, int c, int ldi, uint16_t* y,
                                  size_t yLo, void* stream) {
   if (ldi == 0) ldi = c;
   if (!x || !y || n < 1 || hh < 2 || ww < 2 || hh % 2 || ww % 2 || c < 2 || c % 2 || ldi % 2 || c > ldi || xLo % 2 || yLo % 2)
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   const size_t P = (size_t)n * hh * ww;
   hipLaunchKernelGGL(unet::maxpool2x2_planes_kernel, dim3(grid_for(P / 4 * (c / 2))), dim3(256), 0, s,
                      reinterpret_cast<const uint32_t*>(x), xLo / 2, n, hh, ww, c, ldi, reinterpret_cast<uint32_t*>(y), yLo / 2);
-  HIPCHK(g_opErr, hipGetLastError());
-  HIPCHK(g_opErr, hipStreamSynchronize(s));
-  return UNET_OK;
+  return op_done(hipGetLastError(), s);
 }
 
 int unet_op_head1x1_x3_planes(int device, const uint16_t* x, size_t xLo, int n, int hh, int ww, int c, const float* wHost,
                               float bias, float thr, float* logits, float* probs, uint8_t* mask, void* stream) {
   if (!x || !wHost || !(logits || probs || mask) || n < 1 || hh < 1 || ww < 1 || c < 2 || c % 2 || xLo % 2)
-    return UNET_ERR_INVALID_ARG;
+    return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
+  OpScratch sc(s);
   float* wd = nullptr;
-  HIPCHK(g_opErr, hipMalloc((void**)&wd, c * sizeof(float)));
-  hipError_t e = hipMemcpy(wd, wHost, c * sizeof(float), hipMemcpyHostToDevice);
+  hipError_t e = sc.upload(&wd, wHost, (size_t)c);
   if (e == hipSuccess) {
     const size_t npix = (size_t)n * hh * ww;
     hipLaunchKernelGGL(unet::head1x1_planes_kernel, dim3(grid_for(npix)), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(x),
                        xLo / 2, wd, bias, npix, c, logits, probs, mask, thr);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  hipFree(wd);
-  HIPCHK(g_opErr, e);
-  return UNET_OK;
+  return op_done(e, s);
 }
 
 int unet_op_split_planes_x3(int device, const float* x, size_t count, uint16_t* y, size_t yLo, int* rangeOut, void* stream) {
-  if (!x || !y || count < 2 || count % 2 || yLo % 2) return UNET_ERR_INVALID_ARG;
+  if (!x || !y || count < 2 || count % 2 || yLo % 2) return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   OpRangeScope range;
   hipError_t e = range.arm();
-  if (e == hipSuccess) {
+  if (e == hipSuccess) {   // (not split_to_planes: lo plane where the caller says, range watched)
     hipLaunchKernelGGL(unet::split_planes_kernel, dim3(grid_for(count / 2)), dim3(256), 0, s, x, count / 2,
                        reinterpret_cast<uint32_t*>(y), reinterpret_cast<uint32_t*>(y + yLo), g_errWord);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = range.read(rangeOut);
-  HIPCHK(g_opErr, e);
-  return UNET_OK;
+  return op_done(e, s, 0, &range, rangeOut);
 }
 
 }  // extern "C"
