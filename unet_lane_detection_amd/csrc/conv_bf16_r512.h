@@ -12,7 +12,8 @@
 //    conv_bf16_ws.h ([coTile(64)][chunk(32)][tap][cs][lane][8]), bf16 NHWC in and out: results bit-identical to
 //    both (tests/test_bf16_gpu.py).
 //
-// Needs Cin % 32 == 0, Cout % (256 / WPX) == 0, W % TWX == 0.
+// Block remap, geometry, scale / shift fetch and buffer loads: wave_tile.h.  Needs Cin % 32 == 0,
+// Cout % (256 / WPX) == 0, W % TWX == 0.
 #pragma once
 #include "conv_bf16_ws.h"
 #include "conv_x3_r512.h"
@@ -61,19 +62,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int wp = wave / WCO, wc = wave - wp * WCO;
   const int li = lane & 15, lq = lane >> 4;
   const int G = gridDim.x;
-  const int lb = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int lb = x3_logical_block(G);
   const int numWork = a.pixTiles * a.coTiles;
   if (lb >= numWork) return;
   const unsigned ldsBase = lds_address(smemv);
   const char* lds = reinterpret_cast<const char*>(smemv);
 
   // ---- LDS-DMA: pieces q = wave + 4j of the plane ----
-  int hrc[NJ];
-  unsigned soff[NJ];
+  int hrc[NJ];         // halo row << 8 | halo column of this lane's 16 bytes
+  unsigned soff[NJ];   // byte offset of its source from the halo's top-left pixel (row y0 - 1, column x0 - 1), chunk 0
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     int q = wave + j * 4;
-    q = q < NQX ? q : NQX - 1;
+    q = q < NQX ? q : NQX - 1;   // the last round only exists for some waves: duplicates rewrite the same bytes
     const int v = q * 64 + lane;
     const int qpix = v >> 2;
     const int part = (v & 3) ^ (((qpix >> 2) & 1) << 1);
@@ -83,31 +84,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
   const char* zp = reinterpret_cast<const char*>(a.zeros) + (lane & 3) * 16;
 
-  struct Geo {
-    const char* tb;
-    int hrMin, hrSpan, hcMin, hcSpan;
-    int n, y0, x0, cg;
-  };
-  auto geo_of = [&](int w) __attribute__((always_inline)) {
-    Geo g;
-    const int cInG = w % a.coGroup;
-    const int rest = w / a.coGroup;
-    const int tile = rest % a.pixTiles;
-    g.cg = (rest / a.pixTiles) * a.coGroup + cInG;
-    const int rowTile = tile / a.tilesX;
-    g.x0 = (tile - rowTile * a.tilesX) * TWX;
-    g.n = rowTile / a.tilesY;
-    g.y0 = (rowTile - g.n * a.tilesY) * TH;
-    const int hrMax = a.H - g.y0 < SX::HH2 - 1 ? a.H - g.y0 : SX::HH2 - 1;
-    const int hcMax = a.W - g.x0 < SX::HW2 - 1 ? a.W - g.x0 : SX::HW2 - 1;
-    g.hrMin = g.y0 == 0 ? 1 : 0;
-    g.hcMin = g.x0 == 0 ? 1 : 0;
-    g.hrSpan = hrMax - g.hrMin;
-    g.hcSpan = hcMax - g.hcMin;
-    g.tb = reinterpret_cast<const char*>(a.in) +
-           ((((long)g.n * a.H + g.y0 - 1) * a.W + g.x0 - 1) * (long)a.Cin) * 2;
-    return g;
-  };
+  using Geo = X3Geo;
+  auto geo_of = [&](int w) __attribute__((always_inline)) { return x3_geo_of<SX>(a, w); };
   auto issue_piece = [&](const Geo& g, int kc, int j, int buf) __attribute__((always_inline)) {
     int q = wave + j * 4;
     q = q < NQX ? q : NQX - 1;
@@ -133,16 +111,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
   }
 
-  const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(a.wt), 0, (a.Cout / 64) * a.nChunks * (9 * 4 * 1024), 0x00020000);
+  const __amdgpu_buffer_rsrc_t wrsrc = x3_buffer_of(a.wt, (a.Cout / 64) * a.nChunks * (9 * 4 * 1024));
   const int laneW = lane * 16;
   auto w_block = [&](int cg, int kc) __attribute__((always_inline)) -> int {
     return ((cg * WCO + wc) * a.nChunks + kc) * (9 * 4 * 1024);
   };
   auto w_load = [&](int blk, int tap, int cs) __attribute__((always_inline)) -> f32x4 {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, laneW + cs * 1024, blk + tap * 4096, 0);
-    return __builtin_bit_cast(f32x4, v);
+    return x3_buffer_load16(wrsrc, laneW + cs * 1024, blk + tap * 4096);
   };
 
   if (tid < 4)
@@ -174,12 +149,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       for (int cs = 0; cs < 4; ++cs) acc[f][cs] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int cbase = (gCur.cg * WCO + wc) * 64 + lq * 16;
     f32x4 sc[4], sh[4];
-#pragma unroll
-    for (int cs = 0; cs < 4; ++cs) {
-      sc[cs] = *reinterpret_cast<const f32x4*>(a.scale + cbase + cs * 4);
-      sh[cs] = *reinterpret_cast<const f32x4*>(a.shift + cbase + cs * 4);
-      asm volatile("" : "+v"(sc[cs]), "+v"(sh[cs]));
-    }
+    x3_scale_shift<true>(a.scale, a.shift, cbase, sc, sh);
 
     unsigned keep = 0xFFFFFFFFu;
     if (FLAT) {

@@ -14,8 +14,9 @@
 //
 // Data: the hi plane is the f16x3 tier's; the lo plane's place (same offset, same 2 bytes per element) is taken by
 // the "q plane": per pixel and 32-channel block 64 bytes = fp8(x_hi / 8) of the 32 channels, then fp8(256 x_lo)
-// (planes_to_q8_kernel below, or a producer's epilogue).  Geometry, LDS-DMA staging, tiles, FLAT instances and the
-// epilogue are conv_x3_r512.h's (read that header first); what differs:
+// (planes_to_q8_kernel below, or a producer's epilogue).  The structure is conv_x3_r512.h's (read that header first; the
+// shared pieces are in wave_tile.h, the rest is repeated here because helpers changed its register allocation); what is
+// this kernel's own:
 //  * the q plane is staged with its own bank swizzle (16-byte part ^ bit 2 of the pixel position): a lane reads 32
 //    contiguous bytes of a pixel as two ds_read_b128, conflict free at the same pitches (tools/lds_conflicts.py --q8);
 //  * a chunk is 5 steps (tap pairs (0,0)+(1,0), (0,1)+(1,1), (0,2)+(1,2), (2,0)+(2,1), (2,2) alone) of 14 fragments;
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lq = lane >> 4;
   const int G = gridDim.x;
-  const int lb = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int lb = x3_logical_block(G);
   const int numWork = a.pixTiles * a.coTiles;   // coTiles: groups of 256 output channels
   if (lb >= numWork) return;
   const unsigned ldsBase = lds_address(smemv);
@@ -219,7 +220,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     int q = wave + j * 4;
-    q = q < NQX ? q : NQX - 1;
+    q = q < NQX ? q : NQX - 1;   // the last round only exists for some waves: duplicates rewrite the same bytes
     const int v = q * 64 + lane;
     const int qpix = v >> 2;
     const int part = (v & 3) ^ (((qpix >> 2) & 1) << 1);
@@ -231,31 +232,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const char* zp = reinterpret_cast<const char*>(a.zeros) + (lane & 3) * 16;
   const size_t inLoB = a.inLo * 2;
 
-  struct Geo {
-    const char* tb;
-    int hrMin, hrSpan, hcMin, hcSpan;
-    int n, y0, x0, cg;
-  };
-  auto geo_of = [&](int w) __attribute__((always_inline)) {
-    Geo g;
-    const int cInG = w % a.coGroup;
-    const int rest = w / a.coGroup;
-    const int tile = rest % a.pixTiles;
-    g.cg = (rest / a.pixTiles) * a.coGroup + cInG;
-    const int rowTile = tile / a.tilesX;
-    g.x0 = (tile - rowTile * a.tilesX) * TWX;
-    g.n = rowTile / a.tilesY;
-    g.y0 = (rowTile - g.n * a.tilesY) * TH;
-    const int hrMax = a.H - g.y0 < S::HH2 - 1 ? a.H - g.y0 : S::HH2 - 1;
-    const int hcMax = a.W - g.x0 < S::HW2 - 1 ? a.W - g.x0 : S::HW2 - 1;
-    g.hrMin = g.y0 == 0 ? 1 : 0;
-    g.hcMin = g.x0 == 0 ? 1 : 0;
-    g.hrSpan = hrMax - g.hrMin;
-    g.hcSpan = hcMax - g.hcMin;
-    g.tb = reinterpret_cast<const char*>(a.in) +
-           ((((long)g.n * a.H + g.y0 - 1) * a.W + g.x0 - 1) * (long)a.Cin) * 2;
-    return g;
-  };
+  using Geo = X3Geo;
+  auto geo_of = [&](int w) __attribute__((always_inline)) { return x3_geo_of<S>(a, w); };
   auto issue_piece = [&](const Geo& g, int kc, int j, int buf) __attribute__((always_inline)) {
     int q = wave + j * 4;
     q = q < NQX ? q : NQX - 1;
@@ -285,23 +263,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int qOffH = qHalf + (tapB ? 64 : 0);       // horizontal pair: tap B one column right
 
   // ---- weights ----
-  const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(a.wt), 0, (a.Cout / 64) * a.chunksTotal * (9 * 2 * 4 * 1024), 0x00020000);
-  const __amdgpu_buffer_rsrc_t qrsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint32_t*>(a.wq), 0, (a.Cout / 64) * a.chunksTotal * (5 * 4 * 2 * 1024), 0x00020000);
+  const __amdgpu_buffer_rsrc_t wrsrc = x3_buffer_of(a.wt, (a.Cout / 64) * a.chunksTotal * kX3WChunk);
+  const __amdgpu_buffer_rsrc_t qrsrc = x3_buffer_of(a.wq, (a.Cout / 64) * a.chunksTotal * (5 * 4 * 2 * 1024));
   const int laneW = lane * 16;
   auto w_block = [&](int cg, int kc) __attribute__((always_inline)) -> int {
     return ((cg * 4 + wave) * a.chunksTotal + kc);   // (channel tile of 64, chunk)
   };
-  auto wh_load = [&](int blk, int tap, int cs) __attribute__((always_inline)) -> f32x4 {
-    const int ky = tap / 3, kx = tap - ky * 3;
-    const i32x4 v = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                  wrsrc, laneW + cs * 1024, blk * (9 * 2 * 4 * 1024) + ((ky * 2) * 3 + kx) * 4096, 0));
-    return __builtin_bit_cast(f32x4, v);
+  auto wh_load = [&](int blk, int tap, int cs) __attribute__((always_inline)) -> f32x4 {   // plane 0 of the f16x3 pack
+    return x3_w_load(wrsrc, laneW, blk * kX3WChunk, tap, 0, cs);
   };
   auto wq_load = [&](int blk, int step, int cs, int half) __attribute__((always_inline)) -> i32x4 {
-    return __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                         qrsrc, laneW + (cs * 2 + half) * 1024, blk * (5 * 4 * 2 * 1024) + step * 8192, 0));
+    return __builtin_bit_cast(i32x4, x3_buffer_load16(qrsrc, laneW + (cs * 2 + half) * 1024, blk * (5 * 4 * 2 * 1024) + step * 8192));
   };
   // taps of a step
   auto tapA_of = [](int s) { return s < 3 ? s : (s == 3 ? 6 : 8); };
@@ -545,7 +517,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
     }
 
-    // ---- epilogue (conv_x3_r512.h, EPI 0) ----
+    // ---- epilogue (wave_tile.h) ----
     f32x4 sc[4], sh[4];
 #pragma unroll
     for (int cs = 0; cs < 4; ++cs) {
@@ -606,15 +578,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        auto r1 = __builtin_amdgcn_permlane16_swap(ph[k], ph[4 + k], false, false);
-        auto q1 = __builtin_amdgcn_permlane32_swap(r1[0], r1[1], false, false);
-        ph[k] = q1[0];
-        ph[4 + k] = q1[1];
+        x3_swap64(ph[k], ph[4 + k]);
         if (EPI == 0) {
-          auto rl = __builtin_amdgcn_permlane16_swap(pl[k], pl[4 + k], false, false);
-          auto q2 = __builtin_amdgcn_permlane32_swap(rl[0], rl[1], false, false);
-          pl[k] = q2[0];
-          pl[4 + k] = q2[1];
+          x3_swap64(pl[k], pl[4 + k]);
         } else {
           // lanes lq = 0, 1 hold the two halves of the wave's first 32-channel block, lq = 2, 3 of its second; a block
           // is [x_hi h0 | x_hi h1 | x_lo h0 | x_lo h1] x 16 bytes.  Swapping the upper half wave of qh with the lower
@@ -626,11 +592,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
       uint16_t* rowp = a.out + pix * (size_t)a.ldo + a.co_off + (cbase - lq * 16) + lq * 8;
       if (ok) {
-        *reinterpret_cast<uint4*>(rowp) = make_uint4(ph[0], ph[1], ph[2], ph[3]);
-        *reinterpret_cast<uint4*>(rowp + 32) = make_uint4(ph[4], ph[5], ph[6], ph[7]);
+        x3_store_plane64(rowp, ph);
         if (EPI == 0) {
-          *reinterpret_cast<uint4*>(rowp + a.outLo) = make_uint4(pl[0], pl[1], pl[2], pl[3]);
-          *reinterpret_cast<uint4*>(rowp + a.outLo + 32) = make_uint4(pl[4], pl[5], pl[6], pl[7]);
+          x3_store_plane64(rowp + a.outLo, pl);
         } else {
           // q plane: same offset and pixel stride (in bytes) as the lo plane; the wave's 64 channels are 128 bytes of it
           uint16_t* qp = a.out + a.outLo + pix * (size_t)a.ldo + a.co_off + (cbase - lq * 16) + lq * 8;

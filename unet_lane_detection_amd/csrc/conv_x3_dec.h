@@ -92,8 +92,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int pa = WCO == 1 ? wp >> 1 : wp;    // the wave's row parity
   const int pbw = WCO == 1 ? wp & 1 : 0;     // its first column parity
   const int li = lane & 15, lq = lane >> 4;
-  const int G = gridDim.x;   // multiple of 8: consecutive logical blocks share an XCD (and its L2)
-  const int lb = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int G = gridDim.x;   // multiple of 8 (wave_tile.h)
+  const int lb = x3_logical_block(G);
   const int numWork = a.pixTiles * a.coTiles;
   if (lb >= numWork) return;
   const unsigned ldsBase = lds_address(smemv);
@@ -201,8 +201,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
   // ---- weights: per 64-channel tile, skip chunks then x chunks (UpcatX3Args::wt) ----
   const int perCt = a.nS * S::SKIP_CHUNK + a.nX * S::X_CHUNK;
-  const __amdgpu_buffer_rsrc_t wrsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.wt), 0, (a.F / 64) * perCt, 0x00020000);
+  const __amdgpu_buffer_rsrc_t wrsrc = x3_buffer_of(a.wt, (a.F / 64) * perCt);
   const int laneW = lane * 16;
   const int parOff = (WCO == 1 ? (pa * 2 + pbw) : pa * 2) * (4 * 8192);   // this wave's parity block of an x chunk
   auto w_block = [&](int cg, int kc) __attribute__((always_inline)) -> int {   // byte offset of (channel tile, chunk)
@@ -210,9 +209,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     return ct * perCt + (kc < a.nS ? kc * S::SKIP_CHUNK : a.nS * S::SKIP_CHUNK + (kc - a.nS) * S::X_CHUNK + parOff);
   };
   auto w_load = [&](int blk, int vt, int plane, int cs) __attribute__((always_inline)) -> f32x4 {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, laneW + cs * 1024, blk + (vt * 2 + plane) * 4096, 0);
-    return __builtin_bit_cast(f32x4, v);
+    return x3_buffer_load16(wrsrc, laneW + cs * 1024, blk + (vt * 2 + plane) * 4096);
   };
 
   // ---- prologue: chunk 0 of the first item (a skip chunk), weights of its taps 0 and 1 ----
@@ -351,11 +348,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // ---- epilogue: lane (li, lq) holds channels 16 lq + [0, 16) of its pixel of each fragment ----
     // the per-channel constants only now: 32 registers the chunk loop needs for its weight ring
     f32x4 sc[4], sh[4];
-#pragma unroll
-    for (int cs = 0; cs < 4; ++cs) {
-      sc[cs] = *reinterpret_cast<const f32x4*>(a.scale + cbase + cs * 4);
-      sh[cs] = *reinterpret_cast<const f32x4*>(a.shift + cbase + cs * 4);
-    }
+    x3_scale_shift<false>(a.scale, a.shift, cbase, sc, sh);
     const float floorV = a.relu ? 0.f : -3.4e38f;
     const bool border = gCur.y0 == 0 || gCur.y0 + S::TH >= a.H || gCur.x0 == 0 || gCur.x0 + S::TWX >= a.W;
 #pragma unroll
@@ -378,42 +371,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
       const size_t pix = ((size_t)gCur.n * a.H + gy) * a.W + gx;
       float v[16];
-#pragma unroll
-      for (int e = 0; e < 16; ++e)
-        v[e] = fmaxf(fmaf(acc[f][e >> 2][e & 3], sc[e >> 2][e & 3], shE[e >> 2][e & 3]), floorV);
+      x3_affine16(acc[f], sc, shE, floorV, v);
       uint32_t ph[8], pl[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {   // not clamped: out-of-range values become inf and are reported (amax)
-        amax3(amax, v[2 * e], v[2 * e + 1]);
-        split_pk_f16_mix(v[2 * e], v[2 * e + 1], ph[e], pl[e]);
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        auto rr = __builtin_amdgcn_permlane16_swap(ph[k], ph[4 + k], false, false);
-        auto q = __builtin_amdgcn_permlane32_swap(rr[0], rr[1], false, false);
-        ph[k] = q[0];
-        ph[4 + k] = q[1];
-        auto rl = __builtin_amdgcn_permlane16_swap(pl[k], pl[4 + k], false, false);
-        auto ql2 = __builtin_amdgcn_permlane32_swap(rl[0], rl[1], false, false);
-        pl[k] = ql2[0];
-        pl[4 + k] = ql2[1];
-      }
+      x3_split16(v, amax, ph, pl);
+      x3_swap_planes64(ph, pl);   // 64 contiguous bytes per pixel and store instruction
       uint16_t* rowp = a.out + pix * (size_t)a.ldo + (cbase - lq * 16) + lq * 8;
-      if (ok) {
-        if (WCO == 1) {   // non-temporal as in conv_x3_t448.h's 64-channel form
-          typedef unsigned u32x4nt __attribute__((ext_vector_type(4)));
-          __builtin_nontemporal_store((u32x4nt){ph[0], ph[1], ph[2], ph[3]}, reinterpret_cast<u32x4nt*>(rowp));
-          __builtin_nontemporal_store((u32x4nt){ph[4], ph[5], ph[6], ph[7]}, reinterpret_cast<u32x4nt*>(rowp + 32));
-          __builtin_nontemporal_store((u32x4nt){pl[0], pl[1], pl[2], pl[3]}, reinterpret_cast<u32x4nt*>(rowp + a.outLo));
-          __builtin_nontemporal_store((u32x4nt){pl[4], pl[5], pl[6], pl[7]},
-                                      reinterpret_cast<u32x4nt*>(rowp + a.outLo + 32));
-        } else {
-          *reinterpret_cast<uint4*>(rowp) = make_uint4(ph[0], ph[1], ph[2], ph[3]);
-          *reinterpret_cast<uint4*>(rowp + 32) = make_uint4(ph[4], ph[5], ph[6], ph[7]);
-          *reinterpret_cast<uint4*>(rowp + a.outLo) = make_uint4(pl[0], pl[1], pl[2], pl[3]);
-          *reinterpret_cast<uint4*>(rowp + a.outLo + 32) = make_uint4(pl[4], pl[5], pl[6], pl[7]);
-        }
-      }
+      // non-temporal as in conv_x3_t448.h's 64-channel form
+      if (ok) x3_store_planes64<WCO == 1>(rowp, a.outLo, ph, pl);
       __builtin_amdgcn_sched_barrier(0);   // one fragment at a time: 16 values live
     }
     gCur = gNext;

@@ -35,9 +35,13 @@
 // configuration's 320-, 160-, 80- and 40-wide levels; the 7 x 32 tile also in the two-wave form (Cout = 128 at 320 x 320).
 //
 // Needs Cin % 32 == 0, Cout % (256 / WPX) == 0, W % TWX == 0.
+//
+// The block remap, the geometry of a work item, the weight loads, split_pk_f16_mix and the epilogue's swap / store / fp32
+// pieces are wave_tile.h's.  Staging, FLAT mask, scale / shift, affine, split and partial-sum text stays here: as calls
+// of helpers each changed the register allocation of some instance (profiles/r13/wave_tile_refactor.md).
 #pragma once
-#include "conv_x3_ws.h"
 #include "lds_dma.h"
+#include "wave_tile.h"
 
 // Diagnostic build (-DUNET_R512_STAMPS=1, tools/probes only): s_memtime sums of wave 0 per block - chunk loops, barrier
 // waits, epilogues, whole kernel, and the kernel in 100 MHz ticks - written to ConvX3Args::logits (unused by this
@@ -58,38 +62,12 @@
 #ifndef UNET_R512_ABLATE
 #define UNET_R512_ABLATE 0
 #endif
-// 1 = the epilogue transposes 16-byte halves between the four lanes of a pixel so that a store writes 64 contiguous bytes
-#ifndef UNET_R512_STORE64
-#define UNET_R512_STORE64 1
-#endif
-
 namespace unet {
 
 // acc += A * B with acc in the accumulator file.  Operands come from loads only (the compiler places their
 // s_waitcnt in front of the statement); nothing reads acc but the next MFMA on it until the epilogue's pad.
 __device__ __forceinline__ void mfma_x3_acc(f32x4& c, const f32x4& a, const f32x4& b) {
   asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-}
-
-// split_pk_f16 (values clamped to the fp16 range, as conv_x3_ws.h promises: an out-of-range value is stored as +-65504 and
-// reported through amax, never as inf) in 6 instructions per pair: two v_med3_f32, hi = v_cvt_pk_f16_f32, lo = rn16(v - hi)
-// as one mixed-precision FMA per value that reads hi as fp16 and writes its fp16 result into one half of the destination
-// (v - hi is exact in fp32, so the single rounding is the same as in split_pk_f16: the two kernel structures stay
-// bit-identical, tests/test_x3_gpu.py).  Callers take amax from the unclamped values first.
-__device__ __forceinline__ void split_pk_f16_mix(float v0, float v1, uint32_t& hi, uint32_t& lo) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-  v0 = __builtin_amdgcn_fmed3f(v0, -65504.f, 65504.f);
-  v1 = __builtin_amdgcn_fmed3f(v1, -65504.f, 65504.f);
-  hi = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){v0, v1}, f16x2));
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-      : "=&v"(lo)
-      : "v"(hi), "v"(v0), "v"(v1));
-}
-// amax = max(amax, |v0|, |v1|) in one instruction
-__device__ __forceinline__ void amax3(float& amax, float v0, float v1) {
-  asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(v0), "v"(v1));
 }
 
 template <int TWX_>
@@ -136,8 +114,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wp = wave / WCO, wc = wave - wp * WCO;
   const int li = lane & 15, lq = lane >> 4;
-  const int G = gridDim.x;   // multiple of 8: consecutive logical blocks share an XCD (and its L2)
-  const int lb = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int G = gridDim.x;   // multiple of 8 (wave_tile.h)
+  const int lb = x3_logical_block(G);
   const int numWork = a.pixTiles * a.coTiles;   // coTiles: groups of 64 * WCO output channels
   if (lb >= numWork) return;
   const unsigned ldsBase = lds_address(smemv);
@@ -160,32 +138,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const char* zp = reinterpret_cast<const char*>(a.zeros) + (lane & 3) * 16;
   const size_t inLoB = a.inLo * 2;
 
-  // geometry of a work item: uniform values only
-  struct Geo {
-    const char* tb;   // address of the halo's top-left pixel, chunk 0, hi plane (not dereferenced where out of image)
-    int hrMin, hrSpan, hcMin, hcSpan;
-    int n, y0, x0, cg;
-  };
-  auto geo_of = [&](int w) __attribute__((always_inline)) {
-    Geo g;
-    const int cInG = w % a.coGroup;
-    const int rest = w / a.coGroup;
-    const int tile = rest % a.pixTiles;
-    g.cg = (rest / a.pixTiles) * a.coGroup + cInG;
-    const int rowTile = tile / a.tilesX;
-    g.x0 = (tile - rowTile * a.tilesX) * TWX;
-    g.n = rowTile / a.tilesY;
-    g.y0 = (rowTile - g.n * a.tilesY) * TH;
-    const int hrMax = a.H - g.y0 < S::HH2 - 1 ? a.H - g.y0 : S::HH2 - 1;
-    const int hcMax = a.W - g.x0 < S::HW2 - 1 ? a.W - g.x0 : S::HW2 - 1;
-    g.hrMin = g.y0 == 0 ? 1 : 0;
-    g.hcMin = g.x0 == 0 ? 1 : 0;
-    g.hrSpan = hrMax - g.hrMin;
-    g.hcSpan = hcMax - g.hcMin;
-    g.tb = reinterpret_cast<const char*>(a.in) +
-           ((((long)g.n * a.H + g.y0 - 1) * a.W + g.x0 - 1) * (long)a.Cin) * 2;
-    return g;
-  };
+  using Geo = X3Geo;
+  auto geo_of = [&](int w) __attribute__((always_inline)) { return x3_geo_of<S>(a, w); };
   // both planes of piece index j of (item geometry g, chunk kc) -> halo buffer `buf`
   auto issue_piece = [&](const Geo& g, int kc, int j, int buf) __attribute__((always_inline)) {
     int q = wave + j * 4;
@@ -210,19 +164,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
   // ---- weights: this wave's channel tile of 64; packed [coTile][chunk][tapRow][plane][kx][cs][lane][8 halfs].
   //      Buffer loads: descriptor and block offset in SGPRs, the lane's 16 bytes as the only vector operand ----
-  const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(a.wt), 0, (a.Cout / 64) * a.chunksTotal * (9 * 2 * 4 * 1024), 0x00020000);
+  const __amdgpu_buffer_rsrc_t wrsrc = x3_buffer_of(a.wt, (a.Cout / 64) * a.chunksTotal * kX3WChunk);
   const int laneW = lane * 16;
   auto w_block = [&](int cg, int kc) __attribute__((always_inline)) -> int {   // byte offset of (channel tile, chunk)
     const int ct = cg * WCO + wc;
-    return (ct * a.chunksTotal + kc) * (9 * 2 * 4 * 1024);
+    return (ct * a.chunksTotal + kc) * kX3WChunk;
   };
   auto w_load = [&](int blk, int tap, int plane, int cs) __attribute__((always_inline)) -> f32x4 {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const int ky = tap / 3, kx = tap - ky * 3;
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, laneW + cs * 1024,
-                                                          blk + ((ky * 2 + plane) * 3 + kx) * 4096, 0);
-    return __builtin_bit_cast(f32x4, v);
+    return x3_w_load(wrsrc, laneW, blk, tap, plane, cs);
   };
 
   if (tid < 8)   // the two zero slots
@@ -448,79 +397,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             ssq[e] = fmaf(t, t, ssq[e]);
           }
         }
-#if UNET_R512_STORE64
-        // 4 x 4 transpose of 16-byte pieces across the four lanes of a pixel (two swap stages): store k then writes
-        // bytes [64 k + 16 lq, + 16) of the pixel's 256 - 64 contiguous bytes per pixel and instruction
-        uint32_t u[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) u[e] = __builtin_bit_cast(uint32_t, v[e]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          auto r01 = __builtin_amdgcn_permlane16_swap(u[j], u[4 + j], false, false);
-          auto r23 = __builtin_amdgcn_permlane16_swap(u[8 + j], u[12 + j], false, false);
-          auto s02 = __builtin_amdgcn_permlane32_swap(r01[0], r23[0], false, false);
-          auto s13 = __builtin_amdgcn_permlane32_swap(r01[1], r23[1], false, false);
-          u[j] = s02[0];
-          u[8 + j] = s02[1];
-          u[4 + j] = s13[0];
-          u[12 + j] = s13[1];
-        }
-        float* rowp = a.outF + pix * (size_t)a.ldo + a.co_off + (cbase - lq * 16) + lq * 4;
-        if (ok) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            *reinterpret_cast<uint4*>(rowp + 16 * k) = make_uint4(u[4 * k], u[4 * k + 1], u[4 * k + 2], u[4 * k + 3]);
-        }
-#else
-        float* rowp = a.outF + pix * (size_t)a.ldo + a.co_off + cbase;
-        if (ok) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            *reinterpret_cast<f32x4*>(rowp + 4 * q) = (f32x4){v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
-        }
-#endif
+        x3_store_f32_64(a.outF + pix * (size_t)a.ldo + a.co_off + (cbase - lq * 16) + lq * 4, ok, v);
       } else {
         uint32_t ph[8], pl[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {   // amax before the clamp in split_pk_f16_mix: out-of-range values are stored as +-65504 and reported
+        for (int e = 0; e < 8; ++e) {   // amax before the clamp in split_pk_f16_mix
           amax3(amax, v[2 * e], v[2 * e + 1]);
           split_pk_f16_mix(v[2 * e], v[2 * e + 1], ph[e], pl[e]);
         }
-#if UNET_R512_STORE64
-        // The four lanes of a pixel (lq = 0..3) hold bytes [32 lq, 32 lq + 32) of its 128 bytes per plane as two 16-byte
-        // halves; stored as they are, every store instruction writes 16-byte pieces 32 bytes apart.  Two lane-row
-        // swaps per register (rows of 16 lanes: odd <-> even rows, then upper <-> lower half wave) hand lane row q
-        // bytes [16 q, 16 q + 16) of the first 64 bytes in one register set and of the second 64 in the other: each
-        // store instruction then writes 64 contiguous bytes per pixel.
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          auto r = __builtin_amdgcn_permlane16_swap(ph[k], ph[4 + k], false, false);
-          auto q = __builtin_amdgcn_permlane32_swap(r[0], r[1], false, false);
-          ph[k] = q[0];
-          ph[4 + k] = q[1];
-          auto rl = __builtin_amdgcn_permlane16_swap(pl[k], pl[4 + k], false, false);
-          auto ql = __builtin_amdgcn_permlane32_swap(rl[0], rl[1], false, false);
-          pl[k] = ql[0];
-          pl[4 + k] = ql[1];
-        }
+        x3_swap_planes64(ph, pl);   // 64 contiguous bytes per pixel and store instruction
         uint16_t* rowp = a.out + pix * (size_t)a.ldo + a.co_off + (cbase - lq * 16) + lq * 8;
-        if (ok) {
-          *reinterpret_cast<uint4*>(rowp) = make_uint4(ph[0], ph[1], ph[2], ph[3]);
-          *reinterpret_cast<uint4*>(rowp + 32) = make_uint4(ph[4], ph[5], ph[6], ph[7]);
-          *reinterpret_cast<uint4*>(rowp + a.outLo) = make_uint4(pl[0], pl[1], pl[2], pl[3]);
-          *reinterpret_cast<uint4*>(rowp + a.outLo + 32) = make_uint4(pl[4], pl[5], pl[6], pl[7]);
-        }
-#else
-        uint16_t* rowp = a.out + pix * (size_t)a.ldo + a.co_off + cbase;
-        if (ok) {
-          uint4* o = reinterpret_cast<uint4*>(rowp);
-          o[0] = make_uint4(ph[0], ph[1], ph[2], ph[3]);
-          o[1] = make_uint4(ph[4], ph[5], ph[6], ph[7]);
-          uint4* ol = reinterpret_cast<uint4*>(rowp + a.outLo);
-          ol[0] = make_uint4(pl[0], pl[1], pl[2], pl[3]);
-          ol[1] = make_uint4(pl[4], pl[5], pl[6], pl[7]);
-        }
-#endif
+        if (ok) x3_store_planes64(rowp, a.outLo, ph, pl);
       }
       __builtin_amdgcn_sched_barrier(0);   // one fragment at a time: 16 values live, not 224
     }
@@ -529,7 +416,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     R5_ACCUM(tEpi, tE0);
   }
   if (EPI != 3) x3_report_range(amax, a.err);
-  if (EPI == 3 && a.statPartial) {   // sum over the 16 pixels of a fragment row (lanes li), then one lane per 16 channels
+  if (EPI == 3 && a.statPartial) {   // sum over the 16 pixels of a fragment (lanes li), then one lane per 16 channels
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
 #pragma unroll

@@ -25,7 +25,7 @@
 //        32-channel chunk's halo tile are 68 KiB (TWX = 28), double buffered 136 KiB;
 //      - the 2 x 2 max-pool windows lie inside a fragment: horizontal partner lane li ^ 1, vertical partner li ^ 4, both
 //        DPP operands - the pooled epilogue needs no second fragment and no LDS;
-//  * the plane stores write 64 contiguous bytes per pixel and instruction (conv_x3_r512.h).  Whole 128-byte lines - one
+//  * the plane stores write 64 contiguous bytes per pixel and instruction (wave_tile.h).  Whole 128-byte lines - one
 //    more exchange between the lanes of pixels li and li ^ 8 - were built and measured: the epilogue's 7.8k / 15.5k cycles
 //    per item (7 / 14 fragments) did not move (profiles/r04/t448_experiments.md): a CU stores ~15 bytes per cycle whatever
 //    the shape of the instruction;
@@ -38,6 +38,9 @@
 // EPI 0 stores the two planes, 1 the planes and their 2 x 2 max-pool, 2 runs the fused 1 x 1 head (Cout = 64; activation
 // not stored), 3 stores fp32 (training; optional BatchNorm partial sums).  Needs Cin % 32 == 0, Cout % (64 WCO) == 0,
 // W % TWX == 0; any H (rows past the bottom read the zero page and are not stored).
+//
+// Block remap, geometry, weight loads, split_pk_f16_mix and the plane swap / store are wave_tile.h's; the staging, scale /
+// shift, affine, split, fp32 store and partial-sum text is repeated here: as helper calls each changed some instance.
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -110,8 +113,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wp = wave / WCO, wc = wave - wp * WCO;
   const int li = lane & 15, lq = lane >> 4;
-  const int G = gridDim.x;   // multiple of 8: consecutive logical blocks share an XCD (and its L2)
-  const int lb = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int G = gridDim.x;   // multiple of 8 (wave_tile.h)
+  const int lb = x3_logical_block(G);
   const int numWork = a.pixTiles * a.coTiles;   // coTiles: groups of 64 * WCO output channels
   if (lb >= numWork) return;
   const unsigned ldsBase = lds_address(smemv);
@@ -134,31 +137,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const char* zp = reinterpret_cast<const char*>(a.zeros) + (lane & 3) * 16;
   const size_t inLoB = a.inLo * 2;
 
-  struct Geo {
-    const char* tb;   // address of the halo's top-left pixel, chunk 0, hi plane (not dereferenced where out of image)
-    int hrMin, hrSpan, hcMin, hcSpan;
-    int n, y0, x0, cg;
-  };
-  auto geo_of = [&](int w) __attribute__((always_inline)) {
-    Geo g;
-    const int cInG = w % a.coGroup;
-    const int rest = w / a.coGroup;
-    const int tile = rest % a.pixTiles;
-    g.cg = (rest / a.pixTiles) * a.coGroup + cInG;
-    const int rowTile = tile / a.tilesX;
-    g.x0 = (tile - rowTile * a.tilesX) * TWX;
-    g.n = rowTile / a.tilesY;
-    g.y0 = (rowTile - g.n * a.tilesY) * TH;
-    const int hrMax = a.H - g.y0 < S::HH2 - 1 ? a.H - g.y0 : S::HH2 - 1;
-    const int hcMax = a.W - g.x0 < S::HW2 - 1 ? a.W - g.x0 : S::HW2 - 1;
-    g.hrMin = g.y0 == 0 ? 1 : 0;
-    g.hcMin = g.x0 == 0 ? 1 : 0;
-    g.hrSpan = hrMax - g.hrMin;
-    g.hcSpan = hcMax - g.hcMin;
-    g.tb = reinterpret_cast<const char*>(a.in) +
-           ((((long)g.n * a.H + g.y0 - 1) * a.W + g.x0 - 1) * (long)a.Cin) * 2;
-    return g;
-  };
+  using Geo = X3Geo;
+  auto geo_of = [&](int w) __attribute__((always_inline)) { return x3_geo_of<S>(a, w); };
   // both planes of piece index j of (item geometry g, chunk kc) -> halo buffer `buf`
   auto issue_piece = [&](const Geo& g, int kc, int j, int buf) __attribute__((always_inline)) {
     int q = wave + j * 4;
@@ -184,19 +164,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
 
   // ---- weights: this wave's channel tile of 64; packed [coTile][chunk][tapRow][plane][kx][cs][lane][8 halfs] ----
-  const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(a.wt), 0, (a.Cout / 64) * a.chunksTotal * (9 * 2 * 4 * 1024), 0x00020000);
+  const __amdgpu_buffer_rsrc_t wrsrc = x3_buffer_of(a.wt, (a.Cout / 64) * a.chunksTotal * kX3WChunk);
   const int laneW = lane * 16;
   auto w_block = [&](int cg, int kc) __attribute__((always_inline)) -> int {   // byte offset of (channel tile, chunk)
     const int ct = cg * WCO + wc;
-    return (ct * a.chunksTotal + kc) * (9 * 2 * 4 * 1024);
+    return (ct * a.chunksTotal + kc) * kX3WChunk;
   };
   auto w_load = [&](int blk, int tap, int plane, int cs) __attribute__((always_inline)) -> f32x4 {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const int ky = tap / 3, kx = tap - ky * 3;
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, laneW + cs * 1024,
-                                                          blk + ((ky * 2 + plane) * 3 + kx) * 4096, 0);
-    return __builtin_bit_cast(f32x4, v);
+    return x3_w_load(wrsrc, laneW, blk, tap, plane, cs);
   };
 
   if (EPI == 2 && tid < 64) reinterpret_cast<float*>(reinterpret_cast<char*>(smemv) + S::TOFF)[tid] = a.headW[tid];
@@ -303,7 +278,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             ssq[e] = fmaf(t, t, ssq[e]);
           }
         }
-        // 4 x 4 transpose of 16-byte pieces across the four lanes of a pixel: a store writes 64 contiguous bytes per pixel
+        // x3_store_f32_64 (wave_tile.h) as inline text: the call changes the accumulator reads of <28,1,3>
         uint32_t u[16];
 #pragma unroll
         for (int e = 0; e < 16; ++e) u[e] = __builtin_bit_cast(uint32_t, v[e]);
@@ -327,7 +302,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       } else {
         uint32_t ph[8], pl[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {   // amax before the clamp in split_pk_f16_mix: out-of-range values are stored as +-65504 and reported
+        for (int e = 0; e < 8; ++e) {   // amax before the clamp in split_pk_f16_mix
           amax3(amax, v[2 * e], v[2 * e + 1]);
           split_pk_f16_mix(v[2 * e], v[2 * e + 1], ph[e], pl[e]);
         }
@@ -372,40 +347,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
               ol[1] = make_uint4(ql[4], ql[5], ql[6], ql[7]);
             }
           }
-          // two lane-row swaps per register hand lane row q bytes [16 q, 16 q + 16) of the first 64 bytes of the pixel's
-          // 128 in one register set and of the second 64 in the other (conv_x3_r512.h)
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            auto rr = __builtin_amdgcn_permlane16_swap(ph[k], ph[4 + k], false, false);
-            auto q = __builtin_amdgcn_permlane32_swap(rr[0], rr[1], false, false);
-            ph[k] = q[0];
-            ph[4 + k] = q[1];
-            auto rl = __builtin_amdgcn_permlane16_swap(pl[k], pl[4 + k], false, false);
-            auto ql2 = __builtin_amdgcn_permlane32_swap(rl[0], rl[1], false, false);
-            pl[k] = ql2[0];
-            pl[4 + k] = ql2[1];
-          }
+          x3_swap_planes64(ph, pl);   // 64 contiguous bytes per pixel and store instruction
           uint16_t* rowp = a.out + pix * (size_t)a.ldo + a.co_off + (cbase - lq * 16) + lq * 8;
-          if (ok) {
-            if (WCO == 1) {
-              // 64-channel layers (the 224 x 224 level): non-temporal stores.  With plain stores the output lines push the
-              // input's out of the XCD's 4 MiB L2 between the two 32-channel chunks that share each 128-byte line, and
-              // every input line is fetched twice: 2 x FETCH_SIZE 10.4 -> 8.5 GB per launch of the 128 -> 64 layer (7.9
-              // with no re-fetch at all), 4.12 -> 4.09 ms; 64 -> 64 pooled 2.56 -> 2.52 ms.  Not on the 128- and
-              // 256-channel forms: no gain at 112 x 112, 0.9 % slower at 56 x 56 (profiles/r04/t448_experiments.md)
-              typedef unsigned u32x4nt __attribute__((ext_vector_type(4)));
-              __builtin_nontemporal_store((u32x4nt){ph[0], ph[1], ph[2], ph[3]}, reinterpret_cast<u32x4nt*>(rowp));
-              __builtin_nontemporal_store((u32x4nt){ph[4], ph[5], ph[6], ph[7]}, reinterpret_cast<u32x4nt*>(rowp + 32));
-              __builtin_nontemporal_store((u32x4nt){pl[0], pl[1], pl[2], pl[3]}, reinterpret_cast<u32x4nt*>(rowp + a.outLo));
-              __builtin_nontemporal_store((u32x4nt){pl[4], pl[5], pl[6], pl[7]},
-                                          reinterpret_cast<u32x4nt*>(rowp + a.outLo + 32));
-            } else {
-              *reinterpret_cast<uint4*>(rowp) = make_uint4(ph[0], ph[1], ph[2], ph[3]);
-              *reinterpret_cast<uint4*>(rowp + 32) = make_uint4(ph[4], ph[5], ph[6], ph[7]);
-              *reinterpret_cast<uint4*>(rowp + a.outLo) = make_uint4(pl[0], pl[1], pl[2], pl[3]);
-              *reinterpret_cast<uint4*>(rowp + a.outLo + 32) = make_uint4(pl[4], pl[5], pl[6], pl[7]);
-            }
-          }
+          // 64-channel layers (the 224 x 224 level): non-temporal stores.  With plain stores the output lines push the
+          // input's out of the XCD's 4 MiB L2 between the two 32-channel chunks that share each 128-byte line, and
+          // every input line is fetched twice: 2 x FETCH_SIZE 10.4 -> 8.5 GB per launch of the 128 -> 64 layer (7.9
+          // with no re-fetch at all), 4.12 -> 4.09 ms; 64 -> 64 pooled 2.56 -> 2.52 ms.  Not on the 128- and
+          // 256-channel forms: no gain at 112 x 112, 0.9 % slower at 56 x 56 (profiles/r04/t448_experiments.md)
+          if (ok) x3_store_planes64<WCO == 1>(rowp, a.outLo, ph, pl);
         }
       }
       __builtin_amdgcn_sched_barrier(0);   // one fragment at a time: 16 values live

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lq = lane >> 4;
   const int G = gridDim.x;
-  const int lb = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int lb = x3_logical_block(G);
   const int numWork = a.pixTiles * a.coTiles;   // consecutive items: the channel tiles of one pixel tile
   if (lb >= numWork) return;
   const unsigned ldsBase = lds_address(smemv);
@@ -63,14 +63,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   for (int j = 0; j < 2; ++j) xa[j] = li * 128 + (((j * 4 + lq) ^ ((li >> 1) & 7)) << 4);
 
   // ---- weights: packed [coTile][chunk(64)][kstep(2)][ab(4)][cs(4)][lane][8]; wave w reads (a,b) = w ----
-  const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(a.wt), 0, a.coTiles * a.nChunks * (32 * 1024), 0x00020000);
+  const __amdgpu_buffer_rsrc_t wrsrc = x3_buffer_of(a.wt, a.coTiles * a.nChunks * (32 * 1024));
   const int laneW = lane * 16 + wave * 4096;
   auto w_load = [&](int coTile, int kc, int ks, int cs) __attribute__((always_inline)) -> f32x4 {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, laneW + ks * 16384 + cs * 1024,
-                                                          (coTile * a.nChunks + kc) * (32 * 1024), 0);
-    return __builtin_bit_cast(f32x4, v);
+    return x3_buffer_load16(wrsrc, laneW + ks * 16384 + cs * 1024, (coTile * a.nChunks + kc) * (32 * 1024));
   };
 
   // ---- prologue: stage 0 of the first item ----
@@ -164,6 +160,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const int cs = e >> 1, r = (2 * e) & 3;
         pk[e] = pk_bf16(acc[f][cs][r] + bi[cs][r], acc[f][cs][r + 1] + bi[cs][r + 1]);
       }
+      // x3_swap_plane64 (wave_tile.h) as inline text: the call moves a compare in this kernel
       // the four lanes of a pixel hold 32 bytes each as two 16-byte halves; after two lane-row swaps per register lane row
       // q holds bytes [16 q, +16) of the pixel's first 64 bytes in pk[0..3] and of its second 64 in pk[4..7]
 #pragma unroll
@@ -175,10 +172,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
       uint16_t* op = a.out + (((size_t)(2 * row + oa) * (size_t)(2 * a.w)) + 2 * x + ob) * (size_t)a.ldo + a.co_off +
                      ctCur * 64 + lq * 8;
-      if (ok) {
-        *reinterpret_cast<uint4*>(op) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-        *reinterpret_cast<uint4*>(op + 32) = make_uint4(pk[4], pk[5], pk[6], pk[7]);
-      }
+      if (ok) x3_store_plane64(op, pk);
       x += 16;
 #pragma unroll
       for (int k = 0; k < 4; ++k)   // 16 pixels cross up to four row ends (w >= 4; the host checks)

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lq = lane >> 4;
   const int G = gridDim.x;
-  const int lb = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int lb = x3_logical_block(G);
   const int numWork = a.pixTiles * a.coTiles;   // consecutive items: the channel tiles of one pixel tile
   if (lb >= numWork) return;
   const unsigned ldsBase = lds_address(smemv);
@@ -69,14 +69,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int xa0 = li * 64 + ((lq ^ (((li >> 2) & 1) << 1)) << 4);
 
   // ---- weights: packed [coTile][chunk(32)][plane(2)][ab(4)][cs(4)][lane][8 halfs]; wave w reads group (a,b) = w ----
-  const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint16_t*>(a.wt), 0, a.coTiles * a.nChunks * (2 * 16 * 1024), 0x00020000);
+  const __amdgpu_buffer_rsrc_t wrsrc = x3_buffer_of(a.wt, a.coTiles * a.nChunks * (2 * 16 * 1024));
   const int laneW = lane * 16 + wave * 4096;
   auto w_load = [&](int coTile, int kc32, int plane, int cs) __attribute__((always_inline)) -> f32x4 {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, laneW + plane * 16384 + cs * 1024,
-                                                          (coTile * a.nChunks + kc32) * (2 * 16 * 1024), 0);
-    return __builtin_bit_cast(f32x4, v);
+    return x3_buffer_load16(wrsrc, laneW + plane * 16384 + cs * 1024, (coTile * a.nChunks + kc32) * (2 * 16 * 1024));
   };
 
   // ---- prologue: stage 0 of the first item ----
@@ -246,18 +242,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             ql[e] = q8_pack4(lf[4 * e], lf[4 * e + 1], lf[4 * e + 2], lf[4 * e + 3]);
           }
         }
-        // 64 contiguous bytes per pixel and store instruction (conv_x3_r512.h)
+        // 64 contiguous bytes per pixel and store instruction (wave_tile.h)
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          auto r1 = __builtin_amdgcn_permlane16_swap(ph[k], ph[4 + k], false, false);
-          auto q1 = __builtin_amdgcn_permlane32_swap(r1[0], r1[1], false, false);
-          ph[k] = q1[0];
-          ph[4 + k] = q1[1];
+          x3_swap64(ph[k], ph[4 + k]);
           if (!OUTQ) {
-            auto rl = __builtin_amdgcn_permlane16_swap(pl[k], pl[4 + k], false, false);
-            auto q2 = __builtin_amdgcn_permlane32_swap(rl[0], rl[1], false, false);
-            pl[k] = q2[0];
-            pl[4 + k] = q2[1];
+            x3_swap64(pl[k], pl[4 + k]);
           } else {   // block 0 of the wave's 64 channels complete in qh, block 1 in ql (conv_q8_r512.h, EPI 4)
             auto sw = __builtin_amdgcn_permlane32_swap(qh[k], ql[k], false, false);
             qh[k] = sw[0];
@@ -267,6 +257,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         uint16_t* op = a.out + (((size_t)(2 * row + oa) * (size_t)(2 * a.w)) + 2 * x + ob) * (size_t)a.ldo + a.co_off +
                        ctCur * 64 + lq * 8;
         if (ok) {
+          // x3_store_plane64 (wave_tile.h) as inline text: the call spills 8 more SGPRs in MODE 0
           *reinterpret_cast<uint4*>(op) = make_uint4(ph[0], ph[1], ph[2], ph[3]);
           *reinterpret_cast<uint4*>(op + 32) = make_uint4(ph[4], ph[5], ph[6], ph[7]);
           if (!OUTQ) {
