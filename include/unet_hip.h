@@ -480,8 +480,9 @@ int unet_op_head1x1_bf16(int device, const uint16_t* x_dev, int n, int h, int w,
  * Conv3x3(2f -> f) -> scale/shift (+ ReLU) (reference README.md:1476-1479) - as the composed operator
  * (csrc/conv_x3_dec.h: the transposed convolution folded into the 3x3 convolution's up half on the host, float64).
  * skip (N,H,W,f) and x (N,H/2,W/2,2f) fp32 NHWC -> y (N,H,W,f); w_t (2f,f,2,2), b_t (f), w3 (f,2f,3,3), scale / shift (f)
- * on the host.  f 64 or 128, W % 28 == 0, H even; UNET_ERR_INVALID_ARG otherwise.  Not bit-identical to the two-kernel
- * path (a different summation). */
+ * on the host.  f 64, 128, 192 or 256 (more than 128: several channel groups per pixel tile, which the forward does not
+ * use), W % 28 == 0, H even; UNET_ERR_INVALID_ARG otherwise.  Runs the block tile unet_set_x3_dec_form selects.  Not
+ * bit-identical to the two-kernel path (a different summation). */
 int unet_op_upcat_conv3x3_x3(int device, const float* skip_dev, const float* x_dev, int n, int h, int w, int f,
                              const float* wt_host, const float* bt_host, const float* w3_host, const float* scale_host,
                              const float* shift_host, int relu, float* y_dev, void* stream);
@@ -515,6 +516,11 @@ int unet_host_plan_upconv2x2_x3(const int* query, int n_query, int* plan_out, in
  * Environment UNET_X3_COMPOSE=0 sets the initial value to 0.  A captured HIP graph keeps the setting it was captured
  * with.  Returns the previous setting. */
 int unet_set_x3_compose(int mode);
+/* Process-wide switch for the block tile of the composed decoder step (csrc/conv_x3_dec.h): -1 = automatic (default),
+ * 1 = the 64-channel form everywhere, 2 = the 128-channel form wherever f % 128 == 0 (the 64-channel form elsewhere).
+ * The two forms give bit-identical results (tests/test_x3_dec_forms_gpu.py).  Environment UNET_X3_DEC_FORM=1 or 2 sets
+ * the initial value.  A captured HIP graph keeps the setting it was captured with.  Returns the previous setting. */
+int unet_set_x3_dec_form(int mode);
 
 /* Which kernel structure the split-operand tier's ConvTranspose2d (and the plain GEMMs of its training path) run on
  * (reference README.md:1442, :1476): -1 = automatic - the one-wave-per-SIMD kernel (csrc/upconv_x3_r512.h: 224-pixel

@@ -176,6 +176,7 @@ SIGNATURES = {
     "unet_set_x3_upconv_r512": (C.c_int, [C.c_int]),
     "unet_set_x3_cross_fp8": (C.c_int, [C.c_int]),
     "unet_set_x3_compose": (C.c_int, [C.c_int]),
+    "unet_set_x3_dec_form": (C.c_int, [C.c_int]),
     "unet_op_upcat_conv3x3_x3": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "unet_host_compose_upcat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

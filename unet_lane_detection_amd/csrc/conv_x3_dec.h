@@ -128,7 +128,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     hrcX[j] = (hr << 8) | hc;
     soffX[j] = (unsigned)(((hr * wX + hc) * cX + part * 8) * 2);
   }
-  const char* zp = reinterpret_cast<const char*>(a.zeros) + (lane & 3) * 16;
+  // the zero page's 16 bytes of this lane: formed at each use (opaque laneW), a 64-bit lane pointer held instead costs two
+  // of the registers the 128-channel form does not have
+  auto zero_src = [&]() __attribute__((always_inline)) -> const char* {
+    int lw = lane * 16;
+    asm volatile("" : "+v"(lw));
+    return reinterpret_cast<const char*>(a.zeros) + (lw & 48);
+  };
   const size_t skipLoB = a.skipLo * 2, xLoB = a.xLo * 2;
 
   struct Geo {
@@ -162,9 +168,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     if (kc < a.nS) {
       int q = wave + j * 4;
       q = q < S::NQS ? q : S::NQS - 1;
-      const int hr = hrcS[j] >> 8, hc = hrcS[j] & 255;
+      int hrc = hrcS[j];
+      asm volatile("" : "+v"(hrc));   // unpacked here: hoisted out of the loops the two halves would double the table
+      const int hr = hrc >> 8, hc = hrc & 255;
       const bool ok = (unsigned)(hr - g.hrMin) <= (unsigned)g.hrSpan && (unsigned)(hc - g.hcMin) <= (unsigned)g.hcSpan;
-      const char* src = g.tb + soffS[j] + (unsigned)(kc * 64);
+      unsigned so = soffS[j];
+      asm volatile("" : "+v"(so));   // widened here: held as a 64-bit offset every entry carries a zero register
+      const char* src = g.tb + so + (unsigned)(kc * 64);
+      const char* zp = zero_src();
       lds_dma16(ok ? src : zp, dstB + q * 1024);
       lds_dma16(ok ? src + skipLoB : zp, dstB + q * 1024 + S::XPL);
     } else if (j < S::NJX) {
@@ -174,9 +185,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       const int hrMinX = i0 == 0 ? 1 : 0, hcMinX = j0 == 0 ? 1 : 0;
       const int hrMaxX = hX - i0 < S::HHX - 1 ? hX - i0 : S::HHX - 1;
       const int hcMaxX = wX - j0 < S::HWX - 1 ? wX - j0 : S::HWX - 1;
-      const int hr = hrcX[j] >> 8, hc = hrcX[j] & 255;
+      int hrc = hrcX[j];
+      asm volatile("" : "+v"(hrc));
+      const int hr = hrc >> 8, hc = hrc & 255;
       const bool ok = (unsigned)(hr - hrMinX) <= (unsigned)(hrMaxX - hrMinX) && (unsigned)(hc - hcMinX) <= (unsigned)(hcMaxX - hcMinX);
-      const char* src = g.txb + soffX[j] + (unsigned)((kc - a.nS) * 64);
+      unsigned so = soffX[j];
+      asm volatile("" : "+v"(so));
+      const char* src = g.txb + so + (unsigned)((kc - a.nS) * 64);
+      const char* zp = zero_src();
       lds_dma16(ok ? src : zp, dstB + q * 1024);
       lds_dma16(ok ? src + xLoB : zp, dstB + q * 1024 + S::XPL);
     }
@@ -240,7 +256,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     for (int f = 0; f < NF; ++f)
 #pragma unroll
       for (int cs = 0; cs < 4; ++cs) acc[f][cs] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int cbase = (gCur.cg * WCO + wc) * 64 + lq * 16;
 
     auto chunk = [&](int kc, auto xkC) __attribute__((always_inline)) {
       constexpr bool XK = decltype(xkC)::value;
@@ -337,23 +352,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #undef D4_GAP
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     };
-    for (int kc = 0; kc < nCh; ++kc, ++cc) {
-      if (kc < a.nS)
-        chunk(kc, std::false_type{});
-      else
-        chunk(kc, std::true_type{});
-    }
+    // two loops in sequence, not one loop that branches between the two unrolled bodies: with a branch the
+    // accumulators' live ranges join across both bodies and the allocator moves them about
+    for (int kc = 0; kc < a.nS; ++kc, ++cc) chunk(kc, std::false_type{});
+    for (int kc = a.nS; kc < nCh; ++kc, ++cc) chunk(kc, std::true_type{});
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // the last MFMAs' results before the first accumulator read
 
     // ---- epilogue: lane (li, lq) holds channels 16 lq + [0, 16) of its pixel of each fragment ----
     // the per-channel constants only now: 32 registers the chunk loop needs for its weight ring
+    // the lane's part of the geometry again from the thread index, opaque to the compiler: held from the kernel's
+    // start these values are live across both chunk loops, which the 128-channel form has no registers for
+    int tidE = tid;
+    asm volatile("" : "+v"(tidE));
+    const int lqE = (tidE >> 4) & 3;
+    const int cbase = (gCur.cg * WCO + wc) * 64 + lqE * 16;
     f32x4 sc[4], sh[4];
     x3_scale_shift<false>(a.scale, a.shift, cbase, sc, sh);
-    const float floorV = a.relu ? 0.f : -3.4e38f;
+    int reluE = a.relu;
+    asm volatile("" : "+s"(reluE));
+    const float floorV = reluE ? 0.f : -3.4e38f;
     const bool border = gCur.y0 == 0 || gCur.y0 + S::TH >= a.H || gCur.x0 == 0 || gCur.x0 + S::TWX >= a.W;
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
-      int liE = li;
+      int liE = tidE & 15;
       asm volatile("" : "+v"(liE));
       const int r = 2 * (liE >> 1) + pa, c = (f % CB) * 4 + 2 * (liE & 1) + pbw + f / CB;
       const int gy = gCur.y0 + r, gx = gCur.x0 + c;
@@ -375,7 +396,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       uint32_t ph[8], pl[8];
       x3_split16(v, amax, ph, pl);
       x3_swap_planes64(ph, pl);   // 64 contiguous bytes per pixel and store instruction
-      uint16_t* rowp = a.out + pix * (size_t)a.ldo + (cbase - lq * 16) + lq * 8;
+      uint16_t* rowp = a.out + pix * (size_t)a.ldo + (cbase - lqE * 16) + lqE * 8;
       // non-temporal as in conv_x3_t448.h's 64-channel form
       if (ok) x3_store_planes64<WCO == 1>(rowp, a.outLo, ph, pl);
       __builtin_amdgcn_sched_barrier(0);   // one fragment at a time: 16 values live

@@ -1146,19 +1146,33 @@ int& x3_compose_mode() {
   return mode;
 }
 
+// unet_set_x3_dec_form: which block tile the composed decoder step runs on.  -1 = automatic, 1 = the 64-channel form
+// (upcat_conv3x3_dec_f16x3_kernel<1>) everywhere, 2 = the 128-channel form (<2>) wherever f % 128 == 0.  Both forms add
+// each accumulator's terms in the same order from the same packed weights: bit-identical results.  UNET_X3_DEC_FORM=1 / 2
+// in the environment sets the initial value
+int& x3_dec_form_mode() {
+  static int mode = [] {
+    const char* e = getenv("UNET_X3_DEC_FORM");
+    return (e && (e[0] == '1' || e[0] == '2') && !e[1]) ? e[0] - '0' : -1;
+  }();
+  return mode;
+}
+
 // the composed decoder step: skip planes (n,h,w) pixel stride ldSkip, x planes (n,h/2,w/2,2f) -> out planes (n,h,w,f)
 // pixel stride ldo.  Returns false (nothing launched) where the shape rules or, with forced == false, the work count do
-// not allow it: f % 64 == 0 and f <= 128 (the 8-row, 256-channel tiles of the wider levels are not built), w % 28 == 0,
-// h even, a work item for half of the CUs and 16-row tiles filled to >= 90 %
+// not allow it: f % 64 == 0 and f <= fMax (the forward: 128 - the 8-row, 256-channel tiles of the wider levels are not
+// built; the operator entry point: 256, several channel groups per pixel tile), w % 28 == 0, h even, a work item for
+// half of the CUs and 16-row tiles filled to >= 90 %
 bool run_upcat_x3(const DecOpX3& op, const uint16_t* zeros, const uint16_t* skip, size_t skipLo, int ldSkip, const uint16_t* x,
-                  size_t xLo, int n, int h, int w, uint16_t* out, size_t outLo, int ldo, bool forced, hipStream_t s,
+                  size_t xLo, int n, int h, int w, uint16_t* out, size_t outLo, int ldo, bool forced, int fMax, hipStream_t s,
                   hipError_t* err) {
   *err = hipSuccess;
   const int f = op.f;
-  if (!op.wt || f % 64 || f > 128 || w % 28 || h % 2 || h < 2) return false;
-  // 64 output channels per block at both levels: the 128-channel form (two column parities per wave, 14 fragments)
-  // spills 200 registers to scratch beside its 224 accumulators and the four-tap weight ring
-  const int wco = 1;
+  if (!op.wt || f % 64 || f > fMax || w % 28 || h % 2 || h < 2) return false;
+  // 128 output channels per block where the channels allow (the 112 x 112 level of model A): both halos staged once per
+  // pixel tile instead of twice, every skip weight fragment serves 14 pixel fragments instead of 7
+  const int form = x3_dec_form_mode();
+  const int wco = (form != 1 && f % 128 == 0) ? 2 : 1;
   unet::UpcatX3Args a;
   a.skip = skip;
   a.skipLo = skipLo;
@@ -1200,7 +1214,7 @@ bool run_upcat_x3(const DecOpX3& op, const uint16_t* zeros, const uint16_t* skip
     }
     return e;
   };
-  *err = launch(unet::upcat_conv3x3_dec_f16x3_kernel<1>);
+  *err = wco == 2 ? launch(unet::upcat_conv3x3_dec_f16x3_kernel<2>) : launch(unet::upcat_conv3x3_dec_f16x3_kernel<1>);
   prof_end(s);
   return true;
 }
@@ -1535,7 +1549,7 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
     if (!qs && x3_compose_mode() != 0) {
       hipError_t ec;
       composed = run_upcat_x3(X->comp[j], X->zeros, U(p.cat[l]), p.cat[l].elems, 2 * f, U(*cur), cur->elems, n, 2 * ch, 2 * cw,
-                              U(p.tmpA), p.tmpA.elems, f, x3_compose_mode() == 1, s, &ec);
+                              U(p.tmpA), p.tmpA.elems, f, x3_compose_mode() == 1, 128, s, &ec);
       HIPCHK(h->err, ec);
     }
     ch *= 2;
@@ -1701,7 +1715,7 @@ float unet_debug_act_scale(float gamma, float beta) { return act_from_bn(&gamma,
 int unet_op_upcat_conv3x3_x3(int device, const float* skip, const float* x, int n, int hh, int ww, int f, const float* wt,
                              const float* bt, const float* w3, const float* scale, const float* shift, int relu, float* y,
                              void* stream) {
-  if (!skip || !x || !wt || !bt || !w3 || !scale || !shift || !y || n < 1 || f % 64 || f > 128 || ww % 28 || hh % 2 || hh < 2)
+  if (!skip || !x || !wt || !bt || !w3 || !scale || !shift || !y || n < 1 || f % 64 || f > 256 || ww % 28 || hh % 2 || hh < 2)
     return op_bad_args();
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
@@ -1719,7 +1733,7 @@ int unet_op_upcat_conv3x3_x3(int device, const float* skip, const float* x, int 
   if (e == hipSuccess) {
     split_to_planes(skip, es, ps, s);
     split_to_planes(x, ex, pxl, s);
-    if (!run_upcat_x3(g.op, zeros, ps, es, f, pxl, ex, n, hh, ww, po, eo, f, true, s, &e) && e == hipSuccess)
+    if (!run_upcat_x3(g.op, zeros, ps, es, f, pxl, ex, n, hh, ww, po, eo, f, true, 256, s, &e) && e == hipSuccess)
       e = hipErrorInvalidValue;
   }
   if (e == hipSuccess) {
@@ -1788,6 +1802,12 @@ int unet_host_plan_upconv2x2_x3(const int* query, int nQuery, int* planOut, int 
 int unet_set_x3_compose(int mode) {
   const int prev = x3_compose_mode();
   x3_compose_mode() = mode < 0 ? -1 : (mode > 1 ? 1 : mode);
+  return prev;
+}
+
+int unet_set_x3_dec_form(int mode) {
+  const int prev = x3_dec_form_mode();
+  x3_dec_form_mode() = (mode == 1 || mode == 2) ? mode : -1;
   return prev;
 }
 
