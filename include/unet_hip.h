@@ -638,6 +638,32 @@ int unet_num_range_tensors(unet_handle_t h);
 int unet_forward_u8_ranges(unet_handle_t h, const uint8_t* frames_dev, int n, int height, int width,
                            float* ranges_host, void* stream);
 
+/* Calibration beyond min/max (README.md:3407-3412 'mmse' / 'kl_divergence'): the distribution of every range tensor.
+ * Binning rule (csrc/calib_kernels.cpp; quant.histogram_model restates it bit for bit): inv = float(bins) / (hi - lo)
+ * in fp32; per element t = (v - lo) * inv, one fp32 subtraction and one fp32 multiplication; bin 0 for t < 0,
+ * bins - 1 for t >= bins, else (int)t.  NaN is counted nowhere; an element equal to 0 is counted in no bin but in word
+ * `bins`, so a histogram is bins + 1 64-bit words whose sum is the number of non-NaN elements.  bins: a power of two
+ * from 64 to 4096.  The words are added to, never cleared.
+ *
+ * unet_op_histogram_f32: the kernel on its own (test entry point): x_dev is npix pixels of c channels at pixel stride
+ * ld (floats).  UNET_ERR_INVALID_ARG for hi <= lo, a span that is not finite, unsupported bins, c > ld or null
+ * pointers, before anything is launched.  Synchronises the stream.
+ *
+ * unet_forward_u8_histograms: the forward of unet_forward_u8_ranges with a histogram behind every layer instead:
+ * spans_host holds (lo, hi) per tensor and hist_dev bins + 1 words per tensor, both in the order of
+ * quant.tensor_names(); hist_dev accumulates across calls (clear it before the first).  Tensor 0, the input, is counted
+ * over its 3 real channels.  No host synchronisation. */
+int unet_op_histogram_f32(int device, const float* x_dev, size_t npix, int c, int ld, float lo, float hi, int bins,
+                          unsigned long long* hist_dev, void* stream);
+int unet_forward_u8_histograms(unet_handle_t h, const uint8_t* frames_dev, int n, int height, int width,
+                               const float* spans_host, int bins, unsigned long long* hist_dev, void* stream);
+
+/* The reference's acceptance check of a quantised model (README.md:3512-3565 `compare_outputs`): acc_dev[f] += the sum
+ * over frame f of |pa - pb| for `frames` frames of per_frame floats each (probabilities of two tiers on the same
+ * frames).  Every term is an fp32 value, the sums are float64 in a fixed order.  No host synchronisation. */
+int unet_prob_mae_accumulate(int device, const float* pa_dev, const float* pb_dev, int frames, size_t per_frame,
+                             double* acc_dev, void* stream);
+
 /* ---- camera stage on the GPU ----------------------------------------------------
  * Replaces the OpenCV calls of the reference's ROS callback (src/unet_ros_node.py:296-311) and of
  * RKNNLaneInference.preprocess_image / postprocess_output (src/unet.py:33, :70).  Integer arithmetic restated from

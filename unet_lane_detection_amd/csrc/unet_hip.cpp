@@ -46,6 +46,7 @@
 #include "wgrad_gemm_f32.h"
 #include "wgrad_x3_ws.h"
 #include "camera_stage.h"
+#include "calib_kernels.h"
 
 namespace {
 
@@ -579,6 +580,11 @@ struct unet_ctx {
   unsigned* errHost = nullptr;
   unsigned* errDev = nullptr;
   unsigned* rangeKeys = nullptr;   // calibration pass (unet_forward_u8_ranges): 2 order keys per activation tensor
+  // histogram pass (unet_forward_u8_histograms), armed while hist is set: (lo, hi) per tensor on the host, bins + 1
+  // words per tensor on the device
+  unsigned long long* hist = nullptr;
+  const float* histSpans = nullptr;
+  int histBins = 0;
   void ensure_err_word() {
     if (errHost) return;
     if (hipHostMalloc((void**)&errHost, 2 * sizeof(unsigned), hipHostMallocMapped) != hipSuccess) {
@@ -736,8 +742,19 @@ int forward_common(unet_ctx* h, int n, int height, int width, float* logits, flo
   int ch = height, cw = width;
   float* tmpA = ws + p.tmpA;
   float* tmpB = ws + p.tmpB;
-  // calibration pass: (min, max) of tensor `idx` (order: quant.tensor_names) right after it has been produced
+  // calibration passes, on tensor `idx` (order: quant.tensor_names) right after it has been produced: its (min, max),
+  // or its histogram over the span the caller gave for it
+  hipError_t histStatus = hipSuccess;   // the first failing histogram launch, reported when the walk is through
   auto probe = [&](int idx, const float* x, size_t npx, int cc, int ld) {
+    if (h->hist) {
+      // the input is counted over its real channels: the pad channel of the NHWC4 image would add 25 % exact zeros
+      // that the int8 input never holds
+      const hipError_t e = unet::launch_histogram_f32(x, npx, idx == 0 ? c.in_channels : cc, ld, h->histSpans[2 * idx],
+                                                      h->histSpans[2 * idx + 1], h->histBins,
+                                                      h->hist + (size_t)idx * (h->histBins + 1), s);
+      if (histStatus == hipSuccess) histStatus = e;
+      return;
+    }
     if (!h->rangeKeys) return;
     hipLaunchKernelGGL(unet::minmax_f32_kernel, dim3(grid_for(npx * cc)), dim3(256), 0, s, x, npx, cc, ld,
                        h->rangeKeys + 2 * idx);
@@ -784,6 +801,7 @@ int forward_common(unet_ctx* h, int n, int height, int width, float* logits, flo
   }
   HIPCHK(h->err, run_head(cur, h->headW, h->headB, (size_t)n * height * width, c.features[0], logits, probs, mask,
                           thr, s));
+  HIPCHK(h->err, histStatus);
   return h->async_error();
 }
 

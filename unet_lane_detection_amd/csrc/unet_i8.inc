@@ -562,4 +562,58 @@ int unet_forward_u8_ranges(unet_handle_t h, const uint8_t* frames, int n, int he
   return rc ? rc : rc2;
 }
 
+// ---- histogram calibration ('mmse', 'kl_divergence'): the distribution of every range tensor over a given span ----
+// The kernel on its own (tests): hist_dev[0 .. bins] += the histogram of x over [lo, hi), exact zeros in word `bins`.
+int unet_op_histogram_f32(int device, const float* x, size_t npix, int c, int ld, float lo, float hi, int bins,
+                          unsigned long long* histDev, void* stream) {
+  if (!x || !histDev || npix == 0 || c < 1 || c > ld || !unet::histogram_bins_supported(bins) || !(hi > lo) ||
+      !std::isfinite(lo) || !std::isfinite(hi) || !std::isfinite(hi - lo) || !std::isfinite(unet::histogram_inv(lo, hi, bins)))
+    return op_bad_args();
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  return op_done(unet::launch_histogram_f32(x, npix, c, ld, lo, hi, bins, histDev, s), s, kOpMapCodes);
+}
+
+// The forward of unet_forward_u8_ranges with the probes in their second mode: tensor i (order: quant.tensor_names) is
+// binned over spans_host[2 i], spans_host[2 i + 1] into hist_dev[i * (bins + 1) ...], which accumulates across calls and
+// stays on the device.  No host synchronisation.
+int unet_forward_u8_histograms(unet_handle_t h, const uint8_t* frames, int n, int height, int width,
+                               const float* spansHost, int bins, unsigned long long* histDev, void* stream) {
+  if (!h || !frames || !spansHost || !histDev) return UNET_ERR_INVALID_ARG;
+  if (!unet::histogram_bins_supported(bins)) {
+    h->err = "histogram bins must be a power of two from 64 to 4096";
+    return UNET_ERR_INVALID_ARG;
+  }
+  const int nt = unet_num_range_tensors(h);
+  for (int i = 0; i < nt; ++i) {
+    const float lo = spansHost[2 * i], hi = spansHost[2 * i + 1];
+    if (!(hi > lo) || !std::isfinite(hi - lo) || !std::isfinite(unet::histogram_inv(lo, hi, bins))) {
+      h->err = "histogram span of range tensor " + std::to_string(i) + " is empty or not finite";
+      return UNET_ERR_INVALID_ARG;
+    }
+  }
+  h->hist = histDev;
+  h->histSpans = spansHost;
+  h->histBins = bins;
+  const int rc = unet_forward_u8(h, frames, n, height, width, nullptr, nullptr, nullptr, 0.f, stream);
+  h->hist = nullptr;
+  h->histSpans = nullptr;
+  h->histBins = 0;
+  return rc;
+}
+
+// compare_outputs (reference README.md:3512-3565): acc_dev[f] += sum over frame f of |pa - pb|, f < frames, each frame
+// per_frame floats.  Two fixed-order passes into float64; no host synchronisation.
+int unet_prob_mae_accumulate(int device, const float* paDev, const float* pbDev, int frames, size_t perFrame,
+                             double* accDev, void* stream) {
+  if (!paDev || !pbDev || !accDev || frames < 1 || frames > 65535 || perFrame == 0) return op_bad_args();
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  double* partial = nullptr;
+  HIPCHK(g_opErr, hipMallocAsync((void**)&partial, (size_t)frames * unet::MAE_BLOCKS_PER_FRAME * sizeof(double), s));
+  const hipError_t e = unet::launch_prob_mae(paDev, pbDev, frames, perFrame, partial, accDev, s);
+  HIPCHK(g_opErr, hipFreeAsync(partial, s));
+  return op_done(e, s, kOpNoSync);
+}
+
 }  // extern "C"

@@ -3,8 +3,11 @@
 `RKNN_model_container.run` (src/py_utils/rknn_executor.py:26-38): uint8 NHWC frames in, probabilities out.
 
   ranges = calibrate(float_model, frames)                  # device pass over calibration frames (README.md:3046-3078)
+  ranges = calibrate(float_model, frames, algorithm="mmse")    # or "kl_divergence" (README.md:3407-3412): a second device
+                                                           # pass takes histograms, the host chooses ranges from them
   qmodel = quant.quantize_model(state_dict, ranges)        # README.md:3106-3116 scheme, host arithmetic on weights
   net = UNetInt8(qmodel, device=0); net.run_u8(frames)
+  compare_outputs(float_model, net, frames)                # float-vs-int8 MAE of probabilities (README.md:3512-3565)
 
 All arithmetic on activations runs in libunet_hip.so (csrc/conv_i8.h); there is no CPU fallback.
 """
@@ -19,16 +22,55 @@ from . import _lib, quant
 from .model import _logit, _pack
 
 
-def calibrate(float_model, frames_u8, batch=8):
+def calibrate(float_model, frames_u8, batch=8, algorithm="normal", bins=quant.HIST_BINS, return_histograms=False):
     """Per-tensor activation ranges of the float network over `frames_u8` ((N,H,W,3) uint8, host or device):
-    {tensor name: (min, max)} for quant.quantize_model.  Runs the fp32 HIP tier with a min/max probe behind every
-    layer (unet_forward_u8_ranges); frames are processed `batch` at a time and the ranges merged."""
+    {tensor name: (r_min, r_max)} for quant.quantize_model, by the reference's `quantized_algorithm`
+    (README.md:3407-3412):
+
+      "normal"          (min, max): the fp32 HIP tier with a min/max probe behind every layer
+                        (unet_forward_u8_ranges); frames are processed `batch` at a time and the ranges merged;
+      "mmse",           that pass first; its ranges, widened to contain 0, are the spans of a second pass over the same
+      "kl_divergence"   frames with a histogram of `bins` bins behind every layer (unet_forward_u8_histograms).  The
+                        histograms stay on the device across batches and are read once; quant.range_from_histogram
+                        then chooses every tensor's range inside its (min, max).
+
+    return_histograms: also return {tensor name: (uint64 histogram[bins + 1], lo, hi)} (quant.histogram_model's
+    layout; None for "normal").  Raises ValueError when a tensor holds NaN."""
+    if algorithm not in quant.ALGORITHMS:
+        raise ValueError(f"algorithm={algorithm!r}: one of {quant.ALGORITHMS}")
+    names = quant.tensor_names(len(float_model.features))
+    frames = torch.as_tensor(frames_u8)
+    normal = minmax_pass(float_model, frames, batch)
+    if algorithm == "normal":
+        return (normal, None) if return_histograms else normal
+    for k in names:        # the order keys of the range pass put NaN beyond +-inf: it shows as a bound
+        if not (np.isfinite(normal[k][0]) and np.isfinite(normal[k][1])):
+            raise ValueError(f"calibrate: tensor {k!r} holds NaN or inf (range {normal[k]}); its range cannot be chosen")
+    # a tensor that is 0 everywhere has no span to bin: it is counted over (0, 1) and keeps its (min, max)
+    spans = np.array([(min(lo, 0.0), max(hi, 0.0)) for lo, hi in (normal[k] for k in names)], dtype=np.float32)
+    dead = ~(spans[:, 1] > spans[:, 0])
+    spans[dead] = (0.0, 1.0)
+    hist_dev, elements = histogram_pass(float_model, frames, spans, bins, batch)
+    hist = hist_dev.cpu().numpy().view(np.uint64)
+    ranges, hists = {}, {}
+    for i, name in enumerate(names):
+        counted = int(hist[i].sum())
+        if counted != int(elements[i]):
+            raise ValueError(f"calibrate: tensor {name!r} holds {int(elements[i]) - counted} NaN of {int(elements[i])} "
+                             "elements; its range cannot be chosen")
+        lo, hi = float(spans[i, 0]), float(spans[i, 1])
+        hists[name] = (hist[i].copy(), lo, hi)
+        ranges[name] = normal[name] if dead[i] else quant.range_from_histogram(hist[i], lo, hi, algorithm)
+    return (ranges, hists) if return_histograms else ranges
+
+
+def minmax_pass(float_model, frames, batch=8):
+    """{tensor name: (min, max)} over `frames`: the range pass of calibrate (one host read per batch)."""
     lib = _lib.load()
     h = float_model._h
     nt = int(lib.unet_num_range_tensors(h))
     names = quant.tensor_names(len(float_model.features))
     assert nt == len(names), (nt, names)
-    frames = torch.as_tensor(frames_u8)
     lo = np.full(nt, np.inf)
     hi = np.full(nt, -np.inf)
     buf = (C.c_float * (2 * nt))()
@@ -42,6 +84,84 @@ def calibrate(float_model, frames_u8, batch=8):
         lo = np.minimum(lo, r[:, 0])
         hi = np.maximum(hi, r[:, 1])
     return {name: (float(lo[i]), float(hi[i])) for i, name in enumerate(names)}
+
+
+def histogram_pass(float_model, frames, spans, bins=quant.HIST_BINS, batch=8):
+    """The histogram pass of calibrate: every range tensor of the float network over `frames`, binned over its row of
+    `spans` ((tensors, 2) float32: lo, hi).  Returns the (tensors, bins + 1) int64 device tensor of 64-bit counters,
+    which stayed on the device across the batches and has not been waited for, and every tensor's element count."""
+    lib = _lib.load()
+    h = float_model._h
+    nt = int(lib.unet_num_range_tensors(h))
+    spans = np.ascontiguousarray(spans, dtype=np.float32)
+    if spans.shape != (nt, 2):
+        raise ValueError(f"spans must be ({nt}, 2)")
+    hist_dev = torch.zeros((nt, bins + 1), dtype=torch.int64, device=float_model.device)
+    elements = np.zeros(nt, dtype=np.int64)
+    shapes = quant.tensor_shapes(float_model.features)
+    for i in range(0, frames.shape[0], batch):
+        f = frames[i:i + batch].to(float_model.device).contiguous()
+        n, hh, ww, _ = f.shape
+        rc = lib.unet_forward_u8_histograms(h, C.c_void_p(f.data_ptr()), n, hh, ww, spans.ctypes.data_as(C.c_void_p),
+                                            int(bins), C.c_void_p(hist_dev.data_ptr()),
+                                            C.c_void_p(torch.cuda.current_stream(float_model.device).cuda_stream))
+        _lib.check(rc, "unet_forward_u8_histograms", h)
+        elements += [n * (hh >> level) * (ww >> level) * c for c, level in shapes]
+    return hist_dev, elements
+
+
+class OutputComparison:
+    """Per-frame mean absolute error between the probabilities of two tiers, with the reference's verdict on their mean
+    (README.md:3553-3562): GOOD below 0.05, ACCEPTABLE below 0.10, POOR otherwise.  Pure numpy."""
+    GOOD, ACCEPTABLE = 0.05, 0.10
+
+    def __init__(self, per_frame):
+        self.per_frame = np.asarray(per_frame, dtype=np.float64).reshape(-1).copy()
+        if self.per_frame.size == 0:
+            raise ValueError("OutputComparison needs at least one frame")
+        self.mean = float(self.per_frame.mean())
+        self.max = float(self.per_frame.max())
+
+    @property
+    def grade(self):
+        return "GOOD" if self.mean < self.GOOD else "ACCEPTABLE" if self.mean < self.ACCEPTABLE else "POOR"
+
+    def __repr__(self):
+        return "OutputComparison(frames=%d, mean=%.6f, max=%.6f, grade=%s)" % (self.per_frame.size, self.mean, self.max,
+                                                                             self.grade)
+
+
+def prob_mae(probs_a, probs_b):
+    """Per-frame sum of |a - b| over two (N, ...) float32 device tensors divided by the frame size, as a float64 device
+    tensor (unet_prob_mae_accumulate: the sums are formed on the device)."""
+    if probs_a.shape != probs_b.shape or probs_a.dtype != torch.float32 or probs_b.dtype != torch.float32:
+        raise ValueError("prob_mae takes two float32 tensors of one shape")
+    if probs_a.device != probs_b.device or probs_a.device.type != "cuda":
+        raise ValueError("prob_mae takes two tensors on one HIP device")
+    a, b = probs_a.contiguous(), probs_b.contiguous()
+    n = int(a.shape[0])
+    acc = torch.zeros(n, dtype=torch.float64, device=a.device)
+    rc = _lib.load().unet_prob_mae_accumulate(a.device.index, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), n,
+                                              a.numel() // n, C.c_void_p(acc.data_ptr()),
+                                              C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
+    _lib.check(rc, "unet_prob_mae_accumulate")
+    return acc / (a.numel() // n)
+
+
+def compare_outputs(float_model, int8_net, frames_u8, batch=8):
+    """The reference's `compare_outputs` (README.md:3512-3565): per-frame MAE between the probabilities of the float
+    tier (fp32) and of the int8 tier over `frames_u8` ((N,H,W,3) uint8).  The probabilities stay on the device, where
+    each frame's |difference| is summed in float64; one number per frame is read.  Returns OutputComparison."""
+    frames = torch.as_tensor(frames_u8)
+    if float_model.device != int8_net.device:
+        raise ValueError("compare_outputs needs both tiers on one device")
+    out = []
+    for i in range(0, frames.shape[0], batch):
+        f = frames[i:i + batch].to(float_model.device).contiguous()
+        _, pf = float_model.run_u8(f, return_probs=True)
+        _, pq = int8_net.run_u8(f, return_probs=True)
+        out.append(prob_mae(pf, pq))
+    return OutputComparison(torch.cat(out).cpu().numpy())
 
 
 class UNetInt8:

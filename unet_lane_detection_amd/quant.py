@@ -12,8 +12,9 @@ with q in [-128, 127].  The conversion itself happens inside Rockchip's closed t
 Parity against the shipped .rknn blobs is **unpinned** (they cannot be executed and hold no float weights).
 
 Scheme implemented here (the integer-exact contract of the int8 tier; oracle/int8_oracle.py restates the forward):
-  * activations: per-tensor asymmetric int8; (r_min, r_max) from calibration ("normal" = min/max), widened to contain
-    0 so that zero is exactly representable (padding, ReLU);
+  * activations: per-tensor asymmetric int8; (r_min, r_max) from calibration ("normal" = min/max; "mmse" and
+    "kl_divergence" choose a range inside min/max from a device histogram: range_from_histogram below), widened to
+    contain 0 so that zero is exactly representable (padding, ReLU);
   * weights: per-output-channel ('channel') asymmetric int8 of the BatchNorm-folded weights (the blob's 14 ConvRelu
     nodes carry folded weight/bias pairs, SURVEY.md section 2);
   * bias: int32 in units of x_scale * w_scale[co];
@@ -90,6 +91,166 @@ def tensor_names(depth):
     for j in range(depth):
         names += [f"dec{j}.a", f"dec{j}.b"]
     return names
+
+
+def tensor_shapes(features):
+    """(channels, pooling level) of every tensor of tensor_names(len(features)), in that order: the tensor holds
+    N * (H >> level) * (W >> level) * channels elements (the input counts its 3 real channels)."""
+    d = len(features)
+    shapes = [(3, 0)]
+    for l in range(d):
+        shapes += [(features[l], l), (2 * features[l], l)]
+    shapes += [(2 * features[-1], d)] * 2
+    for j in range(d):
+        shapes += [(features[d - 1 - j], d - 1 - j)] * 2
+    return shapes
+
+
+# ---- calibration algorithms beyond min/max (README.md:3407-3412: 'normal', 'mmse', 'kl_divergence') ----------------
+ALGORITHMS = ("normal", "mmse", "kl_divergence")
+HIST_BINS = 2048            # default resolution of a calibration histogram
+KL_MIN_BINS = 128           # 'kl_divergence' skips candidates that keep fewer bins than this
+
+
+def _f32_span(lo, hi, bins):
+    """(lo, inv) of the binning rule in float32: inv = float32(bins) / (hi - lo)."""
+    lo32, hi32 = np.float32(lo), np.float32(hi)
+    with np.errstate(all="ignore"):
+        inv = np.float32(bins) / (hi32 - lo32)
+    if not (hi32 > lo32) or not np.isfinite(inv) or not inv > 0:
+        raise ValueError(f"histogram span ({lo}, {hi}) is empty or not finite")
+    return lo32, inv
+
+
+def _bin_index(v, lo32, inv, bins):
+    """Bin of every element of the float32 array v (NaN: undefined, callers mask it):
+    t = (v - lo) * inv in float32, two roundings; 0 below the span, bins - 1 at or above its end, else trunc(t)."""
+    with np.errstate(all="ignore"):
+        t = (v - lo32) * inv
+    idx = np.zeros(t.shape, dtype=np.int64)
+    inside = (t >= 0) & (t < bins)
+    idx[inside] = t[inside].astype(np.int64)
+    idx[t >= bins] = bins - 1
+    return idx
+
+
+def histogram_model(values, lo, hi, bins, c=None, ld=None):
+    """numpy restatement, bit for bit, of the device histogram (csrc/calib_kernels.cpp, include/unet_hip.h): uint64
+    [bins + 1].  Words 0 .. bins - 1: the elements binned over [lo, hi) in float32 arithmetic, elements outside the
+    span in the first / last bin; word `bins`: the elements equal to 0 (either sign), which are in no bin.  NaN is not
+    counted.  c, ld: `values` is pixels of ld floats of which the first c are counted."""
+    v = np.ascontiguousarray(np.asarray(values, dtype=np.float32)).reshape(-1)
+    if c is not None or ld is not None:
+        if c is None or ld is None or not 1 <= c <= ld:
+            raise ValueError("c and ld go together, 1 <= c <= ld")
+        v = v.reshape(-1, ld)[:, :c].reshape(-1)
+    lo32, inv = _f32_span(lo, hi, bins)
+    zero = v == 0
+    counted = ~zero & ~np.isnan(v)
+    out = np.zeros(bins + 1, dtype=np.uint64)
+    out[:bins] = np.bincount(_bin_index(v[counted], lo32, inv, bins), minlength=bins).astype(np.uint64)
+    out[bins] = np.uint64(int(zero.sum()))
+    return out
+
+
+def zero_bin(lo, hi, bins):
+    """The bin the binning rule gives the value 0 (where the exact-zero word belongs when a histogram is folded)."""
+    lo32, inv = _f32_span(lo, hi, bins)
+    return int(_bin_index(np.zeros(1, dtype=np.float32), lo32, inv, bins)[0])
+
+
+def bin_centres(lo, hi, bins):
+    """float64 value a non-zero bin stands for: lo + (k + 0.5) (hi - lo) / bins."""
+    return float(lo) + (np.arange(bins, dtype=np.float64) + 0.5) * (float(hi) - float(lo)) / bins
+
+
+def _mmse_error(v, w, r_min, r_max):
+    scale, zp = affine_params(r_min, r_max)
+    e = dequantize(quantize(v, scale, zp), scale, zp) - v
+    return float(np.dot(w, e * e))
+
+
+def mmse_objective(hist, lo, hi, r_min, r_max):
+    """sum count * (dequantize(quantize(v)) - v)^2 of a histogram under affine_params(r_min, r_max); the zero word stands
+    for the value 0."""
+    hist = np.asarray(hist)
+    v = np.append(bin_centres(lo, hi, hist.size - 1), 0.0)
+    return _mmse_error(v, hist.astype(np.float64), r_min, r_max)
+
+
+def _kl_objective(h, centres, r_min, r_max):
+    """KL(P || Q) of the folded histogram h clipped to [r_min, r_max]; None when fewer than KL_MIN_BINS bins are kept."""
+    keep = np.nonzero((centres >= r_min) & (centres <= r_max))[0]
+    if keep.size < KL_MIN_BINS:
+        return None
+    first, last = int(keep[0]), int(keep[-1])
+    own = h[first:last + 1]
+    p = own.copy()
+    p[0] += h[:first].sum()
+    p[-1] += h[last + 1:].sum()
+    total = p.sum()
+    if total <= 0:
+        return 0.0
+    scale, zp = affine_params(r_min, r_max)
+    code = quantize(centres[first:last + 1], scale, zp).astype(np.int64)
+    code -= code.min()
+    live = p > 0
+    mass = np.bincount(code, weights=own)
+    members = np.bincount(code, weights=live.astype(np.float64))
+    q = (mass[code] / np.maximum(members[code], 1.0))[live]
+    if np.any(q <= 0):          # mass beyond an end whose code holds none of the kept mass: nothing to model it with
+        return float("inf")
+    pn = p[live] / total
+    return float(np.sum(pn * np.log(pn / (q / q.sum()))))
+
+
+def range_from_histogram(hist, lo, hi, algorithm, steps=64):
+    """(r_min, r_max) for affine_params from a histogram (histogram_model layout) taken over [lo, hi).
+
+    'normal': (lo, hi).  Otherwise the candidates (a / steps * lo', b / steps * hi'), a, b = 1 .. steps, of the span
+    widened to contain 0 (an end that is 0 keeps its factor at 1) are scored and the best is returned, ties going to the
+    wider candidate (larger b, then larger a):
+      'mmse'           sum count * (dequantize(quantize(v)) - v)^2, every non-zero bin standing for its centre and
+                       the zero word for 0;
+      'kl_divergence'  sum_{P>0} p log(p / q): the zero word is added to the bin that contains 0; P is the histogram over
+                       the bins whose centres lie inside the candidate, mass outside added to the first / last kept
+                       bin; Q groups the kept bins by their int8 code and spreads each group's own mass - the kept
+                       bins' counts, before the outside mass went to P's edges - evenly over its bins with P > 0; both
+                       normalised; candidates that keep fewer than KL_MIN_BINS bins are skipped, and one whose edge
+                       code holds none of the kept mass while mass lies beyond it scores +inf.  (Q is built from the
+                       kept counts, as in the published entropy calibration, so that clipping costs something: built
+                       from P, every candidate of at most 256 kept bins has one bin per code, Q = P and KL = 0, and
+                       at 2048 bins the search then returns an eighth of the span.)
+    The result lies within [min(lo, 0), max(hi, 0)] and contains 0."""
+    if algorithm not in ALGORITHMS:
+        raise ValueError(f"algorithm={algorithm!r}: one of {ALGORITHMS}")
+    if algorithm == "normal":
+        return float(lo), float(hi)
+    hist = np.asarray(hist)
+    bins = hist.size - 1
+    _f32_span(lo, hi, bins)
+    lo_w, hi_w = min(float(lo), 0.0), max(float(hi), 0.0)
+    centres = bin_centres(lo, hi, bins)
+    if algorithm == "mmse":
+        used = np.nonzero(hist[:bins])[0]               # the zero word's own error is 0 under every candidate
+        v, w = centres[used], hist[used].astype(np.float64)
+
+        def objective(r_min, r_max):
+            return _mmse_error(v, w, r_min, r_max)
+    else:
+        h = hist[:bins].astype(np.float64)
+        h[zero_bin(lo, hi, bins)] += float(hist[bins])
+
+        def objective(r_min, r_max):
+            return _kl_objective(h, centres, r_min, r_max)
+    best, best_range = None, (lo_w, hi_w)
+    for b in (range(steps, 0, -1) if hi_w > 0 else (steps,)):          # widest first: a tie keeps what it has
+        for a in (range(steps, 0, -1) if lo_w < 0 else (steps,)):
+            cand = (a / steps * lo_w, b / steps * hi_w)
+            score = objective(*cand)
+            if score is not None and (best is None or score < best):
+                best, best_range = score, cand
+    return best_range
 
 
 def conv_units(features):
