@@ -521,6 +521,40 @@ int unet_set_x3_compose(int mode);
  * The two forms give bit-identical results (tests/test_x3_dec_forms_gpu.py).  Environment UNET_X3_DEC_FORM=1 or 2 sets
  * the initial value.  A captured HIP graph keeps the setting it was captured with.  Returns the previous setting. */
 int unet_set_x3_dec_form(int mode);
+/* Process-wide switch for the split form of the decoder step on the levels with f % 256 == 0 and a low-resolution map at
+ * most 28 wide (csrc/upconv_x3_win.h + the addend epilogue of csrc/conv_x3_t448.h; DESIGN.md, "The decoder's composed
+ * first convolution"): 1 = on (default; environment UNET_X3_COMPOSE_DEEP=0 makes it 0), 0 = those levels keep the
+ * two-kernel path.  unet_set_x3_compose(0) turns it off together with the composed operator; unet_set_x3_compose(1) lifts
+ * its work-item rule as well.  Returns the previous setting. */
+int unet_set_x3_compose_deep(int on);
+/* The two launches of that step on caller-owned planes (layouts as in "The split-operand tier's operators on planes").
+ * wt_host (2f,f,2,2), bt_host (f), w3_host (f,2f,3,3); h, w: the low-resolution map of x, 4 <= w <= 28.
+ * unet_op_updeep_window_x3_planes: kernel 1 alone.  x (N,h,w,2f) -> P, the up half of the 3x3 convolution with the
+ *   border-class constants, into channels [co_off, co_off + f) of y (N,2h,2w,ldo); f a multiple of 64; in_act_host (2f)
+ *   or NULL.
+ * unet_op_updeep_conv3x3_x3_planes: both kernels.  cat (N,2h,2w,2f): the skip in channels [0,f) (read only), P is
+ *   written to channels [f,2f); out (N,2h,2w,f) = relu?((conv3x3(skip) + P) scale + shift); f a multiple of 256;
+ *   x_act_host (2f) / skip_act_host (f) or NULL.
+ * UNET_ERR_INVALID_ARG for a shape neither kernel takes. */
+int unet_op_updeep_window_x3_planes(int device, const uint16_t* x_dev, size_t x_lo_off, int n, int h, int w, int f,
+                                    const float* wt_host, const float* bt_host, const float* w3_host,
+                                    const float* in_act_host, uint16_t* y_dev, size_t y_lo_off, int ldo, int co_off,
+                                    int* range_out, void* stream);
+int unet_op_updeep_conv3x3_x3_planes(int device, const uint16_t* x_dev, size_t x_lo_off, int n, int h, int w, int f,
+                                     const float* wt_host, const float* bt_host, const float* w3_host,
+                                     const float* scale_host, const float* shift_host, int relu, const float* x_act_host,
+                                     const float* skip_act_host, uint16_t* cat_dev, size_t cat_lo_off, uint16_t* out_dev,
+                                     size_t out_lo_off, int* range_out, void* stream);
+/* Test hooks, host arithmetic only.  unet_host_pack_updeep_x3: what kernel 1 is given - ordered_out: the float64 window
+ * weights at the hi-plane positions of the pack [f/64][2f/32][tap = di * 2 + dj][plane 2][parity 4][cs 4][lane 64][8]
+ * (row j = lane & 15 of subtile cs is channel 64 ct + 16 (j >> 2) + 4 cs + (j & 3), input channel 32 kc + 8 (lane >> 4)
+ * + e), packed_out: the fp16 hi / lo planes of weight / x_act * pre, pre_out [f], cls_out [9][f] in float64 (the kernel
+ * is given them rounded to fp32).
+ * unet_host_plan_updeep_x3: query[7] = n, h, w, f, compose mode, deep switch, f16q8 on -> plan_out[8] = taken, kernel 1's
+ * widest map / pixel tiles / channel tiles / grid, kernel 2's grid / flat tiling / pixel tiles (all 0: declined). */
+int unet_host_pack_updeep_x3(const float* wt_host, const float* bt_host, const float* w3_host, int f, const float* x_act_host,
+                             double* ordered_out, uint16_t* packed_out, float* pre_out, double* cls_out);
+int unet_host_plan_updeep_x3(const int* query, int n_query, int* plan_out, int n_plan);
 
 /* Which kernel structure the split-operand tier's ConvTranspose2d (and the plain GEMMs of its training path) run on
  * (reference README.md:1442, :1476): -1 = automatic - the one-wave-per-SIMD kernel (csrc/upconv_x3_r512.h: 224-pixel

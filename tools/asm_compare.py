@@ -31,7 +31,9 @@ def parse(path):
             if cur:
                 bodies[cur] = []
             continue
-        s = line.split(";")[0].strip()
+        # block labels carry the function's ordinal in the module (.LBB<function>_<block>): a kernel added ahead of this one
+        # renumbers them without touching the text
+        s = re.sub(r"\.LBB\d+_", ".LBB_", line.split(";")[0].strip())
         if cur and s.startswith(".Lfunc_end"):
             cur = None
         elif cur and s and not s.startswith(".") or cur and s.startswith(".L"):

@@ -182,6 +182,17 @@ SIGNATURES = {
     "unet_set_x3_cross_fp8": (C.c_int, [C.c_int]),
     "unet_set_x3_compose": (C.c_int, [C.c_int]),
     "unet_set_x3_dec_form": (C.c_int, [C.c_int]),
+    "unet_set_x3_compose_deep": (C.c_int, [C.c_int]),
+    "unet_op_updeep_window_x3_planes": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                  C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "unet_op_updeep_conv3x3_x3_planes": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                   C.c_void_p, C.c_void_p]),
+    "unet_host_pack_updeep_x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "unet_host_plan_updeep_x3": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "unet_op_upcat_conv3x3_x3": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "unet_host_compose_upcat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

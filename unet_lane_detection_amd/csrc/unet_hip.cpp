@@ -19,6 +19,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <thread>
 #include <utility>
 #include <vector>
 
@@ -37,6 +38,7 @@
 #include "conv_bf16_r512.h"
 #include "upconv_x3_ws.h"
 #include "upconv_x3_r512.h"
+#include "upconv_x3_win.h"
 #include "conv_first_x3.h"
 #include "conv_i8.h"
 #include "wino_f32.h"

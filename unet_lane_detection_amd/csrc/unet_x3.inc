@@ -1019,18 +1019,30 @@ void compose_upcat(const float* wt, const float* bt, const float* w3, int f, std
         for (int b = 0; b < 2; ++b) {
           const int py = (a + ky - 1) & 1, px = (b + kx - 1) & 1;
           const int di = fl2(a + ky - 1) - (a - 1), dj = fl2(b + kx - 1) - (b - 1);
+          // wtp [c][ci]: the sum over c runs as f updates of a row of 2f sums (contiguous, independent: the compiler
+          // vectorises it), each sum adding its terms in the order c = 0, 1, ... of the plain dot product - the same bits
           for (int ci = 0; ci < c2; ++ci)
-            for (int c = 0; c < f; ++c) wtp[(size_t)ci * f + c] = wt[(((size_t)ci * f + c) * 2 + py) * 2 + px];
-          for (int co = 0; co < f; ++co) {
-            const double* wr = &w3u[(size_t)co * f];
-            double* out = &wp[((size_t)(a * 2 + b) * f + co) * c2 * 4];
-            for (int ci = 0; ci < c2; ++ci) {
-              const double* tr = &wtp[(size_t)ci * f];
-              double s = 0.0;
-              for (int c = 0; c < f; ++c) s += wr[c] * tr[c];
-              out[(size_t)ci * 4 + di * 2 + dj] += s;
+            for (int c = 0; c < f; ++c) wtp[(size_t)c * c2 + ci] = wt[(((size_t)ci * f + c) * 2 + py) * 2 + px];
+          auto rows = [&](int co0, int co1) {
+            std::vector<double> acc(c2);
+            for (int co = co0; co < co1; ++co) {
+              const double* wr = &w3u[(size_t)co * f];
+              double* out = &wp[((size_t)(a * 2 + b) * f + co) * c2 * 4];
+              std::fill(acc.begin(), acc.end(), 0.0);
+              for (int c = 0; c < f; ++c) {
+                const double s = wr[c];
+                const double* tr = &wtp[(size_t)c * c2];
+                for (int ci = 0; ci < c2; ++ci) acc[ci] += s * tr[ci];
+              }
+              for (int ci = 0; ci < c2; ++ci) out[(size_t)ci * 4 + di * 2 + dj] += acc[ci];
             }
-          }
+          };
+          // output channels over a few host threads where the level is wide (f = 512: 10 G multiply-adds in all)
+          const int nThr = f >= 256 ? 8 : 1;
+          std::vector<std::thread> pool;
+          for (int t = 1; t < nThr; ++t) pool.emplace_back(rows, f * t / nThr, f * (t + 1) / nThr);
+          rows(0, f / nThr);
+          for (auto& th : pool) th.join();
         }
       // the bias through this tap, into every class whose pixels see the tap inside the image
       for (int co = 0; co < f; ++co) {
@@ -1219,6 +1231,258 @@ bool run_upcat_x3(const DecOpX3& op, const uint16_t* zeros, const uint16_t* skip
   return true;
 }
 
+// ---- the deep decoder levels' split first convolution (upconv_x3_win.h + the addend epilogue of conv_x3_t448.h) ----
+// The same algebra as the composed operator above, as two launches: kernel 1 forms P = the up half (2 x 2-tap window
+// convolution of x per output parity + the border-class constant) into the up half of the concat buffer, where the
+// transposed convolution writes on the two-kernel path; kernel 2 runs the 3x3 convolution over the skip half only and
+// adds P in its epilogue.  In real units y = relu((accS / preS + P) scale + shift) out; P is stored as P aP with aP a
+// power of two from the magnitude estimate of x (1 where there is none), so sP = scale out / aP.
+
+// unet_set_x3_compose_deep: 1 = on (default; UNET_X3_COMPOSE_DEEP=0 in the environment makes it 0), 0 = the deep levels
+// keep the two-kernel path.  unet_set_x3_compose(0) turns both composed paths off
+int& x3_compose_deep_mode() {
+  static int mode = [] {
+    const char* e = getenv("UNET_X3_COMPOSE_DEEP");
+    return (e && e[0] == '0') ? 0 : 1;
+  }();
+  return mode;
+}
+
+// window weights: [coTile(64)][chunk(32)][tap(4) = di * 2 + dj][plane(2)][ab(4)][cs(4)][lane(64)][8]; lane / e as in every
+// f16x3 pack (row j = lane & 15 of subtile cs is channel 64 ct + 16 (j >> 2) + 4 cs + (j & 3), k = 32 kc + 8 (lane >> 4) + e)
+inline size_t updeep_pack_index(int nCh, int ct, int kc, int tap, int plane, int ab, int cs, int lane, int e) {
+  return (((((((size_t)ct * nCh + kc) * 4 + tap) * 2 + plane) * 4 + ab) * 4 + cs) * 64 + lane) * 8 + e;
+}
+
+// What both kernels get, on the host: the window weights in float64 in the pack's order (plane 0's positions; `ordered`,
+// optional: the CPU test reads it), packed hi / lo with the per-channel pre-scale, the class constants
+struct DeepHostX3 {
+  std::vector<uint16_t> packed;
+  std::vector<float> pre, cls;   // pre [f]; cls [9][f], unscaled
+  std::vector<double> cls64;     // the same before its rounding to fp32
+  std::vector<double> wp;        // compose_upcat's window weights [parity][co][ci][tap]
+};
+void pack_updeep_x3(const float* wt, const float* bt, const float* w3, int f, const float* xAct, DeepHostX3& hst,
+                    std::vector<double>* ordered) {
+  const int c2 = 2 * f, nCt = f / 64, nCh = c2 / 32;
+  std::vector<double>& wp = hst.wp;
+  std::vector<double> bias;
+  compose_upcat(wt, bt, w3, f, wp, bias);
+  // x's activation scale divided out (exact: powers of two), as float; one pre-scale per output channel
+  std::vector<float> wx(wp.size());
+  hst.pre.assign(f, 0.f);
+  for (int p = 0; p < 4; ++p)
+    for (int co = 0; co < f; ++co) {
+      float mx = hst.pre[co];
+      for (int ci = 0; ci < c2; ++ci)
+        for (int t = 0; t < 4; ++t) {
+          const size_t i = (((size_t)p * f + co) * c2 + ci) * 4 + t;
+          wx[i] = (float)wp[i] / (xAct ? xAct[ci] : 1.f);
+          mx = std::max(mx, std::fabs(wx[i]));
+        }
+      hst.pre[co] = mx;
+    }
+  for (auto& v : hst.pre) v = prescale_pow2(v);
+  hst.cls.resize((size_t)9 * f);
+  for (size_t i = 0; i < hst.cls.size(); ++i) hst.cls[i] = (float)bias[i];
+  hst.cls64 = bias;
+  hst.packed.assign((size_t)nCt * nCh * 4 * 2 * 4 * 4 * 64 * 8, 0);
+  if (ordered) ordered->assign(hst.packed.size(), 0.0);
+  for (int ct = 0; ct < nCt; ++ct)
+    for (int kc = 0; kc < nCh; ++kc)
+      for (int tap = 0; tap < 4; ++tap)
+        for (int ab = 0; ab < 4; ++ab)
+          for (int cs = 0; cs < 4; ++cs)
+            for (int lane = 0; lane < 64; ++lane) {
+              const int j = lane & 15, lq = lane >> 4;
+              const int co = 64 * ct + 16 * (j >> 2) + 4 * cs + (j & 3);
+              for (int e = 0; e < 8; ++e) {
+                const int ci = kc * 32 + lq * 8 + e;
+                const size_t src = (((size_t)ab * f + co) * c2 + ci) * 4 + tap;
+                const size_t ih = updeep_pack_index(nCh, ct, kc, tap, 0, ab, cs, lane, e);
+                const size_t il = updeep_pack_index(nCh, ct, kc, tap, 1, ab, cs, lane, e);
+                host_split_f16(wx[src] * hst.pre[co], hst.packed[ih], hst.packed[il]);
+                if (ordered) (*ordered)[ih] = wp[src];
+              }
+            }
+}
+
+struct DeepOpX3 {
+  int f = 0, relu = 0;
+  uint16_t* wtWin = nullptr;   // kernel 1: the window weights, scale aP / pre, the nine class constants x aP
+  float* scaleWin = nullptr;
+  float* cls = nullptr;
+  uint16_t* wtSkip = nullptr;  // kernel 2: W3[:, :f] packed as every 3x3 weight, s, t, sP
+  float* scale = nullptr;
+  float* shift = nullptr;
+  float* addScale = nullptr;
+  void free_dev() {
+    for (void* p : {(void*)wtWin, (void*)scaleWin, (void*)cls, (void*)wtSkip, (void*)scale, (void*)shift, (void*)addScale})
+      if (p) hipFree(p);
+    wtWin = wtSkip = nullptr;
+    scaleWin = cls = scale = shift = addScale = nullptr;
+  }
+};
+
+// wt (2f,f,2,2), bt (f), w3 (f,2f,3,3) with BatchNorm scale / shift folded; skipIn / xIn / out: activation scales of the
+// skip, of x and of the output (null: none)
+int build_updeep_x3(std::string& err, DeepOpX3& op, const float* wt, const float* bt, const float* w3, int f, const float* scale,
+                    const float* shift, int relu, const ActScale* skipIn, const ActScale* xIn, const ActScale* out) {
+  op.free_dev();
+  op.f = f;
+  op.relu = relu;
+  const int c2 = 2 * f;
+  DeepHostX3 hst;
+  pack_updeep_x3(wt, bt, w3, f, xIn ? xIn->act.data() : nullptr, hst, nullptr);
+  // P's scale: four standard deviations of the window sum (independent channels, as build_upconv_x3 estimates its
+  // output) plus the interior constant, where x carries magnitudes
+  std::vector<float> aP(f, 1.f);
+  if (xIn && std::any_of(xIn->mag.begin(), xIn->mag.end(), [](float m) { return m > 0.f; })) {
+    const std::vector<double>& wp = hst.wp;
+    for (int co = 0; co < f; ++co) {
+      double var = 0;
+      for (int ci = 0; ci < c2; ++ci) {
+        const double sd = xIn->mag[ci] / 4.0;
+        for (int t = 0; t < 4; ++t) {
+          double m = 0;
+          for (int p = 0; p < 4; ++p) m = std::max(m, std::fabs(wp[(((size_t)p * f + co) * c2 + ci) * 4 + t]));
+          var += m * m * sd * sd;
+        }
+      }
+      aP[co] = act_scale_pow2((float)(4.0 * std::sqrt(var)) + std::fabs(hst.cls[(size_t)4 * f + co]));
+    }
+  }
+  std::vector<float> scW(f), cls((size_t)9 * f);
+  for (int co = 0; co < f; ++co) {
+    scW[co] = aP[co] / hst.pre[co];
+    for (int k = 0; k < 9; ++k) cls[(size_t)k * f + co] = hst.cls[(size_t)k * f + co] * aP[co];
+  }
+  // the skip half: W3[:, :f] with the skip's scale divided out
+  std::vector<float> ws((size_t)f * f * 9);
+  for (int co = 0; co < f; ++co)
+    for (int ci = 0; ci < f; ++ci)
+      for (int t = 0; t < 9; ++t)
+        ws[((size_t)co * f + ci) * 9 + t] = w3[((size_t)co * c2 + ci) * 9 + t] / (skipIn ? skipIn->act[ci] : 1.f);
+  const std::vector<float> preS = row_prescale(ws.data(), f, (size_t)f * 9);
+  std::vector<float> sc(f), sh(f), sp(f);
+  for (int co = 0; co < f; ++co) {
+    const float o = out ? out->act[co] : 1.f;
+    sc[co] = scale[co] / preS[co] * o;
+    sh[co] = shift[co] * o;
+    sp[co] = scale[co] * o / aP[co];
+  }
+  int rc = upload_bf(err, &op.wtWin, hst.packed);
+  if (!rc) rc = upload(err, &op.scaleWin, scW);
+  if (!rc) rc = upload(err, &op.cls, cls);
+  if (!rc) rc = upload_bf(err, &op.wtSkip, pack_conv_x3(ws.data(), f, f, preS));
+  if (!rc) rc = upload(err, &op.scale, sc);
+  if (!rc) rc = upload(err, &op.shift, sh);
+  if (!rc) rc = upload(err, &op.addScale, sp);
+  return rc;
+}
+
+// The plan of the two launches: a pure function of integers, like x3_plan_conv / x3_plan_upconv (which keep their answers:
+// this path is asked for first and the others only where it declines).  h, w: the low-resolution map of x
+struct X3UpdeepQuery {
+  int n = 0, h = 0, w = 0, f = 0;
+  int compose = -1;      // x3_compose_mode(): 0 off, -1 automatic, 1 wherever the shapes allow
+  bool deep = true;      // x3_compose_deep_mode()
+  bool q8 = false;       // the f16q8 tier is on: it keeps the two-kernel path
+  bool window_only = false;   // (operator entry point) kernel 1 alone: f % 64 == 0 is enough
+  X3Switches sw;
+};
+struct X3UpdeepPlan {
+  bool take = false;
+  int wmax = 0, pixTiles = 0, coTiles = 0, grid = 0;   // kernel 1
+  X3ConvPlan conv;                                     // kernel 2: the third structure's 256-channel form
+};
+X3UpdeepPlan x3_plan_updeep(const X3UpdeepQuery& q) {
+  X3UpdeepPlan p;
+  const long npix = (long)q.n * q.h * q.w;
+  if (q.compose == 0 || !q.deep || q.q8 || q.n < 1 || q.h < 1 || q.w < 4 || q.w > 28 || q.f < 64 || q.f % 64 ||
+      npix >= (1L << 31) - 224 - 64)
+    return p;
+  p.wmax = q.w <= 14 ? 14 : 28;
+  p.pixTiles = (int)((npix + unet::UpconvX3RShape::TP - 1) / unet::UpconvX3RShape::TP);
+  p.coTiles = q.f / 64;
+  const long items = (long)p.pixTiles * p.coTiles;
+  p.grid = x3_grid(items);
+  if (!q.window_only) {
+    if (q.f % 256) return p;
+    X3ConvQuery c;
+    c.n = q.n, c.h = 2 * q.h, c.w = 2 * q.w, c.cin = q.f, c.cout = q.f, c.epi = 0;
+    c.sw = q.sw;
+    if (q.compose == 1) x3_decode_force(728, &c.force);
+    p.conv = x3_plan_conv(c);
+    // automatic: the work-item rule of the composed path for both launches - the third structure takes the layer by
+    // itself (>= 128 items, tiles filled) and kernel 1 has an item for half of the CUs
+    if (!p.conv.valid || p.conv.path.structure != kX3T448 || p.conv.path.waves != 4) return p;
+    if (q.compose < 0 && items < 128) return p;
+  }
+  p.take = true;
+  return p;
+}
+
+// x planes (n,h,w,2f) and the skip half of the concat buffer `cat` (n,2h,2w; pixel stride 2f; channels [0,f)) -> P into
+// channels [f,2f) of `cat`, then out planes (n,2h,2w,f) with pixel stride ldo.  Returns false (nothing launched) where the
+// plan declines.  windowOnly (operator entry point): kernel 1 alone, into `cat` at pixel stride ldCat, channel offset coOff
+bool run_updeep_x3(const DeepOpX3& op, const uint16_t* zeros, uint16_t* cat, size_t catLo, int ldCat, int coOff,
+                   const uint16_t* x, size_t xLo, int n, int h, int w, uint16_t* out, size_t outLo, int ldo, int compose,
+                   bool q8, bool windowOnly, hipStream_t s, hipError_t* err) {
+  *err = hipSuccess;
+  if (!op.wtWin) return false;
+  X3UpdeepQuery q;
+  q.n = n, q.h = h, q.w = w, q.f = op.f, q.compose = compose, q.deep = x3_compose_deep_mode() != 0, q.q8 = q8;
+  q.window_only = windowOnly;
+  q.sw = x3_switches();
+  const X3UpdeepPlan p = x3_plan_updeep(q);
+  if (!p.take) return false;
+  const int f = op.f;
+  const double pxLo = (double)n * h * w, pxHi = 4.0 * pxLo;
+  {
+    unet::UpconvX3Args a{};
+    a.in = x, a.inLo = xLo, a.zeros = zeros, a.wt = op.wtWin;
+    a.scale = op.scaleWin, a.bias = op.cls;
+    a.out = cat, a.outLo = catLo;
+    a.npix = (long)n * h * w, a.h = h, a.w = w, a.Cin = 2 * f, a.Cout = f, a.ldo = ldCat, a.co_off = coOff;
+    a.nChunks = 2 * f / 32, a.coTiles = p.coTiles, a.pixTiles = p.pixTiles, a.abSplit = 1;
+    a.err = g_errWord ? g_errWord : op_err_word();
+    void (*kern)(const unet::UpconvX3Args) = p.wmax == 14 ? unet::upconv2x2_x3_win_kernel<14> : unet::upconv2x2_x3_win_kernel<28>;
+    const int lds = p.wmax == 14 ? unet::UpconvX3WShape<14>::LDS_BYTES : unet::UpconvX3WShape<28>::LDS_BYTES;
+    *err = ensure_dyn_lds((const void*)kern, lds);
+    if (*err != hipSuccess) return true;
+    // executed multiply-adds: 4 taps x 2f per output pixel and channel; x read, P written, the window weights
+    prof_begin("upconv2x2_win_f16x3", 2.0 * pxHi * 8.0 * f * f, 4.0 * (pxLo * 2 * f + pxHi * f) + 2.0 * 32.0 * f * f, s);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), (size_t)lds, s, a);
+    prof_end(s);
+    *err = hipGetLastError();
+    if (*err != hipSuccess || windowOnly) return true;
+  }
+  const X3ConvPlan& c = p.conv;
+  unet::ConvX3AddArgs a{};
+  a.in = cat, a.inLo = catLo, a.zeros = zeros, a.wt = op.wtSkip;
+  a.scale = op.scale, a.shift = op.shift, a.relu = op.relu;
+  a.out = out, a.outLo = outLo, a.ldo = ldo, a.co_off = 0;
+  a.N = c.N, a.H = c.H, a.W = 2 * w, a.imgH = c.imgH, a.Cin = f, a.Cout = f;
+  a.tilesX = c.tilesX, a.tilesY = c.tilesY, a.pixTiles = c.pixTiles;
+  a.coTiles = c.coTiles, a.coGroup = c.coGroup, a.nChunks = c.nChunks, a.kSplit = 1, a.chunksTotal = f / 32;
+  a.err = g_errWord ? g_errWord : op_err_word();
+  a.ldi = ldCat, a.ldAdd = ldCat, a.add = cat + coOff, a.addLo = catLo, a.addScale = op.addScale;
+  const bool flat = c.path.flat != 0;
+  using S = unet::X3TShape<28, unet::x3t_row_blocks(4)>;
+  void (*kern)(const unet::ConvX3AddArgs) = flat ? unet::conv3x3_x3_t448add_kernel<true> : unet::conv3x3_x3_t448add_kernel<false>;
+  const int lds = flat ? S::LDS_BYTES_FLAT : S::LDS_BYTES_PLAIN;
+  *err = ensure_dyn_lds((const void*)kern, lds);
+  if (*err != hipSuccess) return true;
+  // the skip half's 3x3 convolution; the skip and P read, the output written
+  prof_begin(flat ? "conv3x3_t448add_f16x3_t28_c4_flat" : "conv3x3_t448add_f16x3_t28_c4", 2.0 * pxHi * 9.0 * f * f,
+             4.0 * (pxHi * f + pxHi * f + pxHi * f) + 2.0 * 9.0 * f * f, s);
+  hipLaunchKernelGGL(kern, dim3(c.grid), dim3(256), (size_t)lds, s, a);
+  prof_end(s);
+  *err = hipGetLastError();
+  return true;
+}
+
 // First convolution on conv_first_x3.h: uint8 (N,H,W,3) frames (u8) or an fp32 NCHW image -> planes (N,H,W,op.cout) with
 // pixel stride ldo; op from build_conv_x3(first = true).  mean / stdv: the input normalisation, null = none
 hipError_t run_first_x3(const GemmOpX3& op, const void* input, bool u8, int n, int h, int w, uint16_t* out, size_t outLo,
@@ -1265,6 +1529,7 @@ struct X3Net {
   float* headW = nullptr;        // head weights with the last activation's scale divided out
   std::vector<GemmOpX3> enc, bott, up, dec;
   std::vector<DecOpX3> comp;     // per decoder step j: the composed up + dec[2 j] operator (conv_x3_dec.h), where built
+  std::vector<DeepOpX3> deep;    // per decoder step j: the split form of the same (upconv_x3_win.h + t448add), where built
   GrowBuf ws;
   bool hasQ8 = false;            // the operators carry their fp8 cross-term fragments (f16q8 tier)
   GrowBuf qbuf;                  // q plane of the layer input being consumed (f16q8 tier)
@@ -1275,6 +1540,7 @@ static void x3_free(unet_ctx* h) {
   for (auto* v : {&h->x3->enc, &h->x3->bott, &h->x3->up, &h->x3->dec})
     for (auto& op : *v) op.free_dev();
   for (auto& op : h->x3->comp) op.free_dev();
+  for (auto& op : h->x3->deep) op.free_dev();
   h->x3->ws.release();
   h->x3->qbuf.release();
   if (h->x3->zeros) hipFree(h->x3->zeros);
@@ -1337,6 +1603,7 @@ int x3_build(unet_ctx* h) {
   X->dec.assign(2 * c.depth, GemmOpX3());
   X->up.assign(c.depth, GemmOpX3());
   X->comp.assign(c.depth, DecOpX3());
+  X->deep.assign(c.depth, DeepOpX3());
   X->bott.assign(2, GemmOpX3());
   int rc;
   int cin = 3;
@@ -1374,6 +1641,16 @@ int x3_build(unet_ctx* h) {
       if ((rc = build_upcat_x3(h->err, X->comp[j], P[pu + ".weight"].data(), P[pu + ".bias"].data(), P[pd + ".0.weight"].data(),
                                f, sc.data(), sh.data(), 1, useAct ? &skip[l] : nullptr, useAct ? &cur : nullptr,
                                useAct ? &tmp : nullptr)))
+        return rc;
+    }
+    if (f % 256 == 0) {
+      // the same step split over two launches (upconv_x3_win.h, conv_x3_t448.h's addend epilogue): the 56 x 56 and 28 x 28
+      // levels, whose 8-row tiles the composed kernel's parity fragments do not tile
+      std::vector<float> sc, sh;
+      fold_bn(P, pd + ".1.", f, sc, sh);
+      if ((rc = build_updeep_x3(h->err, X->deep[j], P[pu + ".weight"].data(), P[pu + ".bias"].data(), P[pd + ".0.weight"].data(),
+                                f, sc.data(), sh.data(), 1, useAct ? &skip[l] : nullptr, useAct ? &cur : nullptr,
+                                useAct ? &tmp : nullptr)))
         return rc;
     }
     if ((rc = conv(X->dec[2 * j + 1], pd, 3, 4, f, f, false, &tmp, &cur))) return rc;
@@ -1550,6 +1827,14 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
       hipError_t ec;
       composed = run_upcat_x3(X->comp[j], X->zeros, U(p.cat[l]), p.cat[l].elems, 2 * f, U(*cur), cur->elems, n, 2 * ch, 2 * cw,
                               U(p.tmpA), p.tmpA.elems, f, x3_compose_mode() == 1, 128, s, &ec);
+      HIPCHK(h->err, ec);
+    }
+    // the deep levels' split form: kernel 1 writes P where the transposed convolution would write, kernel 2 reads the
+    // skip half and P and writes tmpA like dec[2 j]
+    if (!composed && x3_compose_mode() != 0) {
+      hipError_t ec;
+      composed = run_updeep_x3(X->deep[j], X->zeros, U(p.cat[l]), p.cat[l].elems, 2 * f, f, U(*cur), cur->elems, n, ch, cw,
+                               U(p.tmpA), p.tmpA.elems, f, x3_compose_mode(), qs != nullptr, false, s, &ec);
       HIPCHK(h->err, ec);
     }
     ch *= 2;
@@ -1751,6 +2036,104 @@ int unet_host_compose_upcat(const float* wt, const float* bt, const float* w3, i
   std::copy(a.begin(), a.end(), wp);
   std::copy(b.begin(), b.end(), bias);
   return UNET_OK;
+}
+
+// Test hook (host arithmetic only, no device): what build_updeep_x3 packs for kernel 1 (pack_updeep_x3).  ordered: the
+// float64 window weights at the pack's hi-plane positions (the lo-plane positions stay 0); packed: the fp16 hi / lo
+// planes of weight / xAct x pre; pre [f]; cls [9][f] in float64 (kernel 1 gets them rounded to fp32)
+int unet_host_pack_updeep_x3(const float* wt, const float* bt, const float* w3, int f, const float* xAct, double* ordered,
+                             uint16_t* packed, float* pre, double* cls) {
+  if (!wt || !bt || !w3 || !ordered || !packed || !pre || !cls || f < 64 || f % 64) return op_bad_args();
+  DeepHostX3 hst;
+  std::vector<double> ord;
+  pack_updeep_x3(wt, bt, w3, f, xAct, hst, &ord);
+  std::copy(ord.begin(), ord.end(), ordered);
+  std::copy(hst.packed.begin(), hst.packed.end(), packed);
+  std::copy(hst.pre.begin(), hst.pre.end(), pre);
+  std::copy(hst.cls64.begin(), hst.cls64.end(), cls);
+  return UNET_OK;
+}
+
+// Test hook (no device): x3_plan_updeep for query = {n, h, w, f, compose mode, deep switch, f16q8 on} (h, w: the
+// low-resolution map) -> planOut = {taken, kernel 1: widest map of its instance, pixel tiles, channel tiles, grid;
+// kernel 2: grid, flat tiling, pixel tiles}, all 0 where the plan declines
+int unet_host_plan_updeep_x3(const int* query, int nQuery, int* planOut, int nPlan) {
+  if (!query || nQuery != 7 || !planOut || nPlan != 8) return op_bad_args();
+  X3UpdeepQuery q;
+  q.n = query[0], q.h = query[1], q.w = query[2], q.f = query[3];
+  q.compose = query[4] < 0 ? -1 : (query[4] > 1 ? 1 : query[4]);
+  q.deep = query[5] != 0, q.q8 = query[6] != 0;
+  const X3UpdeepPlan p = x3_plan_updeep(q);
+  const int v[8] = {1, p.wmax, p.pixTiles, p.coTiles, p.grid, p.conv.grid, p.conv.path.flat, p.conv.pixTiles};
+  std::fill(planOut, planOut + 8, 0);
+  if (p.take) std::copy(v, v + 8, planOut);
+  return UNET_OK;
+}
+
+int unet_set_x3_compose_deep(int on) {
+  const int prev = x3_compose_deep_mode();
+  x3_compose_deep_mode() = on ? 1 : 0;
+  return prev;
+}
+
+// Test entry point: kernel 1 of the deep levels' split step alone (upconv_x3_win.h), on caller-owned planes.  x planes
+// (n,hh,ww,2f) -> P planes (n,2hh,2ww) at pixel stride ldo, channels [coOff, coOff + f) of y; wt (2f,f,2,2), bt (f),
+// w3 (f,2f,3,3) on the host; inAct: x's per-channel activation scales (2f) or null
+int unet_op_updeep_window_x3_planes(int device, const uint16_t* x, size_t xLo, int n, int hh, int ww, int f, const float* wt,
+                                    const float* bt, const float* w3, const float* inAct, uint16_t* y, size_t yLo, int ldo,
+                                    int coOff, int* rangeOut, void* stream) {
+  if (ldo == 0) ldo = f;
+  if (!x || !wt || !bt || !w3 || !y || n < 1 || hh < 1 || ww < 4 || ww > 28 || f < 64 || f % 64 || f > 1024 || xLo % 8 ||
+      yLo % 8 || ldo % 64 || coOff < 0 || coOff % 64 || coOff + f > ldo)
+    return op_bad_args();
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  OpScratch sc(s);
+  OpGuard<DeepOpX3> g;
+  ActScale ia;
+  if (inAct) ia = act_from_host(inAct, 2 * f);
+  std::vector<float> one(f, 1.f), zero(f, 0.f);
+  const int rc = build_updeep_x3(g_opErr, g.op, wt, bt, w3, f, one.data(), zero.data(), 0, nullptr, inAct ? &ia : nullptr, nullptr);
+  if (rc) return rc;
+  uint16_t* zeros = nullptr;
+  OpRangeScope range;
+  hipError_t e = sc.zero_page(&zeros);
+  if (e == hipSuccess) e = range.arm();
+  if (e == hipSuccess &&
+      !run_updeep_x3(g.op, zeros, y, yLo, ldo, coOff, x, xLo, n, hh, ww, nullptr, 0, 0, 1, false, true, s, &e) && e == hipSuccess)
+    e = hipErrorInvalidValue;
+  return op_done(e, s, 0, &range, rangeOut);
+}
+
+// Test entry point: both kernels as the forward runs them.  cat: the concat buffer's planes (n,2hh,2ww,2f) with the skip
+// in channels [0,f) (the caller's bits; they are only read) - P goes to channels [f,2f); out planes (n,2hh,2ww,f).
+// xAct (2f) / skipAct (f): activation scales of x and of the skip, or null
+int unet_op_updeep_conv3x3_x3_planes(int device, const uint16_t* x, size_t xLo, int n, int hh, int ww, int f, const float* wt,
+                                     const float* bt, const float* w3, const float* scale, const float* shift, int relu,
+                                     const float* xAct, const float* skipAct, uint16_t* cat, size_t catLo, uint16_t* out,
+                                     size_t outLo, int* rangeOut, void* stream) {
+  if (!x || !wt || !bt || !w3 || !scale || !shift || !cat || !out || n < 1 || hh < 1 || ww < 4 || ww > 28 || f < 256 ||
+      f % 256 || f > 1024 || xLo % 8 || catLo % 8 || outLo % 8)
+    return op_bad_args();
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  OpScratch sc(s);
+  OpGuard<DeepOpX3> g;
+  ActScale xa, sa;
+  if (xAct) xa = act_from_host(xAct, 2 * f);
+  if (skipAct) sa = act_from_host(skipAct, f);
+  const int rc = build_updeep_x3(g_opErr, g.op, wt, bt, w3, f, scale, shift, relu, skipAct ? &sa : nullptr, xAct ? &xa : nullptr,
+                                 nullptr);
+  if (rc) return rc;
+  uint16_t* zeros = nullptr;
+  OpRangeScope range;
+  hipError_t e = sc.zero_page(&zeros);
+  if (e == hipSuccess) e = range.arm();
+  if (e == hipSuccess &&
+      !run_updeep_x3(g.op, zeros, cat, catLo, 2 * f, f, x, xLo, n, hh, ww, out, outLo, f, 1, false, false, s, &e) &&
+      e == hipSuccess)
+    e = hipErrorInvalidValue;
+  return op_done(e, s, 0, &range, rangeOut);
 }
 
 // Test hooks (host arithmetic only, no device): the plan the dispatch makes for a query given as integers, the switches

@@ -29,6 +29,11 @@ struct X3Geo {
   int hrMin, hrSpan, hcMin, hcSpan;   // halo rows / columns inside the image: [min, min + span]
   int n, y0, x0, cg;
 };
+// the input's pixel stride in elements: the channel count, unless the argument struct says otherwise (an overload)
+template <class A>
+__device__ __forceinline__ int x3_in_stride(const A& a) {
+  return a.Cin;
+}
 // item w of ConvX3Args / ConvQ8Args / ConvBfRArgs: channel group innermost within a group of coGroup, then pixel tiles
 template <class S, class A>
 __device__ __forceinline__ X3Geo x3_geo_of(const A& a, int w) {
@@ -48,7 +53,7 @@ __device__ __forceinline__ X3Geo x3_geo_of(const A& a, int w) {
   g.hrSpan = hrMax - g.hrMin;
   g.hcSpan = hcMax - g.hcMin;
   g.tb = reinterpret_cast<const char*>(a.in) +
-         ((((long)g.n * a.H + g.y0 - 1) * a.W + g.x0 - 1) * (long)a.Cin) * 2;
+         ((((long)g.n * a.H + g.y0 - 1) * a.W + g.x0 - 1) * (long)x3_in_stride(a)) * 2;
   return g;
 }
 
