@@ -510,6 +510,30 @@ int unet_host_compose_upcat(const float* wt_host, const float* bt_host, const fl
  * UNET_ERR_INVALID_ARG: a wrong array size, a non-positive shape or a tile_width outside the table. */
 int unet_host_plan_conv3x3_x3(const int* query, int n_query, int* plan_out, int n_plan, char* label_out, int label_cap);
 int unet_host_plan_upconv2x2_x3(const int* query, int n_query, int* plan_out, int n_plan, char* label_out, int label_cap);
+/* The same for one decoder step ConvTranspose2d -> cat -> Conv3x3 (x3_plan_dec_step): which form it runs in.
+ * query[17]: n, h, w (the LOW-resolution map of x), f, unet_set_x3_compose's mode, unet_set_x3_compose_deep's switch,
+ *   unet_set_x3_dec_form's mode, f16q8 scratch present, who asks (0 the forward, 1 an operator entry point, which forces
+ *   its operator), the operators the asker holds (bit 0 composed, bit 1 deep: the forward 3, an entry point the one it
+ *   built; the plan intersects it with those a step of width f can have), 1 = kernel 1 of the deep form alone (entry
+ *   point), unet_set_x3_upconv_r512's mode (read by the two-kernel form's labels only), then the four switches and
+ *   unet_set_x3_cross_fp8's mode as above.
+ *   plan_out[16]: form (0 two kernels, 1 composed, 2 deep); composed: wco (64-channel tiles per block), tilesX, tilesY,
+ *   pixTiles, coTiles, grid; [7] the launches of a composed / deep step; [8..15] deep: the eight ints of
+ *   unet_host_plan_updeep_x3.  Whatever does not belong to the form is 0.
+ * label_out (optional, label_cap >= 128): the profiler labels of the step's launches up to its second convolution, comma-
+ *   separated; two kernels: those of the transposed and the first convolution as the forward launches them while no q
+ *   plane is handed on, a split-K finish pass included. */
+int unet_host_plan_dec_step_x3(const int* query, int n_query, int* plan_out, int n_plan, char* label_out, int label_cap);
+/* Test hook, host arithmetic only: the packed fp16 hi / lo fragments of host weights times pre_host[cout] (powers of two),
+ * as the operators upload them.  kind 0: 3x3 convolution, w (cout,cin,3,3) -> [cout/64][cin/32][tap row 3][plane 2][kx 3]
+ * [cs 4][lane 64][8]; 1: transposed convolution, w (cin,cout,2,2) -> [cout/64][cin/32][plane 2][ab 4][cs 4][lane 64][8];
+ * 2: first convolution, w (cout,3,3,3), cin = 3 -> [cout/64][cs 4][plane 2][lane 64][8] with k = tap * 3 + ci, k >= 27
+ * zero; 3: composed decoder step, w = the skip half (f,f,3,3), wx_host = the window weights [parity 4][f][2f][tap 4],
+ * cout = f, cin = 2f -> per 64-channel tile [f/32][tap 9][plane 2][cs 4][lane 64][8] then [2f/32][parity 4][tap 4][plane 2]
+ * [cs 4][lane 64][8].  In every layout row j = lane & 15 of subtile cs of tile ct is channel 64 ct + 16 (j >> 2) + 4 cs +
+ * (j & 3) and the lane's eight halfs are k = 32 chunk + 8 (lane >> 4) + e.  n_packed: the pack's size in halfs (checked). */
+int unet_host_pack_x3(int kind, const float* w_host, const float* wx_host, int cout, int cin, const float* pre_host,
+                      uint16_t* packed_out, size_t n_packed);
 /* Process-wide switch for the composed decoder step in the f16x3 tier's forward (not the f16q8 tier, not training):
  * -1 = automatic (default) - the levels with f <= 128 on maps of width 28k with a work item for half of the CUs;
  * 0 = off: ConvTranspose2d + the 3x3 convolution as two kernels everywhere; 1 = wherever the shape rules allow.

@@ -1,9 +1,11 @@
-"""The f16x3 tier's dispatch on the CPU: x3_plan_conv / x3_plan_upconv (csrc/unet_x3.inc; DESIGN.md, "f16x3 dispatch")
-through the host hooks unet_host_plan_conv3x3_x3 / unet_host_plan_upconv2x2_x3.  No device is touched.
+"""The f16x3 tier's dispatch on the CPU: x3_plan_conv / x3_plan_upconv / x3_plan_dec_step (csrc/unet_x3.inc; DESIGN.md,
+"f16x3 dispatch") through the host hooks unet_host_plan_conv3x3_x3 / unet_host_plan_upconv2x2_x3 /
+unet_host_plan_dec_step_x3.  No device is touched.
 
 What the plan is held to was not produced by the plan: the path tuples the GPU operator tests assert against real
-launches, the per-layer labels of two recorded batch-256 runs, and a table generated from the decision code as it was
-before it became a plan (tests/golden/x3_dispatch.json; tests/golden/make_golden_x3_dispatch.py regenerates it)."""
+launches, the per-layer labels of two recorded batch-256 runs, and two tables generated from the decision code as it was
+before it became a plan (tests/golden/x3_dispatch.json, x3_dec_step.json; tests/golden/make_golden_x3_*.py regenerate
+them)."""
 import ctypes as C
 import json
 import os
@@ -14,11 +16,13 @@ import pytest
 import test_train_x3_ops_gpu as TT
 import test_x3_ops_gpu as TX
 from unet_lane_detection_amd import _lib
-from x3_dispatch_queries import GRID, PATH, STAT_ROWS, VALID, ask, conv_query, upconv_query
+from x3_dispatch_queries import (COMPOSED, DEEP, GRID, PATH, STAT_ROWS, TWO_KERNEL, VALID, ask, conv_query, dec_step_query,
+                                 upconv_query)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_golden_x3_dispatch as G  # noqa: E402
+import make_golden_x3_dec_step as GD  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -99,7 +103,8 @@ def recorded_layer_labels(path):
 @pytest.mark.parametrize("compose", ["on", "off"])
 def test_plan_labels_equal_the_recorded_batch_256_run(lib, compose):
     """model A, batch 256, 224 x 224, fp8 tier off.  With the composed decoder on, a recorded upcat row stands for the
-    transposed convolution and the decoder's first convolution of that step (conv_x3_dec.h: not this dispatch)."""
+    transposed convolution and the decoder's first convolution of that step: the step's plan says which (the deep
+    switch off: the recordings predate the deep form)."""
     want = recorded_layer_labels(os.path.join(HERE, "..", "profiles", "r05", f"layers_batch256_compose_{compose}.txt"))
     assert want[0] == "conv3x3_first_f16x3" and len(want) == (22 if compose == "off" else 20)
     n, size = 256, 224
@@ -113,15 +118,18 @@ def test_plan_labels_equal_the_recorded_batch_256_run(lib, compose):
 
     for name, hh, ww, cin, cout, epi in G.network_layers(size, size):
         if name.startswith("dec") and name.endswith("conv1"):
-            if want[k] == "upcat_conv3x3_dec_f16x3":
+            step, labels = ask(lib, "dec", dec_step_query(n, hh // 2, ww // 2, cout, compose=-1 if compose == "on" else 0, deep=0))
+            if step[0] == COMPOSED:
                 assert compose == "on" and cout <= 128, name
-                got.append(want[k])
+                got += labels.split(",")
                 k += 1
                 continue
+            assert step[0] == TWO_KERNEL
             plan, label = ask(lib, "upconv", upconv_query(n, hh // 2, ww // 2, cin, cout, co_off=cout))
             assert plan[VALID] == 1
             got.append(label)
             k += 1
+            assert labels.split(",") == [label, conv_label(hh, ww, cin, cout, epi)], name
         got.append(conv_label(hh, ww, cin, cout, epi))
         k += 1
     assert got == want[1:]
@@ -150,6 +158,26 @@ def test_plan_reproduces_the_dispatch_table(lib):
     # the sweep reaches every family of both dispatches, split-K and the refusals
     assert structures >= {("conv", 1, False), ("conv", 1, True), ("conv", 2, False), ("conv", 3, False), ("conv", 4, False),
                           ("conv", 0, False), ("upconv", 1, False), ("upconv", 2, False), ("upconv", 0, False)}
+
+
+def test_plan_reproduces_the_decoder_step_table(lib):
+    with open(GD.TABLE) as f:
+        table = json.load(f)
+    queries = GD.sweep()
+    assert (len(queries), G.queries_digest(queries)) == (table["queries"], table["queries_sha256"]) and \
+        len(table["rows"]) == len(queries), "the table's queries are not the sweep's: regenerate it on purpose"
+    forms = set()
+    for q, k in zip(queries, table["rows"]):
+        plan, labels = ask(lib, "dec", q)
+        assert [*plan, labels] == table["plans"][k], q
+        forms.add((plan[0], q[8]))
+        n_labels = len(labels.split(","))
+        assert n_labels == plan[7] if plan[0] != TWO_KERNEL else n_labels >= 2, q
+        if plan[0] == COMPOSED:             # the geometry the kernel gets is consistent with the grid
+            wco, tx, ty, pix, co_t, grid = plan[1:7]
+            assert pix == q[0] * ty * tx and co_t * 64 * wco == q[3] and grid == max(8, min(256, pix * co_t // 8 * 8)), q
+    # the sweep reaches every form from both askers (an entry point is never handed the two kernels' launches, only told)
+    assert forms == {(form, who) for form in (TWO_KERNEL, COMPOSED, DEEP) for who in (0, 1)}
 
 
 # ---- the forced form ----------------------------------------------------------------------------------------------------------

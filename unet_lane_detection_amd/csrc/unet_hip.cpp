@@ -1115,7 +1115,7 @@ struct OpScratch {
   hipError_t zero_page(uint16_t** p, size_t bytes = 4096) { return get(p, bytes, true); }
 };
 
-// The operator a call builds (GemmOp, GemmOpBf, GemmOpX3, DecOpX3): its device arrays are released on every exit
+// The operator a call builds (GemmOp, GemmOpBf, GemmOpX3, DecStepX3): its device arrays are released on every exit
 template <class Op>
 struct OpGuard {
   Op op;

@@ -46,28 +46,34 @@ inline float prescale_pow2(float maxabs) {
   return std::ldexp(1.f, 10 - e);  // maxabs * 2^(10-e) in [512, 1024)
 }
 
-// 3x3: w (O,I,3,3) -> [coTile][chunk(32)][tapRow][plane][kx][cs][lane][8]; row j of subtile cs of tile ct is channel
-// 64*ct + 16*(j>>2) + 4*cs + (j&3) (conv_bf16_ws.h), k = chunk*32 + 8*(lane>>4) + e
+// The lane order of every weight fragment of the tier (conv_bf16_ws.h), here and nowhere else on the host: row
+// j = lane & 15 of subtile cs of channel tile ct is channel x3_frag_channel(ct, cs, j); the lane's eight halfs are
+// k = 32 kc + 8 (lane >> 4) + e.  x3_each_frag_elem visits the 64 x 8 elements of one subtile fragment in memory order
+inline int x3_frag_channel(int ct, int cs, int j) { return 64 * ct + 16 * (j >> 2) + 4 * cs + (j & 3); }
+template <class F>
+void x3_each_frag_elem(int ct, int kc, int cs, F&& f) {
+  for (int lane = 0; lane < 64; ++lane)
+    for (int e = 0; e < 8; ++e) f(lane * 8 + e, x3_frag_channel(ct, cs, lane & 15), kc * 32 + (lane >> 4) * 8 + e);
+}
+// hi / lo: the 64 x 8 halfs of subtile cs in the two planes; val(co, k): the weight, pre-scaled
+template <class V>
+void x3_put_frag(uint16_t* hi, uint16_t* lo, int ct, int kc, int cs, V&& val) {
+  x3_each_frag_elem(ct, kc, cs, [&](int i, int co, int k) { host_split_f16(val(co, k), hi[i], lo[i]); });
+}
+constexpr size_t kX3Frag = 64 * 8;
+
+// 3x3: w (O,I,3,3) -> [coTile][chunk(32)][tapRow][plane][kx][cs][lane][8]
 std::vector<uint16_t> pack_conv_x3(const float* w, int cout, int cin, const std::vector<float>& pre) {
   const int nCt = cout / 64, nCh = cin / 32;
-  std::vector<uint16_t> out((size_t)nCt * nCh * 3 * 2 * 3 * 4 * 64 * 8, 0);
+  std::vector<uint16_t> out((size_t)nCt * nCh * 3 * 2 * 3 * 4 * kX3Frag, 0);
   for (int ct = 0; ct < nCt; ++ct)
     for (int kc = 0; kc < nCh; ++kc)
       for (int r = 0; r < 3; ++r)
         for (int kx = 0; kx < 3; ++kx)
           for (int cs = 0; cs < 4; ++cs) {
-            const size_t base = (((size_t)ct * nCh + kc) * 3 + r) * (2 * 3 * 4 * 64 * 8);
-            uint16_t* dh = out.data() + base + ((size_t)(0 * 3 + kx) * 4 + cs) * 64 * 8;
-            uint16_t* dl = out.data() + base + ((size_t)(1 * 3 + kx) * 4 + cs) * 64 * 8;
-            for (int lane = 0; lane < 64; ++lane) {
-              const int j = lane & 15, lq = lane >> 4;
-              const int co = 64 * ct + 16 * (j >> 2) + 4 * cs + (j & 3);
-              for (int e = 0; e < 8; ++e) {
-                const int ci = kc * 32 + lq * 8 + e;
-                const float v = w[((size_t)co * cin + ci) * 9 + r * 3 + kx] * pre[co];
-                host_split_f16(v, dh[lane * 8 + e], dl[lane * 8 + e]);
-              }
-            }
+            uint16_t* row = out.data() + (((size_t)ct * nCh + kc) * 3 + r) * (2 * 3 * 4 * kX3Frag);
+            x3_put_frag(row + ((0 * 3 + kx) * 4 + cs) * kX3Frag, row + ((1 * 3 + kx) * 4 + cs) * kX3Frag, ct, kc, cs,
+                        [&](int co, int ci) { return w[((size_t)co * cin + ci) * 9 + r * 3 + kx] * pre[co]; });
           }
   return out;
 }
@@ -106,8 +112,8 @@ std::vector<uint8_t> pack_conv_q8(const float* w, int cout, int cin, const std::
         for (int cs = 0; cs < 4; ++cs)
           for (int half = 0; half < 2; ++half)
             for (int lane = 0; lane < 64; ++lane) {
-              const int j = lane & 15, lq = lane >> 4;
-              const int co = 64 * ct + 16 * (j >> 2) + 4 * cs + (j & 3);
+              const int lq = lane >> 4;
+              const int co = x3_frag_channel(ct, cs, lane & 15);
               const int tap = (lq >> 1) ? tapB[s] : tapA[s];
               uint8_t* d = out.data() + ((((((size_t)ct * nCh + kc) * 5 + s) * 4 + cs) * 2 + half) * 64 + lane) * 16;
               if (tap < 0) continue;
@@ -124,41 +130,27 @@ std::vector<uint8_t> pack_conv_q8(const float* w, int cout, int cin, const std::
 // upconv: w (I,O,2,2) -> [coTile][chunk(32)][plane][ab][cs][lane][8]
 std::vector<uint16_t> pack_upconv_x3(const float* w, int cin, int cout, const std::vector<float>& pre) {
   const int nCt = cout / 64, nCh = cin / 32;
-  std::vector<uint16_t> out((size_t)nCt * nCh * 2 * 16 * 64 * 8, 0);
+  std::vector<uint16_t> out((size_t)nCt * nCh * 2 * 16 * kX3Frag, 0);
   for (int ct = 0; ct < nCt; ++ct)
     for (int kc = 0; kc < nCh; ++kc)
       for (int ab = 0; ab < 4; ++ab)
         for (int cs = 0; cs < 4; ++cs) {
-          const size_t base = ((size_t)ct * nCh + kc) * (2 * 16 * 64 * 8);
-          uint16_t* dh = out.data() + base + ((size_t)0 * 16 + ab * 4 + cs) * 64 * 8;
-          uint16_t* dl = out.data() + base + ((size_t)1 * 16 + ab * 4 + cs) * 64 * 8;
-          for (int lane = 0; lane < 64; ++lane) {
-            const int j = lane & 15, lq = lane >> 4;
-            const int co = 64 * ct + 16 * (j >> 2) + 4 * cs + (j & 3);
-            for (int e = 0; e < 8; ++e) {
-              const int ci = kc * 32 + lq * 8 + e;
-              host_split_f16(w[((size_t)ci * cout + co) * 4 + ab] * pre[co], dh[lane * 8 + e], dl[lane * 8 + e]);
-            }
-          }
+          uint16_t* chunk = out.data() + ((size_t)ct * nCh + kc) * (2 * 16 * kX3Frag);
+          x3_put_frag(chunk + (0 * 16 + ab * 4 + cs) * kX3Frag, chunk + (1 * 16 + ab * 4 + cs) * kX3Frag, ct, kc, cs,
+                      [&](int co, int ci) { return w[((size_t)ci * cout + co) * 4 + ab] * pre[co]; });
         }
   return out;
 }
 
 // first convolution: w (O,3,3,3) -> [coTile][cs][hi|lo][lane][8], k = tap*3 + ci (27..31 zero)
 std::vector<uint16_t> pack_first_x3(const float* w, int cout, const std::vector<float>& pre) {
-  std::vector<uint16_t> pw((size_t)(cout / 64) * 4 * 2 * 64 * 8, 0);
+  std::vector<uint16_t> pw((size_t)(cout / 64) * 4 * 2 * kX3Frag, 0);
   for (int ct = 0; ct < cout / 64; ++ct)
-    for (int cs = 0; cs < 4; ++cs)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int j = lane & 15, lq = lane >> 4;
-        const int co = 64 * ct + 16 * (j >> 2) + 4 * cs + (j & 3);
-        for (int e = 0; e < 8; ++e) {
-          const int k = lq * 8 + e;
-          const float v = k < 27 ? w[((size_t)co * 3 + (k % 3)) * 9 + k / 3] * pre[co] : 0.f;
-          host_split_f16(v, pw[((((size_t)ct * 4 + cs) * 2 + 0) * 64 + lane) * 8 + e],
-                         pw[((((size_t)ct * 4 + cs) * 2 + 1) * 64 + lane) * 8 + e]);
-        }
-      }
+    for (int cs = 0; cs < 4; ++cs) {
+      uint16_t* sub = pw.data() + ((size_t)ct * 4 + cs) * 2 * kX3Frag;
+      x3_put_frag(sub, sub + kX3Frag, ct, 0, cs,
+                  [&](int co, int k) { return k < 27 ? w[((size_t)co * 3 + (k % 3)) * 9 + k / 3] * pre[co] : 0.f; });
+    }
   return pw;
 }
 
@@ -209,6 +201,7 @@ ActScale act_concat(const ActScale& a, const ActScale& b) {
   return r;
 }
 
+inline bool x3_conv_has_q8(int cin, int cout) { return cin % 64 == 0 && cout % 256 == 0; }   // the 3x3 operators that get fp8 fragments
 int build_conv_x3(std::string& err, GemmOpX3& op, const float* w, int cout, int cin, const float* scale,
                   const float* shift, int relu, bool first, const ActScale* in = nullptr,
                   const ActScale* out = nullptr, bool withQ8 = false) {
@@ -236,7 +229,7 @@ int build_conv_x3(std::string& err, GemmOpX3& op, const float* w, int cout, int 
   }
   const std::vector<uint16_t> packed = first ? pack_first_x3(w, cout, pre) : pack_conv_x3(w, cout, cin, pre);
   int rc = upload_bf(err, &op.wt, packed);
-  if (!rc && withQ8 && !first && cin % 64 == 0 && cout % 256 == 0) {
+  if (!rc && withQ8 && !first && x3_conv_has_q8(cin, cout)) {
     const std::vector<uint8_t> q = pack_conv_q8(w, cout, cin, pre);
     if (hipMalloc((void**)&op.wq, q.size()) != hipSuccess ||
         hipMemcpy(op.wq, q.data(), q.size(), hipMemcpyHostToDevice) != hipSuccess) {
@@ -319,18 +312,18 @@ struct X3Switches {
   bool flat = true, r512 = true, t448 = true, t448c4 = true;
   int crossFp8 = 0;
 };
+inline bool x3_env_off(const char* name) {   // NAME=0 in the environment
+  const char* e = getenv(name);
+  return e && e[0] == '0';
+}
 thread_local int g_x3CrossFp8 = 0;   // per calling thread: a caller's set / restore around its own forward cannot leak into another thread's
 X3Switches x3_switches() {
   static const X3Switches env = [] {
-    auto on = [](const char* name) {
-      const char* e = getenv(name);
-      return !(e && e[0] == '0');
-    };
     X3Switches s;
-    s.flat = on("UNET_X3_FLAT");
-    s.r512 = on("UNET_X3_R512");
-    s.t448 = on("UNET_X3_T448");
-    s.t448c4 = on("UNET_X3_T448_C4");
+    s.flat = !x3_env_off("UNET_X3_FLAT");
+    s.r512 = !x3_env_off("UNET_X3_R512");
+    s.t448 = !x3_env_off("UNET_X3_T448");
+    s.t448c4 = !x3_env_off("UNET_X3_T448_C4");
     return s;
   }();
   X3Switches s = env;
@@ -887,10 +880,7 @@ hipError_t run_conv_x3(const GemmOpX3& op, const X3ConvIo& io, const X3ConvOpts&
 std::atomic<int> g_x3UpconvR512{-1};
 
 int x3_upconv_r512_mode() {
-  static const bool envOff = [] {
-    const char* e = getenv("UNET_X3_UPCONV_R512");
-    return e && e[0] == '0';
-  }();
+  static const bool envOff = x3_env_off("UNET_X3_UPCONV_R512");
   const int m = g_x3UpconvR512;
   return m < 0 ? (envOff ? 0 : -1) : m;
 }
@@ -1056,105 +1046,69 @@ void compose_upcat(const float* wt, const float* bt, const float* w3, int f, std
     }
 }
 
-struct DecOpX3 {
-  int f = 0, relu = 0;
-  uint16_t* wt = nullptr;   // UpcatX3Args::wt
-  float* scale = nullptr;
-  float* shift = nullptr;
-  float* dshift = nullptr;
-  void free_dev() {
-    for (void* p : {(void*)wt, (void*)scale, (void*)shift, (void*)dshift})
-      if (p) hipFree(p);
-    wt = nullptr;
-    scale = shift = dshift = nullptr;
-  }
+// What every form of one decoder step is built from, on the host: wt (2f,f,2,2), bt (f), w3 (f,2f,3,3) with the BatchNorm
+// scale / shift folded -> compose_upcat's result and both halves of the weights with their inputs' activation scales
+// (skipAct (f), xAct (2f); null: none) divided out (exact: powers of two), as float
+struct DecHostX3 {
+  int f = 0;
+  std::vector<double> wp, bias;   // compose_upcat
+  std::vector<float> ws;          // the skip half W3[:, :f] / skipAct, (f,f,3,3)
+  std::vector<float> wx;          // wp / xAct, [parity][co][ci (2f)][tap]
+  std::vector<float> maxS, maxX;  // max |ws|, max |wx| per output channel: what the pre-scales come from
 };
-
-// the composed operator of one decoder step: wt (2f,f,2,2), bt (f), w3 (f,2f,3,3) with BatchNorm scale / shift folded;
-// skipIn / xIn / out: activation scales of the skip, of x (the transposed convolution's input) and of the output
-int build_upcat_x3(std::string& err, DecOpX3& op, const float* wt, const float* bt, const float* w3, int f, const float* scale,
-                   const float* shift, int relu, const ActScale* skipIn, const ActScale* xIn, const ActScale* out) {
-  op.free_dev();
-  op.f = f;
-  op.relu = relu;
+void dec_host_x3(DecHostX3& hst, const float* wt, const float* bt, const float* w3, int f, const float* skipAct, const float* xAct) {
   const int c2 = 2 * f;
-  std::vector<double> wp, bias;
-  compose_upcat(wt, bt, w3, f, wp, bias);
-  // both halves with their inputs' scales divided out (exact: powers of two), as float
-  std::vector<float> ws((size_t)f * f * 9), wx((size_t)4 * f * c2 * 4);
+  hst.f = f;
+  compose_upcat(wt, bt, w3, f, hst.wp, hst.bias);
+  hst.ws.resize((size_t)f * f * 9);
+  hst.wx.resize(hst.wp.size());
+  hst.maxS.assign(f, 0.f);
+  hst.maxX.assign(f, 0.f);
   for (int co = 0; co < f; ++co)
     for (int ci = 0; ci < f; ++ci)
-      for (int t = 0; t < 9; ++t)
-        ws[((size_t)co * f + ci) * 9 + t] = w3[((size_t)co * c2 + ci) * 9 + t] / (skipIn ? skipIn->act[ci] : 1.f);
+      for (int t = 0; t < 9; ++t) {
+        const float v = w3[((size_t)co * c2 + ci) * 9 + t] / (skipAct ? skipAct[ci] : 1.f);
+        hst.ws[((size_t)co * f + ci) * 9 + t] = v;
+        hst.maxS[co] = std::max(hst.maxS[co], std::fabs(v));
+      }
   for (int p = 0; p < 4; ++p)
     for (int co = 0; co < f; ++co)
       for (int ci = 0; ci < c2; ++ci)
         for (int t = 0; t < 4; ++t) {
           const size_t i = (((size_t)p * f + co) * c2 + ci) * 4 + t;
-          wx[i] = (float)wp[i] / (xIn ? xIn->act[ci] : 1.f);
+          hst.wx[i] = (float)hst.wp[i] / (xAct ? xAct[ci] : 1.f);
+          hst.maxX[co] = std::max(hst.maxX[co], std::fabs(hst.wx[i]));
         }
-  // one power-of-two pre-scale per output channel over both halves (they feed one accumulator)
-  std::vector<float> pre(f);
-  for (int co = 0; co < f; ++co) {
-    float mx = 0.f;
-    for (size_t i = 0; i < (size_t)f * 9; ++i) mx = std::max(mx, std::fabs(ws[(size_t)co * f * 9 + i]));
-    for (int p = 0; p < 4; ++p)
-      for (size_t i = 0; i < (size_t)c2 * 4; ++i) mx = std::max(mx, std::fabs(wx[((size_t)p * f + co) * c2 * 4 + i]));
-    pre[co] = prescale_pow2(mx);
-  }
-  std::vector<float> sc(f), sh(f), dsh((size_t)9 * f);
-  for (int co = 0; co < f; ++co) {
-    const float o = out ? out->act[co] : 1.f;
-    sc[co] = scale[co] / pre[co] * o;
-    double cls[9];
-    for (int k = 0; k < 9; ++k) cls[k] = ((double)shift[co] + (double)scale[co] * bias[(size_t)k * f + co]) * o;
-    sh[co] = (float)cls[4];
-    for (int k = 0; k < 9; ++k) dsh[(size_t)k * f + co] = k == 4 ? 0.f : (float)(cls[k] - (double)sh[co]);
-  }
-  // pack: per 64-channel tile the f / 32 skip chunks [tap 9][plane][cs][lane][8], then the 2f / 32 x chunks
-  // [parity 4][tap 4][plane][cs][lane][8]; row j of subtile cs is channel 64 ct + 16 (j >> 2) + 4 cs + (j & 3)
-  const int nS = f / 32, nX = c2 / 32, nCt = f / 64;
-  const size_t frag = 64 * 8, skipChunk = 9 * 2 * 4 * frag, xChunk = 16 * 2 * 4 * frag;
-  const size_t perCt = nS * skipChunk + nX * xChunk;
+}
+
+// composed form (conv_x3_dec.h): per 64-channel tile the f / 32 skip chunks [tap 9][plane][cs][lane][8], then the 2f / 32
+// x chunks [parity 4][tap 4][plane][cs][lane][8]; one pre-scale per output channel over both halves (one accumulator)
+std::vector<uint16_t> pack_upcat_x3(const float* ws, const float* wx, int f, const std::vector<float>& pre) {
+  const int c2 = 2 * f, nS = f / 32, nX = c2 / 32, nCt = f / 64;
+  const size_t tap = 2 * 4 * kX3Frag, skipChunk = 9 * tap, xChunk = 16 * tap, perCt = nS * skipChunk + nX * xChunk;
   std::vector<uint16_t> packed(nCt * perCt, 0);
   auto put = [&](size_t base, int ct, int kc, auto&& val) {   // one tap: [plane][cs][lane][8]
     for (int cs = 0; cs < 4; ++cs)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int j = lane & 15, lq = lane >> 4;
-        const int co = 64 * ct + 16 * (j >> 2) + 4 * cs + (j & 3);
-        for (int e = 0; e < 8; ++e) {
-          const int ci = kc * 32 + lq * 8 + e;
-          uint16_t* dh = packed.data() + base + ((size_t)(0 * 4 + cs) * 64 + lane) * 8 + e;
-          uint16_t* dl = packed.data() + base + ((size_t)(1 * 4 + cs) * 64 + lane) * 8 + e;
-          host_split_f16(val(co, ci) * pre[co], *dh, *dl);
-        }
-      }
+      x3_put_frag(packed.data() + base + cs * kX3Frag, packed.data() + base + (4 + cs) * kX3Frag, ct, kc, cs,
+                  [&](int co, int ci) { return val(co, ci) * pre[co]; });
   };
   for (int ct = 0; ct < nCt; ++ct) {
     for (int kc = 0; kc < nS; ++kc)
       for (int t = 0; t < 9; ++t)
-        put(ct * perCt + kc * skipChunk + t * 2 * 4 * frag, ct, kc,
-            [&](int co, int ci) { return ws[((size_t)co * f + ci) * 9 + t]; });
+        put(ct * perCt + kc * skipChunk + t * tap, ct, kc, [&](int co, int ci) { return ws[((size_t)co * f + ci) * 9 + t]; });
     for (int kc = 0; kc < nX; ++kc)
       for (int p = 0; p < 4; ++p)
         for (int t = 0; t < 4; ++t)
-          put(ct * perCt + nS * skipChunk + kc * xChunk + (p * 4 + t) * 2 * 4 * frag, ct, kc,
+          put(ct * perCt + nS * skipChunk + kc * xChunk + (p * 4 + t) * tap, ct, kc,
               [&](int co, int ci) { return wx[(((size_t)p * f + co) * c2 + ci) * 4 + t]; });
   }
-  int rc = upload_bf(err, &op.wt, packed);
-  if (!rc) rc = upload(err, &op.scale, sc);
-  if (!rc) rc = upload(err, &op.shift, sh);
-  if (!rc) rc = upload(err, &op.dshift, dsh);
-  return rc;
+  return packed;
 }
 
 // unet_set_x3_compose: -1 = automatic (default; UNET_X3_COMPOSE=0 in the environment makes it 0), 0 = the two-kernel
 // path everywhere, 1 = the composed operator wherever its shape rules allow (also below the work-item threshold)
 int& x3_compose_mode() {
-  static int mode = [] {
-    const char* e = getenv("UNET_X3_COMPOSE");
-    return (e && e[0] == '0') ? 0 : -1;
-  }();
+  static int mode = x3_env_off("UNET_X3_COMPOSE") ? 0 : -1;
   return mode;
 }
 
@@ -1170,67 +1124,6 @@ int& x3_dec_form_mode() {
   return mode;
 }
 
-// the composed decoder step: skip planes (n,h,w) pixel stride ldSkip, x planes (n,h/2,w/2,2f) -> out planes (n,h,w,f)
-// pixel stride ldo.  Returns false (nothing launched) where the shape rules or, with forced == false, the work count do
-// not allow it: f % 64 == 0 and f <= fMax (the forward: 128 - the 8-row, 256-channel tiles of the wider levels are not
-// built; the operator entry point: 256, several channel groups per pixel tile), w % 28 == 0, h even, a work item for
-// half of the CUs and 16-row tiles filled to >= 90 %
-bool run_upcat_x3(const DecOpX3& op, const uint16_t* zeros, const uint16_t* skip, size_t skipLo, int ldSkip, const uint16_t* x,
-                  size_t xLo, int n, int h, int w, uint16_t* out, size_t outLo, int ldo, bool forced, int fMax, hipStream_t s,
-                  hipError_t* err) {
-  *err = hipSuccess;
-  const int f = op.f;
-  if (!op.wt || f % 64 || f > fMax || w % 28 || h % 2 || h < 2) return false;
-  // 128 output channels per block where the channels allow (the 112 x 112 level of model A): both halos staged once per
-  // pixel tile instead of twice, every skip weight fragment serves 14 pixel fragments instead of 7
-  const int form = x3_dec_form_mode();
-  const int wco = (form != 1 && f % 128 == 0) ? 2 : 1;
-  unet::UpcatX3Args a;
-  a.skip = skip;
-  a.skipLo = skipLo;
-  a.x = x;
-  a.xLo = xLo;
-  a.wt = op.wt;
-  a.zeros = zeros;
-  a.scale = op.scale;
-  a.shift = op.shift;
-  a.dshift = op.dshift;
-  a.out = out;
-  a.outLo = outLo;
-  a.N = n;
-  a.H = h;
-  a.W = w;
-  a.F = f;
-  a.ldSkip = ldSkip;
-  a.ldo = ldo;
-  a.tilesX = w / 28;
-  a.tilesY = (h + 15) / 16;
-  a.nS = f / 32;
-  a.nX = 2 * f / 32;
-  a.relu = op.relu;
-  a.coTiles = f / (64 * wco);
-  a.pixTiles = n * a.tilesY * a.tilesX;
-  a.err = g_errWord ? g_errWord : op_err_word();
-  const long items = (long)a.pixTiles * a.coTiles;
-  if (!forced && (items < 128 || 10 * h < 9 * 16 * a.tilesY)) return false;
-  const int grid = (int)std::max<long>(8, std::min<long>(256, items / 8 * 8));
-  const double px = (double)n * h * w;
-  // executed multiply-adds: 9 f^2 (skip) + 8 f^2 (x: 4 taps x 2f) per pixel
-  prof_begin("upcat_conv3x3_dec_f16x3", 2.0 * px * 17.0 * f * f,
-             4.0 * (px * f + px / 4 * 2 * f + px * f) + 2.0 * (9.0 * f * f + 32.0 * f * f), s);
-  auto launch = [&](auto kern) {
-    hipError_t e = ensure_dyn_lds((const void*)kern, unet::X3DShape::LDS_BYTES);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), (size_t)unet::X3DShape::LDS_BYTES, s, a);
-      e = hipGetLastError();
-    }
-    return e;
-  };
-  *err = wco == 2 ? launch(unet::upcat_conv3x3_dec_f16x3_kernel<2>) : launch(unet::upcat_conv3x3_dec_f16x3_kernel<1>);
-  prof_end(s);
-  return true;
-}
-
 // ---- the deep decoder levels' split first convolution (upconv_x3_win.h + the addend epilogue of conv_x3_t448.h) ----
 // The same algebra as the composed operator above, as two launches: kernel 1 forms P = the up half (2 x 2-tap window
 // convolution of x per output parity + the border-class constant) into the up half of the concat buffer, where the
@@ -1241,162 +1134,157 @@ bool run_upcat_x3(const DecOpX3& op, const uint16_t* zeros, const uint16_t* skip
 // unet_set_x3_compose_deep: 1 = on (default; UNET_X3_COMPOSE_DEEP=0 in the environment makes it 0), 0 = the deep levels
 // keep the two-kernel path.  unet_set_x3_compose(0) turns both composed paths off
 int& x3_compose_deep_mode() {
-  static int mode = [] {
-    const char* e = getenv("UNET_X3_COMPOSE_DEEP");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
+  static int mode = x3_env_off("UNET_X3_COMPOSE_DEEP") ? 0 : 1;
   return mode;
 }
 
-// window weights: [coTile(64)][chunk(32)][tap(4) = di * 2 + dj][plane(2)][ab(4)][cs(4)][lane(64)][8]; lane / e as in every
-// f16x3 pack (row j = lane & 15 of subtile cs is channel 64 ct + 16 (j >> 2) + 4 cs + (j & 3), k = 32 kc + 8 (lane >> 4) + e)
-inline size_t updeep_pack_index(int nCh, int ct, int kc, int tap, int plane, int ab, int cs, int lane, int e) {
-  return (((((((size_t)ct * nCh + kc) * 4 + tap) * 2 + plane) * 4 + ab) * 4 + cs) * 64 + lane) * 8 + e;
-}
-
-// What both kernels get, on the host: the window weights in float64 in the pack's order (plane 0's positions; `ordered`,
-// optional: the CPU test reads it), packed hi / lo with the per-channel pre-scale, the class constants
-struct DeepHostX3 {
-  std::vector<uint16_t> packed;
-  std::vector<float> pre, cls;   // pre [f]; cls [9][f], unscaled
-  std::vector<double> cls64;     // the same before its rounding to fp32
-  std::vector<double> wp;        // compose_upcat's window weights [parity][co][ci][tap]
-};
-void pack_updeep_x3(const float* wt, const float* bt, const float* w3, int f, const float* xAct, DeepHostX3& hst,
-                    std::vector<double>* ordered) {
-  const int c2 = 2 * f, nCt = f / 64, nCh = c2 / 32;
-  std::vector<double>& wp = hst.wp;
-  std::vector<double> bias;
-  compose_upcat(wt, bt, w3, f, wp, bias);
-  // x's activation scale divided out (exact: powers of two), as float; one pre-scale per output channel
-  std::vector<float> wx(wp.size());
-  hst.pre.assign(f, 0.f);
-  for (int p = 0; p < 4; ++p)
-    for (int co = 0; co < f; ++co) {
-      float mx = hst.pre[co];
-      for (int ci = 0; ci < c2; ++ci)
-        for (int t = 0; t < 4; ++t) {
-          const size_t i = (((size_t)p * f + co) * c2 + ci) * 4 + t;
-          wx[i] = (float)wp[i] / (xAct ? xAct[ci] : 1.f);
-          mx = std::max(mx, std::fabs(wx[i]));
-        }
-      hst.pre[co] = mx;
-    }
-  for (auto& v : hst.pre) v = prescale_pow2(v);
-  hst.cls.resize((size_t)9 * f);
-  for (size_t i = 0; i < hst.cls.size(); ++i) hst.cls[i] = (float)bias[i];
-  hst.cls64 = bias;
-  hst.packed.assign((size_t)nCt * nCh * 4 * 2 * 4 * 4 * 64 * 8, 0);
-  if (ordered) ordered->assign(hst.packed.size(), 0.0);
+// window weights: [coTile(64)][chunk(32)][tap(4) = di * 2 + dj][plane(2)][ab(4)][cs(4)][lane(64)][8], packed hi / lo with
+// the per-channel pre-scale `pre`; `ordered` (optional: the CPU test reads it): the window weights in float64 in the
+// pack's order (plane 0's positions)
+std::vector<uint16_t> pack_updeep_x3(const DecHostX3& hst, std::vector<float>& pre, std::vector<double>* ordered) {
+  const int f = hst.f, c2 = 2 * f, nCt = f / 64, nCh = c2 / 32;
+  pre.resize(f);
+  for (int co = 0; co < f; ++co) pre[co] = prescale_pow2(hst.maxX[co]);
+  std::vector<uint16_t> packed((size_t)nCt * nCh * 4 * 2 * 4 * 4 * kX3Frag, 0);
+  if (ordered) ordered->assign(packed.size(), 0.0);
   for (int ct = 0; ct < nCt; ++ct)
     for (int kc = 0; kc < nCh; ++kc)
       for (int tap = 0; tap < 4; ++tap)
         for (int ab = 0; ab < 4; ++ab)
-          for (int cs = 0; cs < 4; ++cs)
-            for (int lane = 0; lane < 64; ++lane) {
-              const int j = lane & 15, lq = lane >> 4;
-              const int co = 64 * ct + 16 * (j >> 2) + 4 * cs + (j & 3);
-              for (int e = 0; e < 8; ++e) {
-                const int ci = kc * 32 + lq * 8 + e;
-                const size_t src = (((size_t)ab * f + co) * c2 + ci) * 4 + tap;
-                const size_t ih = updeep_pack_index(nCh, ct, kc, tap, 0, ab, cs, lane, e);
-                const size_t il = updeep_pack_index(nCh, ct, kc, tap, 1, ab, cs, lane, e);
-                host_split_f16(wx[src] * hst.pre[co], hst.packed[ih], hst.packed[il]);
-                if (ordered) (*ordered)[ih] = wp[src];
-              }
-            }
+          for (int cs = 0; cs < 4; ++cs) {
+            const size_t hi = ((((((size_t)ct * nCh + kc) * 4 + tap) * 2 + 0) * 4 + ab) * 4 + cs) * kX3Frag, lo = hi + 16 * kX3Frag;
+            auto src = [&](int co, int ci) { return (((size_t)ab * f + co) * c2 + ci) * 4 + tap; };
+            x3_put_frag(&packed[hi], &packed[lo], ct, kc, cs, [&](int co, int ci) { return hst.wx[src(co, ci)] * pre[co]; });
+            if (ordered) x3_each_frag_elem(ct, kc, cs, [&](int i, int co, int ci) { (*ordered)[hi + i] = hst.wp[src(co, ci)]; });
+          }
+  return packed;
 }
 
-struct DeepOpX3 {
+// ---- one decoder step: ConvTranspose2d(2f -> f) -> cat([skip, up]) -> Conv3x3(2f -> f) -> Conv3x3(f -> f) ----
+// Its operators in every form the step can run in (x3_plan_dec_step chooses per launch): the two-kernel form's up +
+// conv1, the composed and the deep operator where the width has them (x3_dec_step_forms), and the second convolution
+enum { kX3DecTwoKernel = 0, kX3DecComposed = 1, kX3DecDeep = 2 };   // X3DecStepPlan::form; as bits 1 / 2: a set of operators
+struct DecStepX3 {
   int f = 0, relu = 0;
-  uint16_t* wtWin = nullptr;   // kernel 1: the window weights, scale aP / pre, the nine class constants x aP
-  float* scaleWin = nullptr;
-  float* cls = nullptr;
-  uint16_t* wtSkip = nullptr;  // kernel 2: W3[:, :f] packed as every 3x3 weight, s, t, sP
-  float* scale = nullptr;
-  float* shift = nullptr;
-  float* addScale = nullptr;
-  void free_dev() {
-    for (void* p : {(void*)wtWin, (void*)scaleWin, (void*)cls, (void*)wtSkip, (void*)scale, (void*)shift, (void*)addScale})
+  GemmOpX3 up, conv1, conv2;
+  struct Composed {   // UpcatX3Args::wt, scale, shift, dshift
+    uint16_t* wt = nullptr;
+    float *scale = nullptr, *shift = nullptr, *dshift = nullptr;
+  } comp;
+  struct Deep {   // kernel 1: the window weights, scale aP / pre, the nine class constants x aP; kernel 2: W3[:, :f] packed
+    uint16_t *wtWin = nullptr, *wtSkip = nullptr;   // as every 3x3 weight, s, t, sP
+    float *scaleWin = nullptr, *cls = nullptr, *scale = nullptr, *shift = nullptr, *addScale = nullptr;
+  } deep;
+  void free_forms() {
+    for (void* p : {(void*)comp.wt, (void*)comp.scale, (void*)comp.shift, (void*)comp.dshift, (void*)deep.wtWin, (void*)deep.wtSkip,
+                    (void*)deep.scaleWin, (void*)deep.cls, (void*)deep.scale, (void*)deep.shift, (void*)deep.addScale})
       if (p) hipFree(p);
-    wtWin = wtSkip = nullptr;
-    scaleWin = cls = scale = shift = addScale = nullptr;
+    comp = Composed(), deep = Deep();
   }
+  void free_dev() { up.free_dev(), conv1.free_dev(), conv2.free_dev(), free_forms(); }
 };
+// Which of the two operators a step of width f can have.  The forward's handle: composed up to 128 channels (the 8-row,
+// 256-channel tiles of the wider levels are not built), deep where kernel 2's 256-channel form tiles f.  An operator entry
+// point: composed up to 256 channels (several channel groups per pixel tile), deep at any width x3_plan_updeep takes
+inline int x3_dec_step_forms(int f, bool entry) {
+  return (f % 64 == 0 && f <= (entry ? 256 : 128) ? kX3DecComposed : 0) | (entry || f % 256 == 0 ? kX3DecDeep : 0);
+}
 
-// wt (2f,f,2,2), bt (f), w3 (f,2f,3,3) with BatchNorm scale / shift folded; skipIn / xIn / out: activation scales of the
-// skip, of x and of the output (null: none)
-int build_updeep_x3(std::string& err, DeepOpX3& op, const float* wt, const float* bt, const float* w3, int f, const float* scale,
-                    const float* shift, int relu, const ActScale* skipIn, const ActScale* xIn, const ActScale* out) {
-  op.free_dev();
-  op.f = f;
-  op.relu = relu;
+// The operators `forms` of one step (st.comp, st.deep) from one composition: wt (2f,f,2,2), bt (f), w3 (f,2f,3,3) with
+// BatchNorm scale / shift folded; skipIn / xIn / out: activation scales of the skip, of x (the transposed convolution's
+// input) and of the output (null: none)
+int build_dec_step_x3(std::string& err, DecStepX3& st, int forms, const float* wt, const float* bt, const float* w3, int f,
+                      const float* scale, const float* shift, int relu, const ActScale* skipIn, const ActScale* xIn,
+                      const ActScale* out) {
+  st.free_forms();
+  st.f = f, st.relu = relu;
+  if (!forms) return UNET_OK;
   const int c2 = 2 * f;
-  DeepHostX3 hst;
-  pack_updeep_x3(wt, bt, w3, f, xIn ? xIn->act.data() : nullptr, hst, nullptr);
-  // P's scale: four standard deviations of the window sum (independent channels, as build_upconv_x3 estimates its
-  // output) plus the interior constant, where x carries magnitudes
-  std::vector<float> aP(f, 1.f);
-  if (xIn && std::any_of(xIn->mag.begin(), xIn->mag.end(), [](float m) { return m > 0.f; })) {
-    const std::vector<double>& wp = hst.wp;
+  DecHostX3 hst;
+  dec_host_x3(hst, wt, bt, w3, f, skipIn ? skipIn->act.data() : nullptr, xIn ? xIn->act.data() : nullptr);
+  int rc = UNET_OK;
+  if (forms & kX3DecComposed) {
+    DecStepX3::Composed& op = st.comp;
+    std::vector<float> pre(f), sc(f), sh(f), dsh((size_t)9 * f);
     for (int co = 0; co < f; ++co) {
-      double var = 0;
-      for (int ci = 0; ci < c2; ++ci) {
-        const double sd = xIn->mag[ci] / 4.0;
-        for (int t = 0; t < 4; ++t) {
-          double m = 0;
-          for (int p = 0; p < 4; ++p) m = std::max(m, std::fabs(wp[(((size_t)p * f + co) * c2 + ci) * 4 + t]));
-          var += m * m * sd * sd;
-        }
-      }
-      aP[co] = act_scale_pow2((float)(4.0 * std::sqrt(var)) + std::fabs(hst.cls[(size_t)4 * f + co]));
+      pre[co] = prescale_pow2(std::max(hst.maxS[co], hst.maxX[co]));
+      const float o = out ? out->act[co] : 1.f;
+      sc[co] = scale[co] / pre[co] * o;
+      double cls[9];
+      for (int k = 0; k < 9; ++k) cls[k] = ((double)shift[co] + (double)scale[co] * hst.bias[(size_t)k * f + co]) * o;
+      sh[co] = (float)cls[4];
+      for (int k = 0; k < 9; ++k) dsh[(size_t)k * f + co] = k == 4 ? 0.f : (float)(cls[k] - (double)sh[co]);
     }
+    rc = upload_bf(err, &op.wt, pack_upcat_x3(hst.ws.data(), hst.wx.data(), f, pre));
+    if (!rc) rc = upload(err, &op.scale, sc);
+    if (!rc) rc = upload(err, &op.shift, sh);
+    if (!rc) rc = upload(err, &op.dshift, dsh);
   }
-  std::vector<float> scW(f), cls((size_t)9 * f);
-  for (int co = 0; co < f; ++co) {
-    scW[co] = aP[co] / hst.pre[co];
-    for (int k = 0; k < 9; ++k) cls[(size_t)k * f + co] = hst.cls[(size_t)k * f + co] * aP[co];
+  if (!rc && (forms & kX3DecDeep)) {
+    DecStepX3::Deep& op = st.deep;
+    std::vector<float> preW;
+    const std::vector<uint16_t> win = pack_updeep_x3(hst, preW, nullptr);
+    auto cls0 = [&](int k, int co) { return (float)hst.bias[(size_t)k * f + co]; };   // the class constants, unscaled
+    // P's scale: four standard deviations of the window sum (independent channels, as build_upconv_x3 estimates its
+    // output) plus the interior constant, where x carries magnitudes
+    std::vector<float> aP(f, 1.f);
+    if (xIn && std::any_of(xIn->mag.begin(), xIn->mag.end(), [](float m) { return m > 0.f; })) {
+      for (int co = 0; co < f; ++co) {
+        double var = 0;
+        for (int ci = 0; ci < c2; ++ci) {
+          const double sd = xIn->mag[ci] / 4.0;
+          for (int t = 0; t < 4; ++t) {
+            double m = 0;
+            for (int p = 0; p < 4; ++p) m = std::max(m, std::fabs(hst.wp[(((size_t)p * f + co) * c2 + ci) * 4 + t]));
+            var += m * m * sd * sd;
+          }
+        }
+        aP[co] = act_scale_pow2((float)(4.0 * std::sqrt(var)) + std::fabs(cls0(4, co)));
+      }
+    }
+    std::vector<float> scW(f), cls((size_t)9 * f), preS(f), sc(f), sh(f), sp(f);
+    for (int co = 0; co < f; ++co) {
+      scW[co] = aP[co] / preW[co];
+      for (int k = 0; k < 9; ++k) cls[(size_t)k * f + co] = cls0(k, co) * aP[co];
+      preS[co] = prescale_pow2(hst.maxS[co]);   // the skip half runs as a 3x3 convolution of its own
+      const float o = out ? out->act[co] : 1.f;
+      sc[co] = scale[co] / preS[co] * o;
+      sh[co] = shift[co] * o;
+      sp[co] = scale[co] * o / aP[co];
+    }
+    rc = upload_bf(err, &op.wtWin, win);
+    if (!rc) rc = upload(err, &op.scaleWin, scW);
+    if (!rc) rc = upload(err, &op.cls, cls);
+    if (!rc) rc = upload_bf(err, &op.wtSkip, pack_conv_x3(hst.ws.data(), f, f, preS));
+    if (!rc) rc = upload(err, &op.scale, sc);
+    if (!rc) rc = upload(err, &op.shift, sh);
+    if (!rc) rc = upload(err, &op.addScale, sp);
   }
-  // the skip half: W3[:, :f] with the skip's scale divided out
-  std::vector<float> ws((size_t)f * f * 9);
-  for (int co = 0; co < f; ++co)
-    for (int ci = 0; ci < f; ++ci)
-      for (int t = 0; t < 9; ++t)
-        ws[((size_t)co * f + ci) * 9 + t] = w3[((size_t)co * c2 + ci) * 9 + t] / (skipIn ? skipIn->act[ci] : 1.f);
-  const std::vector<float> preS = row_prescale(ws.data(), f, (size_t)f * 9);
-  std::vector<float> sc(f), sh(f), sp(f);
-  for (int co = 0; co < f; ++co) {
-    const float o = out ? out->act[co] : 1.f;
-    sc[co] = scale[co] / preS[co] * o;
-    sh[co] = shift[co] * o;
-    sp[co] = scale[co] * o / aP[co];
-  }
-  int rc = upload_bf(err, &op.wtWin, hst.packed);
-  if (!rc) rc = upload(err, &op.scaleWin, scW);
-  if (!rc) rc = upload(err, &op.cls, cls);
-  if (!rc) rc = upload_bf(err, &op.wtSkip, pack_conv_x3(ws.data(), f, f, preS));
-  if (!rc) rc = upload(err, &op.scale, sc);
-  if (!rc) rc = upload(err, &op.shift, sh);
-  if (!rc) rc = upload(err, &op.addScale, sp);
   return rc;
 }
 
-// The plan of the two launches: a pure function of integers, like x3_plan_conv / x3_plan_upconv (which keep their answers:
-// this path is asked for first and the others only where it declines).  h, w: the low-resolution map of x
-struct X3UpdeepQuery {
+// ---- which form a decoder step runs in (DESIGN.md, section 4.15): a pure function of integers, like the other plans ----
+// Asked in this order: the composed operator, the deep levels' split form, else the two kernels (whose own dispatch is
+// x3_plan_upconv / x3_plan_conv).  h, w: the LOW-resolution map of x, here and in X3DecIo; H = 2h, W = 2w below
+struct X3DecStepQuery {
   int n = 0, h = 0, w = 0, f = 0;
-  int compose = -1;      // x3_compose_mode(): 0 off, -1 automatic, 1 wherever the shapes allow
-  bool deep = true;      // x3_compose_deep_mode()
-  bool q8 = false;       // the f16q8 tier is on: it keeps the two-kernel path
-  bool window_only = false;   // (operator entry point) kernel 1 alone: f % 64 == 0 is enough
+  int compose = -1;         // x3_compose_mode(): 0 two kernels everywhere, -1 automatic, 1 wherever the shapes allow
+  bool deep = true;         // x3_compose_deep_mode()
+  int decForm = -1;         // x3_dec_form_mode()
+  bool q8 = false;          // the forward holds f16q8 scratch
+  bool entry = false;       // who asks: the forward, or an operator entry point (which forces its operator: compose = 1)
+  int have = kX3DecComposed | kX3DecDeep;   // the operators the asker holds, of those x3_dec_step_forms gives its width
+  bool windowOnly = false;  // (entry point) the deep form's kernel 1 alone: f % 64 == 0 is enough
+  int upconvMode = -1;      // x3_upconv_r512_mode(): only the two-kernel form's labels depend on it
   X3Switches sw;
 };
+// The deep form's own plan (its two launches); it reads n, h, w, f, compose, deep, q8, windowOnly and the switches
 struct X3UpdeepPlan {
   bool take = false;
   int wmax = 0, pixTiles = 0, coTiles = 0, grid = 0;   // kernel 1
   X3ConvPlan conv;                                     // kernel 2: the third structure's 256-channel form
 };
-X3UpdeepPlan x3_plan_updeep(const X3UpdeepQuery& q) {
+X3UpdeepPlan x3_plan_updeep(const X3DecStepQuery& q) {
   X3UpdeepPlan p;
   const long npix = (long)q.n * q.h * q.w;
   if (q.compose == 0 || !q.deep || q.q8 || q.n < 1 || q.h < 1 || q.w < 4 || q.w > 28 || q.f < 64 || q.f % 64 ||
@@ -1407,7 +1295,7 @@ X3UpdeepPlan x3_plan_updeep(const X3UpdeepQuery& q) {
   p.coTiles = q.f / 64;
   const long items = (long)p.pixTiles * p.coTiles;
   p.grid = x3_grid(items);
-  if (!q.window_only) {
+  if (!q.windowOnly) {
     if (q.f % 256) return p;
     X3ConvQuery c;
     c.n = q.n, c.h = 2 * q.h, c.w = 2 * q.w, c.cin = q.f, c.cout = q.f, c.epi = 0;
@@ -1423,64 +1311,155 @@ X3UpdeepPlan x3_plan_updeep(const X3UpdeepQuery& q) {
   return p;
 }
 
-// x planes (n,h,w,2f) and the skip half of the concat buffer `cat` (n,2h,2w; pixel stride 2f; channels [0,f)) -> P into
-// channels [f,2f) of `cat`, then out planes (n,2h,2w,f) with pixel stride ldo.  Returns false (nothing launched) where the
-// plan declines.  windowOnly (operator entry point): kernel 1 alone, into `cat` at pixel stride ldCat, channel offset coOff
-bool run_updeep_x3(const DeepOpX3& op, const uint16_t* zeros, uint16_t* cat, size_t catLo, int ldCat, int coOff,
-                   const uint16_t* x, size_t xLo, int n, int h, int w, uint16_t* out, size_t outLo, int ldo, int compose,
-                   bool q8, bool windowOnly, hipStream_t s, hipError_t* err) {
-  *err = hipSuccess;
-  if (!op.wtWin) return false;
-  X3UpdeepQuery q;
-  q.n = n, q.h = h, q.w = w, q.f = op.f, q.compose = compose, q.deep = x3_compose_deep_mode() != 0, q.q8 = q8;
-  q.window_only = windowOnly;
-  q.sw = x3_switches();
-  const X3UpdeepPlan p = x3_plan_updeep(q);
-  if (!p.take) return false;
-  const int f = op.f;
-  const double pxLo = (double)n * h * w, pxHi = 4.0 * pxLo;
+struct X3DecStepPlan {
+  int form = kX3DecTwoKernel;
+  int wco = 0, tilesX = 0, tilesY = 0, pixTiles = 0, coTiles = 0, grid = 0;   // composed: upcat_conv3x3_dec_f16x3_kernel<wco>
+  X3UpdeepPlan deep;        // deep
+  int nLaunch = 0;          // composed / deep: the launches run_dec_step_x3 makes and their profiler labels
+  const char* label[2] = {nullptr, nullptr};
+};
+X3DecStepPlan x3_plan_dec_step(const X3DecStepQuery& q) {
+  X3DecStepPlan p;
+  const int have = q.have & x3_dec_step_forms(q.f, q.entry);
+  if (q.compose == 0) return p;
+  const int H = 2 * q.h, W = 2 * q.w;   // (H is even as the composed kernel needs it)
+  if ((have & kX3DecComposed) && (q.entry || !q.q8) && W % 28 == 0 && H >= 2) {
+    // 128 output channels per block where the channels allow (the 112 x 112 level of model A): both halos staged once per
+    // pixel tile instead of twice, every skip weight fragment serves 14 pixel fragments instead of 7
+    p.wco = (q.decForm != 1 && q.f % 128 == 0) ? 2 : 1;
+    p.tilesX = W / 28, p.tilesY = (H + 15) / 16;
+    p.coTiles = q.f / (64 * p.wco), p.pixTiles = q.n * p.tilesY * p.tilesX;
+    const long items = (long)p.pixTiles * p.coTiles;
+    // unless forced: a work item for half of the CUs and 16-row tiles filled to >= 90 %
+    if (q.entry || q.compose == 1 || !(items < 128 || 10 * H < 9 * 16 * p.tilesY)) {
+      p.form = kX3DecComposed, p.grid = x3_grid(items);
+      p.nLaunch = 1, p.label[0] = "upcat_conv3x3_dec_f16x3";
+      return p;
+    }
+  }
+  if (have & kX3DecDeep) {
+    p.deep = x3_plan_updeep(q);
+    if (p.deep.take) {
+      p.form = kX3DecDeep, p.nLaunch = q.windowOnly ? 1 : 2;
+      p.label[0] = "upconv2x2_win_f16x3";
+      p.label[1] = p.deep.conv.path.flat ? "conv3x3_t448add_f16x3_t28_c4_flat" : "conv3x3_t448add_f16x3_t28_c4";
+    }
+  }
+  return p;
+}
+// the query as the library's switches stand
+X3DecStepQuery x3_dec_step_query(int n, int h, int w, int f, bool q8, bool entry, int have = kX3DecComposed | kX3DecDeep) {
+  X3DecStepQuery q;
+  q.n = n, q.h = h, q.w = w, q.f = f, q.q8 = q8, q.entry = entry, q.have = have;
+  q.compose = entry ? 1 : x3_compose_mode(), q.deep = x3_compose_deep_mode() != 0, q.decForm = x3_dec_form_mode();
+  q.upconvMode = x3_upconv_r512_mode(), q.sw = x3_switches();
+  return q;
+}
+// The profiler labels of the step's launches up to its second convolution, comma-separated.  Two-kernel form: of the
+// launches as the forward makes them while no q plane is handed on (X3Q8Link), its split-K scratch included
+void x3_dec_step_labels(const X3DecStepQuery& q, const X3DecStepPlan& p, char* buf, size_t cap) {
+  std::string out;
+  auto add = [&](const char* lb) { out += (out.empty() ? "" : ",") + std::string(lb); };
+  for (int i = 0; i < p.nLaunch; ++i) add(p.label[i]);
+  if (p.form == kX3DecTwoKernel) {
+    X3UpconvQuery u;
+    u.npix = (long)q.n * q.h * q.w, u.w = q.w, u.cin = 2 * q.f, u.cout = q.f, u.coOff = q.f, u.mode = q.upconvMode;
+    add(x3_upconv_label(x3_plan_upconv(u)));
+    X3ConvQuery c;
+    c.n = q.n, c.h = 2 * q.h, c.w = 2 * q.w, c.cin = 2 * q.f, c.cout = q.f;
+    c.splitScratch = true, c.splitFloats = kSplitFloats, c.sw = q.sw;
+    c.qScratch = q.q8, c.wq = q.q8 && x3_conv_has_q8(c.cin, c.cout);
+    const X3ConvPlan cp = x3_plan_conv(c);
+    char lb[48];
+    x3_conv_label(cp, lb, sizeof(lb));
+    if (cp.toQ8Pass) add("planes_to_q8");
+    add(lb);
+    if (cp.finishPass) add("splitk_finish_f16x3");
+  }
+  snprintf(buf, cap, "%s", out.c_str());
+}
+
+// The tensors of one decoder step.  xo: x planes (n,h,w,2f) in -> out planes (n,2h,2w,f) at pixel stride ldo (xo.coOff
+// unused; n, h, w as in the query: the low-resolution map).  cat: planes (n,2h,2w) at pixel stride ldCat whose channels
+// [0,f) hold the skip; the deep form writes P into its channels [upOff, upOff + f) (composed: only the skip is read)
+struct X3DecIo {
+  X3ConvIo xo;
+  uint16_t* cat = nullptr;
+  size_t catLo = 0;
+  int ldCat = 0, upOff = 0;
+};
+
+// Runs a composed or deep plan (a two-kernel plan is the caller's: run_upconv_x3 + run_conv_x3).  A deep plan of one launch
+// (windowOnly) writes P alone and leaves `out` alone
+hipError_t run_dec_step_x3(const DecStepX3& st, const X3DecStepPlan& p, const X3DecIo& io, hipStream_t s) {
+  const X3ConvIo& xo = io.xo;
+  const int n = xo.n, h = xo.h, w = xo.w, f = st.f;
+  const double pxLo = (double)n * h * w, px = 4.0 * pxLo;
+  if (p.form == kX3DecComposed && st.comp.wt) {
+    const DecStepX3::Composed& op = st.comp;
+    unet::UpcatX3Args a;
+    a.skip = io.cat, a.skipLo = io.catLo, a.ldSkip = io.ldCat;
+    a.x = xo.in, a.xLo = xo.inLo;
+    a.wt = op.wt, a.zeros = xo.zeros, a.scale = op.scale, a.shift = op.shift, a.dshift = op.dshift, a.relu = st.relu;
+    a.out = xo.out, a.outLo = xo.outLo, a.ldo = xo.ldo;
+    a.N = n, a.H = 2 * h, a.W = 2 * w, a.F = f;
+    a.tilesX = p.tilesX, a.tilesY = p.tilesY, a.pixTiles = p.pixTiles, a.coTiles = p.coTiles;
+    a.nS = f / 32, a.nX = 2 * f / 32;
+    a.err = g_errWord ? g_errWord : op_err_word();
+    void (*kern)(const unet::UpcatX3Args) = p.wco == 2 ? unet::upcat_conv3x3_dec_f16x3_kernel<2> : unet::upcat_conv3x3_dec_f16x3_kernel<1>;
+    // executed multiply-adds: 9 f^2 (skip) + 8 f^2 (x: 4 taps x 2f) per pixel
+    prof_begin(p.label[0], 2.0 * px * 17.0 * f * f, 4.0 * (px * f + px / 4 * 2 * f + px * f) + 2.0 * (9.0 * f * f + 32.0 * f * f), s);
+    hipError_t e = ensure_dyn_lds((const void*)kern, unet::X3DShape::LDS_BYTES);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), (size_t)unet::X3DShape::LDS_BYTES, s, a);
+      e = hipGetLastError();
+    }
+    prof_end(s);
+    return e;
+  }
+  if (p.form != kX3DecDeep || !st.deep.wtWin) return hipErrorInvalidValue;
+  const DecStepX3::Deep& op = st.deep;
   {
     unet::UpconvX3Args a{};
-    a.in = x, a.inLo = xLo, a.zeros = zeros, a.wt = op.wtWin;
+    a.in = xo.in, a.inLo = xo.inLo, a.zeros = xo.zeros, a.wt = op.wtWin;
     a.scale = op.scaleWin, a.bias = op.cls;
-    a.out = cat, a.outLo = catLo;
-    a.npix = (long)n * h * w, a.h = h, a.w = w, a.Cin = 2 * f, a.Cout = f, a.ldo = ldCat, a.co_off = coOff;
-    a.nChunks = 2 * f / 32, a.coTiles = p.coTiles, a.pixTiles = p.pixTiles, a.abSplit = 1;
+    a.out = io.cat, a.outLo = io.catLo;
+    a.npix = (long)n * h * w, a.h = h, a.w = w, a.Cin = 2 * f, a.Cout = f, a.ldo = io.ldCat, a.co_off = io.upOff;
+    a.nChunks = 2 * f / 32, a.coTiles = p.deep.coTiles, a.pixTiles = p.deep.pixTiles, a.abSplit = 1;
     a.err = g_errWord ? g_errWord : op_err_word();
-    void (*kern)(const unet::UpconvX3Args) = p.wmax == 14 ? unet::upconv2x2_x3_win_kernel<14> : unet::upconv2x2_x3_win_kernel<28>;
-    const int lds = p.wmax == 14 ? unet::UpconvX3WShape<14>::LDS_BYTES : unet::UpconvX3WShape<28>::LDS_BYTES;
-    *err = ensure_dyn_lds((const void*)kern, lds);
-    if (*err != hipSuccess) return true;
+    const bool w14 = p.deep.wmax == 14;
+    void (*kern)(const unet::UpconvX3Args) = w14 ? unet::upconv2x2_x3_win_kernel<14> : unet::upconv2x2_x3_win_kernel<28>;
+    const int lds = w14 ? unet::UpconvX3WShape<14>::LDS_BYTES : unet::UpconvX3WShape<28>::LDS_BYTES;
+    hipError_t e = ensure_dyn_lds((const void*)kern, lds);
+    if (e != hipSuccess) return e;
     // executed multiply-adds: 4 taps x 2f per output pixel and channel; x read, P written, the window weights
-    prof_begin("upconv2x2_win_f16x3", 2.0 * pxHi * 8.0 * f * f, 4.0 * (pxLo * 2 * f + pxHi * f) + 2.0 * 32.0 * f * f, s);
-    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), (size_t)lds, s, a);
+    prof_begin(p.label[0], 2.0 * px * 8.0 * f * f, 4.0 * (pxLo * 2 * f + px * f) + 2.0 * 32.0 * f * f, s);
+    hipLaunchKernelGGL(kern, dim3(p.deep.grid), dim3(256), (size_t)lds, s, a);
     prof_end(s);
-    *err = hipGetLastError();
-    if (*err != hipSuccess || windowOnly) return true;
+    e = hipGetLastError();
+    if (e != hipSuccess || p.nLaunch == 1) return e;
   }
-  const X3ConvPlan& c = p.conv;
+  const X3ConvPlan& c = p.deep.conv;
   unet::ConvX3AddArgs a{};
-  a.in = cat, a.inLo = catLo, a.zeros = zeros, a.wt = op.wtSkip;
-  a.scale = op.scale, a.shift = op.shift, a.relu = op.relu;
-  a.out = out, a.outLo = outLo, a.ldo = ldo, a.co_off = 0;
+  a.in = io.cat, a.inLo = io.catLo, a.zeros = xo.zeros, a.wt = op.wtSkip;
+  a.scale = op.scale, a.shift = op.shift, a.relu = st.relu;
+  a.out = xo.out, a.outLo = xo.outLo, a.ldo = xo.ldo, a.co_off = 0;
   a.N = c.N, a.H = c.H, a.W = 2 * w, a.imgH = c.imgH, a.Cin = f, a.Cout = f;
   a.tilesX = c.tilesX, a.tilesY = c.tilesY, a.pixTiles = c.pixTiles;
   a.coTiles = c.coTiles, a.coGroup = c.coGroup, a.nChunks = c.nChunks, a.kSplit = 1, a.chunksTotal = f / 32;
   a.err = g_errWord ? g_errWord : op_err_word();
-  a.ldi = ldCat, a.ldAdd = ldCat, a.add = cat + coOff, a.addLo = catLo, a.addScale = op.addScale;
+  a.ldi = io.ldCat, a.ldAdd = io.ldCat, a.add = io.cat + io.upOff, a.addLo = io.catLo, a.addScale = op.addScale;
   const bool flat = c.path.flat != 0;
   using S = unet::X3TShape<28, unet::x3t_row_blocks(4)>;
   void (*kern)(const unet::ConvX3AddArgs) = flat ? unet::conv3x3_x3_t448add_kernel<true> : unet::conv3x3_x3_t448add_kernel<false>;
   const int lds = flat ? S::LDS_BYTES_FLAT : S::LDS_BYTES_PLAIN;
-  *err = ensure_dyn_lds((const void*)kern, lds);
-  if (*err != hipSuccess) return true;
+  const hipError_t e = ensure_dyn_lds((const void*)kern, lds);
+  if (e != hipSuccess) return e;
   // the skip half's 3x3 convolution; the skip and P read, the output written
-  prof_begin(flat ? "conv3x3_t448add_f16x3_t28_c4_flat" : "conv3x3_t448add_f16x3_t28_c4", 2.0 * pxHi * 9.0 * f * f,
-             4.0 * (pxHi * f + pxHi * f + pxHi * f) + 2.0 * 9.0 * f * f, s);
+  prof_begin(p.label[1], 2.0 * px * 9.0 * f * f, 4.0 * (px * f + px * f + px * f) + 2.0 * 9.0 * f * f, s);
   hipLaunchKernelGGL(kern, dim3(c.grid), dim3(256), (size_t)lds, s, a);
   prof_end(s);
-  *err = hipGetLastError();
-  return true;
+  return hipGetLastError();
 }
 
 // First convolution on conv_first_x3.h: uint8 (N,H,W,3) frames (u8) or an fp32 NCHW image -> planes (N,H,W,op.cout) with
@@ -1527,9 +1506,8 @@ struct X3Net {
   float* splitScratch = nullptr; // split-K partial sums (kSplitFloats floats)
   uint16_t* zeros = nullptr;
   float* headW = nullptr;        // head weights with the last activation's scale divided out
-  std::vector<GemmOpX3> enc, bott, up, dec;
-  std::vector<DecOpX3> comp;     // per decoder step j: the composed up + dec[2 j] operator (conv_x3_dec.h), where built
-  std::vector<DeepOpX3> deep;    // per decoder step j: the split form of the same (upconv_x3_win.h + t448add), where built
+  std::vector<GemmOpX3> enc, bott;
+  std::vector<DecStepX3> dec;    // per decoder step j: its operators in every form it can run in
   GrowBuf ws;
   bool hasQ8 = false;            // the operators carry their fp8 cross-term fragments (f16q8 tier)
   GrowBuf qbuf;                  // q plane of the layer input being consumed (f16q8 tier)
@@ -1537,10 +1515,9 @@ struct X3Net {
 
 static void x3_free(unet_ctx* h) {
   if (!h->x3) return;
-  for (auto* v : {&h->x3->enc, &h->x3->bott, &h->x3->up, &h->x3->dec})
+  for (auto* v : {&h->x3->enc, &h->x3->bott})
     for (auto& op : *v) op.free_dev();
-  for (auto& op : h->x3->comp) op.free_dev();
-  for (auto& op : h->x3->deep) op.free_dev();
+  for (auto& st : h->x3->dec) st.free_dev();
   h->x3->ws.release();
   h->x3->qbuf.release();
   if (h->x3->zeros) hipFree(h->x3->zeros);
@@ -1585,10 +1562,7 @@ int x3_build(unet_ctx* h) {
   const bool withQ8 = g_x3CrossFp8 == 1;   // pack the fp8 cross-term fragments too (58 MB for model A)
   X->hasQ8 = withQ8;
   // UNET_X3_ACT_SCALE=0: planes hold the activations themselves (A/B against the per-channel scales)
-  const bool useAct = [] {
-    const char* e = getenv("UNET_X3_ACT_SCALE");
-    return !(e && e[0] == '0');
-  }();
+  const bool useAct = !x3_env_off("UNET_X3_ACT_SCALE");
   auto conv = [&](GemmOpX3& o, const std::string& prefix, int convIdx, int bnIdx, int cin, int cout, bool first,
                   const ActScale* in, ActScale* out) -> int {
     const auto& w = P[prefix + "." + std::to_string(convIdx) + ".weight"];
@@ -1600,10 +1574,7 @@ int x3_build(unet_ctx* h) {
                          useAct ? out : nullptr, withQ8);
   };
   X->enc.assign(2 * c.depth, GemmOpX3());
-  X->dec.assign(2 * c.depth, GemmOpX3());
-  X->up.assign(c.depth, GemmOpX3());
-  X->comp.assign(c.depth, DecOpX3());
-  X->deep.assign(c.depth, DeepOpX3());
+  X->dec.assign(c.depth, DecStepX3());
   X->bott.assign(2, GemmOpX3());
   int rc;
   int cin = 3;
@@ -1624,7 +1595,7 @@ int x3_build(unet_ctx* h) {
     const int f = c.features[l];
     const std::string pu = "decoder_blocks." + std::to_string(2 * j);
     ActScale upOut;
-    if ((rc = build_upconv_x3(h->err, X->up[j], P[pu + ".weight"].data(), 2 * f, f, P[pu + ".bias"].data(),
+    if ((rc = build_upconv_x3(h->err, X->dec[j].up, P[pu + ".weight"].data(), 2 * f, f, P[pu + ".bias"].data(),
                               useAct ? &cur : nullptr, useAct ? &upOut : nullptr)))
       return rc;
     if (!useAct) {
@@ -1633,27 +1604,18 @@ int x3_build(unet_ctx* h) {
     }
     const ActScale cat = act_concat(skip[l], upOut);   // torch.cat([skip, x]) (reference README.md:1478)
     const std::string pd = "decoder_blocks." + std::to_string(2 * j + 1);
-    if ((rc = conv(X->dec[2 * j], pd, 0, 1, 2 * f, f, false, &cat, &tmp))) return rc;
-    if (f % 64 == 0 && f <= 128) {
-      // the same step composed (conv_x3_dec.h): x = the transposed convolution's input, scale `cur`
+    if ((rc = conv(X->dec[j].conv1, pd, 0, 1, 2 * f, f, false, &cat, &tmp))) return rc;
+    {
+      // the same step composed (conv_x3_dec.h) and split over two launches (upconv_x3_win.h, conv_x3_t448.h's addend
+      // epilogue), where the width has them: x = the transposed convolution's input, scale `cur`
       std::vector<float> sc, sh;
       fold_bn(P, pd + ".1.", f, sc, sh);
-      if ((rc = build_upcat_x3(h->err, X->comp[j], P[pu + ".weight"].data(), P[pu + ".bias"].data(), P[pd + ".0.weight"].data(),
-                               f, sc.data(), sh.data(), 1, useAct ? &skip[l] : nullptr, useAct ? &cur : nullptr,
-                               useAct ? &tmp : nullptr)))
+      if ((rc = build_dec_step_x3(h->err, X->dec[j], x3_dec_step_forms(f, false), P[pu + ".weight"].data(), P[pu + ".bias"].data(),
+                                  P[pd + ".0.weight"].data(), f, sc.data(), sh.data(), 1, useAct ? &skip[l] : nullptr,
+                                  useAct ? &cur : nullptr, useAct ? &tmp : nullptr)))
         return rc;
     }
-    if (f % 256 == 0) {
-      // the same step split over two launches (upconv_x3_win.h, conv_x3_t448.h's addend epilogue): the 56 x 56 and 28 x 28
-      // levels, whose 8-row tiles the composed kernel's parity fragments do not tile
-      std::vector<float> sc, sh;
-      fold_bn(P, pd + ".1.", f, sc, sh);
-      if ((rc = build_updeep_x3(h->err, X->deep[j], P[pu + ".weight"].data(), P[pu + ".bias"].data(), P[pd + ".0.weight"].data(),
-                                f, sc.data(), sh.data(), 1, useAct ? &skip[l] : nullptr, useAct ? &cur : nullptr,
-                                useAct ? &tmp : nullptr)))
-        return rc;
-    }
-    if ((rc = conv(X->dec[2 * j + 1], pd, 3, 4, f, f, false, &tmp, &cur))) return rc;
+    if ((rc = conv(X->dec[j].conv2, pd, 3, 4, f, f, false, &tmp, &cur))) return rc;
   }
   {   // the 1x1 head reads the last activation: its scale goes into the head's weights
     const int f0 = c.features[0];
@@ -1788,8 +1750,8 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
     if (conv2OnQ8) {
       const int jd = c.depth - 1 - l;
       const GemmOpX3& nextConv1 = l + 1 < c.depth ? X->enc[2 * (l + 1)] : X->bott[0];
-      catQ[l] = lands_on_q8(X->dec[2 * jd], io_of(p.cat[l], ch, cw, p.tmpA, f, 0), nullptr) &&
-                x3_plan_upconv(x3_upconv_query(X->up[jd], io_of(p.tmpB, ch / 2, cw / 2, p.cat[l], 2 * f, f), true)).valid;
+      catQ[l] = lands_on_q8(X->dec[jd].conv1, io_of(p.cat[l], ch, cw, p.tmpA, f, 0), nullptr) &&
+                x3_plan_upconv(x3_upconv_query(X->dec[jd].up, io_of(p.tmpB, ch / 2, cw / 2, p.cat[l], 2 * f, f), true)).valid;
       poolQ[l] = lands_on_q8(nextConv1, io_of(p.pool[l], ch / 2, cw / 2, p.tmpA, 2 * f, 0), nullptr);
       lk2.poolSrcQ = catQ[l];
       lk2.poolDstQ = poolQ[l];
@@ -1819,23 +1781,15 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
     const int f = c.features[l];
     // ConvTranspose writes the upper channel half of the concat buffer: torch.cat([skip, x]) elided
     const bool headNext = j == c.depth - 1 && f == 64;
-    // the composed operator (conv_x3_dec.h) in place of upconv + dec[2 j] in the f16x3 tier without the fp8 cross
-    // terms, where its shape rules allow (unet_set_x3_compose); it reads the skip half of the concat buffer and x
-    // itself and writes tmpA like dec[2 j]
-    bool composed = false;
-    if (!qs && x3_compose_mode() != 0) {
-      hipError_t ec;
-      composed = run_upcat_x3(X->comp[j], X->zeros, U(p.cat[l]), p.cat[l].elems, 2 * f, U(*cur), cur->elems, n, 2 * ch, 2 * cw,
-                              U(p.tmpA), p.tmpA.elems, f, x3_compose_mode() == 1, 128, s, &ec);
-      HIPCHK(h->err, ec);
-    }
-    // the deep levels' split form: kernel 1 writes P where the transposed convolution would write, kernel 2 reads the
-    // skip half and P and writes tmpA like dec[2 j]
-    if (!composed && x3_compose_mode() != 0) {
-      hipError_t ec;
-      composed = run_updeep_x3(X->deep[j], X->zeros, U(p.cat[l]), p.cat[l].elems, 2 * f, f, U(*cur), cur->elems, n, ch, cw,
-                               U(p.tmpA), p.tmpA.elems, f, x3_compose_mode(), qs != nullptr, false, s, &ec);
-      HIPCHK(h->err, ec);
+    // the step's form (x3_plan_dec_step): composed (conv_x3_dec.h) or deep (upconv_x3_win.h + the addend epilogue), it
+    // reads the skip half of the concat buffer and x itself and writes tmpA like conv1; else the two kernels below
+    const DecStepX3& st = X->dec[j];
+    const X3DecStepPlan dp = x3_plan_dec_step(x3_dec_step_query(n, ch, cw, f, qs != nullptr, false));
+    const bool composed = dp.form != kX3DecTwoKernel;
+    if (composed) {
+      const X3DecIo dio{x3_from(X->zeros, U(*cur), cur->elems, n, ch, cw).to(U(p.tmpA), p.tmpA.elems, f), U(p.cat[l]),
+                        p.cat[l].elems, 2 * f, f};
+      HIPCHK(h->err, run_dec_step_x3(st, dp, dio, s));
     }
     ch *= 2;
     cw *= 2;
@@ -1844,11 +1798,11 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
     if (!composed) {
       X3Q8Link lku;
       lku.wantOutQ = catQ[l];
-      HIPCHK(h->err, run_upconv_x3(X->up[j], io_of(*cur, ch / 2, cw / 2, p.cat[l], 2 * f, f), s, &lku));
+      HIPCHK(h->err, run_upconv_x3(st.up, io_of(*cur, ch / 2, cw / 2, p.cat[l], 2 * f, f), s, &lku));
       lk1.inIsQ = catQ[l];
       // (the fused-head launch below is handed no q-plane scratch: it never takes a q plane)
-      lk1.wantOutQ = !headNext && lands_on_q8(X->dec[2 * j + 1], conv2Io, nullptr);
-      HIPCHK(h->err, run_conv_x3(X->dec[2 * j], io_of(p.cat[l], ch, cw, p.tmpA, f, 0), opts_of(&lk1, nullptr), s));
+      lk1.wantOutQ = !headNext && lands_on_q8(st.conv2, conv2Io, nullptr);
+      HIPCHK(h->err, run_conv_x3(st.conv1, io_of(p.cat[l], ch, cw, p.tmpA, f, 0), opts_of(&lk1, nullptr), s));
     }
     lk2 = X3Q8Link();
     lk2.inIsQ = lk1.wroteQ;
@@ -1863,10 +1817,10 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
       fz.mask = mask;
       X3ConvOpts oh;
       oh.fuse = &fz;
-      HIPCHK(h->err, run_conv_x3(X->dec[2 * j + 1], conv2Io, oh, s));
+      HIPCHK(h->err, run_conv_x3(st.conv2, conv2Io, oh, s));
       headFused = true;
     } else {
-      HIPCHK(h->err, run_conv_x3(X->dec[2 * j + 1], conv2Io, opts_of(&lk2, nullptr), s));
+      HIPCHK(h->err, run_conv_x3(st.conv2, conv2Io, opts_of(&lk2, nullptr), s));
     }
     cur = &p.tmpB;
   }
@@ -1887,6 +1841,35 @@ ActScale act_from_host(const float* act, int c) {
   a.act.assign(act, act + c);
   a.mag.assign(c, 0.f);
   return a;
+}
+
+// An operator entry point's decoder step: the plan for the one operator it built (`have`), forced; a plan that declines
+// is an invalid call
+hipError_t run_dec_step_entry(const DecStepX3& st, int have, bool windowOnly, const X3DecIo& io, int f, hipStream_t s) {
+  X3DecStepQuery q = x3_dec_step_query(io.xo.n, io.xo.h, io.xo.w, f, false, true, have);
+  q.windowOnly = windowOnly;
+  const X3DecStepPlan p = x3_plan_dec_step(q);
+  return p.form == kX3DecTwoKernel ? hipErrorInvalidValue : run_dec_step_x3(st, p, io, s);
+}
+
+// the deep operator's two entry points: build it, run it (or its kernel 1 alone) on caller-owned planes under a range watch
+int updeep_entry(int device, const float* wt, const float* bt, const float* w3, int f, const float* scale, const float* shift,
+                 int relu, const float* xAct, const float* skipAct, bool windowOnly, X3DecIo io, int* rangeOut, void* stream) {
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  OpScratch sc(s);
+  OpGuard<DecStepX3> g;
+  const ActScale xa = act_from_host(xAct, xAct ? 2 * f : 0), sa = act_from_host(skipAct, skipAct ? f : 0);
+  const int rc = build_dec_step_x3(g_opErr, g.op, kX3DecDeep, wt, bt, w3, f, scale, shift, relu, skipAct ? &sa : nullptr,
+                                   xAct ? &xa : nullptr, nullptr);
+  if (rc) return rc;
+  uint16_t* zeros = nullptr;
+  OpRangeScope range;
+  hipError_t e = sc.zero_page(&zeros);
+  io.xo.zeros = zeros;
+  if (e == hipSuccess) e = range.arm();
+  if (e == hipSuccess) e = run_dec_step_entry(g.op, kX3DecDeep, windowOnly, io, f, s);
+  return op_done(e, s, 0, &range, rangeOut);
 }
 
 void path_to_ints(const X3Path& p, int* out) {
@@ -2005,8 +1988,8 @@ int unet_op_upcat_conv3x3_x3(int device, const float* skip, const float* x, int 
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   OpScratch sc(s);
-  OpGuard<DecOpX3> g;
-  const int rc = build_upcat_x3(g_opErr, g.op, wt, bt, w3, f, scale, shift, relu, nullptr, nullptr, nullptr);
+  OpGuard<DecStepX3> g;
+  const int rc = build_dec_step_x3(g_opErr, g.op, kX3DecComposed, wt, bt, w3, f, scale, shift, relu, nullptr, nullptr, nullptr);
   if (rc) return rc;
   const size_t px = (size_t)n * hh * ww;
   const size_t es = px * f, ex = px / 4 * 2 * f, eo = px * f;
@@ -2018,8 +2001,7 @@ int unet_op_upcat_conv3x3_x3(int device, const float* skip, const float* x, int 
   if (e == hipSuccess) {
     split_to_planes(skip, es, ps, s);
     split_to_planes(x, ex, pxl, s);
-    if (!run_upcat_x3(g.op, zeros, ps, es, f, pxl, ex, n, hh, ww, po, eo, f, true, 256, s, &e) && e == hipSuccess)
-      e = hipErrorInvalidValue;
+    e = run_dec_step_entry(g.op, kX3DecComposed, false, {x3_from(zeros, pxl, ex, n, hh / 2, ww / 2).to(po, eo, f), ps, es, f, 0}, f, s);
   }
   if (e == hipSuccess) {
     merge_from_planes(po, eo, y, s);
@@ -2038,35 +2020,83 @@ int unet_host_compose_upcat(const float* wt, const float* bt, const float* w3, i
   return UNET_OK;
 }
 
-// Test hook (host arithmetic only, no device): what build_updeep_x3 packs for kernel 1 (pack_updeep_x3).  ordered: the
-// float64 window weights at the pack's hi-plane positions (the lo-plane positions stay 0); packed: the fp16 hi / lo
-// planes of weight / xAct x pre; pre [f]; cls [9][f] in float64 (kernel 1 gets them rounded to fp32)
+// Test hook (host arithmetic only, no device): the packed fp16 hi / lo halfs of host weights x pre[cout], as the
+// operators upload them.  kind 0: 3x3, w (cout,cin,3,3); 1: transposed, w (cin,cout,2,2); 2: first convolution, w
+// (cout,3,3,3), cin = 3; 3: the composed decoder step, w = the skip half (f,f,3,3), wx = the window weights
+// [parity 4][f][2f][tap 4], cout = f, cin = 2f.  nPacked: the pack's size in halfs, checked
+int unet_host_pack_x3(int kind, const float* w, const float* wx, int cout, int cin, const float* pre, uint16_t* packed,
+                      size_t nPacked) {
+  if (!w || !pre || !packed || kind < 0 || kind > 3 || cout < 64 || cout % 64 || (kind == 2 ? cin != 3 : cin < 32 || cin % 32) ||
+      (kind == 3 && (!wx || cin != 2 * cout)))
+    return op_bad_args();
+  const std::vector<float> pv(pre, pre + cout);
+  const std::vector<uint16_t> out = kind == 0   ? pack_conv_x3(w, cout, cin, pv)
+                                    : kind == 1 ? pack_upconv_x3(w, cin, cout, pv)
+                                    : kind == 2 ? pack_first_x3(w, cout, pv)
+                                                : pack_upcat_x3(w, wx, cout, pv);
+  if (out.size() != nPacked) return op_bad_args();
+  std::copy(out.begin(), out.end(), packed);
+  return UNET_OK;
+}
+
+// Test hook (host arithmetic only, no device): what build_dec_step_x3 packs for kernel 1 of the deep form
+// (pack_updeep_x3).  ordered: the float64 window weights at the pack's hi-plane positions (the lo-plane positions stay
+// 0); packed: the fp16 hi / lo planes of weight / xAct x pre; pre [f]; cls [9][f] in float64 (kernel 1 gets them rounded
+// to fp32)
 int unet_host_pack_updeep_x3(const float* wt, const float* bt, const float* w3, int f, const float* xAct, double* ordered,
                              uint16_t* packed, float* pre, double* cls) {
   if (!wt || !bt || !w3 || !ordered || !packed || !pre || !cls || f < 64 || f % 64) return op_bad_args();
-  DeepHostX3 hst;
+  DecHostX3 hst;
+  std::vector<float> preW;
   std::vector<double> ord;
-  pack_updeep_x3(wt, bt, w3, f, xAct, hst, &ord);
+  dec_host_x3(hst, wt, bt, w3, f, nullptr, xAct);
+  const std::vector<uint16_t> win = pack_updeep_x3(hst, preW, &ord);
   std::copy(ord.begin(), ord.end(), ordered);
-  std::copy(hst.packed.begin(), hst.packed.end(), packed);
-  std::copy(hst.pre.begin(), hst.pre.end(), pre);
-  std::copy(hst.cls64.begin(), hst.cls64.end(), cls);
+  std::copy(win.begin(), win.end(), packed);
+  std::copy(preW.begin(), preW.end(), pre);
+  std::copy(hst.bias.begin(), hst.bias.end(), cls);
   return UNET_OK;
 }
+
+namespace {
+void updeep_to_ints(const X3UpdeepPlan& p, int* out) {   // all 0 where the plan declines
+  const int v[8] = {1, p.wmax, p.pixTiles, p.coTiles, p.grid, p.conv.grid, p.conv.path.flat, p.conv.pixTiles};
+  std::fill(out, out + 8, 0);
+  if (p.take) std::copy(v, v + 8, out);
+}
+inline int mode3(int v) { return v < 0 ? -1 : (v > 1 ? 1 : v); }
+}  // namespace
 
 // Test hook (no device): x3_plan_updeep for query = {n, h, w, f, compose mode, deep switch, f16q8 on} (h, w: the
 // low-resolution map) -> planOut = {taken, kernel 1: widest map of its instance, pixel tiles, channel tiles, grid;
 // kernel 2: grid, flat tiling, pixel tiles}, all 0 where the plan declines
 int unet_host_plan_updeep_x3(const int* query, int nQuery, int* planOut, int nPlan) {
   if (!query || nQuery != 7 || !planOut || nPlan != 8) return op_bad_args();
-  X3UpdeepQuery q;
+  X3DecStepQuery q;
   q.n = query[0], q.h = query[1], q.w = query[2], q.f = query[3];
-  q.compose = query[4] < 0 ? -1 : (query[4] > 1 ? 1 : query[4]);
+  q.compose = mode3(query[4]);
   q.deep = query[5] != 0, q.q8 = query[6] != 0;
-  const X3UpdeepPlan p = x3_plan_updeep(q);
-  const int v[8] = {1, p.wmax, p.pixTiles, p.coTiles, p.grid, p.conv.grid, p.conv.path.flat, p.conv.pixTiles};
-  std::fill(planOut, planOut + 8, 0);
-  if (p.take) std::copy(v, v + 8, planOut);
+  updeep_to_ints(x3_plan_updeep(q), planOut);
+  return UNET_OK;
+}
+
+// Test hook (no device): x3_plan_dec_step and the labels of the step's launches (include/unet_hip.h lists the layouts)
+int unet_host_plan_dec_step_x3(const int* query, int nQuery, int* planOut, int nPlan, char* labelOut, int labelCap) {
+  if (!query || nQuery != 17 || !planOut || nPlan != 16 || (labelOut && labelCap < 128)) return op_bad_args();
+  if (query[0] < 1 || query[1] < 1 || query[2] < 1 || query[3] < 64 || query[3] % 64) return op_bad_args();
+  X3DecStepQuery q;
+  q.n = query[0], q.h = query[1], q.w = query[2], q.f = query[3];
+  q.compose = mode3(query[4]), q.deep = query[5] != 0, q.decForm = (query[6] == 1 || query[6] == 2) ? query[6] : -1;
+  q.q8 = query[7] != 0, q.entry = query[8] != 0, q.have = query[9], q.windowOnly = query[10] != 0;
+  q.upconvMode = mode3(query[11]);
+  q.sw.flat = query[12] != 0, q.sw.r512 = query[13] != 0, q.sw.t448 = query[14] != 0, q.sw.t448c4 = query[15] != 0;
+  q.sw.crossFp8 = query[16];
+  const X3DecStepPlan p = x3_plan_dec_step(q);
+  const int head[8] = {p.form, p.wco, p.tilesX, p.tilesY, p.pixTiles, p.coTiles, p.grid, p.nLaunch};
+  std::fill(planOut, planOut + 16, 0);
+  if (p.form == kX3DecComposed) std::copy(head, head + 8, planOut);
+  if (p.form == kX3DecDeep) planOut[0] = p.form, planOut[7] = p.nLaunch, updeep_to_ints(p.deep, planOut + 8);
+  if (labelOut) x3_dec_step_labels(q, p, labelOut, (size_t)labelCap);
   return UNET_OK;
 }
 
@@ -2086,23 +2116,9 @@ int unet_op_updeep_window_x3_planes(int device, const uint16_t* x, size_t xLo, i
   if (!x || !wt || !bt || !w3 || !y || n < 1 || hh < 1 || ww < 4 || ww > 28 || f < 64 || f % 64 || f > 1024 || xLo % 8 ||
       yLo % 8 || ldo % 64 || coOff < 0 || coOff % 64 || coOff + f > ldo)
     return op_bad_args();
-  HIPCHK(g_opErr, hipSetDevice(device));
-  hipStream_t s = (hipStream_t)stream;
-  OpScratch sc(s);
-  OpGuard<DeepOpX3> g;
-  ActScale ia;
-  if (inAct) ia = act_from_host(inAct, 2 * f);
-  std::vector<float> one(f, 1.f), zero(f, 0.f);
-  const int rc = build_updeep_x3(g_opErr, g.op, wt, bt, w3, f, one.data(), zero.data(), 0, nullptr, inAct ? &ia : nullptr, nullptr);
-  if (rc) return rc;
-  uint16_t* zeros = nullptr;
-  OpRangeScope range;
-  hipError_t e = sc.zero_page(&zeros);
-  if (e == hipSuccess) e = range.arm();
-  if (e == hipSuccess &&
-      !run_updeep_x3(g.op, zeros, y, yLo, ldo, coOff, x, xLo, n, hh, ww, nullptr, 0, 0, 1, false, true, s, &e) && e == hipSuccess)
-    e = hipErrorInvalidValue;
-  return op_done(e, s, 0, &range, rangeOut);
+  const std::vector<float> one(f, 1.f), zero(f, 0.f);
+  return updeep_entry(device, wt, bt, w3, f, one.data(), zero.data(), 0, inAct, nullptr, true,
+                      {x3_from(nullptr, x, xLo, n, hh, ww), y, yLo, ldo, coOff}, rangeOut, stream);
 }
 
 // Test entry point: both kernels as the forward runs them.  cat: the concat buffer's planes (n,2hh,2ww,2f) with the skip
@@ -2115,25 +2131,8 @@ int unet_op_updeep_conv3x3_x3_planes(int device, const uint16_t* x, size_t xLo, 
   if (!x || !wt || !bt || !w3 || !scale || !shift || !cat || !out || n < 1 || hh < 1 || ww < 4 || ww > 28 || f < 256 ||
       f % 256 || f > 1024 || xLo % 8 || catLo % 8 || outLo % 8)
     return op_bad_args();
-  HIPCHK(g_opErr, hipSetDevice(device));
-  hipStream_t s = (hipStream_t)stream;
-  OpScratch sc(s);
-  OpGuard<DeepOpX3> g;
-  ActScale xa, sa;
-  if (xAct) xa = act_from_host(xAct, 2 * f);
-  if (skipAct) sa = act_from_host(skipAct, f);
-  const int rc = build_updeep_x3(g_opErr, g.op, wt, bt, w3, f, scale, shift, relu, skipAct ? &sa : nullptr, xAct ? &xa : nullptr,
-                                 nullptr);
-  if (rc) return rc;
-  uint16_t* zeros = nullptr;
-  OpRangeScope range;
-  hipError_t e = sc.zero_page(&zeros);
-  if (e == hipSuccess) e = range.arm();
-  if (e == hipSuccess &&
-      !run_updeep_x3(g.op, zeros, cat, catLo, 2 * f, f, x, xLo, n, hh, ww, out, outLo, f, 1, false, false, s, &e) &&
-      e == hipSuccess)
-    e = hipErrorInvalidValue;
-  return op_done(e, s, 0, &range, rangeOut);
+  return updeep_entry(device, wt, bt, w3, f, scale, shift, relu, xAct, skipAct, false,
+                      {x3_from(nullptr, x, xLo, n, hh, ww).to(out, outLo, f), cat, catLo, 2 * f, f}, rangeOut, stream);
 }
 
 // Test hooks (host arithmetic only, no device): the plan the dispatch makes for a query given as integers, the switches
