@@ -685,6 +685,17 @@ int unet_i8_forward_u8(unet_i8_handle_t h, const uint8_t* frames_dev, int n, int
 /* Parity aid: copy one int8 activation tensor of the last forward to the host, dense NHWC with its real channels.
  * name: "im2col", "enc<l>.a", "cat<l>", "cat<l>.pool", "bott.a", "bott.b", "dec<j>.a", "dec<j>.b". */
 int unet_i8_read_tensor(unet_i8_handle_t h, const char* name, int8_t* dst_host, size_t cap_bytes, int* channels);
+/* Hybrid quantisation (README.md:3466-3474 "mixed precision"; unet_lane_detection_amd/quant.py states the arithmetic):
+ * a unit whose arrays include `<unit>.hybrid` (int32 1) with `.w_h` (fp16 bits, shape of `.w_q`), `.gain`, `.bias_f`,
+ * `.x_scale` (float32) and `.y_scale` runs on v_mfma_f32_16x16x32_f16 with fp32 accumulation; a tensor whose writers and
+ * readers are all hybrid is stored as fp16, every other tensor stays int8 with its calibrated parameters.
+ * unet_i8_set_hybrid(h, 0) before unet_i8_finalize runs the same arrays as pure int8 (1, the default, honours the marks).
+ * unet_i8_tensor_dtype: 0 int8, 1 fp16, -1 unknown name or not finalized (names as unet_i8_read_tensor, plus "input").
+ * unet_i8_read_tensor_f16 is unet_i8_read_tensor for fp16 tensors (fp16 bits out); each of the two returns
+ * UNET_ERR_INVALID_ARG for a tensor of the other type. */
+int unet_i8_set_hybrid(unet_i8_handle_t h, int on);
+int unet_i8_tensor_dtype(unet_i8_handle_t h, const char* name);
+int unet_i8_read_tensor_f16(unet_i8_handle_t h, const char* name, uint16_t* dst_host, size_t cap_bytes, int* channels);
 int unet_i8_destroy(unet_i8_handle_t h);
 const char* unet_i8_last_error(unet_i8_handle_t h);
 

@@ -110,6 +110,9 @@ SIGNATURES = {
     "unet_i8_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_float, C.c_void_p]),
     "unet_i8_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
+    "unet_i8_set_hybrid": (C.c_int, [C.c_void_p, C.c_int]),
+    "unet_i8_tensor_dtype": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "unet_i8_read_tensor_f16": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     "unet_i8_destroy": (C.c_int, [C.c_void_p]),
     "unet_i8_last_error": (C.c_char_p, [C.c_void_p]),
     "unet_num_range_tensors": (C.c_int, [C.c_void_p]),

@@ -27,9 +27,10 @@ CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(CSRC, "libunet_hip.so")
 HASHFILE = LIB + ".srchash"
-# the others: kernels of the validation pass, of the general loss, of the augmentation stage and of the histogram
-# calibration, code objects of their own
-SOURCES = ["unet_hip.cpp", "validate_kernels.cpp", "loss_kernels.cpp", "augment_kernels.cpp", "calib_kernels.cpp"]
+# the others: kernels of the validation pass, of the general loss, of the augmentation stage, of the histogram
+# calibration and of the int8 tier's hybrid (fp16) units, code objects of their own
+SOURCES = ["unet_hip.cpp", "validate_kernels.cpp", "loss_kernels.cpp", "augment_kernels.cpp", "calib_kernels.cpp",
+           "conv_h16.cpp"]
 FLAGS = ["-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result",
          "-Wno-unused-value"]
 

@@ -49,6 +49,7 @@
 #include "wgrad_x3_ws.h"
 #include "camera_stage.h"
 #include "calib_kernels.h"
+#include "conv_h16.h"
 
 namespace {
 

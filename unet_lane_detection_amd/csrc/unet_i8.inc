@@ -14,18 +14,26 @@ struct I8Unit {
   int8_t* wt = nullptr;
   int32_t *c0 = nullptr, *wzp = nullptr;
   float* mult = nullptr;
+  // hybrid unit (quant.py, "hybrid quantisation"; conv_h16.h): fp16 weights in fragment order, m and b per column
+  bool hyb = false, in16 = false, out16 = false, narrow = false;
+  int cinStage = 0, chunks = 0;
+  float yscale = 1.f;
+  uint16_t* wh = nullptr;
+  float *hm = nullptr, *hb = nullptr;
   void free_dev() {
-    for (void* p : {(void*)wt, (void*)c0, (void*)wzp, (void*)mult})
+    for (void* p : {(void*)wt, (void*)c0, (void*)wzp, (void*)mult, (void*)wh, (void*)hm, (void*)hb})
       if (p) hipFree(p);
     wt = nullptr;
     c0 = wzp = nullptr;
-    mult = nullptr;
+    mult = hm = hb = nullptr;
+    wh = nullptr;
   }
 };
 
 struct I8Tensor {
-  int c = 0, ld = 0;      // real channels, pixel stride (multiple of 64)
+  int c = 0, ld = 0;      // real channels, pixel stride in elements (multiple of 64, or 32)
   int level = 0;          // spatial size = input >> level
+  int f16 = 0;            // elements are fp16 (every unit that writes or reads the tensor is hybrid), two bytes each
   size_t off = 0;         // byte offset in the workspace
 };
 
@@ -43,6 +51,12 @@ struct unet_i8_ctx {
   int8_t* headW = nullptr;
   int headWzp = 0, headXzp = 0, headBias = 0;
   float headMult = 0.f;
+  // hybrid quantisation: honoured unless unet_i8_set_hybrid(h, 0); which tensors are fp16 (by name, cat<l>.pool as cat<l>)
+  bool hybridOn = true;
+  std::map<std::string, int> f16Tensor;
+  bool headHyb = false;
+  uint16_t* headWh = nullptr;
+  float headM = 0.f, headB = 0.f;
   std::map<std::string, I8Tensor> tensors;   // by name, incl. "im2col"
   GrowBuf ws;
   int wsN = 0, wsH = 0, wsW = 0;
@@ -53,8 +67,10 @@ struct unet_i8_ctx {
     first.free_dev();
     if (lut) hipFree(lut);
     if (headW) hipFree(headW);
+    if (headWh) hipFree(headWh);
     ws.release();
     lut = headW = nullptr;
+    headWh = nullptr;
   }
 };
 
@@ -207,6 +223,207 @@ int i8_build_upconv(unet_i8_ctx* h, I8Unit& u, const std::string& key, int cinRe
                        wzc, bc, mc);
 }
 
+// ---- hybrid units (quant.py, "hybrid quantisation"; kernels: conv_h16.h) ----
+bool i8_unit_hybrid(const unet_i8_ctx* h, const std::string& key) {
+  if (!h->hybridOn) return false;
+  auto it = h->arrays.find(key + ".hybrid");
+  if (it == h->arrays.end() || it->second.size() != sizeof(int32_t)) return false;
+  int32_t v = 0;
+  std::memcpy(&v, it->second.data(), sizeof(v));
+  return v != 0;
+}
+
+// A tensor is fp16 iff every unit that writes it and every unit that reads it is hybrid (quant.tensor_dtypes states the
+// same rule); cat<l>.pool goes with cat<l>; the input is always int8.
+void i8_derive_dtypes(unet_i8_ctx* h) {
+  const int d = h->depth;
+  std::map<std::string, bool> all;
+  auto use = [&](const std::string& key, const std::string& x, const std::string& y) {
+    const bool hy = i8_unit_hybrid(h, key);
+    for (const std::string* t : {&x, &y})
+      if (!t->empty()) {
+        auto it = all.find(*t);
+        if (it == all.end())
+          all[*t] = hy;
+        else
+          it->second = it->second && hy;
+      }
+  };
+  for (int l = 0; l < d; ++l) {
+    const std::string p = "encoder_blocks." + std::to_string(l), ea = "enc" + std::to_string(l) + ".a";
+    use(p + ".0", l == 0 ? std::string("input") : "cat" + std::to_string(l - 1), ea);
+    use(p + ".3", ea, "cat" + std::to_string(l));
+  }
+  use("bottleneck.0", "cat" + std::to_string(d - 1), "bott.a");
+  use("bottleneck.3", "bott.a", "bott.b");
+  for (int j = 0; j < d; ++j) {
+    const std::string cat = "cat" + std::to_string(d - 1 - j), dj = "dec" + std::to_string(j);
+    use("decoder_blocks." + std::to_string(2 * j), j == 0 ? std::string("bott.b") : "dec" + std::to_string(j - 1) + ".b", cat);
+    use("decoder_blocks." + std::to_string(2 * j + 1) + ".0", cat, dj + ".a");
+    use("decoder_blocks." + std::to_string(2 * j + 1) + ".3", dj + ".a", dj + ".b");
+  }
+  use("output", "dec" + std::to_string(d - 1) + ".b", "");
+  all["input"] = false;
+  h->f16Tensor.clear();
+  for (auto& kv : all) h->f16Tensor[kv.first] = kv.second ? 1 : 0;
+  for (int l = 0; l < d; ++l) h->f16Tensor["cat" + std::to_string(l) + ".pool"] = h->f16Tensor["cat" + std::to_string(l)];
+  h->f16Tensor["im2col"] = 0;
+}
+
+// Pack one hybrid unit.  W(t, k, col) gives the fp16 bits of the weight of tap t, GEMM row k (< kReal) and column col
+// (< colsReal); everything padded is +0.  Fragment order of conv_h16.h: [coTile][chunk][tap][kstep][cs][lane][8], with four
+// subtiles cs per 64-column tile, or - a plain unit of <= 32 columns (u.narrow) - two per 32-column tile.
+template <class F>
+int h16_build_unit(unet_i8_ctx* h, I8Unit& u, int taps, int kReal, int colsReal, int colsPad, F&& W,
+                   const std::vector<float>& mCol, const std::vector<float>& bCol) {
+  u.cinStage = round_up(kReal, 8);
+  u.chunks = (u.cinStage + 63) / 64;
+  u.narrow = !u.scatter && colsReal <= 32;
+  const int nCt = colsPad / 64, ncs = u.narrow ? 2 : 4;
+  std::vector<uint16_t> packed((size_t)nCt * u.chunks * taps * 2 * ncs * 64 * 8, 0);
+  for (int ct = 0; ct < nCt; ++ct)
+    for (int kc = 0; kc < u.chunks; ++kc)
+      for (int t = 0; t < taps; ++t)
+        for (int ks = 0; ks < 2; ++ks)
+          for (int cs = 0; cs < ncs; ++cs) {
+            uint16_t* dst = packed.data() + (((((size_t)ct * u.chunks + kc) * taps + t) * 2 + ks) * ncs + cs) * 64 * 8;
+            for (int lane = 0; lane < 64; ++lane) {
+              const int j = lane & 15, lq = lane >> 4;
+              const int col = 64 * ct + 4 * ncs * (j >> 2) + 4 * cs + (j & 3);
+              for (int e = 0; e < 8; ++e) {
+                const int k = kc * 64 + ks * 32 + lq * 8 + e;
+                if (col < colsReal && k < kReal) dst[lane * 8 + e] = W(t, k, col);
+              }
+            }
+          }
+  std::vector<float> m(colsPad, 0.f), b(colsPad, 0.f);
+  for (int col = 0; col < colsReal; ++col) {
+    m[col] = mCol[col];
+    b[col] = bCol[col];
+  }
+  u.taps = taps;
+  u.colsPad = colsPad;
+  u.hyb = true;
+  int rc = i8_upload(h->err, &u.wh, packed);
+  if (!rc) rc = i8_upload(h->err, &u.hm, m);
+  if (!rc) rc = i8_upload(h->err, &u.hb, b);
+  return rc;
+}
+
+// the arrays every hybrid unit carries: gain (x x_scale for an int8 input) and bias per output channel, zero points, scales
+int h16_get_common(unet_i8_ctx* h, I8Unit& u, const std::string& key, int cout, bool hasOut, std::vector<float>& m,
+                   std::vector<float>& b) {
+  std::vector<int32_t> s1;
+  std::vector<float> f1;
+  if (!i8_get(h, key + ".gain", m, cout) || !i8_get(h, key + ".bias_f", b, cout) || !i8_get(h, key + ".x_scale", f1, 1))
+    return UNET_ERR_STATE;
+  if (!u.in16)
+    for (auto& v : m) v *= f1[0];   // a power of two times a float: exact
+  if (!i8_get(h, key + ".x_zp", s1, 1)) return UNET_ERR_STATE;
+  u.xzp = s1[0];
+  u.yzp = 0;
+  u.yscale = 1.f;
+  if (hasOut) {
+    if (!i8_get(h, key + ".y_zp", s1, 1) || !i8_get(h, key + ".y_scale", f1, 1)) return UNET_ERR_STATE;
+    u.yzp = s1[0];
+    u.yscale = f1[0];
+  }
+  return UNET_OK;
+}
+
+int h16_build_conv(unet_i8_ctx* h, I8Unit& u, const std::string& key, int cinReal, int cout, bool firstLayer, bool in16,
+                   bool out16) {
+  u.free_dev();
+  u.key = key;
+  u.cinReal = cinReal;
+  u.coutReal = cout;
+  u.coutPad = round_up(cout, 64);
+  u.cols = cout;
+  u.scatter = 0;
+  u.pair = 0;
+  u.in16 = in16;
+  u.out16 = out16;
+  std::vector<uint16_t> wh;
+  std::vector<float> m, b;
+  std::vector<int32_t> s1;
+  if (!i8_get(h, key + ".w_h", wh, (size_t)cout * cinReal * 9)) return UNET_ERR_STATE;
+  if (const int rc = h16_get_common(h, u, key, cout, true, m, b)) return rc;
+  if (!i8_get(h, key + ".relu", s1, 1)) return UNET_ERR_STATE;
+  u.relu = s1[0];
+  if (firstLayer)   // one "tap" over the im2col rows: k = tap*3 + ci
+    return h16_build_unit(h, u, 1, 27, cout, u.coutPad,
+                          [&](int, int k, int col) { return wh[((size_t)col * 3 + (k % 3)) * 9 + k / 3]; }, m, b);
+  return h16_build_unit(h, u, 9, cinReal, cout, u.coutPad,
+                        [&](int t, int k, int col) { return wh[((size_t)col * cinReal + k) * 9 + t]; }, m, b);
+}
+
+// transposed conv: w_h (I,O,2,2); GEMM columns n = ab * coutPad + co
+int h16_build_upconv(unet_i8_ctx* h, I8Unit& u, const std::string& key, int cinReal, int cout, bool in16, bool out16) {
+  u.free_dev();
+  u.key = key;
+  u.cinReal = cinReal;
+  u.coutReal = cout;
+  u.coutPad = round_up(cout, 64);
+  u.cols = 4 * u.coutPad;
+  u.scatter = 1;
+  u.pair = 0;
+  u.relu = 0;
+  u.in16 = in16;
+  u.out16 = out16;
+  std::vector<uint16_t> wh;
+  std::vector<float> m, b;
+  if (!i8_get(h, key + ".w_h", wh, (size_t)cinReal * cout * 4)) return UNET_ERR_STATE;
+  if (const int rc = h16_get_common(h, u, key, cout, true, m, b)) return rc;
+  const int cp = u.coutPad, colsReal = 4 * cp;
+  std::vector<float> mc(colsReal, 0.f), bc(colsReal, 0.f);
+  for (int n = 0; n < colsReal; ++n)
+    if (n % cp < cout) {
+      mc[n] = m[n % cp];
+      bc[n] = b[n % cp];
+    }
+  return h16_build_unit(h, u, 1, cinReal, colsReal, colsReal,
+                        [&](int, int k, int n) -> uint16_t {
+                          const int ab = n / cp, co = n % cp;
+                          return co < cout ? wh[((size_t)k * cout + co) * 4 + ab] : (uint16_t)0;
+                        },
+                        mc, bc);
+}
+
+hipError_t h16_run(const I8Unit& u, const void* in, int ldi, int n, int hh, int ww, void* out, int ldo, int coOff, hipStream_t s) {
+  unet::ConvH16Args a = {};
+  a.in = in;
+  a.wt = u.wh;
+  a.mult = u.hm;
+  a.bias = u.hb;
+  a.out = out;
+  a.N = n;
+  a.H = hh;
+  a.W = ww;
+  a.ldi = ldi;
+  a.ldo = ldo;
+  a.co_off = coOff;
+  a.cinStage = u.cinStage;
+  a.chunks = u.chunks;
+  a.cols = u.cols;
+  a.coutReal = u.coutReal;
+  a.coutPad = u.coutPad;
+  a.xzp = u.xzp;
+  a.yzp = u.yzp;
+  a.lo = u.relu ? u.yzp : -128;
+  a.relu = u.relu;
+  a.scatter = u.scatter;
+  a.narrow = u.narrow;
+  a.yscale = u.yscale;
+  const double px = (double)n * hh * ww;
+  const double k = u.taps == 9 ? 9.0 * u.cinReal : (u.scatter ? 4.0 * u.cinReal : 27.0);
+  prof_begin(u.taps == 9 ? "conv3x3_h16" : (u.scatter ? "upconv2x2_h16" : "conv3x3_first_h16"), 2.0 * px * k * u.coutReal,
+             px * ((u.in16 ? 2.0 : 1.0) * (u.taps == 9 || u.scatter ? u.cinReal : 64) +
+                   (u.out16 ? 2.0 : 1.0) * (u.scatter ? 4.0 : 1.0) * u.coutReal), s);
+  const hipError_t e = unet::launch_conv_h16(a, u.taps, u.in16, u.out16, s);
+  prof_end(s);
+  return e;
+}
+
 int i8_plan(unet_i8_ctx* h, int n, int height, int width) {
   h->tensors.clear();
   size_t off = 0;
@@ -218,7 +435,9 @@ int i8_plan(unet_i8_ctx* h, int n, int height, int width) {
     t.ld = (c <= 32 && !feedsUpconv) ? 32 : round_up(c, 64);
     t.level = level;
     t.off = off;
-    off += (((size_t)n * (height >> level) * (width >> level) * t.ld) + 255) / 256 * 256;
+    auto dt = h->f16Tensor.find(name);
+    t.f16 = dt != h->f16Tensor.end() ? dt->second : 0;   // an fp16 tensor: the same stride in elements, two bytes each
+    off += (((size_t)n * (height >> level) * (width >> level) * t.ld * (t.f16 ? 2 : 1)) + 255) / 256 * 256;
     h->tensors[name] = t;
   };
   const int d = h->depth;
@@ -391,25 +610,57 @@ int unet_i8_finalize(unet_i8_handle_t h) {
   h->bott.assign(2, I8Unit());
   int rc;
   auto pad = [](int c) { return c <= 32 ? 32 : round_up(c, 64); };   // = the pixel stride i8_plan gives a c-channel tensor
+  // a hybrid unit (hybrid quantisation, quant.py) is packed for conv_h16.h instead; x, y: the tensors it reads and writes
+  i8_derive_dtypes(h);
+  h->wsN = h->wsH = h->wsW = 0;   // tensor types may have changed: the next forward plans again
+  auto conv = [&](I8Unit& u, const std::string& key, int cinReal, int cinPad, int cout, bool firstLayer, const std::string& x,
+                  const std::string& y) {
+    if (i8_unit_hybrid(h, key)) return h16_build_conv(h, u, key, cinReal, cout, firstLayer, h->f16Tensor[x], h->f16Tensor[y]);
+    u.hyb = false;
+    return i8_build_conv(h, u, key, cinReal, cinPad, cout, firstLayer);
+  };
   for (int l = 0; l < d; ++l) {
-    const std::string p = "encoder_blocks." + std::to_string(l);
+    const std::string p = "encoder_blocks." + std::to_string(l), ea = "enc" + std::to_string(l) + ".a";
     const int f = h->features[l];
     if (l == 0) {
-      if ((rc = i8_build_conv(h, h->enc[0], p + ".0", 3, 64, f, true))) return rc;
+      if ((rc = conv(h->enc[0], p + ".0", 3, 64, f, true, "input", ea))) return rc;
     } else {
-      if ((rc = i8_build_conv(h, h->enc[2 * l], p + ".0", h->features[l - 1], pad(h->features[l - 1]), f, false))) return rc;
+      if ((rc = conv(h->enc[2 * l], p + ".0", h->features[l - 1], pad(h->features[l - 1]), f, false,
+                     "cat" + std::to_string(l - 1), ea)))
+        return rc;
     }
-    if ((rc = i8_build_conv(h, h->enc[2 * l + 1], p + ".3", f, pad(f), f, false))) return rc;
+    if ((rc = conv(h->enc[2 * l + 1], p + ".3", f, pad(f), f, false, ea, "cat" + std::to_string(l)))) return rc;
   }
   const int fl = h->features[d - 1];
-  if ((rc = i8_build_conv(h, h->bott[0], "bottleneck.0", fl, pad(fl), 2 * fl, false))) return rc;
-  if ((rc = i8_build_conv(h, h->bott[1], "bottleneck.3", 2 * fl, pad(2 * fl), 2 * fl, false))) return rc;
+  if ((rc = conv(h->bott[0], "bottleneck.0", fl, pad(fl), 2 * fl, false, "cat" + std::to_string(d - 1), "bott.a"))) return rc;
+  if ((rc = conv(h->bott[1], "bottleneck.3", 2 * fl, pad(2 * fl), 2 * fl, false, "bott.a", "bott.b"))) return rc;
   for (int j = 0; j < d; ++j) {
     const int f = h->features[d - 1 - j];
-    if ((rc = i8_build_upconv(h, h->up[j], "decoder_blocks." + std::to_string(2 * j), 2 * f, round_up(2 * f, 64), f))) return rc;
+    const std::string cat = "cat" + std::to_string(d - 1 - j), dj = "dec" + std::to_string(j);
+    const std::string src = j == 0 ? std::string("bott.b") : "dec" + std::to_string(j - 1) + ".b";
+    const std::string uk = "decoder_blocks." + std::to_string(2 * j);
+    if (i8_unit_hybrid(h, uk))
+      rc = h16_build_upconv(h, h->up[j], uk, 2 * f, f, h->f16Tensor[src], h->f16Tensor[cat]);
+    else
+      rc = i8_build_upconv(h, h->up[j], uk, 2 * f, round_up(2 * f, 64), f);
+    if (rc) return rc;
     const std::string p = "decoder_blocks." + std::to_string(2 * j + 1);
-    if ((rc = i8_build_conv(h, h->dec[2 * j], p + ".0", 2 * f, pad(2 * f), f, false))) return rc;
-    if ((rc = i8_build_conv(h, h->dec[2 * j + 1], p + ".3", f, pad(f), f, false))) return rc;
+    if ((rc = conv(h->dec[2 * j], p + ".0", 2 * f, pad(2 * f), f, false, cat, dj + ".a"))) return rc;
+    if ((rc = conv(h->dec[2 * j + 1], p + ".3", f, pad(f), f, false, dj + ".a", dj + ".b"))) return rc;
+  }
+  h->headHyb = i8_unit_hybrid(h, "output");
+  if (h->headHyb) {
+    I8Unit hu;
+    hu.in16 = h->f16Tensor["dec" + std::to_string(d - 1) + ".b"];
+    std::vector<uint16_t> wh;
+    std::vector<float> m, b;
+    if (!i8_get(h, "output.w_h", wh, h->features[0])) return UNET_ERR_STATE;
+    if ((rc = h16_get_common(h, hu, "output", 1, false, m, b))) return rc;
+    h->headM = m[0];
+    h->headB = b[0];
+    if (h->headWh) hipFree(h->headWh);
+    h->headWh = nullptr;
+    if ((rc = i8_upload(h->err, &h->headWh, wh))) return rc;
   }
   std::vector<int8_t> lut, hw;
   std::vector<int32_t> s1;
@@ -462,40 +713,54 @@ int unet_i8_forward_u8(unet_i8_handle_t h, const uint8_t* frames, int n, int hei
   HIPCHK(h->err, hipGetLastError());
   int ch = height, cw = width;
   const I8Tensor* cur = nullptr;
+  // one unit: the int8 kernels, or the fp16 kernels of a hybrid unit between tensors of either type (co_off in elements)
+  auto run = [&](const I8Unit& u, const I8Tensor& x, int hh, int ww, const I8Tensor& y, int coOff) {
+    return u.hyb ? h16_run(u, P(x), x.ld, n, hh, ww, P(y), y.ld, coOff, s) : i8_run(u, P(x), n, hh, ww, P(y), y.ld, coOff, s);
+  };
   for (int l = 0; l < d; ++l) {
     const I8Tensor &ea = T("enc" + std::to_string(l) + ".a"), &cat = T("cat" + std::to_string(l)),
                    &pl = T("cat" + std::to_string(l) + ".pool");
     if (l == 0)
-      HIPCHK(h->err, i8_run(h->enc[0], P(T("im2col")), n, ch, cw, P(ea), ea.ld, 0, s));
+      HIPCHK(h->err, run(h->enc[0], T("im2col"), ch, cw, ea, 0));
     else
-      HIPCHK(h->err, i8_run(h->enc[2 * l], P(*cur), n, ch, cw, P(ea), ea.ld, 0, s));
-    HIPCHK(h->err, i8_run(h->enc[2 * l + 1], P(ea), n, ch, cw, P(cat), cat.ld, 0, s));   // skip half of the concat
-    const size_t tot = (size_t)n * (ch / 2) * (cw / 2) * (h->features[l] / 16);
-    hipLaunchKernelGGL(unet::maxpool2x2_i8_kernel, dim3(grid_for(tot)), dim3(256), 0, s, P(cat), n, ch, cw, h->features[l],
-                       cat.ld, P(pl), pl.ld);
-    HIPCHK(h->err, hipGetLastError());
+      HIPCHK(h->err, run(h->enc[2 * l], *cur, ch, cw, ea, 0));
+    HIPCHK(h->err, run(h->enc[2 * l + 1], ea, ch, cw, cat, 0));   // skip half of the concat
+    if (cat.f16) {
+      HIPCHK(h->err, unet::launch_maxpool2x2_h16(reinterpret_cast<const uint16_t*>(P(cat)), n, ch, cw, h->features[l], cat.ld,
+                                                 reinterpret_cast<uint16_t*>(P(pl)), pl.ld, s));
+    } else {
+      const size_t tot = (size_t)n * (ch / 2) * (cw / 2) * (h->features[l] / 16);
+      hipLaunchKernelGGL(unet::maxpool2x2_i8_kernel, dim3(grid_for(tot)), dim3(256), 0, s, P(cat), n, ch, cw, h->features[l],
+                         cat.ld, P(pl), pl.ld);
+      HIPCHK(h->err, hipGetLastError());
+    }
     cur = &pl;
     ch /= 2;
     cw /= 2;
   }
-  HIPCHK(h->err, i8_run(h->bott[0], P(*cur), n, ch, cw, P(T("bott.a")), T("bott.a").ld, 0, s));
-  HIPCHK(h->err, i8_run(h->bott[1], P(T("bott.a")), n, ch, cw, P(T("bott.b")), T("bott.b").ld, 0, s));
+  HIPCHK(h->err, run(h->bott[0], *cur, ch, cw, T("bott.a"), 0));
+  HIPCHK(h->err, run(h->bott[1], T("bott.a"), ch, cw, T("bott.b"), 0));
   cur = &T("bott.b");
   for (int j = 0; j < d; ++j) {
     const int l = d - 1 - j;
     const int f = h->features[l];
     const I8Tensor &cat = T("cat" + std::to_string(l)), &da = T("dec" + std::to_string(j) + ".a"),
                    &db = T("dec" + std::to_string(j) + ".b");
-    HIPCHK(h->err, i8_run(h->up[j], P(*cur), n, ch, cw, P(cat), cat.ld, f, s));   // upper half: cat([skip, x]) elided
+    HIPCHK(h->err, run(h->up[j], *cur, ch, cw, cat, f));   // upper half: cat([skip, x]) elided
     ch *= 2;
     cw *= 2;
-    HIPCHK(h->err, i8_run(h->dec[2 * j], P(cat), n, ch, cw, P(da), da.ld, 0, s));
-    HIPCHK(h->err, i8_run(h->dec[2 * j + 1], P(da), n, ch, cw, P(db), db.ld, 0, s));
+    HIPCHK(h->err, run(h->dec[2 * j], cat, ch, cw, da, 0));
+    HIPCHK(h->err, run(h->dec[2 * j + 1], da, ch, cw, db, 0));
     cur = &db;
   }
-  hipLaunchKernelGGL(unet::head_i8_kernel, dim3(grid_for(npix)), dim3(256), 0, s, P(*cur), cur->ld, h->features[0], npix,
-                     h->headW, h->headWzp, h->headXzp, h->headBias, h->headMult, logits, probs, mask, thr);
-  HIPCHK(h->err, hipGetLastError());
+  if (h->headHyb) {
+    HIPCHK(h->err, unet::launch_head_h16(P(*cur), cur->f16, cur->ld, h->features[0], npix, h->headWh, h->headXzp, h->headM,
+                                         h->headB, logits, probs, mask, thr, s));
+  } else {
+    hipLaunchKernelGGL(unet::head_i8_kernel, dim3(grid_for(npix)), dim3(256), 0, s, P(*cur), cur->ld, h->features[0], npix,
+                       h->headW, h->headWzp, h->headXzp, h->headBias, h->headMult, logits, probs, mask, thr);
+    HIPCHK(h->err, hipGetLastError());
+  }
   return UNET_OK;
 }
 
@@ -508,11 +773,51 @@ int unet_i8_read_tensor(unet_i8_handle_t h, const char* name, int8_t* dstHost, s
   HIPCHK(h->err, hipSetDevice(h->device));
   HIPCHK(h->err, hipDeviceSynchronize());
   const I8Tensor& t = it->second;
+  if (t.f16) {
+    h->err = std::string(name) + " is an fp16 tensor of a hybrid model: unet_i8_read_tensor_f16 reads it";
+    return UNET_ERR_INVALID_ARG;
+  }
   const size_t px = (size_t)h->wsN * (h->wsH >> t.level) * (h->wsW >> t.level);
   if (capBytes < px * t.c) return UNET_ERR_INVALID_ARG;
   if (channels) *channels = t.c;
   HIPCHK(h->err, hipMemcpy2D(dstHost, t.c, h->ws.p + t.off, t.ld, t.c, px, hipMemcpyDeviceToHost));
   return UNET_OK;
+}
+
+// The fp16 twin: dense NHWC fp16 bits of a tensor that unet_i8_tensor_dtype reports as fp16 (UNET_ERR_INVALID_ARG for an
+// int8 tensor).
+int unet_i8_read_tensor_f16(unet_i8_handle_t h, const char* name, uint16_t* dstHost, size_t capBytes, int* channels) {
+  if (!h || !name || !dstHost || !h->ws.p) return UNET_ERR_INVALID_ARG;
+  auto it = h->tensors.find(name);
+  if (it == h->tensors.end()) return UNET_ERR_UNKNOWN_PARAM;
+  HIPCHK(h->err, hipSetDevice(h->device));
+  HIPCHK(h->err, hipDeviceSynchronize());
+  const I8Tensor& t = it->second;
+  if (!t.f16) {
+    h->err = std::string(name) + " is an int8 tensor: unet_i8_read_tensor reads it";
+    return UNET_ERR_INVALID_ARG;
+  }
+  const size_t px = (size_t)h->wsN * (h->wsH >> t.level) * (h->wsW >> t.level);
+  if (capBytes < px * t.c * 2) return UNET_ERR_INVALID_ARG;
+  if (channels) *channels = t.c;
+  HIPCHK(h->err, hipMemcpy2D(dstHost, (size_t)t.c * 2, h->ws.p + t.off, (size_t)t.ld * 2, (size_t)t.c * 2, px, hipMemcpyDeviceToHost));
+  return UNET_OK;
+}
+
+// Hybrid quantisation: on (the default) = the units a model marks '<key>.hybrid' run in fp16; off = the same arrays run
+// as pure int8.  Takes effect at the next unet_i8_finalize.
+int unet_i8_set_hybrid(unet_i8_handle_t h, int on) {
+  if (!h) return UNET_ERR_INVALID_ARG;
+  h->hybridOn = on != 0;
+  h->finalized = false;
+  return UNET_OK;
+}
+
+// 0: int8, 1: fp16, -1: no such tensor or not finalized.  Names: "input", "im2col" and those of unet_i8_read_tensor.
+int unet_i8_tensor_dtype(unet_i8_handle_t h, const char* name) {
+  if (!h || !name || !h->finalized) return -1;
+  auto it = h->f16Tensor.find(name);
+  return it == h->f16Tensor.end() ? -1 : it->second;
 }
 
 int unet_i8_destroy(unet_i8_handle_t h) {

@@ -8,8 +8,10 @@
   qmodel = quant.quantize_model(state_dict, ranges)        # README.md:3106-3116 scheme, host arithmetic on weights
   net = UNetInt8(qmodel, device=0); net.run_u8(frames)
   compare_outputs(float_model, net, frames)                # float-vs-int8 MAE of probabilities (README.md:3512-3565)
+  units = choose_hybrid(float_model, state_dict, ranges, frames, k=3)      # not GOOD?  README.md:3466-3474, fourth remedy:
+  qmodel = quant.quantize_model(state_dict, ranges, hybrid=units)          # those units in fp16 (hybrid quantisation)
 
-All arithmetic on activations runs in libunet_hip.so (csrc/conv_i8.h); there is no CPU fallback.
+All arithmetic on activations runs in libunet_hip.so (csrc/conv_i8.h, csrc/conv_h16.h); there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -164,10 +166,48 @@ def compare_outputs(float_model, int8_net, frames_u8, batch=8):
     return OutputComparison(torch.cat(out).cpu().numpy())
 
 
-class UNetInt8:
-    """Quantised U-Net forward on one MI355X (i8 MFMA)."""
+def _mae_of(float_model, qmodel, frames_u8, batch):
+    net = UNetInt8(qmodel, device=float_model.device.index)
+    try:
+        return compare_outputs(float_model, net, frames_u8, batch=batch).mean
+    finally:
+        net.release()
 
-    def __init__(self, qmodel, device=0):
+
+def sensitivity(float_model, state_dict, ranges, frames_u8, batch=8):
+    """Which units are worth running in fp16 (hybrid quantisation, quant.py): the pure-int8 model and, per unit of
+    quant.unit_names, the model with only that unit hybrid, each compared with the fp32 tier by compare_outputs over
+    `frames_u8`.  Returns [(unit, mae_hybrid_this_unit, mae_int8)], the largest gain (mae_int8 - mae_hybrid) first.
+    Everything runs on the device; one number per frame is read back."""
+    frames = torch.as_tensor(frames_u8)
+    base = _mae_of(float_model, quant.quantize_model(state_dict, ranges), frames, batch)
+    rows = [(u, _mae_of(float_model, quant.quantize_model(state_dict, ranges, hybrid=(u,)), frames, batch), base)
+            for u in quant.unit_names(float_model.features)]
+    return sorted(rows, key=lambda r: r[1])          # stable: ties keep forward order
+
+
+def choose_hybrid(float_model, state_dict, ranges, frames_u8, k, batch=8):
+    """The `k` units to name in quantize_model(hybrid=...), chosen greedily: each pick is the unit that, added to the
+    ones already picked, gives the smallest compare_outputs error; every candidate is re-measured after each pick (a
+    tensor between two hybrid units becomes fp16, so gains do not add up)."""
+    frames = torch.as_tensor(frames_u8)
+    units = quant.unit_names(float_model.features)
+    if not 0 <= k <= len(units):
+        raise ValueError(f"k={k}: the model has {len(units)} units")
+    chosen = []
+    for _ in range(k):
+        rest = [u for u in units if u not in chosen]
+        maes = [_mae_of(float_model, quant.quantize_model(state_dict, ranges, hybrid=chosen + [u]), frames, batch)
+                for u in rest]
+        chosen.append(rest[int(np.argmin(maes))])
+    return chosen
+
+
+class UNetInt8:
+    """Quantised U-Net forward on one MI355X (i8 MFMA; the units a model marks hybrid on f16 MFMA, csrc/conv_h16.h).
+    hybrid=False runs a model with hybrid units as pure int8."""
+
+    def __init__(self, qmodel, device=0, hybrid=True):
         if not torch.cuda.is_available():
             raise RuntimeError("UNetInt8 needs a HIP device; there is no CPU fallback")
         self._lib = _lib.load()
@@ -187,11 +227,20 @@ class UNetInt8:
             if a.dtype == np.int64:
                 a = a.astype(np.int32)
             self._check(self._lib.unet_i8_load(h, k.encode(), a.ctypes.data_as(C.c_void_p), a.nbytes), f"unet_i8_load({k})")
+        self._check(self._lib.unet_i8_set_hybrid(h, 1 if hybrid else 0), "unet_i8_set_hybrid")
         self._check(self._lib.unet_i8_finalize(h), "unet_i8_finalize")
 
     @classmethod
-    def from_file(cls, path, device=0):
-        return cls(quant.load_quantized(path), device=device)
+    def from_file(cls, path, device=0, hybrid=True):
+        return cls(quant.load_quantized(path), device=device, hybrid=hybrid)
+
+    def tensor_dtype(self, name):
+        """'int8' or 'fp16': how activation tensor `name` is stored (quant.tensor_dtypes states the rule)."""
+        self._require_live()
+        rc = int(self._lib.unet_i8_tensor_dtype(self._h, name.encode()))
+        if rc not in (0, 1):
+            raise KeyError(name)
+        return "fp16" if rc else "int8"
 
     def _check(self, rc, where):
         if rc != 0:
@@ -227,9 +276,17 @@ class UNetInt8:
                                         self.run_u8)
 
     def read_tensor(self, name, n, h, w):
-        """int8 activation tensor `name` of the last forward as an (N,C,h,w) numpy array (parity tests); h, w are that
-        tensor's spatial size."""
+        """Activation tensor `name` of the last forward as an (N,C,h,w) numpy array (parity tests); h, w are that
+        tensor's spatial size.  int8 for an int8 tensor, float32 (the stored fp16 values) for an fp16 tensor of a
+        hybrid model."""
         self._require_live()
+        if name != "im2col" and self.tensor_dtype(name) == "fp16":
+            cap = n * h * w * 512 * 2
+            buf = np.empty(cap // 2, dtype=np.float16)
+            c = C.c_int()
+            self._check(self._lib.unet_i8_read_tensor_f16(self._h, name.encode(), buf.ctypes.data_as(C.c_void_p), cap,
+                                                          C.byref(c)), f"unet_i8_read_tensor_f16({name})")
+            return buf[:n * h * w * c.value].reshape(n, h, w, c.value).transpose(0, 3, 1, 2).astype(np.float32)
         cap = n * h * w * 512
         buf = np.empty(cap, dtype=np.int8)
         c = C.c_int()

@@ -270,10 +270,15 @@ def conv_units(features):
     return units
 
 
-def quantize_model(state_dict, ranges, input_mean=INPUT_MEAN, input_std=INPUT_STD):
+def quantize_model(state_dict, ranges, input_mean=INPUT_MEAN, input_std=INPUT_STD, hybrid=()):
     """Float state_dict + calibrated activation ranges {tensor name: (r_min, r_max)} -> quantised model: a flat dict
     of numpy arrays (int8 weights, int32 zero points / biases, float32 multipliers) keyed '<unit>.<field>', the unit
-    names being the reference's state_dict prefixes ('encoder_blocks.0.0', 'decoder_blocks.0', 'output', ...)."""
+    names being the reference's state_dict prefixes ('encoder_blocks.0.0', 'decoder_blocks.0', 'output', ...).
+
+    hybrid: unit keys (a subset of unit_names) that run in fp16 (hybrid quantisation, see the section below).  Each
+    adds '<key>.hybrid', '.w_h', '.gain', '.bias_f', '.x_scale' (and keeps '.y_scale'); its int8 arrays stay, so the
+    same dict runs as pure int8.  ValueError for an unknown key or a tensor that would be stored as fp16 with a
+    calibrated range beyond +-HYBRID_RANGE_LIMIT.  With hybrid=() the dict is what it was before hybrid units existed."""
     feats = []
     while f"encoder_blocks.{len(feats)}.0.weight" in state_dict:
         feats.append(int(np.asarray(state_dict[f"encoder_blocks.{len(feats)}.0.weight"]).shape[0]))
@@ -327,7 +332,233 @@ def quantize_model(state_dict, ranges, input_mean=INPUT_MEAN, input_std=INPUT_ST
     w_q, w_s, w_z = quantize_weight_per_channel(w, axis=0)
     put_unit("output", w_q, w_s, w_z, np.asarray(state_dict["output.bias"], dtype=np.float64), f"dec{d - 1}.b", None,
              False)
+    if len(hybrid):
+        _put_hybrid(q, state_dict, ranges, feats, tq, hybrid)
     return q
+
+
+# ---- hybrid quantisation: chosen units run in fp16 (README.md:3466-3474 "mixed precision"; with every unit named it
+# is the table's "NPU FP16" row, README.md:3386-3393) --------------------------------------------------------------
+# Semantics, stated once (csrc/conv_h16.h computes it in fp32, hybrid_forward_model / unit_model in float64):
+#   * weights of a hybrid unit: the BatchNorm-folded float64 weights (plain weights for the transposed convolutions
+#     and the head) divided per output channel by the power-of-two gain g[co] = 2^ceil(log2 max|w[co]|) (1 for an
+#     all-zero channel) and rounded to IEEE fp16: '.w_h';
+#   * operand: from an int8 tensor x = q - x_zp (an integer of magnitude <= 255, exact in fp16), from an fp16 tensor the
+#     stored value; positions outside the image contribute exactly 0;
+#   * a = sum w16 x in fp32 (every product is exact); v = a m[co] + b[co] in fp32 with m = g x_scale for an int8
+#     input and m = g for an fp16 input, b the folded bias as float32; ReLU where the int8 unit has it;
+#   * into an int8 tensor: clamp(rint(v / y_scale) + y_zp, lo, 127) with the int8 unit's lo; into an fp16 tensor:
+#     fp16(min(v, 65504)), round to nearest even; the head writes v as float32 logits;
+#   * a tensor is fp16 iff every unit that writes it and every unit that reads it is hybrid (tensor_dtypes); 'input'
+#     is always int8, and every int8 tensor keeps its calibrated (scale, zero_point).
+HYBRID_RANGE_LIMIT = 60000.0        # an fp16 tensor's calibrated range must stay inside +-this (fp16 max: 65504)
+FP16_MAX = 65504.0
+
+
+def unit_table(features):
+    """(key, kind, input tensor, output tensor or None, relu) of every unit in forward order; kind is 'conv', 'up' or
+    'head'."""
+    d = len(features)
+    conv = [(f"{p}.{ci}", "conv", x, y, True) for p, ci, _, x, y in conv_units(features)]
+    units = conv[:2 * d + 2]
+    for j in range(d):
+        src = "bott.b" if j == 0 else f"dec{j - 1}.b"
+        units.append((f"decoder_blocks.{2 * j}", "up", src, f"cat{d - 1 - j}", False))
+        units += conv[2 * d + 2 + 2 * j:2 * d + 4 + 2 * j]
+    units.append(("output", "head", f"dec{d - 1}.b", None, False))
+    return units
+
+
+def unit_names(features):
+    """Keys of the units of quantize_model in forward order: what `hybrid=` takes."""
+    return [u[0] for u in unit_table(features)]
+
+
+def _check_hybrid(features, hybrid):
+    names = unit_names(features)
+    hybrid = set(hybrid)
+    unknown = sorted(hybrid - set(names))
+    if unknown:
+        raise ValueError(f"hybrid: unknown unit(s) {unknown}; the units are {names}")
+    return hybrid
+
+
+def tensor_dtypes(features, hybrid):
+    """{activation tensor: 'int8' | 'fp16'} for tensor_names plus the pooled tensors 'cat<l>.pool'.  A tensor is fp16
+    iff every unit that writes it and every unit that reads it is in `hybrid`; cat<l> and cat<l>.pool are one tensor for
+    this rule (max-pooling is type agnostic; cat<l> has two writers and, through the pool, two readers); 'input' is
+    always int8 (it comes from the 256-entry table)."""
+    hybrid = _check_hybrid(features, hybrid)
+    d = len(features)
+    users = {}
+    for key, _, x, y, _ in unit_table(features):
+        for t in (x, y):
+            if t is not None:
+                users.setdefault(t.replace(".pool", ""), []).append(key)
+    out = {}
+    for name in tensor_names(d) + [f"cat{l}.pool" for l in range(d)]:
+        base = name.replace(".pool", "")
+        out[name] = "fp16" if base != "input" and all(u in hybrid for u in users[base]) else "int8"
+    return out
+
+
+def hybrid_units(qmodel):
+    """The hybrid units a quantised model carries, in forward order."""
+    feats = [int(f) for f in qmodel["features"]]
+    return [k for k in unit_names(feats) if k + ".hybrid" in qmodel and int(qmodel[k + ".hybrid"])]
+
+
+def hybrid_weights(w, axis=0):
+    """float64 weights -> (w / g rounded to fp16, g): per-output-channel power-of-two gain (output channels on `axis`)."""
+    w = np.asarray(w, dtype=np.float64)
+    amax = np.abs(np.moveaxis(w, axis, 0).reshape(w.shape[axis], -1)).max(axis=1)
+    g = np.ones_like(amax)
+    g[amax > 0] = 2.0 ** np.ceil(np.log2(amax[amax > 0]))
+    shape = [1] * w.ndim
+    shape[axis] = -1
+    return (w / g.reshape(shape)).astype(np.float16), g
+
+
+def _put_hybrid(q, state_dict, ranges, feats, tq, hybrid):
+    hybrid = _check_hybrid(feats, hybrid)
+    for name, dt in tensor_dtypes(feats, hybrid).items():
+        lo, hi = ranges[name.replace(".pool", "")]
+        if dt == "fp16" and max(abs(float(lo)), abs(float(hi))) > HYBRID_RANGE_LIMIT:
+            raise ValueError(f"hybrid: tensor {name!r} would be stored as fp16 but its calibrated range ({lo}, {hi}) "
+                             f"is beyond +-{HYBRID_RANGE_LIMIT:g}")
+    folded = {f"{p}.{ci}": fold_bn(state_dict, p, ci, bi) for p, ci, bi, _, _ in conv_units(feats)}
+    for key, kind, xname, yname, _ in unit_table(feats):
+        if key not in hybrid:
+            continue
+        if kind == "conv":
+            w, b = folded[key]
+        else:
+            w = np.asarray(state_dict[key + ".weight"], dtype=np.float64)
+            b = np.asarray(state_dict[key + ".bias"], dtype=np.float64)
+        w16, g = hybrid_weights(w, axis=1 if kind == "up" else 0)
+        q[key + ".hybrid"] = np.int32(1)
+        q[key + ".w_h"] = np.ascontiguousarray(w16).view(np.uint16)
+        q[key + ".gain"] = g.astype(np.float32)
+        q[key + ".bias_f"] = np.asarray(b, dtype=np.float64).astype(np.float32)
+        q[key + ".x_scale"] = np.float32(tq[xname][0])
+        if yname is not None:
+            q[key + ".y_scale"] = np.float32(tq[yname][0])
+
+
+def _conv_f64(kind, x, w):
+    """float64 convolution of a unit: x (N,C,H,W); w (O,C,3,3) for 'conv', (I,O,2,2) for 'up', (1,C,1,1) for 'head'.
+    Zero padding: positions outside the image contribute exactly 0."""
+    import torch
+    import torch.nn.functional as F
+    xt, wt = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)), torch.from_numpy(
+        np.ascontiguousarray(w, dtype=np.float64))
+    if kind == "up":
+        return F.conv_transpose2d(xt, wt, stride=2).numpy()
+    return F.conv2d(xt, wt, padding=1 if kind == "conv" else 0).numpy()
+
+
+def unit_model(qmodel, key, x):
+    """One unit of a quantised model on a given input tensor, in float64 (the GPU tests feed it the device's own input).
+
+    x: (N,C,H,W); an int8 array is an int8 tensor (codes), any float array an fp16 tensor (its stored values); for a
+    decoder's first convolution it is the whole concat tensor.  Returns a dict:
+      'dtype'   'int8' | 'fp16' | 'fp32' (the head): how the unit's output is stored (tensor_dtypes of the model's set)
+      'y'       the stored output by this model: int8 codes, fp16 values (as float32) or float32 logits
+    and for a hybrid unit also
+      'v'       a m + b in float64 with the fp16-rounded weights, after the ReLU where the unit has one: unrounded
+      'S'       m sum |w16| |x| + |b| per output element: what the rounding errors of the fp32 evaluation scale with
+      'K'       the real GEMM depth (taps x input channels)
+    A unit that is not hybrid is evaluated by the integer rule of the module header (int8 in, int8 out / logits)."""
+    feats = [int(f) for f in qmodel["features"]]
+    unit = {u[0]: u for u in unit_table(feats)}
+    if key not in unit:
+        raise ValueError(f"unknown unit {key!r}")
+    _, kind, _, yname, relu = unit[key]
+    x = np.asarray(x)
+    x_int8 = x.dtype == np.int8
+    ydt = "fp32" if yname is None else tensor_dtypes(feats, hybrid_units(qmodel))[yname]
+    bshape = (1, -1, 1, 1)
+    if not (key + ".hybrid" in qmodel and int(qmodel[key + ".hybrid"])):
+        if not x_int8 or ydt == "fp16":
+            raise ValueError(f"{key} is not hybrid: its tensors are int8")
+        ax = 1 if kind == "up" else 0
+        wsh = [1, 1, 1, 1]
+        wsh[ax] = -1
+        wz = qmodel[key + ".w_q"].astype(np.float64) - np.asarray(qmodel[key + ".w_zp"], dtype=np.float64).reshape(wsh)
+        acc = np.rint(_conv_f64(kind, x.astype(np.float64) - float(qmodel[key + ".x_zp"]), wz)).astype(np.int64)
+        t = (acc + np.asarray(qmodel[key + ".bias_q"], dtype=np.int64).reshape(bshape)).astype(np.float32)
+        t = t * np.asarray(qmodel[key + ".mult"], dtype=np.float32).reshape(bshape)
+        if yname is None:
+            return {"dtype": "fp32", "y": t.astype(np.float32)}
+        zy = int(qmodel[key + ".y_zp"])
+        y = np.clip(np.rint(t).astype(np.int64) + zy, zy if relu else QMIN, QMAX).astype(np.int8)
+        return {"dtype": "int8", "y": y}
+    w16 = np.asarray(qmodel[key + ".w_h"]).view(np.float16).astype(np.float64)
+    m = np.asarray(qmodel[key + ".gain"], dtype=np.float32).astype(np.float64)
+    if x_int8:
+        xv = x.astype(np.float64) - float(qmodel[key + ".x_zp"])
+        m = m * float(np.float32(qmodel[key + ".x_scale"]))
+    else:
+        xv = x.astype(np.float64)
+    b = np.asarray(qmodel[key + ".bias_f"], dtype=np.float32).astype(np.float64)
+    v = _conv_f64(kind, xv, w16) * m.reshape(bshape) + b.reshape(bshape)
+    big = _conv_f64(kind, np.abs(xv), np.abs(w16)) * m.reshape(bshape) + np.abs(b).reshape(bshape)
+    if relu:
+        v = np.maximum(v, 0.0)
+    k = int(xv.shape[1]) * (9 if kind == "conv" else 1)
+    out = {"dtype": ydt, "v": v, "S": big, "K": k}
+    if ydt == "int8":
+        zy, sy = int(qmodel[key + ".y_zp"]), float(np.float32(qmodel[key + ".y_scale"]))
+        out["y"] = np.clip(np.rint(v / sy) + zy, zy if relu else QMIN, QMAX).astype(np.int8)
+    elif ydt == "fp16":
+        out["y"] = np.minimum(v, FP16_MAX).astype(np.float16).astype(np.float32)
+    else:
+        out["y"] = v.astype(np.float32)
+    return out
+
+
+def hybrid_bound(out, y_scale=None):
+    """Per-element bound of |device - model| for a hybrid unit's unit_model result `out`: gamma = (K + 3) 2^-24 S is the
+    first-order worst case of an fp32 sum of K exact products plus the epilogue's roundings.  int8 output (codes, against
+    clip(v / y_scale + y_zp, lo, 127)): 0.5 + gamma / y_scale; fp16 output: gamma + 2^-11 |v| + 2^-25 (the storage
+    rounding and half the smallest subnormal); float32 logits: gamma."""
+    gamma = (out["K"] + 3) * 2.0 ** -24 * out["S"]
+    if out["dtype"] == "int8":
+        return 0.5 + gamma / float(y_scale)
+    if out["dtype"] == "fp16":
+        return gamma + 2.0 ** -11 * np.abs(out["v"]) + 2.0 ** -25
+    return gamma
+
+
+def hybrid_forward_model(qmodel, frames, taps=None):
+    """The forward of a quantised model with its hybrid units, in float64 with the fp16-rounded weights (unit_model on
+    every unit; max-pooling and the concat on stored values).  frames: (N,H,W,3) uint8.  Returns (logits float32
+    (N,1,H,W), {unit key: {'v', 'S', 'K'}} for the hybrid units).  taps, if a dict, receives every stored tensor by
+    name."""
+    feats = [int(f) for f in qmodel["features"]]
+    d = len(feats)
+    f = np.asarray(frames)
+    lut = np.asarray(qmodel["input.lut"])
+    t = {"input": np.stack([lut[c][f[..., c]] for c in range(3)], axis=1).astype(np.int8)}
+    info = {}
+    logits = None
+    for key, kind, xname, yname, _ in unit_table(feats):
+        if xname.endswith(".pool") and xname not in t:
+            src = t[xname[:-5]][:, :feats[int(xname[3:-5])]]
+            n, c, h, w = src.shape
+            t[xname] = src.reshape(n, c, h // 2, 2, w // 2, 2).max(axis=(3, 5))
+        out = unit_model(qmodel, key, t[xname])
+        if "v" in out:
+            info[key] = {k: out[k] for k in ("v", "S", "K")}
+        if yname is None:
+            logits = out["y"]
+        elif yname.startswith("cat"):                       # skip half first, the transposed convolution's behind it
+            t[yname] = out["y"] if kind == "conv" else np.concatenate([t[yname], out["y"]], axis=1)
+        else:
+            t[yname] = out["y"]
+    if taps is not None:
+        taps.update(t)
+    return logits, info
 
 
 def save_quantized(path, qmodel):
