@@ -580,6 +580,34 @@ int unet_host_pack_updeep_x3(const float* wt_host, const float* bt_host, const f
                              double* ordered_out, uint16_t* packed_out, float* pre_out, double* cls_out);
 int unet_host_plan_updeep_x3(const int* query, int n_query, int* plan_out, int n_plan);
 
+/* The first encoder block of the f16x3 tier as ONE kernel (csrc/conv_x3_enc1.h): enc1.conv1 is computed
+ * per work item into the LDS halo image that enc1.conv2's 64-channel third-structure form reads, so the 64-channel tensor
+ * between them is never stored.  Bit-identical to the two launches it replaces (tests/test_x3_enc1_gpu.py).
+ * unet_set_x3_fuse_first: process-wide switch, 1 = on (default; environment UNET_X3_FUSE_FIRST=0 makes it 0), 0 = the
+ *   block keeps its two launches.  A captured HIP graph keeps the setting it was captured with.  Returns the previous
+ *   setting.
+ * unet_host_plan_enc1_x3 (test hook, host arithmetic only): x3_plan_enc1.  query[13]: input is uint8, n, h, w, cout of
+ *   the block, forced form of the second convolution (tile_width as unet_op_conv3x3_x3; 0 = none, as the forward asks),
+ *   f16q8 scratch present, unet_set_x3_fuse_first's switch, then the four switches and unet_set_x3_cross_fp8's mode as
+ *   for unet_host_plan_conv3x3_x3.  The plan takes the block exactly when the input is uint8, cout == 64, w % 28 == 0,
+ *   no f16q8 scratch, the switch is on and unet_host_plan_conv3x3_x3's own answer for the second convolution (64 -> 64,
+ *   pooled epilogue) is structure 3 on 28-wide tiles with one wave along the channels, the fused pool, no split-K and no
+ *   tall-image tiling.  plan_out[8]: taken, grid, tiles along x, tiles along y, pixel tiles, 0, 0, 0 (all 0: declined).
+ * unet_op_enc1_x3_planes (test entry point): frames (N,H,W,3) uint8 -> y channels [co_off, co_off + 64) of (N,H,W,ldo)
+ *   and pool (N,H/2,W/2,64) dense, both as hi / lo planes, = the block's two convolutions + folded BN + ReLU with
+ *   operators built by the functions the network's build uses.  w1_host (64,3,3,3), w2_host (64,64,3,3); act1_host /
+ *   act2_host (64 each, optional): power-of-two activation scales of the two layers' outputs.  tile_width: the forced
+ *   form of the second convolution (0 or 628); UNET_ERR_INVALID_ARG where the plan declines.  path_out (optional
+ *   int[8]): the second convolution's path as unet_op_conv3x3_x3_planes reports it, [7] = 1: the fused kernel ran. */
+int unet_set_x3_fuse_first(int on);
+int unet_host_plan_enc1_x3(const int* query, int n_query, int* plan_out, int n_plan);
+int unet_op_enc1_x3_planes(int device, const void* frames_dev, int n, int h, int w, const float* w1_host,
+                           const float* scale1_host, const float* shift1_host, int relu1, const float* mean_host,
+                           const float* std_host, const float* act1_host, const float* w2_host, const float* scale2_host,
+                           const float* shift2_host, int relu2, const float* act2_host, int tile_width, uint16_t* y_dev,
+                           size_t y_lo_off, int ldo, int co_off, uint16_t* pool_dev, size_t pool_lo_off, int* path_out,
+                           int* range_out, void* stream);
+
 /* Which kernel structure the split-operand tier's ConvTranspose2d (and the plain GEMMs of its training path) run on
  * (reference README.md:1442, :1476): -1 = automatic - the one-wave-per-SIMD kernel (csrc/upconv_x3_r512.h: 224-pixel
  * tiles, weights straight from L2) where Cin % 128 == 0 and there is a work item for at least half of the CUs, the

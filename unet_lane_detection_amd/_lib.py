@@ -196,6 +196,12 @@ SIGNATURES = {
     "unet_host_pack_updeep_x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),
     "unet_host_plan_updeep_x3": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "unet_set_x3_fuse_first": (C.c_int, [C.c_int]),
+    "unet_host_plan_enc1_x3": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "unet_op_enc1_x3_planes": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "unet_op_upcat_conv3x3_x3": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "unet_host_compose_upcat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

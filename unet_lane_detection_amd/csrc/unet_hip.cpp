@@ -40,6 +40,7 @@
 #include "upconv_x3_r512.h"
 #include "upconv_x3_win.h"
 #include "conv_first_x3.h"
+#include "conv_x3_enc1.h"
 #include "conv_i8.h"
 #include "wino_f32.h"
 #include "train_kernels.h"

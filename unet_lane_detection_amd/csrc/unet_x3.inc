@@ -1499,6 +1499,65 @@ hipError_t run_first_x3(const GemmOpX3& op, const void* input, bool u8, int n, i
   return hipGetLastError();
 }
 
+// ---- the first encoder block as one kernel (conv_x3_enc1.h; DESIGN.md 4.12) ----
+// unet_set_x3_fuse_first: 1 = on (default; UNET_X3_FUSE_FIRST=0 in the environment makes it 0), 0 = the block keeps its
+// two launches (conv_first_x3.h, then conv_x3_t448.h)
+int& x3_fuse_first_mode() {
+  static int mode = x3_env_off("UNET_X3_FUSE_FIRST") ? 0 : 1;
+  return mode;
+}
+
+// The fused kernel stands for exactly one pair of launches: uint8 frames into a 64-channel first convolution, and a
+// second convolution that x3_plan_conv itself puts on the third structure's 64-channel form with the pooled epilogue on
+// 16 x 28 tiles.  Everything else keeps the two launches: fp32 input, batches whose second convolution lands on another
+// structure, widths tiled 32 wide, the training forward, the f16q8 tier (its scratch present).
+// conv2: the second convolution's query, as run_conv_x3 would ask it
+struct X3Enc1Plan {
+  bool take = false;
+  X3ConvPlan conv;   // the second convolution's plan: tiles and grid of the fused launch
+};
+X3Enc1Plan x3_plan_enc1(bool u8, bool on, const X3ConvQuery& conv2) {
+  X3Enc1Plan p;
+  if (!on || !u8 || conv2.cin != 64 || conv2.cout != 64 || conv2.qScratch || conv2.w % 28 != 0) return p;
+  const X3ConvPlan c = x3_plan_conv(conv2);
+  const X3Path& k = c.path;
+  if (!c.valid || k.structure != kX3T448 || k.waves != 1 || k.epi != 1 || k.tileW != 28 || k.kSplit != 1 || k.flat) return p;
+  p.take = true;
+  p.conv = c;
+  return p;
+}
+
+// op1 from build_conv_x3(first = true), op2 the block's second convolution; frames (n,h,w,3) uint8 -> io.out planes
+// (pixel stride io.ldo, channel offset io.coOff) and their pooled copy fuse.pool; io's input side is not read
+hipError_t run_enc1_x3(const X3Enc1Plan& p, const GemmOpX3& op1, const GemmOpX3& op2, const void* frames, const X3ConvIo& io,
+                       const X3Fuse& fuse, const float* mean, const float* stdv, hipStream_t s, X3Path* path = nullptr) {
+  if (!p.take || op1.cout != 64 || op2.cin != 64 || op2.cout != 64 || !fuse.pool) return hipErrorInvalidValue;
+  const X3ConvPlan& c = p.conv;
+  unet::ConvEnc1X3Args a{};
+  a.c.wt = op2.wt, a.c.scale = op2.scale, a.c.shift = op2.shift, a.c.relu = op2.relu;
+  a.c.out = io.out, a.c.outLo = io.outLo, a.c.ldo = io.ldo, a.c.co_off = io.coOff;
+  a.c.N = c.N, a.c.H = c.H, a.c.W = io.w, a.c.imgH = c.imgH, a.c.Cin = 64, a.c.Cout = 64;
+  a.c.tilesX = c.tilesX, a.c.tilesY = c.tilesY, a.c.pixTiles = c.pixTiles;
+  a.c.coTiles = a.c.coGroup = 1, a.c.nChunks = 2, a.c.kSplit = 1, a.c.chunksTotal = 2;
+  a.c.pool = fuse.pool, a.c.poolLo = fuse.poolLo;
+  a.c.err = g_errWord ? g_errWord : op_err_word();
+  a.frames = static_cast<const uint8_t*>(frames);
+  a.wt1 = op1.wt, a.scale1 = op1.scale, a.shift1 = op1.shift, a.relu1 = op1.relu;
+  a.m0 = mean ? mean[0] : 0.f, a.m1 = mean ? mean[1] : 0.f, a.m2 = mean ? mean[2] : 0.f;
+  a.s0 = stdv ? stdv[0] : 1.f, a.s1 = stdv ? stdv[1] : 1.f, a.s2 = stdv ? stdv[2] : 1.f;
+  auto kern = unet::conv3x3_enc1_x3_kernel;
+  const hipError_t e = ensure_dyn_lds((const void*)kern, unet::X3Enc1Shape::LDS_BYTES);
+  if (e != hipSuccess) return e;
+  // the algorithmic flops of both convolutions (the halo's recomputed pixels are not counted); the frames read, the
+  // planes and their pooled copy written
+  const double px = (double)io.n * io.h * io.w;
+  prof_begin("conv3x3_enc1_f16x3", 2.0 * px * (27.0 * 64 + 9.0 * 64 * 64), 3.0 * px + 4.0 * px * 64 + px * 64, s);
+  hipLaunchKernelGGL(kern, dim3(c.grid), dim3(256), (size_t)unet::X3Enc1Shape::LDS_BYTES, s, a);
+  prof_end(s);
+  if (path) *path = c.path;
+  return hipGetLastError();
+}
+
 }  // namespace
 
 struct X3Net {
@@ -1736,6 +1795,15 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
     const X3ConvIo conv2Io = io_of(p.tmpA, ch, cw, p.cat[l], 2 * f, 0);
     const bool conv2OnQ8 = lands_on_q8(X->enc[2 * l + 1], conv2Io, &fz);
     if (l == 0) {
+      // the whole block as one launch where x3_plan_enc1 takes it: the first convolution's planes are never stored
+      const X3Enc1Plan ep = x3_plan_enc1(u8, x3_fuse_first_mode() != 0, x3_conv_query(X->enc[1], conv2Io, opts_of(nullptr, &fz)));
+      if (ep.take) {
+        HIPCHK(h->err, run_enc1_x3(ep, X->enc[0], X->enc[1], input, conv2Io, fz, c.input_mean, c.input_std, s));
+        cur = &p.pool[l];
+        ch /= 2;
+        cw /= 2;
+        continue;
+      }
       HIPCHK(h->err, run_first_x3(X->enc[0], input, u8, n, ch, cw, U(p.tmpA), p.tmpA.elems, f, c.input_mean, c.input_std, s));
     } else {
       // f16q8 tier: tmpA has one consumer, the block's second convolution; where that one runs on conv_q8_r512.h the
@@ -2104,6 +2172,93 @@ int unet_set_x3_compose_deep(int on) {
   const int prev = x3_compose_deep_mode();
   x3_compose_deep_mode() = on ? 1 : 0;
   return prev;
+}
+
+int unet_set_x3_fuse_first(int on) {
+  const int prev = x3_fuse_first_mode();
+  x3_fuse_first_mode() = on ? 1 : 0;
+  return prev;
+}
+
+namespace {
+// the second convolution of the first block as forward_x3 asks for it: 64 -> cout, pooled epilogue, the forward's split-K
+// scratch, the f16q8 scratch and fragments where the tier is on
+X3ConvQuery enc1_conv2_query(int n, int h, int w, int cout, bool q8, const X3Force& force, const X3Switches& sw) {
+  X3ConvQuery q;
+  q.n = n, q.h = h, q.w = w, q.cin = 64, q.cout = cout, q.epi = 1;
+  q.force = force;
+  q.splitScratch = true, q.splitFloats = kSplitFloats;
+  q.qScratch = q.wq = q8;
+  q.sw = sw;
+  return q;
+}
+}  // namespace
+
+// Test hook (no device): x3_plan_enc1 for query = {input is uint8, n, h, w, cout, forced form of the second convolution
+// (0 = none), f16q8 scratch present, unet_set_x3_fuse_first's switch, UNET_X3_FLAT, _R512, _T448, _T448_C4, cross-fp8
+// mode} -> planOut = {taken, grid, tiles along x, tiles along y, pixel tiles, 0, 0, 0}, all 0 where the plan declines
+int unet_host_plan_enc1_x3(const int* query, int nQuery, int* planOut, int nPlan) {
+  if (!query || nQuery != 13 || !planOut || nPlan != 8) return op_bad_args();
+  X3Force force;
+  if (query[1] < 1 || query[2] < 1 || query[3] < 1 || query[4] < 64 || query[4] % 64 || !x3_decode_force(query[5], &force))
+    return op_bad_args();
+  X3Switches sw;
+  sw.flat = query[8] != 0, sw.r512 = query[9] != 0, sw.t448 = query[10] != 0, sw.t448c4 = query[11] != 0;
+  sw.crossFp8 = query[12];
+  const X3Enc1Plan p =
+      x3_plan_enc1(query[0] != 0, query[7] != 0, enc1_conv2_query(query[1], query[2], query[3], query[4], query[6] != 0, force, sw));
+  std::fill(planOut, planOut + 8, 0);
+  if (p.take) {
+    const int v[5] = {1, p.conv.grid, p.conv.tilesX, p.conv.tilesY, p.conv.pixTiles};
+    std::copy(v, v + 5, planOut);
+  }
+  return UNET_OK;
+}
+
+// Test entry point: the first encoder block on the fused kernel (conv_x3_enc1.h), operators built as x3_build builds
+// them.  frames (n,hh,ww,3) uint8 -> y planes (pixel stride ldo, channels [coOff, coOff + 64)) and their pooled planes
+// (n,hh/2,ww/2,64).  act1 / act2 (64 each, or null): the activation scales of the two layers' outputs.  tileWidth: the
+// forced form of the second convolution (0: the dispatch's own answer, 628: the third structure); a plan that declines
+// is an invalid call.  pathOut[0..6]: the second convolution's path, pathOut[7] = 1: the fused kernel ran
+int unet_op_enc1_x3_planes(int device, const void* frames, int n, int hh, int ww, const float* w1Host, const float* scale1,
+                           const float* shift1, int relu1, const float* mean, const float* stdv, const float* act1,
+                           const float* w2Host, const float* scale2, const float* shift2, int relu2, const float* act2,
+                           int tileWidth, uint16_t* y, size_t yLo, int ldo, int coOff, uint16_t* pool, size_t poolLo,
+                           int* pathOut, int* rangeOut, void* stream) {
+  X3Force force;
+  if (ldo == 0) ldo = 64;
+  if (!frames || !w1Host || !scale1 || !shift1 || !mean || !stdv || !w2Host || !scale2 || !shift2 || !y || !pool || n < 1 ||
+      hh < 2 || ww < 2 || hh % 2 || ww % 2 || yLo % 8 || poolLo % 8 || ldo % 64 || coOff < 0 || coOff % 64 || coOff + 64 > ldo ||
+      !x3_decode_force(tileWidth, &force))
+    return op_bad_args();
+  path_to_ints(X3Path(), pathOut);
+  X3Enc1Plan plan = x3_plan_enc1(true, true, enc1_conv2_query(n, hh, ww, 64, false, force, x3_switches()));
+  if (!plan.take) return op_bad_args();
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  OpGuard<GemmOpX3> g1, g2;
+  ActScale a1, a2;
+  if (act1) a1 = act_from_host(act1, 64);
+  if (act2) a2 = act_from_host(act2, 64);
+  int rc = build_conv_x3(g_opErr, g1.op, w1Host, 64, 3, scale1, shift1, relu1, true, nullptr, act1 ? &a1 : nullptr, false);
+  if (!rc)
+    rc = build_conv_x3(g_opErr, g2.op, w2Host, 64, 64, scale2, shift2, relu2, false, act1 ? &a1 : nullptr, act2 ? &a2 : nullptr,
+                       false);
+  if (rc) return rc;
+  OpRangeScope range;
+  X3Path path;
+  hipError_t e = range.arm();
+  if (e == hipSuccess) {
+    X3Fuse fz;
+    fz.pool = pool;
+    fz.poolLo = poolLo;
+    e = run_enc1_x3(plan, g1.op, g2.op, frames, x3_from(nullptr, nullptr, 0, n, hh, ww).to(y, yLo, ldo, coOff), fz, mean, stdv, s,
+                    &path);
+  }
+  const int st = op_done(e, s, 0, &range, rangeOut);
+  path_to_ints(path, pathOut);
+  if (pathOut && st == UNET_OK) pathOut[7] = 1;
+  return st;
 }
 
 // Test entry point: kernel 1 of the deep levels' split step alone (upconv_x3_win.h), on caller-owned planes.  x planes
