@@ -801,6 +801,31 @@ int unet_augment_u8(int device, const uint8_t* images_dev, const uint8_t* masks_
 /* sizeof one record, so a binding can check its layout against the library */
 size_t unet_augment_param_bytes(void);
 
+/* ---- video path on the GPU (csrc/video_kernels.h) --------------------------------------------------------------
+ * The per-frame work of the reference's predict_video (src/unet.py:99-140; the webcam and single-image modes use the
+ * same lines, :210-211, :251-252) around the network, a batch of frames at a time.  Integer resize as in the camera
+ * stage above; parity against cv2 itself is unpinned.  Both calls only enqueue on `stream`.
+ *
+ * unet_resize_u8_batch: src_dev (n, height, width, channels) uint8, dense -> dst_dev (n, out_h, out_w, channels):
+ * every image is what unet_resize_u8 gives for it, bit for bit (equal sizes are a copy).  channels is 1 or 3.  With
+ * swap_rb (3 channels only) channels 0 and 2 are exchanged: cvtColor(BGR2RGB) followed by the resize of
+ * preprocess_image (src/unet.py:121, :33).  A resize to more than 7680 columns is UNET_ERR_SHAPE. */
+int unet_resize_u8_batch(int device, const uint8_t* src_dev, int n, int height, int width, int channels, int swap_rb,
+                         int out_w, int out_h, uint8_t* dst_dev, void* stream);
+
+/* unet_overlay_u8_batch: frames_dev (n, height, width, 3) uint8 and the network's masks masks_dev (n, mask_h, mask_w)
+ * uint8 -> overlay_out_dev (n, height, width, 3), per frame and in one pass (src/unet.py:70, :125-126):
+ *     m      = cv2.resize(mask, (width, height))                 values 0..255
+ *     colour = lut[m]                                            applyColorMap; rows in the frame's channel order
+ *     out[c] = clamp(rint(fl(fl(fl(frame[c] * alpha) + fl(colour[c] * beta)) + gamma)), 0, 255)        addWeighted
+ * where every fl is one fp32 rounding (nothing is contracted into a fused multiply-add) and rint rounds half to
+ * even.  lut_host: 256 * 3 bytes in host memory, consumed before the call returns.  mask_out_dev: NULL, or
+ * (n, height, width) uint8 that receives m.  alpha, beta and gamma must be finite.  A frame wider than 7680 whose
+ * mask has another size is UNET_ERR_SHAPE. */
+int unet_overlay_u8_batch(int device, const uint8_t* frames_dev, int n, int height, int width, const uint8_t* masks_dev,
+                          int mask_h, int mask_w, const uint8_t* lut_host, float alpha, float beta, float gamma,
+                          uint8_t* overlay_out_dev, uint8_t* mask_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

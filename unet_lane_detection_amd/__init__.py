@@ -7,6 +7,8 @@ Public surface:
   LossSpec                     the general BCE + focal + Dice loss as UNetTrainer.set_loss keeps it (metrics.py)
   positive_counts, pos_weight_from_masks, sample_weights
                                mask statistics for sparse lanes (imbalance.py)
+  FramePipeline, predict_video, jet_table
+                               the reference's video mode: batched resize, mask overlay, streamed chunks (video.py)
   seeded_state_dict, ...       reproducible weights / synthetic inputs
 """
 from .state import (DEFAULT_FEATURES, INPUT_MEAN, INPUT_STD, num_parameters, seeded_state_dict,  # noqa: F401
@@ -29,4 +31,7 @@ def __getattr__(name):  # lazy: importing the package must not need torch.cuda o
     if name in ("positive_counts", "pos_weight_from_masks", "sample_weights"):
         from . import imbalance
         return getattr(imbalance, name)
+    if name in ("FramePipeline", "predict_video", "jet_table"):
+        from . import video
+        return getattr(video, name)
     raise AttributeError(name)
