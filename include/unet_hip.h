@@ -826,6 +826,46 @@ int unet_overlay_u8_batch(int device, const uint8_t* frames_dev, int n, int heig
                           int mask_h, int mask_w, const uint8_t* lut_host, float alpha, float beta, float gamma,
                           uint8_t* overlay_out_dev, uint8_t* mask_out_dev, void* stream);
 
+/* ---- checkpoint ensembles and threshold sweeps (csrc/ensemble_kernels.h) ---------------------------------------
+ * Both sit between a head's output and the mask that leaves the device, take a bare device ordinal like
+ * unet_seg_metrics_accumulate (so they serve every tier), only enqueue on `stream`, and refuse bad arguments with
+ * UNET_ERR_INVALID_ARG and a text for unet_op_last_error before any device is touched. */
+#define UNET_ENSEMBLE_MAX 8
+#define UNET_SWEEP_MAX 64
+
+/* The reference's `ensemble_predict` ("model ensembling", README.md:2623-2647:
+ * torch.stack([sigmoid(m(x)) for m in models]).mean(0) > 0.5) on the probability planes the members' heads wrote:
+ * probs_dev is a HOST array of k device pointers, 1 <= k <= UNET_ENSEMBLE_MAX, each to `numel` floats; weights_host k
+ * floats, finite and not negative, consumed before the call returns (NULL: (float)(1.0 / k) each).  Per element
+ *     acc = w[0] * p0;   acc = acc + w[j] * pj   for j = 1 .. k-1, in that order
+ * with every product and every sum rounded to fp32 on its own (nothing is contracted into a fused multiply-add), so
+ * numpy float32 reproduces the result bit for bit.  probs_out_dev: NULL or `numel` floats that receive acc.
+ * mask_out_dev: NULL or `numel` bytes that receive acc > threshold ? 255 : 0, the value the heads write and what the
+ * reference's `> 0.5` yields (a NaN gives 0).  Not both NULL.  The inputs are probabilities and not logits: every tier
+ * writes them from its head, so no exponential is repeated here and the mean is exact against its model. */
+int unet_ensemble_combine(int device, const float* const* probs_dev, int k, const float* weights_host, size_t numel,
+                          float threshold, float* probs_out_dev, uint8_t* mask_out_dev, void* stream);
+
+/* Confusion counts of `numel` scores at n_thresholds thresholds in one pass: what choosing the operating point needs
+ * (the reference's one knob, `predict(image, threshold=0.5)` src/unet.py:74, its advice to tune it README.md:4503-4524,
+ * and the int8 model whose probabilities shift, README.md:3437, :3442-3474).  scores_dev: floats in any domain - logits,
+ * probabilities, an ensemble's means; targets_dev: `numel` floats, positive iff != 0, or with targets_are_u8 `numel`
+ * bytes, positive iff non-zero (for the 0/1 and 0/255 targets unet_seg_metrics_accumulate takes, the same classes).
+ * thresholds_host: 1 <= n_thresholds <= UNET_SWEEP_MAX floats, strictly ascending, no NaN, -inf allowed first and +inf
+ * last, consumed before the call returns.  Per element
+ *     bin = #{ j : score > thresholds[j] }     0 .. n_thresholds; equal is not above; a NaN is above nothing (bin 0)
+ *     counts_dev[cls * (n_thresholds + 1) + bin] += 1      cls = 1 for a positive target
+ * counts_dev: 2 * (n_thresholds + 1) unsigned 64-bit integers owned by the caller, added to and never cleared, so
+ * batches accumulate.  Predicted positive at thresholds[j] is bin > j: TP, FP, FN, TN at every threshold are suffix and
+ * prefix sums of the two rows.  Integer arithmetic: exact and deterministic.  numel at most 2^41 - 1 (UNET_ERR_SHAPE). */
+int unet_score_sweep_accumulate(int device, const float* scores_dev, const void* targets_dev, int targets_are_u8,
+                                size_t numel, const float* thresholds_host, int n_thresholds,
+                                unsigned long long* counts_dev, void* stream);
+/* Process-wide kernel choice of unet_score_sweep_accumulate: 1 (default) = equal bins of a wave are combined with
+ * ballots before they touch the block's LDS counters, 0 = every lane adds its own.  The counts are the same; the
+ * switch is there for tools/ensemble_sweep_timing.py.  Returns the previous setting. */
+int unet_set_sweep_combine(int on);
+
 #ifdef __cplusplus
 }
 #endif

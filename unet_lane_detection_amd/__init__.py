@@ -4,6 +4,9 @@ Public surface:
   UNetHIP                      forward(image) -> logits, run_u8(frames)
   RKNN_model_container         drop-in for the reference's model container
   SegMetrics                   loss / Dice / IoU / precision / recall of a validation pass (metrics.py)
+  ThresholdSweep               confusion counts and metrics at many thresholds from one pass (metrics.py)
+  Ensemble                     the reference's ensemble_predict: several models' probabilities averaged on the device
+                               (ensemble.py)
   LossSpec                     the general BCE + focal + Dice loss as UNetTrainer.set_loss keeps it (metrics.py)
   positive_counts, pos_weight_from_masks, sample_weights
                                mask statistics for sparse lanes (imbalance.py)
@@ -34,4 +37,10 @@ def __getattr__(name):  # lazy: importing the package must not need torch.cuda o
     if name in ("FramePipeline", "predict_video", "jet_table"):
         from . import video
         return getattr(video, name)
+    if name in ("ThresholdSweep", "DEFAULT_THRESHOLDS"):
+        from . import metrics
+        return getattr(metrics, name)
+    if name == "Ensemble":
+        from .ensemble import Ensemble
+        return Ensemble
     raise AttributeError(name)

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, quant
+from .metrics import DEFAULT_THRESHOLDS
 from .model import _logit, _pack
 
 
@@ -274,6 +275,16 @@ class UNetInt8:
         return metrics.evaluate_batches(self._lib, self.device, frames, targets, batch, threshold,
                                         lambda: C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),
                                         self.run_u8)
+
+    def sweep(self, frames, targets, thresholds=DEFAULT_THRESHOLDS, batch=None):
+        """Confusion counts and metrics of the int8 tier at every threshold of `thresholds` in one forward of the set:
+        as UNetHIP.sweep.  `.best()` is the operating point of this quantised model (its probabilities shift against
+        the float model's, reference README.md:3437)."""
+        from . import metrics
+        self._require_live()
+        return metrics.sweep_batches(self._lib, self.device, frames, targets, batch, thresholds, "logit",
+                                     lambda: C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),
+                                     self.run_u8)
 
     def read_tensor(self, name, n, h, w):
         """Activation tensor `name` of the last forward as an (N,C,h,w) numpy array (parity tests); h, w are that

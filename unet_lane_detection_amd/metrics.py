@@ -148,6 +148,193 @@ def accumulate(lib, device_index, logits, targets, acc, stream, threshold=0.5, l
     _lib.check(rc, "unet_seg_metrics_accumulate")
 
 
+# ---- threshold sweeps (include/unet_hip.h, unet_score_sweep_accumulate) ------------------------------------------
+# The operating point is the one knob the reference exposes at every layer (`predict(image, threshold=0.5)`
+# src/unet.py:74, the ROS parameter ~threshold, README.md:4503-4524, and the int8 model whose probabilities shift,
+# README.md:3437).  One pass over scores and targets counts every element into (class, bin); the confusion counts at
+# every threshold are sums over those.
+
+DEFAULT_THRESHOLDS = tuple(round(0.05 * i, 2) for i in range(1, 20))      # 0.05, 0.10, ..., 0.95
+SWEEP_MAX = 64          # UNET_SWEEP_MAX
+DOMAINS = ("probability", "logit")
+
+
+def sweep_model(scores, targets, thresholds):
+    """The counting rule of unet_score_sweep_accumulate in numpy: counts[cls, bin] with bin = #{j : score > t_j} (a
+    score equal to t_j is not above it, a NaN is above nothing) and cls = target != 0.  scores: float32 values in any
+    domain; thresholds: ascending float32.  Returns int64 (2, T + 1)."""
+    s = np.asarray(scores, dtype=np.float32).reshape(-1)
+    c = (np.asarray(targets).reshape(-1) != 0).astype(np.int64)
+    t = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+    if s.size != c.size:
+        raise ValueError("scores and targets differ in size")
+    bins = np.zeros(s.size, dtype=np.int64)
+    with np.errstate(invalid="ignore"):
+        for tj in t:
+            bins += s > tj
+    return np.bincount(c * (t.size + 1) + bins, minlength=2 * (t.size + 1)).reshape(2, t.size + 1).astype(np.int64)
+
+
+def _ratios(num, den):
+    num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+    return np.where(den == 0, 1.0, num / np.where(den == 0, 1.0, den))      # _ratio, element by element
+
+
+class ThresholdSweep:
+    """Confusion counts and the metrics of SegMetrics at every threshold of a sweep, from counts[2, T + 1] as
+    sweep_model / unet_score_sweep_accumulate give them.  `thresholds` are the values the scores were compared with,
+    in `domain` ("probability" or "logit"); `probabilities` are the probabilities they stand for (default: the
+    thresholds themselves, or their sigmoid).  Predicted positive at t_j means bin > j, so tp and fp are suffix sums
+    of the two rows and fn and tn prefix sums.  tp, fp, fn, tn are int64 arrays of length T; iou, f1 (= dice),
+    precision, recall and pixel_accuracy float64 arrays with the empty-denominator convention of SegMetrics."""
+
+    def __init__(self, thresholds, counts, domain="probability", probabilities=None):
+        if domain not in DOMAINS:
+            raise ValueError(f"domain={domain!r}: one of {DOMAINS}")
+        t = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+        c = np.asarray(counts).astype(np.int64).reshape(2, -1)
+        if t.size < 1 or c.shape[1] != t.size + 1:
+            raise ValueError(f"{t.size} thresholds need counts of shape (2, {t.size + 1})")
+        with np.errstate(invalid="ignore"):
+            ascending = bool((np.diff(t) > 0).all())          # written so that a NaN or inf - inf refuses
+        if np.isnan(t).any() or not ascending:
+            raise ValueError("thresholds must be strictly ascending")
+        self.domain = domain
+        self.thresholds = t
+        if probabilities is None:
+            with np.errstate(over="ignore"):
+                probabilities = t if domain == "probability" else 1.0 / (1.0 + np.exp(-t))
+        self.probabilities = np.asarray(probabilities, dtype=np.float64).reshape(-1)
+        if self.probabilities.size != t.size:
+            raise ValueError("one probability per threshold")
+        self.counts = c
+        above = np.cumsum(c[:, ::-1], axis=1)[:, ::-1]        # above[:, b] = sum of bins >= b
+        below = np.cumsum(c, axis=1)                          # below[:, b] = sum of bins <= b
+        self.tp, self.fp = above[1, 1:].copy(), above[0, 1:].copy()
+        self.fn, self.tn = below[1, :-1].copy(), below[0, :-1].copy()
+        self.pixels = int(c.sum())
+
+    def __len__(self):
+        return self.thresholds.size
+
+    @property
+    def iou(self):
+        return _ratios(self.tp, self.tp + self.fp + self.fn)
+
+    @property
+    def precision(self):
+        return _ratios(self.tp, self.tp + self.fp)
+
+    @property
+    def recall(self):
+        return _ratios(self.tp, self.tp + self.fn)
+
+    @property
+    def f1(self):
+        return _ratios(2 * self.tp, 2 * self.tp + self.fp + self.fn)
+
+    dice = f1
+
+    @property
+    def pixel_accuracy(self):
+        return _ratios(self.tp + self.tn, self.tp + self.fp + self.fn + self.tn)
+
+    METRICS = ("iou", "f1", "dice", "precision", "recall", "pixel_accuracy")
+
+    def best(self, metric="f1"):
+        """(threshold as a probability, value, index) of the threshold at which `metric` is largest.  Ties go to the
+        threshold nearest 0.5 in probability, then to the lower one."""
+        if metric not in self.METRICS:
+            raise ValueError(f"metric={metric!r}: one of {self.METRICS}")
+        v = getattr(self, metric)
+        tied = np.flatnonzero(v == v.max())
+        j = int(min(tied, key=lambda i: (abs(self.probabilities[i] - 0.5), self.probabilities[i])))
+        return float(self.probabilities[j]), float(v[j]), j
+
+    def index(self, threshold):
+        """Position of `threshold` in the list: a probability of `probabilities`, or a value of `thresholds`; equal
+        when both round to the same fp32 value, which is what the scores were compared with."""
+        for arr in (self.probabilities, self.thresholds):
+            hit = np.flatnonzero(arr.astype(np.float32) == np.float32(threshold))
+            if hit.size:
+                return int(hit[0])
+        raise KeyError(f"threshold {threshold!r} is not in the sweep")
+
+    def at(self, threshold):
+        """What SegMetrics.as_dict reports from the pooled counts, at one threshold of the list."""
+        j = self.index(threshold)
+        out = {"threshold": float(self.probabilities[j])}
+        for k in ("iou", "precision", "recall", "f1", "pixel_accuracy"):
+            out[k] = float(getattr(self, k)[j])
+        for k in ("tp", "fp", "fn", "tn"):
+            out[k] = int(getattr(self, k)[j])
+        out["pixels"] = self.pixels
+        return out
+
+    def __repr__(self):
+        p, v, _ = self.best("f1")
+        return f"ThresholdSweep({len(self)} thresholds, {self.domain}, pixels={self.pixels}, best f1={v:.6f} at {p:.4f})"
+
+
+def sweep_thresholds(thresholds, domain="probability"):
+    """The float32 array unet_score_sweep_accumulate compares with: the thresholds themselves, or (domain "logit") the
+    logit of each probability as model._logit forms it, rounded to fp32 - what the existing metrics pass compares a
+    logit with."""
+    t = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    if not 1 <= t.size <= SWEEP_MAX:
+        raise ValueError(f"a sweep takes 1 .. {SWEEP_MAX} thresholds, got {t.size}")
+    if domain == "logit":
+        from .model import _logit
+        t = np.array([_logit(p) for p in t], dtype=np.float64)
+    elif domain != "probability":
+        raise ValueError(f"domain={domain!r}: one of {DOMAINS}")
+    return np.ascontiguousarray(t.astype(np.float32))
+
+
+def sweep_accumulate(lib, device_index, scores, targets, thresholds, counts, stream):
+    """Add one batch to the device counters `counts` (2 * (T + 1) int64 on the scores' device, zeroed by the caller).
+    scores: float32 device tensor in any domain; targets: float (positive iff != 0) or uint8 (positive iff non-zero)
+    tensor of the same number of elements; thresholds: T ascending float32 values in the scores' domain (numpy)."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    if targets.dtype == torch.uint8:
+        targets, u8 = targets.to(scores.device).contiguous(), 1
+    else:
+        targets, u8 = targets.to(scores.device, torch.float32).contiguous(), 0
+    if scores.dtype != torch.float32 or not scores.is_contiguous():
+        raise ValueError("scores must be a contiguous float32 tensor")
+    if scores.numel() != targets.numel():
+        raise ValueError("scores and targets differ in size")
+    t = np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1)
+    if counts.dtype != torch.int64 or counts.numel() != 2 * (t.size + 1) or counts.device != scores.device:
+        raise ValueError(f"counts must be {2 * (t.size + 1)} int64 on the scores' device")
+    rc = lib.unet_score_sweep_accumulate(int(device_index), C.c_void_p(scores.data_ptr()), C.c_void_p(targets.data_ptr()),
+                                         u8, scores.numel(), t.ctypes.data_as(C.POINTER(C.c_float)), int(t.size),
+                                         C.c_void_p(counts.data_ptr()), stream)
+    _lib.check(rc, "unet_score_sweep_accumulate")
+
+
+def sweep_batches(lib, device, frames, targets, batch, thresholds, domain, stream_fn, score_fn):
+    """Shared body of UNetHIP.sweep / UNetInt8.sweep / Ensemble.evaluate: score_fn(frames on the device) -> device
+    scores in `domain`, counted batch by batch into one set of counters; 2 * (T + 1) integers are read at the end."""
+    import torch
+    frames, targets = torch.as_tensor(frames), torch.as_tensor(targets)
+    n = int(frames.shape[0])
+    if int(targets.shape[0]) != n:
+        raise ValueError("frames and targets differ in their number of images")
+    probs = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    t = sweep_thresholds(probs, domain)
+    step = n if not batch else int(batch)
+    counts = torch.zeros(2 * (t.size + 1), dtype=torch.int64, device=device)
+    for i in range(0, n, step):
+        scores = score_fn(frames[i:i + step].to(device).contiguous())
+        sweep_accumulate(lib, device.index, scores, targets[i:i + step], t, counts, stream_fn())
+    return ThresholdSweep(t, counts.cpu().numpy(), domain, probabilities=probs)
+
+
 def evaluate_batches(lib, device, frames, targets, batch, threshold, stream_fn, forward_fn):
     """Shared body of UNetHIP.evaluate / UNetInt8.evaluate: forward_fn(frames on the device) -> device logits, reduced
     batch by batch into one accumulator; one host read at the end."""

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .metrics import DEFAULT_THRESHOLDS
 from .state import DEFAULT_FEATURES, INPUT_MEAN, INPUT_STD
 
 
@@ -176,6 +177,18 @@ class UNetHIP:
         return metrics.evaluate_batches(self._lib, self.device, frames, targets, batch, threshold, self._stream,
                                         lambda f: self.run_u8(f, precision=precision) if f.dtype == torch.uint8
                                         else self.forward(f, precision=precision))
+
+    def sweep(self, frames, targets, thresholds=DEFAULT_THRESHOLDS, precision="fp32", batch=None):
+        """Confusion counts and metrics of one arithmetic tier at every threshold of `thresholds` (probabilities,
+        ascending; default metrics.DEFAULT_THRESHOLDS) in one forward of the set: frames, targets and batch as
+        evaluate takes them.  Each threshold is mapped to a logit as evaluate maps its one and compared with the
+        logits, which stay on the device (unet_score_sweep_accumulate); 2 * (T + 1) integers are read at the end.
+        Returns metrics.ThresholdSweep: `.best()` is the tier's own operating point, `.at(0.5)` what evaluate counts."""
+        from . import metrics
+        self._require_live()
+        return metrics.sweep_batches(self._lib, self.device, frames, targets, batch, thresholds, "logit", self._stream,
+                                     lambda f: self.run_u8(f, precision=precision) if f.dtype == torch.uint8
+                                     else self.forward(f, precision=precision))
 
     # ---- per-launch timing ------------------------------------------------------------
     def profile(self, on=True):

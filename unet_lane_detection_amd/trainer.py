@@ -300,6 +300,26 @@ class UNetTrainer:
         m = metrics.SegMetrics(host)
         return (m, kept) if return_logits else m
 
+    def sweep(self, batches, thresholds=metrics.DEFAULT_THRESHOLDS):
+        """Confusion counts and metrics at every threshold of `thresholds` (probabilities, ascending) in one eval-mode
+        forward over `batches` on the live parameters, as validate forwards them: each threshold is mapped to a logit as
+        validate maps its one and compared with the logits on the device (unet_score_sweep_accumulate); 2 * (T + 1)
+        integers are read at the end.  No state of the trainer moves.  Every rank sweeps its own batches (the counts
+        are not summed over a process group).  Raises like validate when the device reports a failed launch or an
+        activation beyond the fp16 range for the pass.  Returns metrics.ThresholdSweep."""
+        probs = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+        t = metrics.sweep_thresholds(probs, "logit")
+        counts = torch.zeros(2 * (t.size + 1), dtype=torch.int64, device=self.device)
+        for images, targets in batches:
+            logits = self.eval_logits(images)
+            metrics.sweep_accumulate(self._lib, self.device.index, logits, torch.as_tensor(targets), t, counts,
+                                     self._stream())
+        rc = self.device_error(current_stream_only=True)
+        if rc != 0:
+            raise _lib.UnetError(rc, "unet_device_error: the sweep is invalid, no metrics are returned",
+                                 self._lib.unet_last_error(self._h).decode())
+        return metrics.ThresholdSweep(t, counts.cpu().numpy(), "logit", probabilities=probs)
+
     def fit(self, train_batches, val_batches, epochs, scheduler=None, save_dir=None, patience=None, on_epoch=None):
         """The reference's train(config) loop: see loop.fit."""
         return loop.fit(self, train_batches, val_batches, epochs, scheduler=scheduler, save_dir=save_dir,
