@@ -866,6 +866,39 @@ int unet_score_sweep_accumulate(int device, const float* scores_dev, const void*
  * switch is there for tools/ensemble_sweep_timing.py.  Returns the previous setting. */
 int unet_set_sweep_combine(int on);
 
+/* ---- lane following on the device (csrc/follow_kernels.h) ------------------------------------------------------
+ * The two things the reference does with a frame besides the network: the HSV colour-threshold extractor the network
+ * is measured against (`extract_white_lanes`, README.md:206-227) and the scan-row lane centre the mask is reduced to
+ * (`LineFollower.find_lane_center`, README.md:4115-4126).  Both take a bare device ordinal, only enqueue on `stream`,
+ * consume their host arrays before they return, and refuse bad arguments with UNET_ERR_INVALID_ARG and a text for
+ * unet_op_last_error that names the call, before any device is touched.  The arithmetic is restated in
+ * tests/follow_model.py and reproduced bit for bit; parity of the HSV conversion with cv2's own is unpinned.
+ *
+ * unet_hsv_lanes_u8_batch: frames_dev (n, height, width, 3) uint8, dense -> mask_out_dev (n, height, width) uint8
+ * holding only 0 and 255, per frame and in one pass over the frames:
+ *     (H, S, V) = the project's 8-bit HSV of the pixel (augment.rgb_to_hsv: integers, round-half-up, H in [0, 180));
+ *                 with is_bgr channels 0 and 2 are exchanged first                            cvtColor(BGR2HSV)
+ *     t         = 255 iff lower[c] <= (H, S, V)[c] <= upper[c] for c = 0, 1, 2, else 0       inRange
+ *     mask      = dilate_ko(erode_ko(erode_kc(dilate_kc(t))))        morphologyEx CLOSE kc x kc, then OPEN ko x ko
+ * Every dilate (erode) is the maximum (minimum) over a k x k all-ones box anchored at its centre, defined on the
+ * whole image in turn; pixels outside the image never take part, at any of the four steps (OpenCV's default border
+ * for erode and dilate).  close_ksize and open_ksize are one of 1, 3, 5, 7; 1 is the identity.  lower_host and
+ * upper_host: 3 bytes each in host memory.  Any positive n, height, width with n * height * width < 2^31; no
+ * alignment requirement on either pointer. */
+int unet_hsv_lanes_u8_batch(int device, const uint8_t* frames_dev, int n, int height, int width, int is_bgr,
+                            const uint8_t* lower_host, const uint8_t* upper_host, int close_ksize, int open_ksize,
+                            uint8_t* mask_out_dev, void* stream);
+
+/* unet_lane_center_u8_batch: masks_dev (n, height, width) uint8, any byte values; rows_host: n_rows row indices in
+ * [0, height), 1 <= n_rows <= UNET_LANE_ROWS_MAX, passed to the kernel by value.  For frame i and row j
+ *     out_dev[(i * n_rows + j) * 2 + 0] = #{ x : mask[i, rows[j], x] > level }
+ *     out_dev[(i * n_rows + j) * 2 + 1] = the sum of those x
+ * 0 <= level <= 255; width <= 65535, so the sum fits 32 bits.  No atomics: one wave per (frame, row).  The
+ * reference's centre is sum / count (integer division) where count > 10 (follow.lane_centers). */
+#define UNET_LANE_ROWS_MAX 64
+int unet_lane_center_u8_batch(int device, const uint8_t* masks_dev, int n, int height, int width, const int* rows_host,
+                              int n_rows, int level, uint32_t* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

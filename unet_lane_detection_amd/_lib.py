@@ -225,6 +225,10 @@ SIGNATURES = {
     "unet_score_sweep_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_float),
                                               C.c_int, C.c_void_p, C.c_void_p]),
     "unet_set_sweep_combine": (C.c_int, [C.c_int]),
+    "unet_hsv_lanes_u8_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "unet_lane_center_u8_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
+                                            C.c_int, C.c_void_p, C.c_void_p]),
     "unet_op_conv3x3": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "unet_op_upconv2x2": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

@@ -12,6 +12,7 @@
 // Every source coordinate passes through reflect101() and the source index is clamped, so no parameter table can make
 // the kernel read outside the data set; the LDS extents depend on the blur radius only through r in {0,1,2,3}.
 #include "augment_kernels.h"
+#include "hsv8.h"
 
 #include "../../include/unet_hip.h"
 
@@ -57,24 +58,8 @@ __device__ __forceinline__ int lut_clip255(float v) { return (int)fminf(fmaxf(v,
 
 // RGB -> 8-bit HSV -> the three shifts -> RGB (augment.py: rgb_to_hsv, hue_lut, shift_lut, hsv_to_rgb)
 __device__ __forceinline__ void hue_saturation_value(int (&c)[3], float dh, float ds, float dv) {
-  const int r = c[0], g = c[1], b = c[2];
-  int v = max(max(r, g), b);
-  const int diff = v - min(min(r, g), b);
-  int s = (int)((unsigned)(510 * diff + v) / (unsigned)max(2 * v, 1));
-  int h = 0;
-  if (diff != 0) {
-    int num, off;
-    if (v == r) {
-      num = g - b, off = 0;
-    } else if (v == g) {
-      num = b - r, off = 60;
-    } else {
-      num = r - g, off = 120;
-    }
-    h = off - 30 + (int)((unsigned)(60 * (num + diff) + diff) / (unsigned)(2 * diff));
-    if (h < 0) h += 180;
-    if (h >= 180) h -= 180;
-  }
+  int h, s, v;
+  rgb_to_hsv8(c[0], c[1], c[2], h, s, v);
   float t = (float)h + dh;
   const float k = floorf(t / 180.f);
   t = t - k * 180.f;
