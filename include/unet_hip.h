@@ -899,6 +899,47 @@ int unet_hsv_lanes_u8_batch(int device, const uint8_t* frames_dev, int n, int he
 int unet_lane_center_u8_batch(int device, const uint8_t* masks_dev, int n, int height, int width, const int* rows_host,
                               int n_rows, int level, uint32_t* out_dev, void* stream);
 
+/* ---- frame and output diagnostics on the device (csrc/diagnose_kernels.h) ---------------------------------------
+ * What the reference tells a user to look at first when "detection is poor": `diagnose_input_image`
+ * (README.md:4476-4496: pixel range, mean brightness - it warns below 50 and above 200 - and the variance of
+ * cv2.Laplacian(cvtColor(img, BGR2GRAY), CV_64F), warned about below 100) and `quick_test` (README.md:4615-4640: the
+ * output's range, its mean and the share of pixels above the threshold), as a few integer words per frame.  Both take
+ * a bare device ordinal, only enqueue on `stream`, and refuse bad arguments with UNET_ERR_INVALID_ARG and a text for
+ * unet_op_last_error that names the call, before any device is touched.  Every call overwrites its output records, so
+ * the caller clears nothing.  Everything summed is an integer: the records do not depend on the order of the
+ * reduction.  The arithmetic is restated in tests/diagnose_model.py and reproduced bit for bit.  Parity with cv2
+ * itself is unpinned: cv2 is not installed where this is tested and the reference ships no fixture.
+ *
+ * unet_frame_stats_u8_batch: frames_dev holds n frames of `height` rows of row_stride bytes each, row_stride >=
+ * 3 * width, 0 = dense; the first 3 * width bytes of a row are pixels, the rest is padding that is never counted and
+ * never read as pixels (a sensor_msgs/Image with its `step`).  The last row may end with its pixels.  out_dev: n
+ * records of eight unsigned 64-bit words, 8-byte aligned:
+ *     [0], [1], [2]   minimum, maximum and sum over all 3 * width * height pixel bytes   img.min(), img.max(), img.mean() * size
+ *     [3]             S1 = sum of L over all pixels, two's complement
+ *     [4]             S2 = sum of L * L
+ *     [5] .. [7]      0
+ *     Y      = (3735 B + 19235 G + 9798 R + 16384) >> 15      OpenCV 4's 8-bit BGR2GRAY; with is_bgr channel 0 is B, else R
+ *     L(x,y) = Y(x-1,y) + Y(x+1,y) + Y(x,y-1) + Y(x,y+1) - 4 Y(x,y)                      cv2.Laplacian, ksize = 1
+ * with neighbours outside the image taken by reflect-101 (index -1 is 1, index w is w - 2), and the pixel itself
+ * where that dimension is 1: cv2's default border.  With N = width * height the host forms, from exact integers and
+ * with one rounding to double each,
+ *     mean = [2] / (3 N)          sharpness = (N S2 - S1^2) / N^2        the variance of L
+ * Any positive n, height, width with n * height * width < 2^31; no alignment requirement on frames_dev. */
+int unet_frame_stats_u8_batch(int device, const uint8_t* frames_dev, int n, int height, int width, int row_stride,
+                              int is_bgr, unsigned long long* out_dev, void* stream);
+
+/* unet_prob_stats_f32_batch: scores_dev (n, numel_per_frame) fp32 probabilities, as every tier's head writes them (no
+ * exponential is evaluated here).  out_dev: n records of four unsigned 64-bit words, 8-byte aligned:
+ *     [0]   low 32 bits: the fp32 bits of the minimum over the non-NaN values; high 32 bits: those of the maximum.
+ *           -0.0 orders below +0.0; a frame of NaNs only gives +inf and -inf
+ *     [1]   #{ s > threshold }: equal is not above and a NaN is above nothing, as in unet_score_sweep_accumulate
+ *     [2]   the sum of floor(clamp(s, 0, 1) * 2^32); a NaN adds 0.  The product is exact in fp32, so the sum is an
+ *           exact integer and [2] / 2^32 / numel_per_frame is the mean probability to within 2^-32, absolute
+ *     [3]   the number of NaNs
+ * 0 < numel_per_frame < 2^31; threshold is not a NaN. */
+int unet_prob_stats_f32_batch(int device, const float* scores_dev, int n, size_t numel_per_frame, float threshold,
+                              unsigned long long* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

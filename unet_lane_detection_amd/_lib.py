@@ -229,6 +229,9 @@ SIGNATURES = {
                                           C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "unet_lane_center_u8_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
                                             C.c_int, C.c_void_p, C.c_void_p]),
+    "unet_frame_stats_u8_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_void_p]),
+    "unet_prob_stats_f32_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
     "unet_op_conv3x3": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "unet_op_upconv2x2": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

@@ -138,10 +138,15 @@ class LaneFollowPipeline:
     source "unet": LanePipelineGPU's steps up to the resized mask (warp + resize, network, threshold, resize back),
     then the centre kernel; `process(msg, return_mask=True)` also returns the mono8 message LanePipelineGPU.process
     publishes, byte for byte.  source "hsv": the warp at full warp size, the extractor, the centre - the reference's
-    "IPM only" path; `model` may then be None (`device=` picks the GPU)."""
+    "IPM only" path; `model` may then be None (`device=` picks the GPU).
+
+    diagnose=True: the message's rows, already on the device for the warp, are also measured there
+    (diagnose.frame_records with the message's `step`; no second upload), and `process` returns (result,
+    diagnose.FrameStats) - brightness and sharpness of the camera frame beside the centres.  The centres, the mask
+    and every launch of the plain path are the same with it on or off."""
 
     def __init__(self, model, source="unet", extractor=None, scan_rows=None, level=127, min_pixels=10, device=None,
-                 **pipeline_kwargs):
+                 diagnose=False, **pipeline_kwargs):
         from .ros_bridge import REF_DST_POINTS, REF_SRC_POINTS, REF_WARP_SIZE, CameraStage, LanePipelineGPU, \
             get_perspective_transform
         if source not in ("unet", "hsv"):
@@ -149,6 +154,8 @@ class LaneFollowPipeline:
         self.source = source
         self.scan_rows = None if scan_rows is None else [int(r) for r in scan_rows]
         self.level, self.min_pixels = int(level), int(min_pixels)
+        self.diagnose = bool(diagnose)
+        self._frame_records = None   # diagnose: the record of the message in flight, on the device
         if source == "unet":
             if model is None:
                 raise ValueError("source \"unet\" needs a model")
@@ -168,6 +175,10 @@ class LaneFollowPipeline:
         """the message's bytes -> (1, out_h, out_w, 3) RGB on the device, as LanePipelineGPU does it"""
         from .ros_bridge import LanePipelineGPU
         rows = LanePipelineGPU.msg_to_device(self, msg)
+        if self.diagnose:
+            from .diagnose import frame_records
+            self._frame_records = frame_records(rows.view(-1), 1, msg.height, msg.width, msg.step,
+                                                msg.encoding == "bgr8")
         frame = torch.empty((1, out_size[1], out_size[0], 3), dtype=torch.uint8, device=self.stage.device)
         minv = np.ascontiguousarray(np.linalg.inv(self.matrix))
         rc = self.stage._lib.unet_ipm_prestage_u8(self.stage.device.index, _ptr(rows), msg.height, msg.width, msg.step,
@@ -189,7 +200,17 @@ class LaneFollowPipeline:
         return self.stage.resize(mask[0], self.warp_size)
 
     def process(self, msg, return_mask=False):
-        """One callback: the centres of the scan rows; with return_mask also the mono8 ImageMsg of the mask."""
+        """One callback: the centres of the scan rows; with return_mask also the mono8 ImageMsg of the mask.  With
+        `diagnose` that result comes first of a pair, the message's diagnose.FrameStats second."""
+        result = self._process(msg, return_mask)
+        if not self.diagnose:
+            return result
+        from .diagnose import FRAME_WORDS, FrameStats
+        words = self._frame_records.cpu().numpy().view(np.uint64).reshape(1, FRAME_WORDS)
+        self._frame_records = None
+        return result, FrameStats(words, msg.height, msg.width)
+
+    def _process(self, msg, return_mask):
         from .ros_bridge import ImageMsg
         mask = self.mask_on_device(msg)
         centres = lane_centers(mask, self.scan_rows, self.level, self.min_pixels)[0]

@@ -41,12 +41,16 @@ def _ptr(t):
 
 
 class FramePipeline:
-    """BGR frames -> (overlay, mask) through a `UNetHIP` (on the tier `precision`) or a `UNetInt8`."""
+    """BGR frames -> (overlay, mask) through a `UNetHIP` (on the tier `precision`) or a `UNetInt8`.
+
+    diagnose=True: every chunk is also measured where it already is, before the resize
+    (diagnose.frame_records: pixel range, brightness, Laplacian sharpness per frame), and `process` and `run` hand out
+    ((overlay, mask), diagnose.FrameStats) instead of (overlay, mask).  Overlay and mask are the same either way."""
 
     SLOTS = 3   # chunk k computes while k+1 is uploaded and k-1 is downloaded
 
     def __init__(self, model, threshold=0.5, input_size=(224, 224), precision="f16x3", lut=None, alpha=0.7, beta=0.3,
-                 gamma=0.0):
+                 gamma=0.0, diagnose=False):
         """input_size: (width, height) of the network's input; lut: (256, 3) uint8 in the frames' channel order
         (default `jet_table()`); alpha, beta, gamma: cv2.addWeighted's."""
         if not torch.cuda.is_available():
@@ -65,6 +69,7 @@ class FramePipeline:
         self.lut = lut
         self.alpha, self.beta, self.gamma = float(alpha), float(beta), float(gamma)
         self._streams = None
+        self.diagnose = bool(diagnose)
 
     # ---- the three stages, each on torch's current stream -----------------------------------------------------
     def _stream(self):
@@ -110,19 +115,35 @@ class FramePipeline:
     def _launch(self, frames, overlay, mask):
         self._overlay(frames, self._network(self._resize(frames)), overlay, mask)
 
+    def _measure(self, frames):
+        """diagnose: the chunk's records, enqueued on the current stream and left on the device"""
+        from .diagnose import frame_records
+        n, h, w, _ = frames.shape
+        return frame_records(frames, n, h, w, 0, True)
+
+    @staticmethod
+    def _frame_stats(records, shape):
+        from .diagnose import FRAME_WORDS, FrameStats
+        words = records.cpu().numpy().view(np.uint64).reshape(shape[0], FRAME_WORDS)
+        return FrameStats(words, shape[1], shape[2])
+
     def process(self, frames_bgr):
         """(N,H,W,3) uint8 BGR, numpy or torch, host or device -> (overlay (N,H,W,3), mask (N,H,W)) device tensors;
-        `mask` is what the reference's `predict` returns for each frame."""
+        `mask` is what the reference's `predict` returns for each frame.  With `diagnose`: ((overlay, mask),
+        FrameStats of the chunk)."""
         frames = torch.as_tensor(frames_bgr)
         if frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
             raise ValueError("frames must be (N,H,W,3) uint8")
         frames = frames.to(self.device).contiguous()
         overlay = torch.empty_like(frames)
         mask = torch.empty(frames.shape[:3], dtype=torch.uint8, device=self.device)
+        records = self._measure(frames) if self.diagnose else None
         self._launch(frames, overlay, mask)
         if not self._verify():
             self._launch(frames, overlay, mask)
             self._verify()
+        if self.diagnose:
+            return (overlay, mask), self._frame_stats(records, frames.shape)
         return overlay, mask
 
     # ---- streamed chunks ---------------------------------------------------------------------------------------
@@ -134,7 +155,7 @@ class FramePipeline:
         staging buffers and three streams (copy in, compute, copy out) tied by events: chunk
         k+1 is uploaded and chunk k-1 is downloaded while chunk k computes, and the host's own copies (into and out of
         the staging buffers) are done in that time too: the device's verdict on chunk k is awaited after them.  No
-        thread and no process is created."""
+        thread and no process is created.  With `diagnose` every item is ((overlay, mask), FrameStats of the chunk)."""
         if self._streams is None:
             self._streams = tuple(torch.cuda.Stream(self.device) for _ in range(3))
         s_in, s_run, s_out = self._streams
@@ -165,6 +186,8 @@ class FramePipeline:
             px, shape = s["px"], s["shape"]
             with torch.cuda.stream(s_run):
                 s_run.wait_event(s["up"])
+                if self.diagnose:
+                    s["rec"] = self._measure(s["dev_in"][:px * 3].view(shape))
                 self._launch(s["dev_in"][:px * 3].view(shape), s["dev_out"][:px * 3].view(shape),
                              s["dev_out"][px * 3:px * 4].view(shape[:3]))
                 done = s_run.record_event()
@@ -189,7 +212,10 @@ class FramePipeline:
             px, shape = s["px"], s["shape"]
             s["down"].synchronize()
             host = s.pop("pin_out").numpy()
-            return host[:px * 3].reshape(shape), host[px * 3:].reshape(shape[:3])
+            result = host[:px * 3].reshape(shape), host[px * 3:].reshape(shape[:3])
+            if self.diagnose:   # the records were complete before the chunk's download began
+                return result, self._frame_stats(s.pop("rec"), shape)
+            return result
 
         # per chunk: launch it, and while the device computes do the host's share - hand out the chunk before, stage
         # and upload the chunk after - and only then wait for the device's verdict on it
@@ -238,7 +264,8 @@ def predict_video(pipeline, read_frames, write_frame, chunk=64):
 
     t0 = time.perf_counter()
     count = 0
-    for overlay, _mask in pipeline.run(chunks()):
+    for item in pipeline.run(chunks()):
+        overlay = item[0][0] if getattr(pipeline, "diagnose", False) else item[0]
         for frame in overlay:
             write_frame(frame)
             count += 1
