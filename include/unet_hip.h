@@ -899,6 +899,64 @@ int unet_hsv_lanes_u8_batch(int device, const uint8_t* frames_dev, int n, int he
 int unet_lane_center_u8_batch(int device, const uint8_t* masks_dev, int n, int height, int width, const int* rows_host,
                               int n_rows, int level, uint32_t* out_dev, void* stream);
 
+/* ---- lane fit on the device (csrc/lanefit_kernels.h) ------------------------------------------------------------
+ * What the reference's bird's-eye warp is there for (README.md:3692: the IPM is in the node "to make the lane-line
+ * fit that follows easy") and its roadmap still lists (README.md:5138-5148: lane-line fit, curvature output,
+ * confidence output): the classic sliding-window search on the warped mask, reduced on the device to the moment sums
+ * a least-squares x = a y^2 + b y + c needs.  The host solves the 3 x 3 normal equations from those exact integers
+ * (unet_lane_detection_amd/lanefit.py).  The reference has no such code, so there is nothing outside to be equal to:
+ * the arithmetic below is restated in tests/lanefit_model.py and reproduced bit for bit, and parity with any outside
+ * implementation (cv2 / numpy tutorials of the same search) is unpinned.  Everything the device sums is an integer:
+ * the records do not depend on the order of the reduction.
+ *
+ * unet_lane_fit_u8_batch: masks_dev (n, height, width) uint8, any byte values; a pixel is ON iff its byte is > level.
+ * out_dev: n x 2 records of UNET_LANE_FIT_WORDS unsigned 64-bit words, 8-byte aligned; lane 0 is the left marking,
+ * lane 1 the right one.  Every call overwrites all 16 words of every record.  A bare device ordinal; the call only
+ * enqueues on `stream`; bad arguments are refused with UNET_ERR_INVALID_ARG and a text for unet_op_last_error that
+ * names the call, before any device is touched; no alignment requirement on masks_dev.
+ *
+ * Window mode (prior_dev == NULL), per frame, all in integers:
+ *     hist[x]  = #{ y in [height / 2, height) : mask[y, x] ON }
+ *     mid      = width / 2; the left lane's range is [0, mid), the right lane's [mid, width)
+ *     a lane whose range is empty or whose histogram maximum is 0 is ABSENT: flags, base, hit, tried and last centre
+ *                are 0, the sums are 0, minimum y is `height`, maximum y is 0
+ *     base     = the first column of the range at which the maximum is attained
+ *     wh       = height / n_windows; window i (0 at the bottom) is rows [height - (i + 1) wh, height - i wh); rows
+ *                above the top window belong to no window
+ *     c = base; for i = 0 .. n_windows - 1:
+ *         the window's columns are [max(c - margin, 0), min(c + margin, width))      half-open: x == c + margin is outside
+ *         every ON pixel in it joins the lane's sums
+ *         if the window's count is > min_pixels (equal does not recentre): c = (sum of its x) / count, hit += 1
+ *     the two lanes' windows may overlap; such a pixel counts for both.
+ * Prior mode (prior_dev: (n, 2, height) int32 on the device): no histogram, no windows.  A row y whose prior[y] is
+ * negative is not searched; otherwise the ON pixels with prior[y] - margin <= x < prior[y] + margin and 0 <= x < width
+ * join the sums.  The bounds are formed in 64 bits: any int32 prior is safe, INT_MAX included.  tried = the rows with
+ * a non-negative prior, hit = those of them that contributed at least one pixel.
+ *
+ * Record words:
+ *     [0]        flags; bit 0: the lane is present (window mode: a base was found; prior mode: tried > 0)
+ *     [1]        base (0 in prior mode)
+ *     [2], [3]   hit, tried (window mode: tried = n_windows, 0 for an absent lane)
+ *     [4]        the last c (0 in prior mode)
+ *     [5 + k]    S_k = sum of y^k over the lane's pixels, k = 0 .. 4
+ *     [10 + k]   T_k = sum of x y^k, k = 0 .. 2
+ *     [13], [14] minimum and maximum y of those pixels (`height` and 0 if there are none)
+ *     [15]       0
+ * The host solves [[S4,S3,S2],[S3,S2,S1],[S2,S1,S0]] (a,b,c) = (T2,T1,T0).
+ *
+ * Domain (anything else is refused): masks_dev and out_dev not null (prior_dev may be); n >= 1; 1 <= height <= 2048;
+ * 1 <= width <= 8192; n * height * width < 2^31; 0 <= level <= 255; 1 <= n_windows <= min(height,
+ * UNET_LANE_FIT_WINDOWS_MAX); 1 <= margin <= 512; min_pixels >= 0.
+ * The bounds on height and margin keep every sum inside 64 bits.  A lane takes at most 2 margin <= 1024 pixels of a
+ * row, so the largest sum is S_4 <= 1024 sum_{y < 2048} y^4 < 1024 * 2048^5 / 5 = 2^65 / 5 = 0.4 * 2^64 (exactly
+ * 7 369 693 362 260 017 152 for 2048 rows, against 2^64 = 18 446 744 073 709 551 616), and
+ * T_2 <= 1024 * 8191 * sum_{y < 2048} y^2 < 2^55. */
+#define UNET_LANE_FIT_WORDS 16
+#define UNET_LANE_FIT_WINDOWS_MAX 64
+int unet_lane_fit_u8_batch(int device, const uint8_t* masks_dev, int n, int height, int width, int level,
+                           int n_windows, int margin, int min_pixels, const int32_t* prior_dev,
+                           unsigned long long* out_dev, void* stream);
+
 /* ---- frame and output diagnostics on the device (csrc/diagnose_kernels.h) ---------------------------------------
  * What the reference tells a user to look at first when "detection is poor": `diagnose_input_image`
  * (README.md:4476-4496: pixel range, mean brightness - it warns below 50 and above 200 - and the variance of

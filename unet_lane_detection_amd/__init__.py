@@ -12,6 +12,9 @@ Public surface:
                                mask statistics for sparse lanes (imbalance.py)
   FramePipeline, predict_video, jet_table
                                the reference's video mode: batched resize, mask overlay, streamed chunks (video.py)
+  FitConfig, LaneFits, LaneTracker
+                               the bird's-eye lane fit on the device: sliding windows, quadratic fit, curvature
+                               (lanefit.py; follow.py and diagnose.py are imported as submodules the same way)
   seeded_state_dict, ...       reproducible weights / synthetic inputs
 """
 from .state import (DEFAULT_FEATURES, INPUT_MEAN, INPUT_STD, num_parameters, seeded_state_dict,  # noqa: F401
@@ -40,6 +43,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch.cuda o
     if name in ("ThresholdSweep", "DEFAULT_THRESHOLDS"):
         from . import metrics
         return getattr(metrics, name)
+    if name in ("FitConfig", "LaneFits", "LaneTracker"):
+        from . import lanefit
+        return getattr(lanefit, name)
     if name == "Ensemble":
         from .ensemble import Ensemble
         return Ensemble

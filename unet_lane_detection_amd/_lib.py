@@ -229,6 +229,8 @@ SIGNATURES = {
                                           C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "unet_lane_center_u8_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
                                             C.c_int, C.c_void_p, C.c_void_p]),
+    "unet_lane_fit_u8_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "unet_frame_stats_u8_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.c_void_p]),
     "unet_prob_stats_f32_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),

@@ -143,10 +143,15 @@ class LaneFollowPipeline:
     diagnose=True: the message's rows, already on the device for the warp, are also measured there
     (diagnose.frame_records with the message's `step`; no second upload), and `process` returns (result,
     diagnose.FrameStats) - brightness and sharpness of the camera frame beside the centres.  The centres, the mask
-    and every launch of the plain path are the same with it on or off."""
+    and every launch of the plain path are the same with it on or off.
+
+    fit=lanefit.FitConfig(...): the mask the centres come from is also fitted where it lies (lanefit.LaneTracker: a
+    window search, then the prior mode around the last fits), and `process` returns (result, lanefit.LaneFits) - both
+    lanes' curves, heading, curvature and confidence beside the centres; 256 more bytes leave the device.  With
+    `diagnose` that pair comes first of the outer pair.  fit=None: every launch and every return value as without it."""
 
     def __init__(self, model, source="unet", extractor=None, scan_rows=None, level=127, min_pixels=10, device=None,
-                 diagnose=False, **pipeline_kwargs):
+                 diagnose=False, fit=None, **pipeline_kwargs):
         from .ros_bridge import REF_DST_POINTS, REF_SRC_POINTS, REF_WARP_SIZE, CameraStage, LanePipelineGPU, \
             get_perspective_transform
         if source not in ("unet", "hsv"):
@@ -156,6 +161,11 @@ class LaneFollowPipeline:
         self.level, self.min_pixels = int(level), int(min_pixels)
         self.diagnose = bool(diagnose)
         self._frame_records = None   # diagnose: the record of the message in flight, on the device
+        self.fit = fit
+        self.tracker = None
+        if fit is not None:
+            from .lanefit import LaneTracker
+            self.tracker = LaneTracker(fit)
         if source == "unet":
             if model is None:
                 raise ValueError("source \"unet\" needs a model")
@@ -201,7 +211,8 @@ class LaneFollowPipeline:
 
     def process(self, msg, return_mask=False):
         """One callback: the centres of the scan rows; with return_mask also the mono8 ImageMsg of the mask.  With
-        `diagnose` that result comes first of a pair, the message's diagnose.FrameStats second."""
+        `fit` that result comes first of a pair, the frame's lanefit.LaneFits second.  With `diagnose` all of that
+        comes first of a pair, the message's diagnose.FrameStats second."""
         result = self._process(msg, return_mask)
         if not self.diagnose:
             return result
@@ -214,8 +225,10 @@ class LaneFollowPipeline:
         from .ros_bridge import ImageMsg
         mask = self.mask_on_device(msg)
         centres = lane_centers(mask, self.scan_rows, self.level, self.min_pixels)[0]
-        if not return_mask:
-            return centres
-        host = mask.cpu().numpy()
-        return centres, ImageMsg(height=host.shape[0], width=host.shape[1], encoding="mono8", data=host.tobytes(),
-                                 step=host.shape[1], is_bigendian=0, header=msg.header)
+        fits = self.tracker.update(mask) if self.tracker is not None else None
+        result = centres
+        if return_mask:
+            host = mask.cpu().numpy()
+            result = centres, ImageMsg(height=host.shape[0], width=host.shape[1], encoding="mono8", data=host.tobytes(),
+                                       step=host.shape[1], is_bigendian=0, header=msg.header)
+        return result if self.tracker is None else (result, fits)
