@@ -957,6 +957,74 @@ int unet_lane_fit_u8_batch(int device, const uint8_t* masks_dev, int n, int heig
                            int n_windows, int margin, int min_pixels, const int32_t* prior_dev,
                            unsigned long long* out_dev, void* stream);
 
+/* ---- lane instances on the device (csrc/label_kernels.h) --------------------------------------------------------
+ * Which pixels of a mask belong together: connected-component labelling of a mask batch, per-component integer
+ * statistics and a component filter that writes a cleaned mask for the kernels above.  The reference lists
+ * "multi-lane detection", "confidence output" and "instance segmentation" on its roadmap (README.md:5138-5153) and
+ * names "lots of noise pixels" as a failure it can only answer by retraining or a higher threshold (README.md:4465,
+ * 4601, 3902); it has no such code.  The arithmetic below is restated in tests/label_model.py and reproduced bit for
+ * bit; the numbering is that of scipy.ndimage.label, which the model is held to.  Parity with cv2's label numbering
+ * is unpinned: cv2 is not installed where this is tested.  Everything the device sums is an integer, so the records
+ * do not depend on the order anything ran in.  All three take a bare device ordinal where they take one, only enqueue
+ * on `stream`, refuse bad arguments with UNET_ERR_INVALID_ARG and a text for unet_op_last_error that names the call,
+ * before any device is touched, have no alignment requirement on uint8 pointers, and overwrite all of their outputs.
+ *
+ * unet_label_work_bytes: a pure host function, the bytes of caller-owned device workspace unet_label_u8_batch needs
+ * for (n, height, width); 0 for arguments outside that call's domain.  Nothing is allocated by either call.
+ *
+ * unet_label_u8_batch: masks_dev (n, height, width) uint8, any byte values; a pixel is ON iff its byte is > level.
+ * connectivity 4: pixels that share an edge connect; 8: those that share a corner do too (cv2's default).
+ *   labels_dev   (n, height, width) int32: 0 for an OFF pixel, else the id 1 .. K of its component.  Ids are in
+ *                increasing order of the raster index y * width + x of the component's first pixel, per frame: a
+ *                canonical numbering.  Components beyond max_components are still labelled; only their records are
+ *                missing.
+ *   header_dev   n records of four unsigned 64-bit words: [0] K, the true count even when it exceeds max_components;
+ *                [1] the number of ON pixels; [2] min(K, max_components); [3] 0.
+ *   records_dev  n x max_components records of UNET_LABEL_WORDS unsigned 64-bit words, 8-byte aligned; record c - 1
+ *                of a frame describes component c:
+ *     [0]        the area (= S_0)
+ *     [1] .. [4] x_min, x_max, y_min, y_max
+ *     [5]        T_0 = sum of x
+ *     [6]        S_1 = sum of y
+ *     [7] .. [9] S_2, S_3, S_4, S_k = sum of y^k
+ *     [10], [11] T_1 = sum of x y, T_2 = sum of x y^2
+ *     [12]       the raster index of the first pixel
+ *     [13]       border flags: bit 0 touches row 0, bit 1 row height - 1, bit 2 column 0, bit 3 column width - 1
+ *     [14], [15] 0
+ *                Records at or beyond min(K, max_components) are all-zero.  S_0 .. S_4 and T_0 .. T_2 are the sums
+ *                lanefit.solve takes: every component has a curve x = a y^2 + b y + c.
+ *   work_dev     work_bytes >= unet_label_work_bytes(n, height, width) bytes, 4-byte aligned; contents are scratch.
+ * Domain (anything else is refused): pointers not null; n >= 1; 1 <= height, width <= 2048; n * height * width <
+ * 2^31; 0 <= level <= 255; connectivity 4 or 8; 1 <= max_components <= 65536; work_bytes as above; labels_dev 4-byte
+ * aligned, header_dev and records_dev 8-byte aligned.
+ * The bounds on height and width keep every sum inside 64 bits.  The largest is S_4 of a full 2048 x 2048 frame,
+ * 2048 sum_{y < 2048} y^4 = 14 739 386 724 520 034 304 < 2^64 = 18 446 744 073 709 551 616 (the lane fit above has
+ * 1024 sum y^4 = 7 369 693 362 260 017 152), and T_2 <= sum_{x < 2048} x * sum_{y < 2048} y^2 < 2^21 * 2^33 = 2^54.
+ *
+ * unet_keep_components_u8_batch: labels_dev, header_dev, records_dev and max_components as the call above left them.
+ *   keep_out_dev (n, max_components) uint8: entry c - 1 is 1 iff component c has a record, its area is >= min_area,
+ *                y_max - y_min + 1 >= min_height, x_max - x_min + 1 >= min_width and, if keep_largest > 0, fewer than
+ *                keep_largest components of that frame that pass those thresholds precede it in the order "larger
+ *                area first, lower id on equal area".  Else 0.
+ *   mask_out_dev (n, height, width) uint8: 255 where the pixel's component is kept, else 0.  A component without a
+ *                record (id > max_components) is never kept.  mask_out_dev may be the buffer the labels were
+ *                computed from; it must not overlap labels_dev.
+ * Domain: pointers not null; n, height, width, max_components as above; min_area, min_height, min_width,
+ * keep_largest >= 0; labels_dev 4-byte aligned, header_dev and records_dev 8-byte aligned (keep_out_dev and
+ * mask_out_dev: any).
+ * What a large max_components costs: the label call clears all n x max_components records on every call (8 MB a frame
+ * at 65536, spread over the whole grid), and with keep_largest > 0 a frame with more than 4096 recorded components
+ * has its records read 41 times by one workgroup. */
+#define UNET_LABEL_WORDS 16
+size_t unet_label_work_bytes(int n, int height, int width);
+int unet_label_u8_batch(int device, const uint8_t* masks_dev, int n, int height, int width, int level,
+                        int connectivity, int32_t* labels_dev, int max_components, unsigned long long* header_dev,
+                        unsigned long long* records_dev, void* work_dev, size_t work_bytes, void* stream);
+int unet_keep_components_u8_batch(int device, const int32_t* labels_dev, int n, int height, int width,
+                                  const unsigned long long* header_dev, const unsigned long long* records_dev,
+                                  int max_components, int min_area, int min_height, int min_width, int keep_largest,
+                                  uint8_t* keep_out_dev, uint8_t* mask_out_dev, void* stream);
+
 /* ---- frame and output diagnostics on the device (csrc/diagnose_kernels.h) ---------------------------------------
  * What the reference tells a user to look at first when "detection is poor": `diagnose_input_image`
  * (README.md:4476-4496: pixel range, mean brightness - it warns below 50 and above 200 - and the variance of

@@ -15,6 +15,9 @@ Public surface:
   FitConfig, LaneFits, LaneTracker
                                the bird's-eye lane fit on the device: sliding windows, quadratic fit, curvature
                                (lanefit.py; follow.py and diagnose.py are imported as submodules the same way)
+  CleanConfig, Components, LaneInstance
+                               lane instances on the device: connected components, statistics, clean-up
+                               (instances.py: label, clean, lane_instances)
   seeded_state_dict, ...       reproducible weights / synthetic inputs
 """
 from .state import (DEFAULT_FEATURES, INPUT_MEAN, INPUT_STD, num_parameters, seeded_state_dict,  # noqa: F401
@@ -46,6 +49,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch.cuda o
     if name in ("FitConfig", "LaneFits", "LaneTracker"):
         from . import lanefit
         return getattr(lanefit, name)
+    if name in ("CleanConfig", "Components", "LaneInstance"):
+        from . import instances
+        return getattr(instances, name)
     if name == "Ensemble":
         from .ensemble import Ensemble
         return Ensemble

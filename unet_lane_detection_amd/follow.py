@@ -148,10 +148,16 @@ class LaneFollowPipeline:
     fit=lanefit.FitConfig(...): the mask the centres come from is also fitted where it lies (lanefit.LaneTracker: a
     window search, then the prior mode around the last fits), and `process` returns (result, lanefit.LaneFits) - both
     lanes' curves, heading, curvature and confidence beside the centres; 256 more bytes leave the device.  With
-    `diagnose` that pair comes first of the outer pair.  fit=None: every launch and every return value as without it."""
+    `diagnose` that pair comes first of the outer pair.  fit=None: every launch and every return value as without it.
+
+    clean=instances.CleanConfig(...): the mask is labelled on the device and only the components the config keeps
+    (min_area, min_height, min_width, keep_largest) stay in it, before the scan-row centres, the fit and return_mask
+    see it: speckle no longer counts.  Return shapes are unchanged; `last_components` holds the frame's
+    instances.Components (128 bytes per recorded component and 32 per frame leave the device).  clean=None: every
+    launch and every return value as without it."""
 
     def __init__(self, model, source="unet", extractor=None, scan_rows=None, level=127, min_pixels=10, device=None,
-                 diagnose=False, fit=None, **pipeline_kwargs):
+                 diagnose=False, fit=None, clean=None, **pipeline_kwargs):
         from .ros_bridge import REF_DST_POINTS, REF_SRC_POINTS, REF_WARP_SIZE, CameraStage, LanePipelineGPU, \
             get_perspective_transform
         if source not in ("unet", "hsv"):
@@ -166,6 +172,8 @@ class LaneFollowPipeline:
         if fit is not None:
             from .lanefit import LaneTracker
             self.tracker = LaneTracker(fit)
+        self.clean = clean
+        self.last_components = None
         if source == "unet":
             if model is None:
                 raise ValueError("source \"unet\" needs a model")
@@ -224,6 +232,10 @@ class LaneFollowPipeline:
     def _process(self, msg, return_mask):
         from .ros_bridge import ImageMsg
         mask = self.mask_on_device(msg)
+        if self.clean is not None:
+            from .instances import clean
+            cleaned, self.last_components, _ = clean(mask, self.clean)
+            mask = cleaned[0]
         centres = lane_centers(mask, self.scan_rows, self.level, self.min_pixels)[0]
         fits = self.tracker.update(mask) if self.tracker is not None else None
         result = centres
