@@ -1025,6 +1025,84 @@ int unet_keep_components_u8_batch(int device, const int32_t* labels_dev, int n, 
                                   int max_components, int min_area, int min_height, int min_width, int keep_largest,
                                   uint8_t* keep_out_dev, uint8_t* mask_out_dev, void* stream);
 
+/* ---- lane view on the device (csrc/laneview_kernels.h) -----------------------------------------------------------
+ * The step that closes a sliding-window lane fit: the area between two fitted curves, the markings and the curves
+ * themselves, all of which live in the bird's-eye image, drawn where the camera looks and blended onto the camera
+ * frame.  The reference's own pictures of a result are such camera-view overlays (assets/demo/normal_unet.jpg), its
+ * debugging advice is `visualize_output` (README.md:4563-4593: overlay[binary > 0] = [0, 255, 0]; blended =
+ * cv2.addWeighted(img, 0.7, overlay, 0.3, 0)), and its roadmap lists "lane + drivable area" and an "end-to-end
+ * interface" (README.md:5150-5153); it has no code that goes back through the IPM.  One kernel goes, per camera
+ * pixel, forward through the perspective matrix, asks the curves and the mask what lies there, and blends.  The
+ * arithmetic below is restated in tests/laneview_model.py and reproduced bit for bit; the mask layer is
+ * cv2.warpPerspective(mask, inv(M), (width, height)) as oracle/camera_oracle.py restates it, thresholded, and parity
+ * with cv2 itself is unpinned.  A bare device ordinal; the call only enqueues on `stream`; bad arguments are refused
+ * with UNET_ERR_INVALID_ARG and a text for unet_op_last_error that names the call, before any device is touched; no
+ * alignment requirement on uint8 pointers; every call overwrites all of its outputs.
+ *
+ * frames_dev: n frames of `height` rows of `step` bytes, 3 interleaved channels, step >= 3 * width; the last row may
+ * end with its pixels.  The channel order is the caller's; colours are given in that order.  m: the perspective
+ * matrix camera -> bird's-eye, row-major, in host memory: the matrix unet_ipm_prestage_u8's minv is the inverse of,
+ * with the sign for which w below is positive on the ground (m and -m are one homography, but only one of them has
+ * the ground below the horizon; laneview.orient chooses it).
+ * masks_dev: (n, warp_h, warp_w) uint8 or NULL.  curves_dev: (n, k, UNET_LANE_VIEW_WORDS) signed 64-bit words on the
+ * device, or NULL with k = 0.  style: host memory, consumed before the call returns; NULL is the default style (0.7,
+ * 0.3, 0, both colours (0, 255, 0), thickness 4, both layers on).  view_out_dev: (n, height, width, 3) dense, or
+ * NULL.  layers_out_dev: (n, height, width), or NULL.  Not both NULL.
+ *
+ * Per camera pixel (x, y), with nothing contracted and every operation one IEEE double operation in this order:
+ *     w  = m6 x + m7 y + m8             a pixel with !(w > 0) is OUTSIDE: at or above the horizon, a NaN included
+ *     fx = (m0 x + m1 y + m2) * (32 / w), fy = (m3 x + m4 y + m5) * (32 / w)
+ *     fx, fy clamped to [-2^31, 2^31 - 1] (a NaN becomes -2^31); X = rint(fx), Y = rint(fy)      as the camera stage
+ *     INSIDE iff 0 <= X < 32 warp_w and 0 <= Y < 32 warp_h       (X, Y: bird's-eye coordinates in 1/32 pixel)
+ * Curve record i of a frame, i < k <= UNET_LANE_VIEW_MAX:
+ *     [0]        flags; bit 0: present, bit 1: fill the area up to record i + 1, bit 2: draw the curve
+ *     [1], [2]   y0 <= y1: the first and last row of the bird's-eye image the curve is valid on
+ *     [3] .. [5] A = rint(a 2^27), B = rint(b 2^32), C = rint(c 2^37) for x = a y^2 + b y + c in pixels, so that
+ *                A Y^2 + B Y + C is 2^32 times the curve's x in 1/32 pixel at the row Y / 32
+ *     [6]        the curve's colour, byte c = channel c
+ *     [7]        0
+ * The kernel cannot have checked a record, so it clamps before use: A into +-(2^30 - 1), B into +-(2^45 - 1), C into
+ * +-(2^57 - 1), y0 and y1 into [0, warp_h - 1].  An INSIDE pixel has 0 <= Y < 32 * 2048 = 2^16, so
+ *     |A Y^2 + B Y + C| < 2^30 2^32 + 2^45 2^16 + 2^57 = 2^62 + 2^61 + 2^57 < 2^63:
+ * no sum leaves 64 bits (7 061 468 290 635 333 631 at the extreme record against 2^63 = 9 223 372 036 854 775 808).
+ *     x32_i(Y) = (A Y^2 + B Y + C) >> 32                  an arithmetic shift: the floor, also below zero
+ *     curve i COVERS Y iff bit 0 is set and 32 y0 <= Y <= 32 y1 + 31
+ * The layer of a pixel, highest first; 0 where nothing hits or the pixel is not INSIDE:
+ *     3 + i   the lowest i with bit 2 set that covers Y and has |X - x32_i(Y)| <= 16 * thickness
+ *     2       masks_dev != NULL, the marking layer is on, and the one-channel bilinear sample of the frame's mask at
+ *             (X, Y) - integer pixel (X >> 5, Y >> 5), fractions X & 31 and Y & 31, taps outside the mask read 0,
+ *             (sum + 2^14) >> 15: the camera stage's - is > level
+ *     1       the area layer is on and there is an i with bit 1 set, i + 1 < k, records i and i + 1 both covering Y,
+ *             and x32_i(Y) <= X <= x32_{i+1}(Y).  Curves that cross leave those rows empty.
+ * layers_out_dev receives that number.  colour = the curve's, style->marking, style->area or, on layer 0, the frame's
+ * own pixel, and on every pixel, whatever its layer,
+ *     out[c] = clamp(rint(fl(fl(fl(frame[c] * alpha) + fl(colour[c] * beta)) + gamma)), 0, 255)
+ * with fl one fp32 rounding and rint half to even: the addWeighted of unet_overlay_u8_batch.
+ *
+ * Domain (anything else is refused): frames_dev and m not null; n >= 1; 1 <= height, width <= 4096; step >= 3 * width;
+ * n * height * step < 2^31; 1 <= warp_w <= 8192; 1 <= warp_h <= 2048; 0 <= level <= 255; 0 <= k <=
+ * UNET_LANE_VIEW_MAX and k == 0 iff curves_dev == NULL; curves_dev 8-byte aligned; all nine m finite; alpha, beta and
+ * gamma finite; 1 <= thickness <= 64 (bird's-eye pixels, measured along x); no unknown bit in style->layers; not
+ * both outputs NULL. */
+#define UNET_LANE_VIEW_WORDS 8
+#define UNET_LANE_VIEW_MAX 8
+#define UNET_LANE_VIEW_AREA 1u      /* unet_lane_view_style.layers: layer 1 is drawn */
+#define UNET_LANE_VIEW_MARKING 2u   /* layer 2 is drawn */
+typedef struct unet_lane_view_style {
+  float alpha, beta, gamma;
+  uint8_t area[3];      /* colour of layer 1 */
+  uint8_t marking[3];   /* colour of layer 2 */
+  uint8_t reserved[2];  /* ignored */
+  int thickness;
+  unsigned layers;      /* UNET_LANE_VIEW_AREA | UNET_LANE_VIEW_MARKING */
+} unet_lane_view_style;
+int unet_lane_view_u8_batch(int device, const uint8_t* frames_dev, int n, int height, int width, int step,
+                            const double m[9], int warp_w, int warp_h, const uint8_t* masks_dev, int level,
+                            const long long* curves_dev, int k, const unet_lane_view_style* style,
+                            uint8_t* view_out_dev, uint8_t* layers_out_dev, void* stream);
+/* sizeof(unet_lane_view_style), so a binding can check its layout against the library */
+size_t unet_lane_view_style_bytes(void);
+
 /* ---- frame and output diagnostics on the device (csrc/diagnose_kernels.h) ---------------------------------------
  * What the reference tells a user to look at first when "detection is poor": `diagnose_input_image`
  * (README.md:4476-4496: pixel range, mean brightness - it warns below 50 and above 200 - and the variance of

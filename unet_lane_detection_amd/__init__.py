@@ -18,6 +18,9 @@ Public surface:
   CleanConfig, Components, LaneInstance
                                lane instances on the device: connected components, statistics, clean-up
                                (instances.py: label, clean, lane_instances)
+  ViewConfig, lane_view, curve_table
+                               the lane view on the device: lane area, markings and curves drawn in the camera frame
+                               (laneview.py)
   seeded_state_dict, ...       reproducible weights / synthetic inputs
 """
 from .state import (DEFAULT_FEATURES, INPUT_MEAN, INPUT_STD, num_parameters, seeded_state_dict,  # noqa: F401
@@ -52,6 +55,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch.cuda o
     if name in ("CleanConfig", "Components", "LaneInstance"):
         from . import instances
         return getattr(instances, name)
+    if name in ("ViewConfig", "lane_view", "curve_table"):
+        from . import laneview
+        return getattr(laneview, name)
     if name == "Ensemble":
         from .ensemble import Ensemble
         return Ensemble

@@ -40,6 +40,20 @@ class LossConfig(C.Structure):
     ]
 
 
+class LaneViewStyle(C.Structure):
+    """unet_lane_view_style of include/unet_hip.h"""
+    _fields_ = [
+        ("alpha", C.c_float),
+        ("beta", C.c_float),
+        ("gamma", C.c_float),
+        ("area", C.c_uint8 * 3),
+        ("marking", C.c_uint8 * 3),
+        ("reserved", C.c_uint8 * 2),
+        ("thickness", C.c_int),
+        ("layers", C.c_uint),
+    ]
+
+
 STATUS = {0: "UNET_OK", 1: "UNET_ERR_INVALID_ARG", 2: "UNET_ERR_SHAPE", 3: "UNET_ERR_STATE", 4: "UNET_ERR_HIP",
           5: "UNET_ERR_NOMEM", 6: "UNET_ERR_UNKNOWN_PARAM", 7: "UNET_ERR_RANGE"}
 UNET_ERR_HIP = 4     # a HIP runtime call or a kernel-side check failed
@@ -237,6 +251,10 @@ SIGNATURES = {
     "unet_keep_components_u8_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p]),
+    "unet_lane_view_u8_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                          C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                          C.POINTER(LaneViewStyle), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "unet_lane_view_style_bytes": (C.c_size_t, []),
     "unet_frame_stats_u8_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.c_void_p]),
     "unet_prob_stats_f32_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "warp_sample.h"
+
 namespace unet {
 
 struct CameraArgs {
@@ -49,21 +51,7 @@ __device__ __forceinline__ void warp_pixel(const CameraArgs& a, int x, int y, in
   fx = fmin(fmax(fx, -2147483648.0), 2147483647.0);
   fy = fmin(fmax(fy, -2147483648.0), 2147483647.0);
   const long long X = (long long)rint(fx), Y = (long long)rint(fy);
-  const long long sx = X >> 5, sy = Y >> 5;
-  const int fa = (int)(X & 31), fb = (int)(Y & 31);
-  const int wgt[4] = {(32 - fb) * (32 - fa) * 32, (32 - fb) * fa * 32, fb * (32 - fa) * 32, fb * fa * 32};
-  int acc[3] = {0, 0, 0};
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const long long yy = sy + (t >> 1), xx = sx + (t & 1);
-    if (yy >= 0 && yy < a.height && xx >= 0 && xx < a.width) {
-      const uint8_t* p = a.img + (size_t)yy * a.step + (size_t)xx * 3;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) acc[c] += wgt[t] * (int)p[c];
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) v[c] = (acc[c] + (1 << 14)) >> 15;
+  warp_sample<3>(a.img, a.height, a.width, (size_t)a.step, X, Y, v);
 }
 
 __global__ __launch_bounds__(256) void ipm_prestage_kernel(const CameraArgs a) {

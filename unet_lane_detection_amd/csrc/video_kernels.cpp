@@ -110,33 +110,6 @@ __device__ __forceinline__ void sample(const uint8_t* __restrict__ img, const Re
   }
 }
 
-// byte j of a run held as dwords; j is a constant after unrolling
-__device__ __forceinline__ uint32_t byte_of(const uint32_t* w, int j) { return (w[j >> 2] >> (8 * (j & 3))) & 255u; }
-__device__ __forceinline__ void put_byte(uint32_t* w, int j, uint32_t v) { w[j >> 2] |= v << (8 * (j & 3)); }
-
-// 16 bytes at p as one access, or its first `bytes` (which may be <= 0) one by one
-__device__ __forceinline__ void load16(const uint8_t* __restrict__ p, bool vec, int bytes, uint32_t* w) {
-  if (vec) {
-    const uint4 v = *reinterpret_cast<const uint4*>(p);
-    w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-  } else {
-    w[0] = w[1] = w[2] = w[3] = 0u;
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-      if (j < bytes) put_byte(w, j, p[j]);
-  }
-}
-
-__device__ __forceinline__ void store16(uint8_t* __restrict__ p, bool vec, int bytes, const uint32_t* w) {
-  if (vec) {
-    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 16; ++j)
-      if (j < bytes) p[j] = (uint8_t)byte_of(w, j);
-  }
-}
-
 // a thread's place in the flat run of destination pixels, and the source image and rows that go with it
 template <int CN>
 struct Cursor {
@@ -244,13 +217,7 @@ __global__ __launch_bounds__(THREADS) void overlay_batch_kernel(const OverlayArg
         const float4 c = colour[m[0]];
         const float cc[3] = {c.x, c.y, c.z};
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          float v = (float)byte_of(in, 3 * i + k) * a.alpha;
-          v = v + cc[k];
-          v = v + a.gamma;
-          v = fminf(fmaxf(rintf(v), 0.f), 255.f);   // rintf: round half to even
-          put_byte(out, 3 * i + k, (uint32_t)(int)v);
-        }
+        for (int k = 0; k < 3; ++k) put_byte(out, 3 * i + k, blend_u8(byte_of(in, 3 * i + k), a.alpha, cc[k], a.gamma));
       }
     }
 #pragma unroll

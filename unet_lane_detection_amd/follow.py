@@ -154,10 +154,18 @@ class LaneFollowPipeline:
     (min_area, min_height, min_width, keep_largest) stay in it, before the scan-row centres, the fit and return_mask
     see it: speckle no longer counts.  Return shapes are unchanged; `last_components` holds the frame's
     instances.Components (128 bytes per recorded component and 32 per frame leave the device).  clean=None: every
-    launch and every return value as without it."""
+    launch and every return value as without it.
+
+    view=laneview.ViewConfig(...): after the centres, the fit and the clean-up, the message's rows (still on the
+    device), the pipeline's `matrix`, the mask and the curves go through laneview.lane_view: the lane area, the
+    markings and the curves drawn in the camera frame.  The curves are the tracker's fits if there is a `fit`,
+    otherwise the kept components of `clean`; with neither, only the mask layer is drawn.  `last_view` holds the
+    (1, height, width, 3) device tensor and `last_view_layers` the layer plane, as `last_components` holds the
+    components; `view_msg()` returns the view as an ImageMsg in the message's encoding.  Return shapes are unchanged.
+    view=None: every launch and every return value as without it."""
 
     def __init__(self, model, source="unet", extractor=None, scan_rows=None, level=127, min_pixels=10, device=None,
-                 diagnose=False, fit=None, clean=None, **pipeline_kwargs):
+                 diagnose=False, fit=None, clean=None, view=None, **pipeline_kwargs):
         from .ros_bridge import REF_DST_POINTS, REF_SRC_POINTS, REF_WARP_SIZE, CameraStage, LanePipelineGPU, \
             get_perspective_transform
         if source not in ("unet", "hsv"):
@@ -174,6 +182,9 @@ class LaneFollowPipeline:
             self.tracker = LaneTracker(fit)
         self.clean = clean
         self.last_components = None
+        self.view = view
+        self.last_view = self.last_view_layers = None
+        self._rows = self._view_msg = None   # view: the rows of the message in flight, and what view_msg() copies from it
         if source == "unet":
             if model is None:
                 raise ValueError("source \"unet\" needs a model")
@@ -193,6 +204,8 @@ class LaneFollowPipeline:
         """the message's bytes -> (1, out_h, out_w, 3) RGB on the device, as LanePipelineGPU does it"""
         from .ros_bridge import LanePipelineGPU
         rows = LanePipelineGPU.msg_to_device(self, msg)
+        if self.view is not None:
+            self._rows = rows
         if self.diagnose:
             from .diagnose import frame_records
             self._frame_records = frame_records(rows.view(-1), 1, msg.height, msg.width, msg.step,
@@ -217,6 +230,30 @@ class LaneFollowPipeline:
             return torch.zeros((self.warp_size[1], self.warp_size[0]), dtype=torch.uint8, device=self.stage.device)
         return self.stage.resize(mask[0], self.warp_size)
 
+    def _draw_view(self, msg, mask, fits, keep):
+        from .laneview import curve_table, lane_view
+        curves = None
+        if fits is not None:
+            curves = curve_table(fits, self.warp_size, self.view)
+        elif keep is not None:
+            from .instances import instances_of
+            m = self.last_components.recorded(0)
+            curves = curve_table(instances_of(self.last_components, keep[:, :m].cpu().numpy()), self.warp_size, self.view)
+        rows, self._rows = self._rows, None
+        self.last_view, self.last_view_layers = lane_view(rows, self.matrix, self.warp_size, mask, curves, self.view,
+                                                          step=msg.step, layers=True, width=msg.width)
+        self._view_msg = (msg.encoding, msg.header)
+
+    def view_msg(self):
+        """The last view as an ImageMsg in its message's encoding (height * width * 3 bytes leave the device); None
+        before the first callback with `view`."""
+        from .ros_bridge import ImageMsg
+        if self.last_view is None:
+            return None
+        host = self.last_view[0].cpu().numpy()
+        return ImageMsg(height=host.shape[0], width=host.shape[1], encoding=self._view_msg[0], data=host.tobytes(),
+                        step=host.shape[1] * 3, is_bigendian=0, header=self._view_msg[1])
+
     def process(self, msg, return_mask=False):
         """One callback: the centres of the scan rows; with return_mask also the mono8 ImageMsg of the mask.  With
         `fit` that result comes first of a pair, the frame's lanefit.LaneFits second.  With `diagnose` all of that
@@ -232,12 +269,15 @@ class LaneFollowPipeline:
     def _process(self, msg, return_mask):
         from .ros_bridge import ImageMsg
         mask = self.mask_on_device(msg)
+        keep = None
         if self.clean is not None:
             from .instances import clean
-            cleaned, self.last_components, _ = clean(mask, self.clean)
+            cleaned, self.last_components, keep = clean(mask, self.clean)
             mask = cleaned[0]
         centres = lane_centers(mask, self.scan_rows, self.level, self.min_pixels)[0]
         fits = self.tracker.update(mask) if self.tracker is not None else None
+        if self.view is not None:
+            self._draw_view(msg, mask, fits, keep)
         result = centres
         if return_mask:
             host = mask.cpu().numpy()
