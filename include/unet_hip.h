@@ -1144,6 +1144,88 @@ int unet_frame_stats_u8_batch(int device, const uint8_t* frames_dev, int n, int 
 int unet_prob_stats_f32_batch(int device, const float* scores_dev, int n, size_t numel_per_frame, float threshold,
                               unsigned long long* out_dev, void* stream);
 
+/* ---- frame correction on the device (csrc/correct_kernels.h) ----------------------------------------------------
+ * The stage between "the message's rows are on the device" and "the warp reads them": a per-frame colour and contrast
+ * correction decided from the frame's own histograms.  It answers the failure the reference is built around - the
+ * white marking leaves HSV [0..180, 0..40, 185..255] under a colour cast, a shadow or glare (README.md:325-342,
+ * :380-429) - which unet_frame_stats_u8_batch can only report.  The reference has no such code, and cv2 is not
+ * installed where this is tested: parity with cv2.createCLAHE or any outside implementation is unpinned.  The
+ * arithmetic below is restated in tests/correct_model.py and reproduced bit for bit.  A bare device ordinal; the call
+ * only enqueues on `stream`; the caller supplies the work buffer; bad arguments are refused with UNET_ERR_INVALID_ARG
+ * and a text for unet_op_last_error that names the call, before any device is touched; every output and every region
+ * of the work buffer is overwritten by the call, so the caller clears nothing; no workgroup waits for another.
+ *
+ * frames_dev: n frames of `height` rows of row_stride bytes (0 = dense, otherwise >= 3 * width); the first 3 * width
+ * bytes of a row are pixels, the rest is padding that is never read as pixels; the last row may end with its pixels.
+ * is_bgr tells which of byte 0 (is_bgr) and byte 2 is blue; it only enters the gray value Y.  out_dev: the corrected
+ * frames in rows of out_row_stride bytes (same rule); padding is never written.  out_dev == frames_dev with equal
+ * strides is allowed: the apply pass reads a pixel before it writes it and reads no other pixel, and every histogram
+ * pass has finished by then.  Any other overlap of the two is refused.  No alignment requirement on either; where both
+ * bases and both strides are multiples of 16 the apply pass moves 16 bytes at a time, otherwise bytes - same bits.
+ *
+ * work_dev: work_bytes >= unet_correct_work_bytes(n, grid_x, grid_y) bytes, 4-byte aligned.  Frame i's part starts at
+ * i * (3872 + 1280 * grid_x * grid_y) and holds, in this order,
+ *     channel histograms   3 x 256 uint32      hist[c][v] = #{pixels whose byte c (memory order) equals v}
+ *     plan words           8 uint32            [0] flags: bit 0 the frame is corrected, bit 1 the stretch is in effect,
+ *                                              bit 2 CLAHE is in effect; [1..3] the gains g_0..g_2 (65536 = 1);
+ *                                              [4], [5] lo, hi (0, 255 without a stretch); [6], [7] S, low and high half
+ *     channel tables       3 x 256 bytes       lut[c][v]
+ *     tile histograms      gy x gx x 256 uint32   zeros where CLAHE is not in effect
+ *     tile tables          gy x gx x 256 bytes    the identity where CLAHE is not in effect
+ *
+ * Every `/` below is the floor division of non-negative integers.  N = height * width.
+ * Plan, per frame.  S_c = sum of v * hist[c][v], S = S_0 + S_1 + S_2 (64 bits).
+ *   gate     if cfg->only_flagged and dark_limit * 3 N <= S <= bright_limit * 3 N (the frame's mean is neither below
+ *            dark_limit nor above bright_limit, the limits FrameStats applies to the same mean) the frame is not
+ *            corrected: identity tables, flags 0, gains 65536, lo 0, hi 255, output bytes = input bytes.
+ *   balance  white_balance 1 (gray world): g_c = clamp((S << 16) / (3 S_c), 65536 / max_gain, 65536 * max_gain);
+ *            g_c = 65536 where S_c = 0 or white_balance is 0.  a_c(v) = min(255, (v g_c + 32768) >> 16).
+ *   stretch  lo_bp, hi_bp in basis points of the 3 N samples, both 0 = off.  P[u] = sum over c and over the v with
+ *            a_c(v) = u of hist[c][v]; lo = the smallest u whose cumulative count exceeds lo_bp * 3 N / 10000; hi = the
+ *            smallest u whose cumulative count reaches 3 N - hi_bp * 3 N / 10000.  hi <= lo: no stretch (bit 1 clear,
+ *            lo and hi are still recorded).  Otherwise s(u) = 0 for u < lo, else
+ *            min(255, ((u - lo) * 255 + (hi - lo) / 2) / (hi - lo)).
+ *   tone     cfg->tone, 256 bytes; the identity = off.  A gamma curve is a table the caller computes: no pow runs here.
+ *   lut_c[v] = tone[s(a_c(v))].
+ * CLAHE (cfg->clahe), OpenCV's scheme in integers.  th = ceil(height / grid_y), tw = ceil(width / grid_x); tile
+ * (ty, tx) holds rows ty th .. min((ty + 1) th, height) - 1 and the columns likewise; a grid that leaves a tile empty,
+ * (grid_y - 1) th >= height or (grid_x - 1) tw >= width, is refused.  With B', G', R' = lut_c[...] of the pixel,
+ *     Y = (3735 B' + 19235 G' + 9798 R' + 16384) >> 15                       unet_frame_stats_u8_batch's gray value
+ *   tile histogram: of Y over the tile's own pixels; A = their number (border tiles are smaller).
+ *   tile table: L = max(1, clip_q8 * A / 65536) (clip_q8 = the clip limit times 256); E = sum of max(hist - L, 0);
+ *     hist = min(hist, L) + E / 256; r = E % 256; if r > 0: step = max(256 / r, 1) and for (i = 0; i < 256 && r > 0;
+ *     i += step) hist[i]++, r--.  T[i] = (255 cdf[i] + A / 2) / A with cdf the inclusive prefix sum.
+ *   apply: X = 2 x + 1 - tw, tx0 = floor(X / (2 tw)) (X may be negative: a true floor, -1 at the least), wx = X - tx0 *
+ *     2 tw, tx1 = tx0 + 1, then both clamped to [0, grid_x - 1]; ty0, ty1, wy likewise from y and th.
+ *     Y2 = ((2 th - wy) ((2 tw - wx) T[ty0][tx0][Y] + wx T[ty0][tx1][Y])
+ *           + wy ((2 tw - wx) T[ty1][tx0][Y] + wx T[ty1][tx1][Y]) + 2 tw th) / (4 tw th)
+ *     out_c = Y2 if Y = 0, else min(255, (p_c Y2 + Y / 2) / Y) with p_c = lut_c[...]: the three channels are scaled by
+ *     the luminance ratio, which keeps the hue.
+ * Without CLAHE in effect out_c = lut_c[...].
+ *
+ * Domain (anything else is refused): no null pointer; n, height, width >= 1; height, width <= 16384; n * height * width
+ * < 2^31; 1 <= grid_x, grid_y <= 16 and no empty tile (also when clahe is 0: the grid sizes the work buffer);
+ * white_balance 0 or 1; 1 <= max_gain <= 8; lo_bp, hi_bp >= 0 with lo_bp + hi_bp < 10000; 1 <= clip_q8 <= 2^24;
+ * 0 <= dark_limit <= bright_limit <= 255; work_dev 4-byte aligned and work_bytes as above. */
+typedef struct unet_correct_config {
+  int white_balance;          /* 0 = off, 1 = gray world */
+  int max_gain;               /* 1 .. 8; default 4 */
+  int lo_bp, hi_bp;           /* basis points clipped below and above; 0, 0 = off */
+  int clahe;                  /* 0 = off */
+  int grid_x, grid_y;         /* tiles across and down, 1 .. 16 */
+  int clip_q8;                /* clip limit * 256; default 512 */
+  int only_flagged;           /* correct only frames whose mean is below dark_limit or above bright_limit */
+  int dark_limit, bright_limit; /* default 50, 200 */
+  uint8_t tone[256];
+} unet_correct_config;
+/* sizeof(unet_correct_config), so a binding can check its layout against the library */
+size_t unet_correct_config_bytes(void);
+/* a pure host function: the bytes of caller-owned device work space; 0 for n < 1 or a grid outside 1 .. 16 */
+size_t unet_correct_work_bytes(int n, int grid_x, int grid_y);
+int unet_correct_u8_batch(int device, const uint8_t* frames_dev, int n, int height, int width, int row_stride,
+                          int is_bgr, const unet_correct_config* cfg, uint8_t* out_dev, int out_row_stride,
+                          void* work_dev, size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

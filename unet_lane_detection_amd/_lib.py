@@ -54,6 +54,24 @@ class LaneViewStyle(C.Structure):
     ]
 
 
+class CorrectConfigStruct(C.Structure):
+    """unet_correct_config of include/unet_hip.h"""
+    _fields_ = [
+        ("white_balance", C.c_int),
+        ("max_gain", C.c_int),
+        ("lo_bp", C.c_int),
+        ("hi_bp", C.c_int),
+        ("clahe", C.c_int),
+        ("grid_x", C.c_int),
+        ("grid_y", C.c_int),
+        ("clip_q8", C.c_int),
+        ("only_flagged", C.c_int),
+        ("dark_limit", C.c_int),
+        ("bright_limit", C.c_int),
+        ("tone", C.c_uint8 * 256),
+    ]
+
+
 STATUS = {0: "UNET_OK", 1: "UNET_ERR_INVALID_ARG", 2: "UNET_ERR_SHAPE", 3: "UNET_ERR_STATE", 4: "UNET_ERR_HIP",
           5: "UNET_ERR_NOMEM", 6: "UNET_ERR_UNKNOWN_PARAM", 7: "UNET_ERR_RANGE"}
 UNET_ERR_HIP = 4     # a HIP runtime call or a kernel-side check failed
@@ -258,6 +276,11 @@ SIGNATURES = {
     "unet_frame_stats_u8_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.c_void_p]),
     "unet_prob_stats_f32_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
+    "unet_correct_config_bytes": (C.c_size_t, []),
+    "unet_correct_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "unet_correct_u8_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.POINTER(CorrectConfigStruct), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]),
     "unet_op_conv3x3": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "unet_op_upconv2x2": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

@@ -162,10 +162,17 @@ class LaneFollowPipeline:
     otherwise the kept components of `clean`; with neither, only the mask layer is drawn.  `last_view` holds the
     (1, height, width, 3) device tensor and `last_view_layers` the layer plane, as `last_components` holds the
     components; `view_msg()` returns the view as an ImageMsg in the message's encoding.  Return shapes are unchanged.
-    view=None: every launch and every return value as without it."""
+    view=None: every launch and every return value as without it.
+
+    correct=correct.CorrectConfig(...): the message's rows are corrected on the device (correct.FrameCorrector: white
+    balance, stretch, tone, CLAHE, decided from the frame's own histograms) into a buffer of the pipeline's own, and
+    the warp reads that buffer - for both sources.  `diagnose` still measures the raw rows (it diagnoses the camera)
+    and `view` still draws on them (what the camera saw).  `last_correction` holds the frame's correct.Plan (32
+    bytes leave the device when it is read).  Return shapes are unchanged.  correct=None: every launch, every buffer
+    and every return value as without it."""
 
     def __init__(self, model, source="unet", extractor=None, scan_rows=None, level=127, min_pixels=10, device=None,
-                 diagnose=False, fit=None, clean=None, view=None, **pipeline_kwargs):
+                 diagnose=False, fit=None, clean=None, view=None, correct=None, **pipeline_kwargs):
         from .ros_bridge import REF_DST_POINTS, REF_SRC_POINTS, REF_WARP_SIZE, CameraStage, LanePipelineGPU, \
             get_perspective_transform
         if source not in ("unet", "hsv"):
@@ -199,6 +206,11 @@ class LaneFollowPipeline:
                                                     pipeline_kwargs.get("dst_points", REF_DST_POINTS))
             self.warp_size = tuple(pipeline_kwargs.get("warp_size", REF_WARP_SIZE))
             self.extractor = extractor if extractor is not None else HSVLaneExtractor(device=index)
+        self.correct = correct
+        self.corrector = self._corrected = None   # correct: the stage and the buffer the warp then reads
+        if correct is not None:
+            from .correct import FrameCorrector
+            self.corrector = FrameCorrector(correct, device=self.stage.device)
 
     def _prestage(self, msg, out_size):
         """the message's bytes -> (1, out_h, out_w, 3) RGB on the device, as LanePipelineGPU does it"""
@@ -210,6 +222,11 @@ class LaneFollowPipeline:
             from .diagnose import frame_records
             self._frame_records = frame_records(rows.view(-1), 1, msg.height, msg.width, msg.step,
                                                 msg.encoding == "bgr8")
+        if self.corrector is not None:
+            if self._corrected is None or self._corrected.shape != rows.shape:
+                self._corrected = torch.empty_like(rows)
+            rows = self.corrector.correct(rows, bgr=msg.encoding == "bgr8", row_stride=msg.step, out=self._corrected,
+                                          width=msg.width)
         frame = torch.empty((1, out_size[1], out_size[0], 3), dtype=torch.uint8, device=self.stage.device)
         minv = np.ascontiguousarray(np.linalg.inv(self.matrix))
         rc = self.stage._lib.unet_ipm_prestage_u8(self.stage.device.index, _ptr(rows), msg.height, msg.width, msg.step,
@@ -243,6 +260,12 @@ class LaneFollowPipeline:
         self.last_view, self.last_view_layers = lane_view(rows, self.matrix, self.warp_size, mask, curves, self.view,
                                                           step=msg.step, layers=True, width=msg.width)
         self._view_msg = (msg.encoding, msg.header)
+
+    @property
+    def last_correction(self):
+        """correct: the correct.Plan of the last message (gains, lo, hi, corrected); None without `correct` or before
+        the first callback"""
+        return None if self.corrector is None else self.corrector.plan()
 
     def view_msg(self):
         """The last view as an ImageMsg in its message's encoding (height * width * 3 bytes leave the device); None

@@ -45,12 +45,17 @@ class FramePipeline:
 
     diagnose=True: every chunk is also measured where it already is, before the resize
     (diagnose.frame_records: pixel range, brightness, Laplacian sharpness per frame), and `process` and `run` hand out
-    ((overlay, mask), diagnose.FrameStats) instead of (overlay, mask).  Overlay and mask are the same either way."""
+    ((overlay, mask), diagnose.FrameStats) instead of (overlay, mask).  Overlay and mask are the same either way.
+
+    correct=correct.CorrectConfig(...): every chunk's BGR frames are corrected on the device before the resize
+    (correct.FrameCorrector, into a buffer of the pipeline's own): the network sees and the overlay is blended onto
+    the corrected frames, while `diagnose` still measures the frames as they came.  correct=None: every launch, every
+    buffer and every return value as without it."""
 
     SLOTS = 3   # chunk k computes while k+1 is uploaded and k-1 is downloaded
 
     def __init__(self, model, threshold=0.5, input_size=(224, 224), precision="f16x3", lut=None, alpha=0.7, beta=0.3,
-                 gamma=0.0, diagnose=False):
+                 gamma=0.0, diagnose=False, correct=None):
         """input_size: (width, height) of the network's input; lut: (256, 3) uint8 in the frames' channel order
         (default `jet_table()`); alpha, beta, gamma: cv2.addWeighted's."""
         if not torch.cuda.is_available():
@@ -70,6 +75,11 @@ class FramePipeline:
         self.alpha, self.beta, self.gamma = float(alpha), float(beta), float(gamma)
         self._streams = None
         self.diagnose = bool(diagnose)
+        self.correct = correct
+        self.corrector = self._corrected = None
+        if correct is not None:
+            from .correct import FrameCorrector
+            self.corrector = FrameCorrector(correct, device=self.device)
 
     # ---- the three stages, each on torch's current stream -----------------------------------------------------
     def _stream(self):
@@ -113,6 +123,13 @@ class FramePipeline:
         _lib.check(rc, "unet_overlay_u8_batch")
 
     def _launch(self, frames, overlay, mask):
+        if self.corrector is not None:
+            # the buffer only grows, and every use of it is enqueued on one stream after the other
+            if self._corrected is None or self._corrected.numel() < frames.numel():
+                if self._corrected is not None:
+                    self._corrected.record_stream(torch.cuda.current_stream(self.device))
+                self._corrected = torch.empty(frames.numel(), dtype=torch.uint8, device=self.device)
+            frames = self.corrector.correct(frames, bgr=True, out=self._corrected[:frames.numel()].view(frames.shape))
         self._overlay(frames, self._network(self._resize(frames)), overlay, mask)
 
     def _measure(self, frames):
