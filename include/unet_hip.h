@@ -1226,6 +1226,44 @@ int unet_correct_u8_batch(int device, const uint8_t* frames_dev, int n, int heig
                           int is_bgr, const unet_correct_config* cfg, uint8_t* out_dev, int out_row_stride,
                           void* work_dev, size_t work_bytes, void* stream);
 
+/* ---- annotations on the device (csrc/annotate_kernels.h) --------------------------------------------------------
+ * The step in front of a device-resident data set: an annotator's polygons rasterised into masks at whatever size a
+ * stage trains at.  The reference does it with labelme_to_mask.py (README.md:1013-1052: np.array(points, np.int32) and
+ * cv2.fillPoly(mask, [points], 255) per shape) and A.Resize on the stored mask (:1996-2055).  cv2 is not installed
+ * where this is tested and the reference ships no fixture: parity with cv2.fillPoly itself is unpinned, and along
+ * boundaries cv2's fixed-point edge walk and its line iterator give other pixels.  What is pinned is the rule below,
+ * restated in tests/annotate_model.py and reproduced bit for bit.  A bare device ordinal; the call only enqueues on
+ * `stream` (one launch, no host synchronisation, no atomics on global memory); every byte of masks_out_dev is written.
+ *
+ * Tables (CSR, all on the device): frame i owns the polygons frame_offsets[i] .. frame_offsets[i + 1] - 1, polygon j the
+ * vertices poly_offsets[j] .. poly_offsets[j + 1] - 1 of vertices_dev, rows of (x, y), and the byte poly_values[j].
+ * P = frame_offsets[n] and V = poly_offsets[P] are the lengths the arrays must have (P + 1 offsets, P values, V rows);
+ * the kernel clamps every other offset into [0, P] or [0, V] and makes each range non-decreasing, and clamps every
+ * coordinate to +-2^20, so that no table makes it read outside arrays of those lengths.  The Python layer refuses such
+ * tables before the launch.  vertices_dev 8-byte aligned, the offsets 4-byte aligned.
+ *
+ * Rule.  Every quantity is an integer; `/` is the floor division of non-negative integers.  Output pixel (X, Y) of
+ * frame i asks about the source point sx = X * src_w / out_w, sy = Y * src_h / out_h (equal sizes: the identity), which
+ * is the same as rasterising at the source size and taking the nearest pixel.  Its byte is the value of the last
+ * polygon of the frame, in order, that covers (sx, sy), and 0 if none does: successive fillPoly calls.  A polygon
+ * covers a point if its parity or its outline does.  Its edges run from vertex k to vertex k + 1 and from the last to
+ * the first; no vertices: skipped; one vertex: a dot; two: a line (the parities cancel).
+ *   parity   even-odd at the pixel centre.  Edges with y0 == y1 are skipped; an edge is oriented so that y0 < y1 and
+ *            counts if y0 <= sy < y1 and (x1 - x0) * (sy - y0) - (y1 - y0) * (sx - x0) > 0.  Odd count: covered.
+ *   outline  an 8-connected line that does not depend on the edge's direction.  dx = x1 - x0, dy = y1 - y0.
+ *            |dx| >= |dy|: oriented so that dx >= 0; dx == 0 is the single point (x0, y0); otherwise the point is on the
+ *            line if x0 <= sx <= x1 and 0 <= 2 * (sx - x0) * dy + dx - 2 * dx * (sy - y0) < 2 * dx, which is
+ *            y = y0 + floor((2 * (sx - x0) * dy + dx) / (2 * dx)) without a division.  |dx| < |dy|: oriented so that
+ *            dy > 0, the same test with x and y exchanged.  A marking's far end is thinner than a pixel; without the
+ *            outline it breaks into dots.
+ *
+ * Domain: no null pointer, n >= 1 (UNET_ERR_INVALID_ARG otherwise); 1 <= src_h, src_w, out_h, out_w <= 16384
+ * (UNET_ERR_SHAPE otherwise); |x|, |y| <= 2^20, so that every expression above fits in 63 bits.  The cost grows with
+ * output pixels times the edges whose rows meet a 64 x 64 tile of them; there is no cap on a frame's edges. */
+int unet_fill_polygons_u8_batch(int device, const int32_t* vertices_dev, const int32_t* poly_offsets_dev,
+                                const uint8_t* poly_values_dev, const int32_t* frame_offsets_dev, int n, int src_h,
+                                int src_w, int out_h, int out_w, uint8_t* masks_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

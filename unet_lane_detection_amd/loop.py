@@ -1,7 +1,8 @@
 """The reference's training loop (README.md:2185-2231) on a trainer object: train epoch -> validate ->
 scheduler.step() -> best_model.pth when the validation Dice improves -> early stop -> checkpoint_epoch{N}.pth every 10th
 epoch -> last_model.pth.  Pure host control flow: `fit` only calls `trainer.step`, `trainer.validate`,
-`trainer.save_checkpoint` and sets `trainer.lr`, so it runs on any object with those (tests/test_validate_cpu.py)."""
+`trainer.save_checkpoint` and sets `trainer.lr`, so it runs on any object with those (tests/test_validate_cpu.py).
+`fit_progressive` runs `fit` once per stage of the reference's progressive training, on the data set at each size."""
 from __future__ import annotations
 
 import os
@@ -53,3 +54,27 @@ def fit(trainer, train_batches, val_batches, epochs, scheduler=None, save_dir=No
     if save_dir is not None:
         trainer.save_checkpoint(os.path.join(save_dir, "last_model.pth"), epoch=None, with_optimizer=False)
     return history
+
+
+REFERENCE_STAGES = [(128, 30, 1e-3), (192, 30, 1e-4), (224, 20, 1e-5)]   # (image_size, epochs, learning_rate)
+
+
+def fit_progressive(trainer, train_source, val_source, stages, batch_size, augmenter, save_dir=None, **fit_kwargs):
+    """The reference's progressive training (tip 4, README.md:2562-2589): one `fit` per stage (size, epochs, lr), each
+    on the data set at that stage's size and each starting from the previous stage's weights.  train_source and
+    val_source give a data set per size through `.at(size)` (annotate.TrainingSource: frames resized, masks rasterised
+    at that size); the batches are augment.AugmentedBatches and augment.val_batches.  Every stage starts with a fresh
+    optimiser, as the reference's `'pretrained': 'stage1_best.pth'` into a new run does: `trainer.reset_optimizer()`
+    zeroes the Adam moments and the step count.  The weights carried over are the last epoch's, not a reloaded best
+    checkpoint.  save_dir: stage i (from 1) writes into save_dir/stage{i}.  The other keywords go to `fit`, which is
+    unchanged.  Returns the per-stage histories.  Pure host control flow, like `fit`."""
+    from .augment import AugmentedBatches, val_batches
+    histories = []
+    for i, (size, epochs, lr) in enumerate(stages, start=1):
+        train = AugmentedBatches(train_source.at(size), batch_size, augmenter)
+        val = val_batches(val_source.at(size), batch_size, mask_threshold=augmenter.mask_threshold)
+        trainer.reset_optimizer()
+        trainer.lr = lr
+        stage_dir = os.path.join(save_dir, f"stage{i}") if save_dir is not None else None
+        histories.append(fit(trainer, train, val, epochs, save_dir=stage_dir, **fit_kwargs))
+    return histories

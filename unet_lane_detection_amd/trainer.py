@@ -202,6 +202,13 @@ class UNetTrainer:
                                             self.weight_decay, 1 if self.decoupled else 0, grad_scale, self._stream())
         _lib.check(rc, "unet_train_adam_step", self._h)
 
+    def reset_optimizer(self):
+        """A fresh Adam: zeroed moments and step count; parameters, BatchNorm buffers and the rate stay
+        (loop.fit_progressive calls this at the start of every stage)."""
+        self.exp_avg.zero_()
+        self.exp_avg_sq.zero_()
+        self.step_count = 0
+
     def device_error(self, current_stream_only=False):
         """Wait for the device (or, with current_stream_only, for torch's current stream of it: everything the trainer
         launches goes there) and return (and clear) the status of every launch on this handle since the last call: 0,
