@@ -195,6 +195,45 @@ int unet_train_forward_backward_f32(unet_handle_t h, const float* image_nchw_dev
 int unet_train_adam_step(unet_handle_t h, int step, float lr, float beta1, float beta2, float eps,
                          float weight_decay, int decoupled, float grad_scale, void* stream);
 
+/* ---- the gradient pass: accumulation, global norm, non-finite count (csrc/grad_kernels.h) -------------------------
+ * No reference counterpart in code: the reference's troubleshooting table names gradient accumulation
+ * (README.md:2356); global-norm clipping and the non-finite guard have torch's semantics
+ * (torch.nn.utils.clip_grad_norm_, GradScaler.step's skip).  The arithmetic is restated in tests/grad_model.py.
+ *
+ * unet_grad_accumulate_f32: one pass over flat fp32 device buffers of `numel` floats,
+ *     dst[i] = a[i] + b[i]        one fp32 addition per element; b == NULL: dst[i] = a[i]
+ * dst may be a or b (or lie apart from them; a partial overlap is refused).  dst == a with b == NULL stores nothing:
+ * a pure reduction.  record (optional, two doubles on the device, 8-byte aligned) is OVERWRITTEN with a description of
+ * the values written to - in the pure reduction read from - dst:
+ *     record[0] = the sum of x * x over the finite elements, squares and sum formed in double
+ *     record[1] = the number of non-finite elements (+-inf, NaN)
+ * With a record, `work` (unet_grad_work_bytes bytes on the device, 8-byte aligned, the caller's) holds the blocks'
+ * partial sums.  The reduction uses no atomics and a grid that depends on numel alone (at most 2048 blocks of 256
+ * threads, on any device): per-thread partials in double, a fixed tree per block, and a one-block second launch that
+ * adds the blocks' partials in a fixed order.  For given numel and given distances of dst, a and b from a 16-byte
+ * boundary the record is the same bits on every run, every device and every rank; it differs from the exactly rounded
+ * sum by at most numel * 2^-53, relative.  Pointers need 4-byte alignment only: the pass uses 16-byte accesses where
+ * dst, a and b are equally far from a 16-byte boundary (a head and a tail of up to three floats are peeled) and 4-byte
+ * accesses where they are not.  numel == 0 is valid and gives the record {0, 0}.  A bare device ordinal; the call only
+ * enqueues on `stream`; bad arguments are refused with UNET_ERR_INVALID_ARG and a text for unet_op_last_error that
+ * names the call, before any device is touched. */
+size_t unet_grad_work_bytes(void);
+int unet_grad_accumulate_f32(int device, float* dst, const float* a, const float* b, size_t numel, double* record,
+                             double* work, void* stream);
+
+/* unet_train_adam_step with the gradient multiplier taken from a record of unet_grad_accumulate_f32 over the attached
+ * gradient buffer, on the device (the host reads nothing; the kernel reads the record with ordinary loads):
+ *     coef = grad_scale * min(1, max_norm / (|grad_scale| * sqrt(record[0]) + 1e-6))
+ * computed in double and rounded once to float: torch.nn.utils.clip_grad_norm_ applied to the gradient scaled by
+ * grad_scale.  max_norm = +inf gives coef == grad_scale exactly; max_norm must be positive.  For an equal multiplier
+ * the update is unet_train_adam_step's bit for bit.  If record[1] != 0 the optimiser kernel writes nothing: parameters
+ * and both moments stay as they are, bit for bit (the repack of the MFMA operands still runs).  record_dev: 8-byte
+ * aligned.  UNET_ERR_INVALID_ARG - before any device is touched - for a null or misaligned record, a handle without
+ * unet_train_attach, step < 1 or a max_norm that is not positive. */
+int unet_train_adam_step_rec(unet_handle_t h, int step, float lr, float beta1, float beta2, float eps,
+                             float weight_decay, int decoupled, float grad_scale, float max_norm,
+                             const double* record_dev, void* stream);
+
 /* Data-parallel overlap (north_star: RCCL all-reduce of the gradients; the reference has no distributed code).  The
  * backward pass finishes the gradients of the decoder, the bottleneck and the head - the tail
  * [unet_train_grad_split, unet_train_param_numel) of the flat gradient buffer - before it starts on the encoder.  With a

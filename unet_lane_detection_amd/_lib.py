@@ -171,6 +171,11 @@ SIGNATURES = {
                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "unet_train_adam_step": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                        C.c_int, C.c_float, C.c_void_p]),
+    "unet_train_adam_step_rec": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                           C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "unet_grad_work_bytes": (C.c_size_t, []),
+    "unet_grad_accumulate_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
     "unet_train_debug_snapshot": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "unet_op_wgrad3x3": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p]),

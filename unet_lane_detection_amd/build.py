@@ -30,12 +30,12 @@ HASHFILE = LIB + ".srchash"
 # the others: kernels of the validation pass, of the general loss, of the augmentation stage, of the histogram
 # calibration, of the int8 tier's hybrid (fp16) units, of the video path, of the ensemble combine and threshold
 # sweep, of lane following (HSV extractor, scan-row centre), of the frame and output diagnostics, of the lane fit, of
-# the component labelling, of the lane view, of the frame correction and of the polygon rasteriser, code objects of
-# their own
+# the component labelling, of the lane view, of the frame correction, of the polygon rasteriser and of the gradient
+# pass (accumulation, norm, non-finite count), code objects of their own
 SOURCES = ["unet_hip.cpp", "validate_kernels.cpp", "loss_kernels.cpp", "augment_kernels.cpp", "calib_kernels.cpp",
            "conv_h16.cpp", "video_kernels.cpp", "ensemble_kernels.cpp", "follow_kernels.cpp", "diagnose_kernels.cpp",
            "lanefit_kernels.cpp", "label_kernels.cpp", "laneview_kernels.cpp", "correct_kernels.cpp",
-           "annotate_kernels.cpp"]
+           "annotate_kernels.cpp", "grad_kernels.cpp"]
 FLAGS = ["-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result",
          "-Wno-unused-value"]
 

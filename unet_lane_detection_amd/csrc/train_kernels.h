@@ -966,6 +966,63 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
+// adam_kernel's update of one element, expression for expression, with every rounding written out as the compiler
+// places it in adam_kernel: there the moments' products and sums round one by one (they are packed multiplies and
+// adds) while the weight-decay terms and the parameter's update are fused multiply-adds.  Left to the compiler, another
+// loop shape (a four-element form was tried) fuses the moments too, and from the second update on (non-zero moments)
+// the last bit differs.
+// tests/test_grad_accum_gpu.py holds the two kernels to each other bit for bit over several updates.
+__device__ __forceinline__ void adam_element(float& pv, float g, float& mOut, float& vOut, float lr, float beta1, float beta2,
+                                             float eps, float wd, int decoupled, float bc1, float bc2sqrt,
+                                             float gradScale) {
+#pragma clang fp contract(off)
+  float gv = g * gradScale;
+  if (wd != 0.f) {
+    if (decoupled)
+      pv *= fmaf(-lr, wd, 1.f);
+    else
+      gv = fmaf(wd, pv, gv);
+  }
+  const float mv = beta1 * mOut + (1.f - beta1) * gv;
+  const float vv = beta2 * vOut + (1.f - beta2) * gv * gv;
+  const float denom = sqrtf(vv) / bc2sqrt + eps;
+  pv = fmaf(-(lr / bc1), mv / denom, pv);
+  mOut = mv;
+  vOut = vv;
+}
+
+// the multiplier of adam_rec_kernel: every operation rounds on its own (no fused multiply-add), so that a host computes
+// the same double with the same expression
+__device__ __forceinline__ float clip_coefficient(float gradScale, double maxNorm, double sumSquares) {
+#pragma clang fp contract(off)
+  const double norm = fabs((double)gradScale) * sqrt(sumSquares);
+  const double total = norm + 1e-6;
+  return (float)((double)gradScale * fmin(1.0, maxNorm / total));
+}
+
+// The same step with the gradient multiplier taken from a record on the device (grad_kernels.h: record[0] the sum of
+// squares of the gradients, record[1] the number of non-finite ones), read with ordinary loads by every thread:
+//   coef = gradScale * min(1, maxNorm / (|gradScale| * sqrt(record[0]) + 1e-6))        in double, rounded once to float
+// which is torch.nn.utils.clip_grad_norm_ applied to the scaled gradient; maxNorm = +inf gives gradScale itself.  With
+// record[1] != 0 nothing is written.  4-byte accesses like adam_kernel's: a form with 16-byte accesses was measured at
+// the same time (both sit at the rate of a device copy of the same bytes), so there is one loop for every alignment.
+__global__ __launch_bounds__(256) void adam_rec_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
+                                                       float beta1, float beta2, float eps, float wd, int decoupled,
+                                                       float bc1, float bc2sqrt, float gradScale, double maxNorm,
+                                                       const double* __restrict__ record) {
+  if (record[1] != 0.0) return;
+  const float coef = clip_coefficient(gradScale, maxNorm, record[0]);
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    float pv = p[i], mv = m[i], vv = v[i];
+    adam_element(pv, g[i], mv, vv, lr, beta1, beta2, eps, wd, decoupled, bc1, bc2sqrt, coef);
+    p[i] = pv;
+    m[i] = mv;
+    v[i] = vv;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Device-side repack of PyTorch-layout weights into MFMA B-fragment order (see igemm_f32.h):
 //   out[(((cs*nChunks + kc)*taps + t)*64 + lane)*KPL + e] = W(n = cs*16 + (lane&15), ci = kc*CK + (lane>>4)*KPL + e, t)

@@ -1936,6 +1936,32 @@ int unet_train_adam_step(unet_handle_t h, int step, float lr, float beta1, float
   return rc;
 }
 
+// unet_train_adam_step with the gradient multiplier formed on the device from a record of unet_grad_accumulate_f32
+// (global-norm clipping; include/unet_hip.h), and no update at all when the record counts a non-finite gradient.  The
+// host reads nothing: the repack runs either way (on unchanged parameters it reproduces the packs it overwrites).
+int unet_train_adam_step_rec(unet_handle_t h, int step, float lr, float beta1, float beta2, float eps, float weightDecay,
+                             int decoupled, float gradScale, float maxNorm, const double* recordDev, void* stream) {
+  if (!h || !h->train || step < 1) return UNET_ERR_INVALID_ARG;
+  if (!recordDev || (reinterpret_cast<uintptr_t>(recordDev) & 7u)) return UNET_ERR_INVALID_ARG;
+  if (!(maxNorm > 0.f)) return UNET_ERR_INVALID_ARG;   // a NaN too
+  TrainState* T = h->train;
+  HIPCHK(h->err, hipSetDevice(h->cfg.device));
+  hipStream_t s = (hipStream_t)stream;
+  const double bc1 = 1.0 - std::pow((double)beta1, step);
+  const double bc2 = 1.0 - std::pow((double)beta2, step);
+  LaunchScope scope(h);
+  prof_begin("adam_rec", 0.0, 28.0 * T->P, s);
+  hipLaunchKernelGGL(unet::adam_rec_kernel, dim3(grid_for(T->P)), dim3(256), 0, s, T->params, T->grads, T->m, T->v, T->P,
+                     lr, beta1, beta2, eps, weightDecay, decoupled, (float)bc1, (float)std::sqrt(bc2), gradScale,
+                     (double)maxNorm, recordDev);
+  prof_end(s);
+  HIPCHK(h->err, hipGetLastError());
+  prof_begin("repack_weights", 0.0, 12.0 * T->P, s);
+  int rc = train_repack(h, s);
+  prof_end(s);
+  return rc;
+}
+
 // Eval-mode forward on the attached parameters and BatchNorm buffers (reference README.md:2087-2099): see
 // train_eval_forward.  Logits (N,1,H,W) to logitsDev; no training state is written.
 int unet_train_eval_u8(unet_handle_t h, const uint8_t* frames, int n, int height, int width, float* logitsDev,

@@ -19,7 +19,10 @@ class UNetTrainer:
 
     def __init__(self, state_dict, device=0, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  decoupled=False, process_group=None, in_channels=3, overlap_allreduce=False,
-                 check_device_status=True):
+                 check_device_status=True, accum_steps=1, max_grad_norm=None, skip_nonfinite=False):
+        """accum_steps, max_grad_norm and skip_nonfinite (also plain attributes, changeable between updates): see
+        step().  With the three defaults step, forward_backward and optimizer_step launch and allocate exactly what they
+        did before these keywords existed."""
         if not torch.cuda.is_available():
             raise RuntimeError("UNetTrainer needs a HIP device; there is no CPU fallback")
         self._lib = _lib.load()
@@ -45,6 +48,18 @@ class UNetTrainer:
         self._split = 0
         self._fb_rc = 0
         self._defer_fb_error = False
+        # gradient accumulation, global-norm clipping, non-finite guard: nothing is allocated until one of them is used
+        self.accum_steps = int(accum_steps)
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.grad_norm = float("nan")     # scaled pre-clip norm of the last update (read only on the checked path)
+        self.skipped_steps = 0
+        self._pending = 0                 # micro-batches in the accumulation buffer
+        self._latched_rc = 0              # several ranks: a micro-step's entry failure, held until the exchange
+        self._acc = None
+        self._grad_rec = None
+        self._grad_work = None
+        self._rec_host = None
 
         # flat buffers in unet_param_name order
         n = self._lib.unet_num_params(h)
@@ -225,7 +240,25 @@ class UNetTrainer:
         would leave the others waiting in the next collective.  So each rank's status word (unet_device_status_to; or the
         status of a forward/backward call that failed at its entry) travels in front of the gradients through the same
         all-reduce; afterwards every rank reads the sum, and either all of them raise or all of them step.  One wait per
-        step, for the trainer's stream only."""
+        step, for the trainer's stream only.
+
+        accum_steps = k > 1: every call still returns its micro-batch's loss; calls 1 .. k-1 add the gradients to an
+        accumulation buffer (the first is a copy), call k writes accumulated + own gradients into the bucket, and only
+        then the exchange and ONE update with grad_scale = 1 / (k * world) follow.  max_grad_norm: the scaled gradient
+        is clipped to that global norm (torch.nn.utils.clip_grad_norm_'s formula; the reference has no counterpart).
+        skip_nonfinite: an update whose gradients hold an inf or a NaN is not applied.  With any of the three the
+        update goes through unet_train_adam_step_rec and a 2-double record on the device (self.grad_record: sum of
+        squares, number of non-finite gradients), taken from the bucket every rank holds after the exchange, so all
+        ranks clip alike and skip together.  With check_device_status the record is read in the step's one wait:
+        self.grad_norm is set, and a skipped update leaves step_count alone and counts in self.skipped_steps; without
+        skip_nonfinite non-finite gradients reach the parameters as they always did.  With
+        check_device_status=False nothing is read: the optimiser kernel's own guard leaves parameters and moments
+        untouched when the record counts a non-finite gradient (whatever skip_nonfinite says), step_count advances
+        all the same, and grad_norm and skipped_steps stay as they are.
+        A failed micro-step on one rank raises as before and discards the pending accumulation; on several ranks it
+        is latched and raised by all of them at the exchange, where none applies."""
+        if self._extended():
+            return self._step_extended(images, targets)
         _, ws = dp.world(self.group)
         if not self.check_device_status:
             self.forward_backward(images, targets)
@@ -259,6 +292,174 @@ class UNetTrainer:
                                  self._lib.unet_last_error(self._h).decode() if local else "")
         self.optimizer_step(scale)
         return self.loss
+
+    # ---- accumulation, clipping, non-finite guard (csrc/grad_kernels.h) -------------------
+    def _extended(self):
+        return (int(self.accum_steps) > 1 or self.max_grad_norm is not None or bool(self.skip_nonfinite)
+                or self._pending > 0)
+
+    @property
+    def grad_record(self):
+        """The 2-double device tensor the gradient pass writes: [sum of squares of the finite gradients of the last
+        update's bucket, before grad_scale; number of non-finite ones].  Allocated on first need."""
+        if self._grad_rec is None:
+            self._grad_rec = torch.zeros(2, dtype=torch.float64, device=self.device)
+            self._grad_work = torch.empty(int(self._lib.unet_grad_work_bytes()) // 8, dtype=torch.float64,
+                                          device=self.device)
+            self._rec_host = torch.zeros(2, dtype=torch.float64).pin_memory()
+        return self._grad_rec
+
+    def _grad_pass(self, dst, a, b=None, record=False):
+        rec = self.grad_record if record else None
+        rc = self._lib.unet_grad_accumulate_f32(self.device.index, self._p(dst), self._p(a), self._p(b), dst.numel(),
+                                                self._p(rec), self._p(self._grad_work if record else None),
+                                                self._stream())
+        _lib.check(rc, "unet_grad_accumulate_f32")
+
+    def optimizer_step_rec(self, grad_scale=1.0):
+        """optimizer_step with the multiplier formed on the device from self.grad_record (unet_train_adam_step_rec):
+        clipping to max_grad_norm (None: none), and no update at all if the record counts a non-finite gradient."""
+        self.step_count += 1
+        max_norm = float("inf") if self.max_grad_norm is None else float(self.max_grad_norm)
+        rc = self._lib.unet_train_adam_step_rec(self._h, self.step_count, self.lr, self.betas[0], self.betas[1],
+                                                self.eps, self.weight_decay, 1 if self.decoupled else 0, grad_scale,
+                                                max_norm, self._p(self.grad_record), self._stream())
+        _lib.check(rc, "unet_train_adam_step_rec", self._h)
+
+    def clip_coefficient(self, grad_scale, sumsq):
+        """The multiplier unet_train_adam_step_rec forms from record[0] = sumsq, in the same double arithmetic."""
+        max_norm = float("inf") if self.max_grad_norm is None else float(np.float32(self.max_grad_norm))
+        gs = float(np.float32(grad_scale))
+        return float(np.float32(gs * min(1.0, max_norm / (abs(gs) * float(np.sqrt(np.float64(sumsq))) + 1e-6))))
+
+    def _step_extended(self, images, targets):
+        _, ws = dp.world(self.group)
+        checked = self.check_device_status
+        together = checked and ws > 1          # the ranks fail together, at the exchange
+        try:
+            self._defer_fb_error = together
+            try:
+                self.forward_backward(images, targets)
+            finally:
+                self._defer_fb_error = False
+            if together and self._fb_rc != 0:
+                self._latched_rc = self._latched_rc or self._fb_rc
+            self._pending += 1
+            if self._pending < max(1, int(self.accum_steps)):
+                if self._acc is None:
+                    self._acc = torch.empty_like(self.params)
+                # acc = grads (first micro-batch) or acc + grads; enqueued before the wait below
+                self._grad_pass(self._acc, self.grads if self._pending == 1 else self._acc,
+                                None if self._pending == 1 else self.grads)
+                if checked and ws == 1:
+                    rc = self.device_error(current_stream_only=True)
+                    if rc != 0:
+                        raise _lib.UnetError(rc, "unet_device_error: the gradients of this micro-step are invalid, the "
+                                             "pending accumulation was discarded")
+                return self.loss
+            self._apply(in_bucket=True)
+        except _lib.UnetError:
+            self._pending, self._latched_rc = 0, 0
+            raise
+        return self.loss
+
+    def apply_update(self):
+        """The second half of step() for a caller that ran forward_backward itself: the bucket as it is counts as one
+        more micro-batch, and what is pending with it is exchanged and applied as one update through the record entry
+        (clipping and guard as configured), whatever accum_steps says."""
+        self._pending += 1
+        try:
+            self._apply(in_bucket=True)
+        except _lib.UnetError:
+            self._pending, self._latched_rc = 0, 0
+            raise
+
+    def flush_accumulation(self):
+        """Apply a partial accumulation (fewer than accum_steps micro-batches, e.g. at an epoch's end) as one update
+        with grad_scale = 1 / (pending * world).  Nothing pending: nothing happens.  Under data parallelism every rank
+        must call it at the same point (loop.fit does)."""
+        if self._pending == 0:
+            return False
+        try:
+            self._apply(in_bucket=False)
+        except _lib.UnetError:
+            self._pending, self._latched_rc = 0, 0
+            raise
+        return True
+
+    def _apply(self, in_bucket):
+        """The boundary of an accumulation: bucket, exchange, record, update.  in_bucket: the last of the pending
+        micro-batches' gradients are still in the bucket (step), else all of them are in the accumulation buffer."""
+        _, ws = dp.world(self.group)
+        checked = self.check_device_status
+        n = self._pending
+        accumulated = n > 1 or not in_bucket
+        one_rank_record = ws == 1
+        if accumulated:      # grads = acc + grads, or the copy of acc; with one rank the record comes from this pass
+            self._grad_pass(self.grads, self._acc, self.grads if in_bucket else None, record=one_rank_record)
+        elif one_rank_record:
+            self._grad_pass(self.grads, self.grads, None, record=True)
+        scale = 1.0 / (n * ws)
+        if ws > 1:
+            if checked:
+                if self._latched_rc != 0:
+                    self._bucket[:1].fill_(1.0)
+                else:
+                    _lib.check(self._lib.unet_device_status_to(self._h, self._p(self._bucket), self._stream()),
+                               "unet_device_status_to", self._h)
+            if accumulated:  # the two-bucket overlap follows the backward pass, which this bucket no longer does
+                dp.allreduce_flat_sum(self._bucket, self.group)
+            else:
+                self.allreduce_grads()
+            self._grad_pass(self.grads, self.grads, None, record=True)    # from what every rank now holds
+        self._pending = 0
+        if not checked:
+            self._latched_rc = 0
+            self.optimizer_step_rec(scale)
+            return
+        self._rec_host.copy_(self.grad_record, non_blocking=True)         # read in the wait that follows
+        if ws > 1:
+            failed = float(self._bucket[0].item())
+            latched, self._latched_rc = self._latched_rc, 0
+            local = latched or self.device_error(current_stream_only=True)
+            if failed != 0.0:
+                who = "this rank" if local else "another rank"
+                raise _lib.UnetError(local or _lib.UNET_ERR_HIP,
+                                     f"data-parallel step: {int(round(failed))} of {ws} ranks reported a failed launch "
+                                     f"({who}); the gradients of this update are invalid, no rank applied it",
+                                     self._lib.unet_last_error(self._h).decode() if local else "")
+        else:
+            rc = self.device_error(current_stream_only=True)
+            if rc != 0:
+                raise _lib.UnetError(rc, "unet_device_error: the gradients of this step are invalid, no update was applied")
+        sumsq, bad = float(self._rec_host[0]), float(self._rec_host[1])
+        self.grad_norm = scale * float(np.sqrt(sumsq))
+        if bad != 0.0:
+            if self.skip_nonfinite:
+                self.skipped_steps += 1
+                return
+            # not guarded: the non-finite gradients reach the parameters, as they do without these features
+            self.optimizer_step(self.clip_coefficient(scale, sumsq))
+            return
+        self.optimizer_step_rec(scale)
+
+    def snapshot_state(self):
+        """Device clones of parameters, BatchNorm buffers and both moments, with step_count, num_batches_tracked, lr
+        and the accumulation settings: what restore_state needs to put the trainer back (loop.find_lr).  A pending
+        accumulation is not part of it."""
+        return {"params": self.params.clone(), "bn": self.bn.clone(), "exp_avg": self.exp_avg.clone(),
+                "exp_avg_sq": self.exp_avg_sq.clone(), "step_count": self.step_count,
+                "num_batches_tracked": self.num_batches_tracked, "lr": self.lr, "accum_steps": self.accum_steps,
+                "max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite}
+
+    def restore_state(self, s):
+        """Back to a snapshot_state(); a pending accumulation is discarded; ends with unet_train_repack."""
+        for name in ("params", "bn", "exp_avg", "exp_avg_sq"):
+            getattr(self, name).copy_(s[name])
+        for name in ("step_count", "num_batches_tracked", "lr", "accum_steps", "max_grad_norm", "skip_nonfinite"):
+            setattr(self, name, s[name])
+        self._pending, self._latched_rc = 0, 0
+        _lib.check(self._lib.unet_train_repack(self._h, self._stream()), "unet_train_repack", self._h)
 
     # ---- validation (reference README.md:2087-2112) and the loop around both (README.md:2185-2231) ----------
     def eval_logits(self, images):
@@ -351,6 +552,8 @@ class UNetTrainer:
         return [(n, off, numel, self._shapes[n]) for (n, isb, off, numel) in self.layout if not isb]
 
     def save_checkpoint(self, path, epoch=0, best_dice=None, with_optimizer=True):
+        """The reference's checkpoint.  A pending gradient accumulation (accum_steps > 1, between updates) is not
+        stored: call flush_accumulation() first if it must not be lost."""
         osd = None
         if with_optimizer:
             osd = checkpoint.optimizer_state_dict(self._param_entries(), self.exp_avg, self.exp_avg_sq,
