@@ -868,7 +868,7 @@ int unet_overlay_u8_batch(int device, const uint8_t* frames_dev, int n, int heig
 /* ---- checkpoint ensembles and threshold sweeps (csrc/ensemble_kernels.h) ---------------------------------------
  * Both sit between a head's output and the mask that leaves the device, take a bare device ordinal like
  * unet_seg_metrics_accumulate (so they serve every tier), only enqueue on `stream`, and refuse bad arguments with
- * UNET_ERR_INVALID_ARG and a text for unet_op_last_error before any device is touched. */
+ * UNET_ERR_INVALID_ARG and a text for unet_op_last_error that names the call, before any device is touched. */
 #define UNET_ENSEMBLE_MAX 8
 #define UNET_SWEEP_MAX 64
 

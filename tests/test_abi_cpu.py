@@ -163,3 +163,66 @@ def test_op_last_error_names_the_failing_call(lib):
     assert seen["other"] == b""
     with pytest.raises(_lib.UnetError, match="hipSetDevice"):   # _lib.check appends the text when there is no handle
         _lib.check(calls["unet_op_maxpool2x2"](), "unet_op_maxpool2x2")
+
+
+# ---- the frame of the handle-less entry points that live in translation units of their own (csrc/op_entry.h) ---------
+FRAMED_ENTRY_POINTS = {
+    "unet_fill_polygons_u8_batch", "unet_augment_u8", "unet_correct_u8_batch", "unet_frame_stats_u8_batch",
+    "unet_prob_stats_f32_batch", "unet_ensemble_combine", "unet_score_sweep_accumulate", "unet_hsv_lanes_u8_batch",
+    "unet_lane_center_u8_batch", "unet_grad_accumulate_f32", "unet_label_u8_batch", "unet_keep_components_u8_batch",
+    "unet_lane_fit_u8_batch", "unet_lane_view_u8_batch", "unet_resize_u8_batch", "unet_overlay_u8_batch"}
+
+
+def _framed_calls(lib):
+    """name -> the arguments between `device` and `stream` of a call that passes every argument check: 8 x 8 images in
+    host memory, every buffer a 4 KB slot of its own on a 64-byte boundary (the checks look at addresses only)"""
+    work = max(int(lib.unet_correct_work_bytes(1, 1, 1)), int(lib.unet_label_work_bytes(1, 8, 8)), 4096)
+    arena = (C.c_uint8 * (8 * 4096 + work + 64))()
+    base = (C.addressof(arena) + 63) & ~63
+    a, b, c, d, e, f, g, big = (C.c_void_p(base + 4096 * i) for i in range(8))
+    cfg = _lib.CorrectConfigStruct()
+    cfg.max_gain, cfg.grid_x, cfg.grid_y, cfg.clip_q8, cfg.bright_limit = 1, 1, 1, 256, 255
+    members = (C.c_void_p * 1)(a.value)
+    thresholds = (C.c_float * 2)(0.25, 0.75)
+    rows = (C.c_int * 1)(5)
+    m = (C.c_double * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1)
+    calls = {
+        "unet_fill_polygons_u8_batch": (a, b, c, d, 1, 8, 8, 8, 8, e),
+        "unet_augment_u8": (a, None, 1, 8, 8, b, 1, 127, c, None),
+        "unet_correct_u8_batch": (a, 1, 8, 8, 0, 0, C.byref(cfg), b, 0, big, work),
+        "unet_frame_stats_u8_batch": (a, 1, 8, 8, 0, 0, b),
+        "unet_prob_stats_f32_batch": (a, 1, 64, 0.5, b),
+        "unet_ensemble_combine": (members, 1, None, 64, 0.5, b, None),
+        "unet_score_sweep_accumulate": (a, b, 0, 64, thresholds, 2, c),
+        "unet_hsv_lanes_u8_batch": (a, 1, 8, 8, 1, b, c, 5, 5, d),
+        "unet_lane_center_u8_batch": (a, 1, 8, 8, rows, 1, 127, b),
+        "unet_grad_accumulate_f32": (a, b, None, 64, None, None),
+        "unet_label_u8_batch": (a, 1, 8, 8, 127, 8, b, 4, c, d, big, work),
+        "unet_keep_components_u8_batch": (a, 1, 8, 8, b, c, 4, 0, 0, 0, 0, d, e),
+        "unet_lane_fit_u8_batch": (a, 1, 8, 8, 127, 4, 2, 1, None, b),
+        "unet_lane_view_u8_batch": (a, 1, 8, 8, 24, m, 8, 8, b, 127, None, 0, None, c, None),
+        "unet_resize_u8_batch": (a, 1, 8, 8, 3, 0, 4, 4, b),
+        "unet_overlay_u8_batch": (a, 1, 8, 8, b, 8, 8, c, 0.5, 0.5, 0.0, d, None),
+    }
+    return calls, (arena, cfg, members, thresholds, rows, m)
+
+
+def test_framed_entry_points_refuse_and_fail_alike(lib):
+    """every entry point built on csrc/op_entry.h, from one table: a null first pointer is refused as an invalid
+    argument with the entry point's name in the text, and a call that passes every check fails at the device
+    selection with the HIP error in the text (an ordinal the runtime refuses: no device is touched)"""
+    calls, keep = _framed_calls(lib)
+    assert set(calls) == FRAMED_ENTRY_POINTS and len(calls) == 16
+    for name, args in calls.items():
+        assert name in _lib.SIGNATURES, name
+        argtypes = _lib.SIGNATURES[name][1]
+        assert len(argtypes) == len(args) + 2 and argtypes[0] is C.c_int and argtypes[-1] is C.c_void_p, name
+        assert argtypes[1] is C.c_void_p or issubclass(argtypes[1], C._Pointer), name   # args[0]: the first pointer
+        fn = getattr(lib, name)
+        assert fn(0, None, *args[1:], None) == 1, name                       # UNET_ERR_INVALID_ARG
+        msg = lib.unet_op_last_error()
+        assert msg.startswith(b"invalid argument: ") and name.encode() in msg, (name, msg)
+        assert fn(1 << 20, *args, None) == _lib.UNET_ERR_HIP, (name, lib.unet_op_last_error())
+        msg = lib.unet_op_last_error()
+        assert b"hipSetDevice" in msg, (name, msg)
+    del keep

@@ -310,7 +310,7 @@ def test_validate_reports_the_general_loss():
     # the existing entry point on the same logits: counts and Dice score
     acc = torch.zeros(metrics.NUM_ACCUMULATORS, dtype=torch.float64, device="cuda")
     for (_, tb), lg in zip(batches, logits):
-        metrics.accumulate(lib, 0, lg, tb, acc, tr._stream(), loss_cfg=None)
+        metrics.accumulate(lib, 0, lg, tb, acc, C.c_void_p(torch.cuda.current_stream(tr.device).cuda_stream), loss_cfg=None)
     torch.cuda.synchronize()
     old = metrics.SegMetrics(acc.cpu().numpy())
     assert (m.tp, m.fp, m.fn, m.tn) == (old.tp, old.fp, old.fn, old.tn) and m.dice == old.dice and old.focal == 0.0

@@ -63,8 +63,7 @@ def measure():
 
     lib = _lib.load()
 
-    def ptr(t):
-        return C.c_void_p(t.data_ptr())
+    ptr = _lib.ptr
 
     def stream():
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -60,7 +60,6 @@ def copy_of(nbytes):
 
 
 def measure_passes():
-    import ctypes as C
     import torch
     sys.path.insert(0, ROOT)
     from unet_lane_detection_amd import _lib, state as S
@@ -71,8 +70,7 @@ def measure_passes():
     tr.grads.normal_(0.0, 1e-3)
     acc = torch.zeros_like(tr.params)
     rec = tr.grad_record
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p, stream = _lib.ptr, lambda: _lib.stream(tr.device)
 
     def run(dst, a, b, with_record):
         rc = lib.unet_grad_accumulate_f32(0, p(dst), p(a), p(b), P, p(rec) if with_record else None,

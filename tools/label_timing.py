@@ -77,36 +77,22 @@ class Calls:
         self.out = torch.empty((n, h, w), dtype=torch.uint8, device="cuda")
         self.fit = torch.empty((n, 2, 16), dtype=torch.int64, device="cuda")
 
-    @staticmethod
-    def _stream():
-        import ctypes as C
-        import torch
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def label(self, masks):
-        import ctypes as C
         from unet_lane_detection_amd import _lib
         n, h, w = self.shape
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        _lib.check(self.lib.unet_label_u8_batch(0, p(masks), n, h, w, 127, 8, p(self.labels), CAP, p(self.header),
-                                                p(self.records), p(self.work), self.work.numel(), self._stream()),
-                   "unet_label_u8_batch")
+        _lib.call("unet_label_u8_batch", masks.device, masks, n, h, w, 127, 8, self.labels, CAP, self.header, self.records,
+                  self.work, self.work.numel())
 
     def keep_components(self):
-        import ctypes as C
         from unet_lane_detection_amd import _lib
         n, h, w = self.shape
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        _lib.check(self.lib.unet_keep_components_u8_batch(0, p(self.labels), n, h, w, p(self.header), p(self.records), CAP,
-                                                          MIN_AREA, 0, 0, 0, p(self.keep), p(self.out), self._stream()),
-                   "unet_keep_components_u8_batch")
+        _lib.call("unet_keep_components_u8_batch", self.labels.device, self.labels, n, h, w, self.header, self.records, CAP,
+                  MIN_AREA, 0, 0, 0, self.keep, self.out)
 
     def lane_fit(self, masks):
-        import ctypes as C
         from unet_lane_detection_amd import _lib
         n, h, w = self.shape
-        _lib.check(self.lib.unet_lane_fit_u8_batch(0, C.c_void_p(masks.data_ptr()), n, h, w, 127, 9, 100, 50, None,
-                                                   C.c_void_p(self.fit.data_ptr()), self._stream()), "unet_lane_fit_u8_batch")
+        _lib.call("unet_lane_fit_u8_batch", masks.device, masks, n, h, w, 127, 9, 100, 50, None, self.fit)
 
 
 def _inputs(kind, n, h, w):

@@ -78,8 +78,7 @@ def measure():
     cfg = LV.ViewConfig()
     style = cfg.style()
 
-    def ptr(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else None
+    ptr = _lib.ptr
 
     def launch(frames, masks, table, view, plane):     # the entry point itself on preallocated buffers
         n = frames.shape[0]

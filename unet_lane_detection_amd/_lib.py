@@ -9,6 +9,10 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+# torch bundles its own libamdhip64; it must be the first HIP runtime in the process, or a second copy pulled in through
+# libunet_hip.so's RPATH-less dependency fails to see the device.
+import torch
+
 from .build import LIB, build_library, is_stale
 
 UNET_MAX_DEPTH = 6
@@ -307,9 +311,6 @@ def load(build_if_missing: bool = True) -> C.CDLL:
     global _lib
     if _lib is not None:
         return _lib
-    # torch bundles its own libamdhip64; it must be the first HIP runtime in the process, or a second
-    # copy pulled in through libunet_hip.so's RPATH-less dependency fails to see the device.
-    import torch  # noqa: F401
     path = os.environ.get("UNET_HIP_LIB", LIB)   # override: A/B timing builds of the same ABI
     if path == LIB and is_stale():
         # content hash of the sources differs from the one the .so was built from (or there is no .so)
@@ -337,3 +338,20 @@ def check(code, where, handle=None):
         msg = load().unet_last_error(handle) if handle else load().unet_op_last_error()
         detail = msg.decode() if msg else ""
         raise UnetError(code, where, detail)
+
+
+def ptr(t):
+    """a tensor's device address as the ABI's void*; None is the null pointer"""
+    return C.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def stream(device):
+    """torch's current stream on `device` as the ABI's void* stream"""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def call(name, device, *args):
+    """Call the handle-less entry point `name(int device, ..., void* stream)` on torch's current stream of `device` and
+    raise UnetError on a failure.  Tensors among `args` pass as their device addresses, everything else unchanged."""
+    argv = [C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]   # None is already null
+    check(getattr(load(), name)(device.index, *argv, stream(device)), name)

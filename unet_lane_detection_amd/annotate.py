@@ -220,12 +220,9 @@ def fill_host(batch, src_size, out_size=None):
 # the kernel behind torch tensors
 # ---------------------------------------------------------------------------------------------------------------
 def _fill_device(batch, src_size, out_size, out):
-    import ctypes as C
-
     import torch
 
     from . import _lib
-    lib = _lib.load()
     src_h, src_w, out_h, out_w = _check_sizes(src_size, src_size if out_size is None else out_size)
     dev, n = batch.device, batch.n
     if out is None:
@@ -234,11 +231,8 @@ def _fill_device(batch, src_size, out_size, out):
           or not out.is_contiguous() or out.device != dev):
         raise ValueError("out must be a contiguous (n, out_h, out_w) uint8 tensor on the batch's device")
     vertices, poly_offsets, poly_values, frame_offsets = batch._dev
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    rc = lib.unet_fill_polygons_u8_batch(dev.index, C.c_void_p(vertices.data_ptr()), C.c_void_p(poly_offsets.data_ptr()),
-                                         C.c_void_p(poly_values.data_ptr()), C.c_void_p(frame_offsets.data_ptr()), n,
-                                         src_h, src_w, out_h, out_w, C.c_void_p(out.data_ptr()), stream)
-    _lib.check(rc, "unet_fill_polygons_u8_batch")
+    _lib.call("unet_fill_polygons_u8_batch", dev, vertices, poly_offsets, poly_values, frame_offsets, n, src_h, src_w, out_h,
+              out_w, out)
     return out
 
 
@@ -309,8 +303,6 @@ class TrainingSource:
         return int(self.frames.shape[0])
 
     def at(self, size=None):
-        import ctypes as C
-
         import torch
 
         from . import _lib
@@ -320,9 +312,6 @@ class TrainingSource:
                                                     (int(size[0]), int(size[1])))
         _check_sizes((h, w), (out_h, out_w))
         images = torch.empty((n, out_h, out_w, 3), dtype=torch.uint8, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = _lib.load().unet_resize_u8_batch(self.device.index, C.c_void_p(self.frames.data_ptr()), n, h, w, 3,
-                                              1 if self.bgr else 0, out_w, out_h, C.c_void_p(images.data_ptr()), stream)
-        _lib.check(rc, "unet_resize_u8_batch")
+        _lib.call("unet_resize_u8_batch", self.device, self.frames, n, h, w, 3, 1 if self.bgr else 0, out_w, out_h, images)
         masks = rasterize(self.batch, (h, w), (out_h, out_w))
         return DeviceDataset(images, masks, device=self.device)

@@ -247,13 +247,10 @@ def apply_model(images, masks, params, mask_threshold=127):
 # the kernel behind torch tensors
 # ---------------------------------------------------------------------------------------------------------------
 def _apply_device(images, masks, params, mask_threshold, out):
-    import ctypes as C
-
     import torch
 
     from . import _lib
-    lib = _lib.load()
-    if int(lib.unet_augment_param_bytes()) != PARAMS_DTYPE.itemsize:
+    if int(_lib.load().unet_augment_param_bytes()) != PARAMS_DTYPE.itemsize:
         raise RuntimeError("augment.PARAMS_DTYPE does not match the library's record")
     if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or not images.is_contiguous():
         raise ValueError("images must be a contiguous (n, H, W, 3) uint8 tensor")
@@ -278,11 +275,8 @@ def _apply_device(images, masks, params, mask_threshold, out):
             raise ValueError("out[1] must be a contiguous (n, 1, H, W) float32 tensor on the images' device")
     # the table goes up on the launch's own stream, ahead of it
     table = torch.from_numpy(np.ascontiguousarray(params).view(np.uint8).copy()).to(dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    rc = lib.unet_augment_u8(dev.index, C.c_void_p(images.data_ptr()), C.c_void_p(masks.data_ptr()) if masks is not None else None,
-                             ns, h, w, C.c_void_p(table.data_ptr()), n, int(mask_threshold), C.c_void_p(out_img.data_ptr()),
-                             C.c_void_p(out_tgt.data_ptr()) if masks is not None else None, stream)
-    _lib.check(rc, "unet_augment_u8")
+    _lib.call("unet_augment_u8", dev, images, masks, ns, h, w, table, n, int(mask_threshold), out_img,
+              out_tgt if masks is not None else None)
     return out_img, (out_tgt if masks is not None else None)
 
 

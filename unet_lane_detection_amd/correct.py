@@ -110,10 +110,6 @@ class Plan:
     mean: np.ndarray
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
 class FrameCorrector:
     """`config` applied to device frames on torch's current stream.  Owns and reuses its work buffer, so one corrector
     serves one stream at a time."""
@@ -168,11 +164,8 @@ class FrameCorrector:
             if self._work is not None:   # the last call may still be running on this stream
                 self._work.record_stream(torch.cuda.current_stream(self._work.device))
             self._work = torch.empty(need, dtype=torch.uint8, device=frames.device)
-        stream = C.c_void_p(torch.cuda.current_stream(frames.device).cuda_stream)
-        rc = self._lib.unet_correct_u8_batch(frames.device.index, _ptr(frames), n, h, w, int(row_stride or 0),
-                                             1 if bgr else 0, C.byref(self._cfg), _ptr(out), int(row_stride or 0),
-                                             _ptr(self._work), self._work.numel(), stream)
-        _lib.check(rc, "unet_correct_u8_batch")
+        _lib.call("unet_correct_u8_batch", frames.device, frames, n, h, w, int(row_stride or 0), 1 if bgr else 0,
+                  C.byref(self._cfg), out, int(row_stride or 0), self._work, self._work.numel())
         per = need // n
         self.last_plan = self._work[:need].view(n, per)[:, 3072:3072 + 4 * PLAN_WORDS].contiguous().view(torch.int32)
         self._shape = (h, w)

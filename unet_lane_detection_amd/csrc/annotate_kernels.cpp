@@ -24,13 +24,7 @@
 // made non-decreasing before use, so no table makes the kernel read outside arrays of those sizes.
 #include "annotate_kernels.h"
 
-#include "../../include/unet_hip.h"
-
-#include <string>
-
-namespace unet {
-int op_fail(int status, const std::string& text);   // unet_hip.cpp: the text behind unet_op_last_error
-}
+#include "op_entry.h"
 
 namespace unet {
 
@@ -200,38 +194,26 @@ hipError_t launch_fill_polygons(const FillParams& p, hipStream_t s) {
 
 }  // namespace unet
 
-namespace {
-
-int refuse(int status, const char* what) {
-  return unet::op_fail(status, std::string(status == UNET_ERR_SHAPE ? "" : "invalid argument: ") +
-                                   "unet_fill_polygons_u8_batch: " + what);
-}
-
-}  // namespace
-
 extern "C" {
 
 int unet_fill_polygons_u8_batch(int device, const int32_t* verticesDev, const int32_t* polyOffsetsDev,
                                 const uint8_t* polyValuesDev, const int32_t* frameOffsetsDev, int n, int srcH, int srcW,
                                 int outH, int outW, uint8_t* masksOutDev, void* stream) {
+  const unet::OpCall op{"unet_fill_polygons_u8_batch"};
   if (!verticesDev || !polyOffsetsDev || !polyValuesDev || !frameOffsetsDev || !masksOutDev)
-    return refuse(UNET_ERR_INVALID_ARG, "a null pointer");
-  if (n <= 0) return refuse(UNET_ERR_INVALID_ARG, "n must be positive");
-  if ((reinterpret_cast<uintptr_t>(verticesDev) & 7u) || (reinterpret_cast<uintptr_t>(polyOffsetsDev) & 3u) ||
-      (reinterpret_cast<uintptr_t>(frameOffsetsDev) & 3u))
-    return refuse(UNET_ERR_INVALID_ARG, "vertices_dev must be 8-byte aligned, the offsets 4-byte aligned");
+    return op.refuse("a null pointer");
+  if (n <= 0) return op.refuse("n must be positive");
+  if (unet::misaligned(verticesDev, 8) || unet::misaligned(polyOffsetsDev, 4) || unet::misaligned(frameOffsetsDev, 4))
+    return op.refuse("vertices_dev must be 8-byte aligned, the offsets 4-byte aligned");
   if (srcH < 1 || srcW < 1 || outH < 1 || outW < 1 || srcH > unet::ANNOTATE_MAX_SIDE || srcW > unet::ANNOTATE_MAX_SIDE ||
       outH > unet::ANNOTATE_MAX_SIDE || outW > unet::ANNOTATE_MAX_SIDE)
-    return refuse(UNET_ERR_SHAPE, "source and output sizes must be 1 .. 16384");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
+    return op.refuse("source and output sizes must be 1 .. 16384", UNET_ERR_SHAPE);
+  if (int rc = op.on(device)) return rc;
   unet::FillParams p;
   p.vertices = verticesDev, p.polyOffsets = polyOffsetsDev, p.polyValues = polyValuesDev;
   p.frameOffsets = frameOffsetsDev, p.out = masksOutDev;
   p.n = n, p.srcH = srcH, p.srcW = srcW, p.outH = outH, p.outW = outW;
-  e = unet::launch_fill_polygons(p, (hipStream_t)stream);
-  if (e == hipSuccess) return UNET_OK;
-  return unet::op_fail(UNET_ERR_HIP, std::string("unet_fill_polygons_u8_batch: ") + hipGetErrorString(e));
+  return op.done(unet::launch_fill_polygons(p, (hipStream_t)stream));
 }
 
 }  // extern "C"

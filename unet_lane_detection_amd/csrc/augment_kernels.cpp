@@ -14,13 +14,7 @@
 #include "augment_kernels.h"
 #include "hsv8.h"
 
-#include "../../include/unet_hip.h"
-
-#include <string>
-
-namespace unet {
-int op_fail(int status, const std::string& text);   // unet_hip.cpp: the text behind unet_op_last_error
-}
+#include "op_entry.h"
 
 // The model rounds every floating-point operation on its own (numpy has no fused multiply-add); so does this file.
 #pragma clang fp contract(off)
@@ -238,18 +232,18 @@ size_t unet_augment_param_bytes(void) { return sizeof(unet::AugmentParams); }
 int unet_augment_u8(int device, const uint8_t* imagesDev, const uint8_t* masksDev, int nSource, int height, int width,
                     const void* paramsDev, int nOut, int maskThreshold, uint8_t* imagesOutDev, float* targetsOutDev,
                     void* stream) {
+  const unet::OpCall op{"unet_augment_u8"};
   if (!imagesDev || !paramsDev || !imagesOutDev || (masksDev == nullptr) != (targetsOutDev == nullptr) ||
       nOut <= 0 || nSource <= 0)
-    return unet::op_fail(UNET_ERR_INVALID_ARG, "invalid argument: refused by the entry point's checks");
+    return op.refuse("refused by the entry point's checks");
   if (height < unet::AUG_MIN_SIDE || width < unet::AUG_MIN_SIDE || height > unet::AUG_MAX_SIDE || width > unet::AUG_MAX_SIDE)
-    return unet::op_fail(UNET_ERR_SHAPE, "height and width must lie between AUG_MIN_SIDE and AUG_MAX_SIDE");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
-  e = unet::launch_augment(imagesDev, masksDev, nSource, height, width,
+    return op.refuse("height and width must lie between AUG_MIN_SIDE and AUG_MAX_SIDE", UNET_ERR_SHAPE);
+  if (int rc = op.on(device)) return rc;
+  const hipError_t e = unet::launch_augment(imagesDev, masksDev, nSource, height, width,
                                             static_cast<const unet::AugmentParams*>(paramsDev), nOut, maskThreshold,
                                             imagesOutDev, targetsOutDev, (hipStream_t)stream);
-  if (e == hipSuccess) return UNET_OK;
-  return unet::op_fail(e == hipErrorInvalidValue ? UNET_ERR_INVALID_ARG : UNET_ERR_HIP, hipGetErrorString(e));
+  const int rc = op.done(e);
+  return e == hipErrorInvalidValue ? UNET_ERR_INVALID_ARG : rc;   // a grid the launch itself refuses
 }
 
 }  // extern "C"

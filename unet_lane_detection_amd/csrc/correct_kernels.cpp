@@ -27,15 +27,10 @@
 // pixels nor written.
 #include "correct_kernels.h"
 
-#include "../../include/unet_hip.h"
+#include "op_entry.h"
+#include "wave_ops.h"
 
-#include <climits>
 #include <cstring>
-#include <string>
-
-namespace unet {
-int op_fail(int status, const std::string& text);   // unet_hip.cpp: the text behind unet_op_last_error
-}
 
 namespace unet {
 
@@ -115,11 +110,6 @@ __global__ __launch_bounds__(THREADS) void hist_kernel(const Geo g) {
 }
 
 // ---- plan -----------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ u64 shfl_xor64(u64 v, int d) {
-  const uint32_t lo = __shfl_xor((uint32_t)v, d, 64), hi = __shfl_xor((uint32_t)(v >> 32), d, 64);
-  return ((u64)hi << 32) | lo;
-}
 
 // inclusive prefix sums over the block's 256 values, thread v's returned; buf is 2 x 256
 __device__ __forceinline__ u64 block_scan(u64 v, u64 (*buf)[THREADS]) {
@@ -453,14 +443,6 @@ hipError_t launch_correct(const CorrectParams& p, hipStream_t s) {
 
 }  // namespace unet
 
-namespace {
-
-int refuse(const char* what) {
-  return unet::op_fail(UNET_ERR_INVALID_ARG, std::string("invalid argument: unet_correct_u8_batch: ") + what);
-}
-
-}  // namespace
-
 extern "C" {
 
 size_t unet_correct_config_bytes(void) { return sizeof(unet_correct_config); }
@@ -473,43 +455,43 @@ size_t unet_correct_work_bytes(int n, int gridX, int gridY) {
 int unet_correct_u8_batch(int device, const uint8_t* framesDev, int n, int height, int width, int rowStride, int isBgr,
                           const unet_correct_config* cfg, uint8_t* outDev, int outRowStride, void* workDev,
                           size_t workBytes, void* stream) {
-  if (!framesDev || !cfg || !outDev || !workDev) return refuse("a null pointer");
-  if (n <= 0 || height <= 0 || width <= 0) return refuse("n, height and width must be positive");
-  if (height > 16384 || width > 16384) return refuse("height and width must be at most 16384");
-  if ((unsigned long long)n * height * width > (unsigned long long)INT_MAX)
-    return refuse("n * height * width must be smaller than 2^31");
+  const unet::OpCall op{"unet_correct_u8_batch"};
+  if (!framesDev || !cfg || !outDev || !workDev) return op.refuse("a null pointer");
+  if (n <= 0 || height <= 0 || width <= 0) return op.refuse("n, height and width must be positive");
+  if (height > 16384 || width > 16384) return op.refuse("height and width must be at most 16384");
+  if (!unet::fits_int((unsigned long long)n * height * width))
+    return op.refuse("n * height * width must be smaller than 2^31");
   if (rowStride != 0 && (long long)rowStride < 3ll * width)
-    return refuse("row_stride must be 0 (dense) or at least 3 * width");
+    return op.refuse("row_stride must be 0 (dense) or at least 3 * width");
   if (outRowStride != 0 && (long long)outRowStride < 3ll * width)
-    return refuse("out_row_stride must be 0 (dense) or at least 3 * width");
+    return op.refuse("out_row_stride must be 0 (dense) or at least 3 * width");
   const long long stride = rowStride ? (long long)rowStride : 3ll * width;
   const long long ostride = outRowStride ? (long long)outRowStride : 3ll * width;
   if (cfg->grid_x < 1 || cfg->grid_x > 16 || cfg->grid_y < 1 || cfg->grid_y > 16)
-    return refuse("grid_x and grid_y must be 1 .. 16");
+    return op.refuse("grid_x and grid_y must be 1 .. 16");
   const int th = (height + cfg->grid_y - 1) / cfg->grid_y, tw = (width + cfg->grid_x - 1) / cfg->grid_x;
   if ((long long)(cfg->grid_y - 1) * th >= height || (long long)(cfg->grid_x - 1) * tw >= width)
-    return refuse("the grid leaves a tile empty");
-  if (cfg->white_balance != 0 && cfg->white_balance != 1) return refuse("white_balance must be 0 or 1");
-  if (cfg->max_gain < 1 || cfg->max_gain > 8) return refuse("max_gain must be 1 .. 8");
+    return op.refuse("the grid leaves a tile empty");
+  if (cfg->white_balance != 0 && cfg->white_balance != 1) return op.refuse("white_balance must be 0 or 1");
+  if (cfg->max_gain < 1 || cfg->max_gain > 8) return op.refuse("max_gain must be 1 .. 8");
   if (cfg->lo_bp < 0 || cfg->hi_bp < 0 || (long long)cfg->lo_bp + cfg->hi_bp >= 10000)
-    return refuse("lo_bp and hi_bp must not be negative and must sum to less than 10000");
-  if (cfg->clip_q8 < 1 || cfg->clip_q8 > (1 << 24)) return refuse("clip_q8 must be 1 .. 2^24");
+    return op.refuse("lo_bp and hi_bp must not be negative and must sum to less than 10000");
+  if (cfg->clip_q8 < 1 || cfg->clip_q8 > (1 << 24)) return op.refuse("clip_q8 must be 1 .. 2^24");
   if (cfg->dark_limit < 0 || cfg->bright_limit > 255 || cfg->dark_limit > cfg->bright_limit)
-    return refuse("0 <= dark_limit <= bright_limit <= 255");
-  if (reinterpret_cast<uintptr_t>(workDev) & 3u) return refuse("work_dev must be 4-byte aligned");
+    return op.refuse("0 <= dark_limit <= bright_limit <= 255");
+  if (unet::misaligned(workDev, 4)) return op.refuse("work_dev must be 4-byte aligned");
   if (workBytes < unet_correct_work_bytes(n, cfg->grid_x, cfg->grid_y))
-    return refuse("work_bytes is smaller than unet_correct_work_bytes(n, grid_x, grid_y)");
+    return op.refuse("work_bytes is smaller than unet_correct_work_bytes(n, grid_x, grid_y)");
   if (outDev == framesDev) {
-    if (stride != ostride) return refuse("in place (out_dev == frames_dev) needs equal strides");
+    if (stride != ostride) return op.refuse("in place (out_dev == frames_dev) needs equal strides");
   } else {
     // two buffers must not overlap: an overlapping output would be read as input by another block
     const long long inBytes = ((long long)n * height - 1) * stride + 3ll * width;
     const long long outBytes = ((long long)n * height - 1) * ostride + 3ll * width;
     const uintptr_t a = reinterpret_cast<uintptr_t>(framesDev), b = reinterpret_cast<uintptr_t>(outDev);
-    if (a < b + (uintptr_t)outBytes && b < a + (uintptr_t)inBytes) return refuse("out_dev overlaps frames_dev");
+    if (a < b + (uintptr_t)outBytes && b < a + (uintptr_t)inBytes) return op.refuse("out_dev overlaps frames_dev");
   }
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
+  if (int rc = op.on(device)) return rc;
   unet::CorrectParams p;
   p.frames = framesDev, p.out = outDev, p.work = static_cast<uint8_t*>(workDev);
   p.n = n, p.height = height, p.width = width, p.stride = stride, p.ostride = ostride;
@@ -519,9 +501,7 @@ int unet_correct_u8_batch(int device, const uint8_t* framesDev, int n, int heigh
   p.clahe = cfg->clahe ? 1 : 0, p.clipQ8 = cfg->clip_q8, p.onlyFlagged = cfg->only_flagged ? 1 : 0;
   p.darkLimit = cfg->dark_limit, p.brightLimit = cfg->bright_limit;
   memcpy(p.tone, cfg->tone, 256);
-  e = unet::launch_correct(p, (hipStream_t)stream);
-  if (e == hipSuccess) return UNET_OK;
-  return unet::op_fail(UNET_ERR_HIP, std::string("unet_correct_u8_batch: ") + hipGetErrorString(e));
+  return op.done(unet::launch_correct(p, (hipStream_t)stream));
 }
 
 }  // extern "C"

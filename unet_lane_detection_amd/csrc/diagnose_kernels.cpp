@@ -27,16 +27,11 @@
 // No argument the entry points accept makes either kernel read or write outside its buffers.
 #include "diagnose_kernels.h"
 
-#include "../../include/unet_hip.h"
+#include "op_entry.h"
+#include "wave_ops.h"
 
-#include <climits>
 #include <cmath>
 #include <cstring>
-#include <string>
-
-namespace unet {
-int op_fail(int status, const std::string& text);   // unet_hip.cpp: the text behind unet_op_last_error
-}
 
 namespace unet {
 
@@ -267,11 +262,6 @@ __device__ __forceinline__ void prob_add(ProbAcc& p, float s, float threshold) {
   p.frac += (uint32_t)(c * 4294967296.0f);         // exact product below 2^32
 }
 
-__device__ __forceinline__ u64 shfl_xor64(u64 v, int d) {
-  const uint32_t lo = __shfl_xor((uint32_t)v, d, 64), hi = __shfl_xor((uint32_t)(v >> 32), d, 64);
-  return ((u64)hi << 32) | lo;
-}
-
 __global__ __launch_bounds__(THREADS) void prob_stats_kernel(const ProbArgs a) {
   __shared__ uint32_t redk[WAVES][2];
   __shared__ u64 reds[WAVES][3];
@@ -381,49 +371,34 @@ hipError_t launch_prob_stats(const float* scores, int n, unsigned numel, float t
 
 }  // namespace unet
 
-namespace {
-
-int refuse(const char* call, const char* what) {
-  return unet::op_fail(UNET_ERR_INVALID_ARG, std::string("invalid argument: ") + call + ": " + what);
-}
-
-int diagnose_done(const char* call, hipError_t e) {
-  if (e == hipSuccess) return UNET_OK;
-  return unet::op_fail(UNET_ERR_HIP, std::string(call) + ": " + hipGetErrorString(e));
-}
-
-}  // namespace
-
 extern "C" {
 
 int unet_frame_stats_u8_batch(int device, const uint8_t* framesDev, int n, int height, int width, int rowStride,
                               int isBgr, unsigned long long* outDev, void* stream) {
-  static const char* const call = "unet_frame_stats_u8_batch";
-  if (!framesDev || !outDev) return refuse(call, "a null pointer");
-  if (reinterpret_cast<uintptr_t>(outDev) & 7u) return refuse(call, "out_dev must be 8-byte aligned");
-  if (n <= 0 || height <= 0 || width <= 0) return refuse(call, "n, height and width must be positive");
-  if ((unsigned long long)n * height * width > (unsigned long long)INT_MAX)
-    return refuse(call, "n * height * width must be smaller than 2^31");
+  const unet::OpCall op{"unet_frame_stats_u8_batch"};
+  if (!framesDev || !outDev) return op.refuse("a null pointer");
+  if (unet::misaligned(outDev, 8)) return op.refuse("out_dev must be 8-byte aligned");
+  if (n <= 0 || height <= 0 || width <= 0) return op.refuse("n, height and width must be positive");
+  if (!unet::fits_int((unsigned long long)n * height * width))
+    return op.refuse("n * height * width must be smaller than 2^31");
   if (rowStride != 0 && (long long)rowStride < 3ll * width)
-    return refuse(call, "row_stride must be 0 (dense) or at least 3 * width");
+    return op.refuse("row_stride must be 0 (dense) or at least 3 * width");
   const long long stride = rowStride ? (long long)rowStride : 3ll * width;
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
-  return diagnose_done(call, unet::launch_frame_stats(framesDev, n, height, width, stride, isBgr, outDev, (hipStream_t)stream));
+  if (int rc = op.on(device)) return rc;
+  return op.done(unet::launch_frame_stats(framesDev, n, height, width, stride, isBgr, outDev, (hipStream_t)stream));
 }
 
 int unet_prob_stats_f32_batch(int device, const float* scoresDev, int n, size_t numelPerFrame, float threshold,
                               unsigned long long* outDev, void* stream) {
-  static const char* const call = "unet_prob_stats_f32_batch";
-  if (!scoresDev || !outDev) return refuse(call, "a null pointer");
-  if (reinterpret_cast<uintptr_t>(scoresDev) & 3u) return refuse(call, "scores_dev must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(outDev) & 7u) return refuse(call, "out_dev must be 8-byte aligned");
-  if (n <= 0 || numelPerFrame == 0) return refuse(call, "n and numel_per_frame must be positive");
-  if (numelPerFrame > (size_t)INT_MAX) return refuse(call, "numel_per_frame must be smaller than 2^31");
-  if (std::isnan(threshold)) return refuse(call, "threshold must not be a NaN");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
-  return diagnose_done(call, unet::launch_prob_stats(scoresDev, n, (unsigned)numelPerFrame, threshold, outDev, (hipStream_t)stream));
+  const unet::OpCall op{"unet_prob_stats_f32_batch"};
+  if (!scoresDev || !outDev) return op.refuse("a null pointer");
+  if (unet::misaligned(scoresDev, 4)) return op.refuse("scores_dev must be 4-byte aligned");
+  if (unet::misaligned(outDev, 8)) return op.refuse("out_dev must be 8-byte aligned");
+  if (n <= 0 || numelPerFrame == 0) return op.refuse("n and numel_per_frame must be positive");
+  if (!unet::fits_int(numelPerFrame)) return op.refuse("numel_per_frame must be smaller than 2^31");
+  if (std::isnan(threshold)) return op.refuse("threshold must not be a NaN");
+  if (int rc = op.on(device)) return rc;
+  return op.done(unet::launch_prob_stats(scoresDev, n, (unsigned)numelPerFrame, threshold, outDev, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -2,15 +2,10 @@
 // kernels, plain C++, 16-byte loads and stores, integer counters, vector stores and vector atomics only.
 #include "ensemble_kernels.h"
 
-#include "../../include/unet_hip.h"
+#include "op_entry.h"
 
 #include <atomic>
 #include <cmath>
-#include <string>
-
-namespace unet {
-int op_fail(int status, const std::string& text);   // unet_hip.cpp: the text behind unet_op_last_error
-}
 
 // ensemble.combine_model rounds every floating-point operation on its own (numpy has no fused multiply-add); so does
 // this file.  The products and sums below are plain operators under this pragma and not __fmul_rn / __fadd_rn: those
@@ -243,54 +238,47 @@ namespace {
 
 std::atomic<int> g_sweepCombine{1};
 
-int ensemble_done(hipError_t e) {
-  if (e == hipSuccess) return UNET_OK;
-  return unet::op_fail(UNET_ERR_HIP, hipGetErrorString(e));
-}
-
-int refuse(const char* what) { return unet::op_fail(UNET_ERR_INVALID_ARG, std::string("invalid argument: ") + what); }
-
 }  // namespace
 
 extern "C" {
 
 int unet_ensemble_combine(int device, const float* const* probsDev, int k, const float* weightsHost, size_t numel,
                           float threshold, float* probsOutDev, uint8_t* maskOutDev, void* stream) {
-  if (!probsDev) return refuse("a null pointer");
-  if (k < 1 || k > UNET_ENSEMBLE_MAX) return refuse("k must lie in 1 .. UNET_ENSEMBLE_MAX");
-  if (!probsOutDev && !maskOutDev) return refuse("both outputs are null");
-  if (numel == 0) return refuse("numel is 0");
+  const unet::OpCall op{"unet_ensemble_combine"};
+  if (!probsDev) return op.refuse("a null pointer");
+  if (k < 1 || k > UNET_ENSEMBLE_MAX) return op.refuse("k must lie in 1 .. UNET_ENSEMBLE_MAX");
+  if (!probsOutDev && !maskOutDev) return op.refuse("both outputs are null");
+  if (numel == 0) return op.refuse("numel is 0");
   unet::EnsembleMembers m = {};
   for (int j = 0; j < k; ++j) {
-    if (!probsDev[j]) return refuse("a null pointer");
+    if (!probsDev[j]) return op.refuse("a null pointer");
     m.p[j] = probsDev[j];
     m.w[j] = weightsHost ? weightsHost[j] : (float)(1.0 / k);
-    if (!std::isfinite(m.w[j]) || m.w[j] < 0.f) return refuse("every weight must be finite and not negative");
+    if (!std::isfinite(m.w[j]) || m.w[j] < 0.f) return op.refuse("every weight must be finite and not negative");
   }
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
-  return ensemble_done(unet::launch_ensemble_combine(m, k, numel, threshold, probsOutDev, maskOutDev, (hipStream_t)stream));
+  if (int rc = op.on(device)) return rc;
+  return op.done(unet::launch_ensemble_combine(m, k, numel, threshold, probsOutDev, maskOutDev, (hipStream_t)stream));
 }
 
 int unet_score_sweep_accumulate(int device, const float* scoresDev, const void* targetsDev, int targetsAreU8, size_t numel,
                                 const float* thresholdsHost, int nThresholds, unsigned long long* countsDev,
                                 void* stream) {
-  if (!scoresDev || !targetsDev || !thresholdsHost || !countsDev) return refuse("a null pointer");
-  if (numel == 0) return refuse("numel is 0");
-  if (nThresholds < 1 || nThresholds > UNET_SWEEP_MAX) return refuse("n_thresholds must lie in 1 .. UNET_SWEEP_MAX");
+  const unet::OpCall op{"unet_score_sweep_accumulate"};
+  if (!scoresDev || !targetsDev || !thresholdsHost || !countsDev) return op.refuse("a null pointer");
+  if (numel == 0) return op.refuse("numel is 0");
+  if (nThresholds < 1 || nThresholds > UNET_SWEEP_MAX) return op.refuse("n_thresholds must lie in 1 .. UNET_SWEEP_MAX");
   unet::SweepThresholds thr = {};
   for (int j = 0; j < nThresholds; ++j) {
     thr.t[j] = thresholdsHost[j];
     // written so that a NaN on either side refuses
     if (std::isnan(thr.t[j]) || (j > 0 && !(thr.t[j] > thr.t[j - 1])))
-      return refuse("the thresholds must be strictly ascending and free of NaN");
+      return op.refuse("the thresholds must be strictly ascending and free of NaN");
   }
   if (!unet::sweep_numel_supported(numel))
-    return unet::op_fail(UNET_ERR_SHAPE, "numel must stay below 2^41 (the 32-bit counters of a block, sweep_grid)");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
-  return ensemble_done(unet::launch_score_sweep(scoresDev, targetsDev, targetsAreU8 != 0, numel, thr, nThresholds,
-                                                g_sweepCombine.load() != 0, countsDev, (hipStream_t)stream));
+    return op.refuse("numel must stay below 2^41 (the 32-bit counters of a block, sweep_grid)", UNET_ERR_SHAPE);
+  if (int rc = op.on(device)) return rc;
+  return op.done(unet::launch_score_sweep(scoresDev, targetsDev, targetsAreU8 != 0, numel, thr, nThresholds,
+                                          g_sweepCombine.load() != 0, countsDev, (hipStream_t)stream));
 }
 
 int unet_set_sweep_combine(int on) { return g_sweepCombine.exchange(on ? 1 : 0); }

@@ -23,15 +23,9 @@
 #include "follow_kernels.h"
 #include "hsv8.h"
 
-#include "../../include/unet_hip.h"
+#include "op_entry.h"
 
-#include <climits>
 #include <cstring>
-#include <string>
-
-namespace unet {
-int op_fail(int status, const std::string& text);   // unet_hip.cpp: the text behind unet_op_last_error
-}
 
 namespace unet {
 
@@ -294,15 +288,6 @@ hipError_t launch_lane_center(const uint8_t* masks, int n, int height, int width
 
 namespace {
 
-int refuse(const char* call, const char* what) {
-  return unet::op_fail(UNET_ERR_INVALID_ARG, std::string("invalid argument: ") + call + ": " + what);
-}
-
-int follow_done(const char* call, hipError_t e) {
-  if (e == hipSuccess) return UNET_OK;
-  return unet::op_fail(UNET_ERR_HIP, std::string(call) + ": " + hipGetErrorString(e));
-}
-
 bool box_size(int k) { return k == 1 || k == 3 || k == 5 || k == 7; }
 
 }  // namespace
@@ -312,37 +297,34 @@ extern "C" {
 int unet_hsv_lanes_u8_batch(int device, const uint8_t* framesDev, int n, int height, int width, int isBgr,
                             const uint8_t* lowerHost, const uint8_t* upperHost, int closeK, int openK,
                             uint8_t* maskOutDev, void* stream) {
-  static const char* const call = "unet_hsv_lanes_u8_batch";
-  if (!framesDev || !lowerHost || !upperHost || !maskOutDev) return refuse(call, "a null pointer");
-  if (n <= 0 || height <= 0 || width <= 0) return refuse(call, "n, height and width must be positive");
-  if ((unsigned long long)n * height * width > (unsigned long long)INT_MAX)
-    return refuse(call, "n * height * width must be smaller than 2^31");
-  if (!box_size(closeK) || !box_size(openK)) return refuse(call, "close_ksize and open_ksize must be 1, 3, 5 or 7");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
-  return follow_done(call, unet::launch_hsv_lanes(framesDev, n, height, width, isBgr, lowerHost, upperHost, closeK, openK,
-                                                  maskOutDev, (hipStream_t)stream));
+  const unet::OpCall op{"unet_hsv_lanes_u8_batch"};
+  if (!framesDev || !lowerHost || !upperHost || !maskOutDev) return op.refuse("a null pointer");
+  if (n <= 0 || height <= 0 || width <= 0) return op.refuse("n, height and width must be positive");
+  if (!unet::fits_int((unsigned long long)n * height * width))
+    return op.refuse("n * height * width must be smaller than 2^31");
+  if (!box_size(closeK) || !box_size(openK)) return op.refuse("close_ksize and open_ksize must be 1, 3, 5 or 7");
+  if (int rc = op.on(device)) return rc;
+  return op.done(unet::launch_hsv_lanes(framesDev, n, height, width, isBgr, lowerHost, upperHost, closeK, openK, maskOutDev,
+                                        (hipStream_t)stream));
 }
 
 int unet_lane_center_u8_batch(int device, const uint8_t* masksDev, int n, int height, int width, const int* rowsHost,
                               int nRows, int level, uint32_t* outDev, void* stream) {
-  static const char* const call = "unet_lane_center_u8_batch";
-  if (!masksDev || !rowsHost || !outDev) return refuse(call, "a null pointer");
-  if (n <= 0 || height <= 0 || width <= 0) return refuse(call, "n, height and width must be positive");
-  if (width > 65535) return refuse(call, "width must be at most 65535 (the sum of x is a 32-bit integer)");
-  if (nRows < 1 || nRows > UNET_LANE_ROWS_MAX) return refuse(call, "n_rows must lie in 1 .. UNET_LANE_ROWS_MAX");
-  if (level < 0 || level > 255) return refuse(call, "level must lie in 0 .. 255");
-  if ((unsigned long long)n * nRows > (unsigned long long)INT_MAX) return refuse(call, "n * n_rows must be smaller than 2^31");
+  const unet::OpCall op{"unet_lane_center_u8_batch"};
+  if (!masksDev || !rowsHost || !outDev) return op.refuse("a null pointer");
+  if (n <= 0 || height <= 0 || width <= 0) return op.refuse("n, height and width must be positive");
+  if (width > 65535) return op.refuse("width must be at most 65535 (the sum of x is a 32-bit integer)");
+  if (nRows < 1 || nRows > UNET_LANE_ROWS_MAX) return op.refuse("n_rows must lie in 1 .. UNET_LANE_ROWS_MAX");
+  if (level < 0 || level > 255) return op.refuse("level must lie in 0 .. 255");
+  if (!unet::fits_int((unsigned long long)n * nRows)) return op.refuse("n * n_rows must be smaller than 2^31");
   unet::LaneRows rows;   // by value in the kernel's arguments: the caller's array is free once this returns
   memset(&rows, 0, sizeof(rows));
   for (int j = 0; j < nRows; ++j) {
-    if (rowsHost[j] < 0 || rowsHost[j] >= height) return refuse(call, "a scan row outside [0, height)");
+    if (rowsHost[j] < 0 || rowsHost[j] >= height) return op.refuse("a scan row outside [0, height)");
     rows.r[j] = rowsHost[j];
   }
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
-  return follow_done(call, unet::launch_lane_center(masksDev, n, height, width, rows, nRows, level, outDev,
-                                                    (hipStream_t)stream));
+  if (int rc = op.on(device)) return rc;
+  return op.done(unet::launch_lane_center(masksDev, n, height, width, rows, nRows, level, outDev, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -19,14 +19,8 @@
 // elements head + 4v .. head + 4v + 3 < head + 4 nvec <= numel, and the edge threads index below numel by construction.
 #include "grad_kernels.h"
 
-#include "../../include/unet_hip.h"
+#include "op_entry.h"
 
-#include <cstdint>
-#include <string>
-
-namespace unet {
-int op_fail(int status, const std::string& text);   // unet_hip.cpp: the text behind unet_op_last_error
-}
 
 namespace unet {
 
@@ -206,10 +200,6 @@ hipError_t launch_grad_accumulate(float* dst, const float* a, const float* b, si
 
 namespace {
 
-int refuse(const char* what) {
-  return unet::op_fail(UNET_ERR_INVALID_ARG, std::string("invalid argument: unet_grad_accumulate_f32: ") + what);
-}
-
 // [p, p + n) and [q, q + n) share some but not all floats
 bool partly_overlap(const float* p, const float* q, size_t n) {
   if (!p || !q || p == q) return false;
@@ -225,20 +215,18 @@ size_t unet_grad_work_bytes(void) { return unet::grad_work_bytes(); }
 
 int unet_grad_accumulate_f32(int device, float* dst, const float* a, const float* b, size_t numel, double* record,
                              double* work, void* stream) {
-  if (!dst || !a) return refuse("dst and a must not be null");
-  if ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 3u)
-    return refuse("dst, a and b must be 4-byte aligned");
-  if (numel > ((size_t)1 << 48)) return refuse("numel must not exceed 2^48");
-  if (record && !work) return refuse("a record needs the work buffer (unet_grad_work_bytes)");
-  if ((reinterpret_cast<uintptr_t>(record) | reinterpret_cast<uintptr_t>(work)) & 7u)
-    return refuse("record and work must be 8-byte aligned");
+  const unet::OpCall op{"unet_grad_accumulate_f32"};
+  if (!dst || !a) return op.refuse("dst and a must not be null");
+  if (unet::misaligned(dst, 4) || unet::misaligned(a, 4) || unet::misaligned(b, 4))
+    return op.refuse("dst, a and b must be 4-byte aligned");
+  if (numel > ((size_t)1 << 48)) return op.refuse("numel must not exceed 2^48");
+  if (record && !work) return op.refuse("a record needs the work buffer (unet_grad_work_bytes)");
+  if (unet::misaligned(record, 8) || unet::misaligned(work, 8))
+    return op.refuse("record and work must be 8-byte aligned");
   if (partly_overlap(dst, a, numel) || partly_overlap(dst, b, numel))
-    return refuse("dst may be a or b, or apart from them, but not overlap them in part");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
-  e = unet::launch_grad_accumulate(dst, a, b, numel, record, work, (hipStream_t)stream);
-  if (e == hipSuccess) return UNET_OK;
-  return unet::op_fail(UNET_ERR_HIP, std::string("unet_grad_accumulate_f32: ") + hipGetErrorString(e));
+    return op.refuse("dst may be a or b, or apart from them, but not overlap them in part");
+  if (int rc = op.on(device)) return rc;
+  return op.done(unet::launch_grad_accumulate(dst, a, b, numel, record, work, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -54,15 +54,11 @@
 // T_2 <= sum_x x * sum_y y^2 < 2^21 * 2^33 = 2^54.
 #include "label_kernels.h"
 
-#include "../../include/unet_hip.h"
+#include "op_entry.h"
+#include "wave_ops.h"
 
 #include <algorithm>
-#include <climits>
-#include <string>
 
-namespace unet {
-int op_fail(int status, const std::string& text);   // unet_hip.cpp: the text behind unet_op_last_error
-}
 
 namespace unet {
 
@@ -130,17 +126,6 @@ __device__ __forceinline__ void g_union(int32_t* P, int a, int b) {
     if (old >= a || old < 0) return;
     a = old;
   }
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
-  return v;
 }
 
 // ---- 1. the tiles
@@ -615,7 +600,7 @@ unsigned grid_for(long long items) { return (unsigned)std::min<long long>(std::m
 
 size_t label_work_bytes(int n, int height, int width) {
   if (n < 1 || height < 1 || height > LABEL_SIDE_MAX || width < 1 || width > LABEL_SIDE_MAX) return 0;
-  if ((unsigned long long)n * height * width > (unsigned long long)INT_MAX) return 0;
+  if (!fits_int((unsigned long long)n * height * width)) return 0;
   return (((size_t)n * height * 2 * sizeof(uint32_t)) + 255) & ~(size_t)255;
 }
 
@@ -656,22 +641,16 @@ hipError_t launch_keep_components(const int32_t* labels, int n, int height, int 
 
 namespace {
 
-int refuse(const char* call, const char* what) {
-  return unet::op_fail(UNET_ERR_INVALID_ARG, std::string("invalid argument: ") + call + ": " + what);
-}
-
 // the checks both entry points share; nullptr if the shape is in the domain
 const char* bad_shape(int n, int height, int width, int maxComponents) {
   if (n <= 0) return "n must be positive";
   if (height < 1 || height > unet::LABEL_SIDE_MAX) return "height must lie in 1 .. 2048";
   if (width < 1 || width > unet::LABEL_SIDE_MAX) return "width must lie in 1 .. 2048";
-  if ((unsigned long long)n * height * width > (unsigned long long)INT_MAX)
+  if (!unet::fits_int((unsigned long long)n * height * width))
     return "n * height * width must be smaller than 2^31";
   if (maxComponents < 1 || maxComponents > unet::LABEL_COMPONENTS_MAX) return "max_components must lie in 1 .. 65536";
   return nullptr;
 }
-
-bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 }  // namespace
 
@@ -682,42 +661,37 @@ size_t unet_label_work_bytes(int n, int height, int width) { return unet::label_
 int unet_label_u8_batch(int device, const uint8_t* masksDev, int n, int height, int width, int level, int connectivity,
                         int32_t* labelsDev, int maxComponents, unsigned long long* headerDev,
                         unsigned long long* recordsDev, void* workDev, size_t workBytes, void* stream) {
-  const char* call = "unet_label_u8_batch";
-  if (!masksDev || !labelsDev || !headerDev || !recordsDev || !workDev) return refuse(call, "a null pointer");
-  if (const char* why = bad_shape(n, height, width, maxComponents)) return refuse(call, why);
-  if (level < 0 || level > 255) return refuse(call, "level must lie in 0 .. 255");
-  if (connectivity != 4 && connectivity != 8) return refuse(call, "connectivity must be 4 or 8");
+  const unet::OpCall op{"unet_label_u8_batch"};
+  if (!masksDev || !labelsDev || !headerDev || !recordsDev || !workDev) return op.refuse("a null pointer");
+  if (const char* why = bad_shape(n, height, width, maxComponents)) return op.refuse(why);
+  if (level < 0 || level > 255) return op.refuse("level must lie in 0 .. 255");
+  if (connectivity != 4 && connectivity != 8) return op.refuse("connectivity must be 4 or 8");
   if (workBytes < unet::label_work_bytes(n, height, width))
-    return refuse(call, "work_bytes is smaller than unet_label_work_bytes(n, height, width)");
-  if (misaligned(labelsDev, 4) || misaligned(workDev, 4) || misaligned(headerDev, 8) || misaligned(recordsDev, 8))
-    return refuse(call, "labels_dev and work_dev must be 4-byte aligned, header_dev and records_dev 8-byte aligned");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
-  e = unet::launch_label(masksDev, n, height, width, level, connectivity, labelsDev, maxComponents, headerDev,
-                         recordsDev, workDev, (hipStream_t)stream);
-  if (e == hipSuccess) return UNET_OK;
-  return unet::op_fail(UNET_ERR_HIP, std::string(call) + ": " + hipGetErrorString(e));
+    return op.refuse("work_bytes is smaller than unet_label_work_bytes(n, height, width)");
+  if (unet::misaligned(labelsDev, 4) || unet::misaligned(workDev, 4) || unet::misaligned(headerDev, 8) ||
+      unet::misaligned(recordsDev, 8))
+    return op.refuse("labels_dev and work_dev must be 4-byte aligned, header_dev and records_dev 8-byte aligned");
+  if (int rc = op.on(device)) return rc;
+  return op.done(unet::launch_label(masksDev, n, height, width, level, connectivity, labelsDev, maxComponents, headerDev,
+                                    recordsDev, workDev, (hipStream_t)stream));
 }
 
 int unet_keep_components_u8_batch(int device, const int32_t* labelsDev, int n, int height, int width,
                                   const unsigned long long* headerDev, const unsigned long long* recordsDev,
                                   int maxComponents, int minArea, int minHeight, int minWidth, int keepLargest,
                                   uint8_t* keepOutDev, uint8_t* maskOutDev, void* stream) {
-  const char* call = "unet_keep_components_u8_batch";
-  if (!labelsDev || !headerDev || !recordsDev || !keepOutDev || !maskOutDev) return refuse(call, "a null pointer");
-  if (const char* why = bad_shape(n, height, width, maxComponents)) return refuse(call, why);
-  if (minArea < 0) return refuse(call, "min_area must not be negative");
-  if (minHeight < 0) return refuse(call, "min_height must not be negative");
-  if (minWidth < 0) return refuse(call, "min_width must not be negative");
-  if (keepLargest < 0) return refuse(call, "keep_largest must not be negative");
-  if (misaligned(labelsDev, 4) || misaligned(headerDev, 8) || misaligned(recordsDev, 8))
-    return refuse(call, "labels_dev must be 4-byte aligned, header_dev and records_dev 8-byte aligned");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
-  e = unet::launch_keep_components(labelsDev, n, height, width, headerDev, recordsDev, maxComponents, minArea, minHeight,
-                                   minWidth, keepLargest, keepOutDev, maskOutDev, (hipStream_t)stream);
-  if (e == hipSuccess) return UNET_OK;
-  return unet::op_fail(UNET_ERR_HIP, std::string(call) + ": " + hipGetErrorString(e));
+  const unet::OpCall op{"unet_keep_components_u8_batch"};
+  if (!labelsDev || !headerDev || !recordsDev || !keepOutDev || !maskOutDev) return op.refuse("a null pointer");
+  if (const char* why = bad_shape(n, height, width, maxComponents)) return op.refuse(why);
+  if (minArea < 0) return op.refuse("min_area must not be negative");
+  if (minHeight < 0) return op.refuse("min_height must not be negative");
+  if (minWidth < 0) return op.refuse("min_width must not be negative");
+  if (keepLargest < 0) return op.refuse("keep_largest must not be negative");
+  if (unet::misaligned(labelsDev, 4) || unet::misaligned(headerDev, 8) || unet::misaligned(recordsDev, 8))
+    return op.refuse("labels_dev must be 4-byte aligned, header_dev and records_dev 8-byte aligned");
+  if (int rc = op.on(device)) return rc;
+  return op.done(unet::launch_keep_components(labelsDev, n, height, width, headerDev, recordsDev, maxComponents, minArea,
+                                              minHeight, minWidth, keepLargest, keepOutDev, maskOutDev, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -25,14 +25,9 @@
 // [frame][lane][y < height], histogram indices below width.
 #include "lanefit_kernels.h"
 
-#include "../../include/unet_hip.h"
+#include "op_entry.h"
+#include "wave_ops.h"
 
-#include <climits>
-#include <string>
-
-namespace unet {
-int op_fail(int status, const std::string& text);   // unet_hip.cpp: the text behind unet_op_last_error
-}
 
 namespace unet {
 
@@ -89,12 +84,6 @@ __device__ __forceinline__ void add_row(Moments& m, uint32_t cnt, uint32_t sx, i
   m.s0 += c, m.s1 += c * y, m.s2 += c * y2, m.s3 += c * (y2 * y), m.s4 += c * (y2 * y2);
   m.t0 += s, m.t1 += s * y, m.t2 += s * y2;
   m.ymin = min(m.ymin, (uint32_t)yy), m.ymax = max(m.ymax, (uint32_t)yy);
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(THREADS) void lane_fit_kernel(const FitArgs a) {
@@ -277,35 +266,25 @@ hipError_t launch_lane_fit(const uint8_t* masks, int n, int height, int width, i
 
 }  // namespace unet
 
-namespace {
-
-int refuse(const char* what) {
-  return unet::op_fail(UNET_ERR_INVALID_ARG, std::string("invalid argument: unet_lane_fit_u8_batch: ") + what);
-}
-
-}  // namespace
-
 extern "C" {
 
 int unet_lane_fit_u8_batch(int device, const uint8_t* masksDev, int n, int height, int width, int level, int nWindows,
                            int margin, int minPixels, const int32_t* priorDev, unsigned long long* outDev, void* stream) {
-  if (!masksDev || !outDev) return refuse("a null pointer");
-  if (n <= 0) return refuse("n must be positive");
-  if (height < 1 || height > unet::LANE_FIT_HEIGHT_MAX) return refuse("height must lie in 1 .. 2048");
-  if (width < 1 || width > unet::LANE_FIT_WIDTH_MAX) return refuse("width must lie in 1 .. 8192");
-  if ((unsigned long long)n * height * width > (unsigned long long)INT_MAX)
-    return refuse("n * height * width must be smaller than 2^31");
-  if (level < 0 || level > 255) return refuse("level must lie in 0 .. 255");
+  const unet::OpCall op{"unet_lane_fit_u8_batch"};
+  if (!masksDev || !outDev) return op.refuse("a null pointer");
+  if (n <= 0) return op.refuse("n must be positive");
+  if (height < 1 || height > unet::LANE_FIT_HEIGHT_MAX) return op.refuse("height must lie in 1 .. 2048");
+  if (width < 1 || width > unet::LANE_FIT_WIDTH_MAX) return op.refuse("width must lie in 1 .. 8192");
+  if (!unet::fits_int((unsigned long long)n * height * width))
+    return op.refuse("n * height * width must be smaller than 2^31");
+  if (level < 0 || level > 255) return op.refuse("level must lie in 0 .. 255");
   if (nWindows < 1 || nWindows > UNET_LANE_FIT_WINDOWS_MAX || nWindows > height)
-    return refuse("n_windows must lie in 1 .. min(height, UNET_LANE_FIT_WINDOWS_MAX)");
-  if (margin < 1 || margin > unet::LANE_FIT_MARGIN_MAX) return refuse("margin must lie in 1 .. 512");
-  if (minPixels < 0) return refuse("min_pixels must not be negative");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
-  e = unet::launch_lane_fit(masksDev, n, height, width, level, nWindows, margin, minPixels, priorDev, outDev,
-                            (hipStream_t)stream);
-  if (e == hipSuccess) return UNET_OK;
-  return unet::op_fail(UNET_ERR_HIP, std::string("unet_lane_fit_u8_batch: ") + hipGetErrorString(e));
+    return op.refuse("n_windows must lie in 1 .. min(height, UNET_LANE_FIT_WINDOWS_MAX)");
+  if (margin < 1 || margin > unet::LANE_FIT_MARGIN_MAX) return op.refuse("margin must lie in 1 .. 512");
+  if (minPixels < 0) return op.refuse("min_pixels must not be negative");
+  if (int rc = op.on(device)) return rc;
+  return op.done(unet::launch_lane_fit(masksDev, n, height, width, level, nWindows, margin, minPixels, priorDev, outDev,
+                                       (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -17,16 +17,12 @@
 // No atomics, no workgroup waits for another, no global scratch.
 #include "laneview_kernels.h"
 
+#include "op_entry.h"
 #include "video_kernels.h"
 #include "warp_sample.h"
 
-#include <climits>
 #include <cmath>
-#include <string>
 
-namespace unet {
-int op_fail(int status, const std::string& text);   // unet_hip.cpp: the text behind unet_op_last_error
-}
 
 // The model rounds every floating-point operation on its own (numpy has no fused multiply-add); so does this file.
 #pragma clang fp contract(off)
@@ -205,14 +201,6 @@ hipError_t launch_lane_view(const uint8_t* frames, int n, int height, int width,
 
 }  // namespace unet
 
-namespace {
-
-int refuse(const char* what) {
-  return unet::op_fail(UNET_ERR_INVALID_ARG, std::string("invalid argument: unet_lane_view_u8_batch: ") + what);
-}
-
-}  // namespace
-
 extern "C" {
 
 size_t unet_lane_view_style_bytes(void) { return sizeof(unet_lane_view_style); }
@@ -221,22 +209,23 @@ int unet_lane_view_u8_batch(int device, const uint8_t* framesDev, int n, int hei
                             const double m[9], int warpW, int warpH, const uint8_t* masksDev, int level,
                             const long long* curvesDev, int k, const unet_lane_view_style* style, uint8_t* viewOutDev,
                             uint8_t* layersOutDev, void* stream) {
-  if (!framesDev || !m) return refuse("a null pointer (frames_dev, m)");
-  if (!viewOutDev && !layersOutDev) return refuse("view_out_dev and layers_out_dev must not both be null");
-  if (n <= 0) return refuse("n must be positive");
-  if (height < 1 || height > unet::LANE_VIEW_SIZE_MAX) return refuse("height must lie in 1 .. 4096");
-  if (width < 1 || width > unet::LANE_VIEW_SIZE_MAX) return refuse("width must lie in 1 .. 4096");
-  if (step < 3 * width) return refuse("step must be at least 3 * width");
-  if ((unsigned long long)n * height * step > (unsigned long long)INT_MAX)
-    return refuse("n * height * step must be smaller than 2^31");
-  if (warpW < 1 || warpW > unet::LANE_VIEW_WARP_W_MAX) return refuse("warp_w must lie in 1 .. 8192");
-  if (warpH < 1 || warpH > unet::LANE_VIEW_WARP_H_MAX) return refuse("warp_h must lie in 1 .. 2048");
-  if (level < 0 || level > 255) return refuse("level must lie in 0 .. 255");
-  if (k < 0 || k > UNET_LANE_VIEW_MAX) return refuse("k must lie in 0 .. UNET_LANE_VIEW_MAX");
-  if ((k == 0) != (curvesDev == nullptr)) return refuse("k must be 0 exactly when curves_dev is null");
-  if (reinterpret_cast<uintptr_t>(curvesDev) & 7u) return refuse("curves_dev must be 8-byte aligned");
+  const unet::OpCall op{"unet_lane_view_u8_batch"};
+  if (!framesDev || !m) return op.refuse("a null pointer (frames_dev, m)");
+  if (!viewOutDev && !layersOutDev) return op.refuse("view_out_dev and layers_out_dev must not both be null");
+  if (n <= 0) return op.refuse("n must be positive");
+  if (height < 1 || height > unet::LANE_VIEW_SIZE_MAX) return op.refuse("height must lie in 1 .. 4096");
+  if (width < 1 || width > unet::LANE_VIEW_SIZE_MAX) return op.refuse("width must lie in 1 .. 4096");
+  if (step < 3 * width) return op.refuse("step must be at least 3 * width");
+  if (!unet::fits_int((unsigned long long)n * height * step))
+    return op.refuse("n * height * step must be smaller than 2^31");
+  if (warpW < 1 || warpW > unet::LANE_VIEW_WARP_W_MAX) return op.refuse("warp_w must lie in 1 .. 8192");
+  if (warpH < 1 || warpH > unet::LANE_VIEW_WARP_H_MAX) return op.refuse("warp_h must lie in 1 .. 2048");
+  if (level < 0 || level > 255) return op.refuse("level must lie in 0 .. 255");
+  if (k < 0 || k > UNET_LANE_VIEW_MAX) return op.refuse("k must lie in 0 .. UNET_LANE_VIEW_MAX");
+  if ((k == 0) != (curvesDev == nullptr)) return op.refuse("k must be 0 exactly when curves_dev is null");
+  if (unet::misaligned(curvesDev, 8)) return op.refuse("curves_dev must be 8-byte aligned");
   for (int i = 0; i < 9; ++i)
-    if (!std::isfinite(m[i])) return refuse("all nine entries of m must be finite");
+    if (!std::isfinite(m[i])) return op.refuse("all nine entries of m must be finite");
   unet_lane_view_style st;
   if (style) {
     st = *style;
@@ -248,15 +237,12 @@ int unet_lane_view_u8_batch(int device, const uint8_t* framesDev, int n, int hei
     st.layers = UNET_LANE_VIEW_AREA | UNET_LANE_VIEW_MARKING;
   }
   if (!std::isfinite(st.alpha) || !std::isfinite(st.beta) || !std::isfinite(st.gamma))
-    return refuse("alpha, beta and gamma must be finite");
-  if (st.thickness < 1 || st.thickness > unet::LANE_VIEW_THICKNESS_MAX) return refuse("thickness must lie in 1 .. 64");
-  if (st.layers & ~(UNET_LANE_VIEW_AREA | UNET_LANE_VIEW_MARKING)) return refuse("an unknown bit in style->layers");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
-  e = unet::launch_lane_view(framesDev, n, height, width, step, m, warpW, warpH, masksDev, level, curvesDev, k, st,
-                             viewOutDev, layersOutDev, (hipStream_t)stream);
-  if (e == hipSuccess) return UNET_OK;
-  return unet::op_fail(UNET_ERR_HIP, std::string("unet_lane_view_u8_batch: ") + hipGetErrorString(e));
+    return op.refuse("alpha, beta and gamma must be finite");
+  if (st.thickness < 1 || st.thickness > unet::LANE_VIEW_THICKNESS_MAX) return op.refuse("thickness must lie in 1 .. 64");
+  if (st.layers & ~(UNET_LANE_VIEW_AREA | UNET_LANE_VIEW_MARKING)) return op.refuse("an unknown bit in style->layers");
+  if (int rc = op.on(device)) return rc;
+  return op.done(unet::launch_lane_view(framesDev, n, height, width, step, m, warpW, warpH, masksDev, level, curvesDev, k, st,
+                                        viewOutDev, layersOutDev, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -51,6 +51,7 @@
 #include "camera_stage.h"
 #include "calib_kernels.h"
 #include "conv_h16.h"
+#include "op_entry.h"
 
 namespace {
 
@@ -1073,9 +1074,9 @@ int unet_debug_set_error_block(unet_handle_t h, int word, unsigned value) {
 
 static thread_local std::string g_opErr;
 
-// for the handle-less entry points of the other translation units (augment_kernels.cpp); not exported
+// declared in op_entry.h for the handle-less entry points of the *_kernels.cpp translation units; not exported
 namespace unet {
-__attribute__((visibility("hidden"))) int op_fail(int status, const std::string& text) {
+int op_fail(int status, const std::string& text) {
   g_opErr = text;
   return status;
 }

@@ -12,16 +12,11 @@
 // outside its buffers.
 #include "video_kernels.h"
 
-#include "../../include/unet_hip.h"
+#include "op_entry.h"
 
-#include <climits>
 #include <cmath>
 #include <cstring>
-#include <string>
 
-namespace unet {
-int op_fail(int status, const std::string& text);   // unet_hip.cpp: the text behind unet_op_last_error
-}
 
 // The model rounds every floating-point operation on its own (numpy has no fused multiply-add); so does this file.
 #pragma clang fp contract(off)
@@ -276,56 +271,44 @@ hipError_t launch_overlay_batch(const uint8_t* frames, int n, int height, int wi
 
 }  // namespace unet
 
-namespace {
-
-// one image of either side must stay inside an int's worth of bytes (the kernels' row offsets are ints)
-bool image_fits(int h, int w, int cn) { return (unsigned long long)h * w * cn <= (unsigned long long)INT_MAX; }
-
-int video_done(hipError_t e) {
-  if (e == hipSuccess) return UNET_OK;
-  return unet::op_fail(UNET_ERR_HIP, hipGetErrorString(e));
-}
-
-}  // namespace
-
 extern "C" {
 
 int unet_resize_u8_batch(int device, const uint8_t* srcDev, int n, int height, int width, int channels, int swapRB,
                          int outW, int outH, uint8_t* dstDev, void* stream) {
-  if (!srcDev || !dstDev) return unet::op_fail(UNET_ERR_INVALID_ARG, "invalid argument: a null pointer");
+  const unet::OpCall op{"unet_resize_u8_batch"};
+  if (!srcDev || !dstDev) return op.refuse("a null pointer");
   if (n <= 0 || height <= 0 || width <= 0 || outW <= 0 || outH <= 0)
-    return unet::op_fail(UNET_ERR_INVALID_ARG, "invalid argument: n and every size must be positive");
-  if (channels != 1 && channels != 3) return unet::op_fail(UNET_ERR_INVALID_ARG, "invalid argument: channels must be 1 or 3");
-  if (swapRB && channels != 3) return unet::op_fail(UNET_ERR_INVALID_ARG, "invalid argument: swap_rb needs 3 channels");
-  if (!image_fits(height, width, channels) || !image_fits(outH, outW, channels))
-    return unet::op_fail(UNET_ERR_SHAPE, "an image must be smaller than 2^31 bytes");
+    return op.refuse("n and every size must be positive");
+  if (channels != 1 && channels != 3) return op.refuse("channels must be 1 or 3");
+  if (swapRB && channels != 3) return op.refuse("swap_rb needs 3 channels");
+  // one image of either side must stay inside an int's worth of bytes (the kernels' row offsets are ints)
+  if (!unet::fits_int((unsigned long long)height * width * channels) ||
+      !unet::fits_int((unsigned long long)outH * outW * channels))
+    return op.refuse("an image must be smaller than 2^31 bytes", UNET_ERR_SHAPE);
   if ((height != outH || width != outW) && outW > unet::VIDEO_MAX_RESIZE_WIDTH)
-    return unet::op_fail(UNET_ERR_SHAPE, "the destination of a resize is at most VIDEO_MAX_RESIZE_WIDTH wide");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
-  return video_done(unet::launch_resize_batch(srcDev, n, height, width, channels, swapRB, outW, outH, dstDev,
-                                              (hipStream_t)stream));
+    return op.refuse("the destination of a resize is at most VIDEO_MAX_RESIZE_WIDTH wide", UNET_ERR_SHAPE);
+  if (int rc = op.on(device)) return rc;
+  return op.done(unet::launch_resize_batch(srcDev, n, height, width, channels, swapRB, outW, outH, dstDev, (hipStream_t)stream));
 }
 
 int unet_overlay_u8_batch(int device, const uint8_t* framesDev, int n, int height, int width, const uint8_t* masksDev,
                           int maskH, int maskW, const uint8_t* lutHost, float alpha, float beta, float gamma,
                           uint8_t* overlayOutDev, uint8_t* maskOutDev, void* stream) {
-  if (!framesDev || !masksDev || !lutHost || !overlayOutDev)
-    return unet::op_fail(UNET_ERR_INVALID_ARG, "invalid argument: a null pointer");
+  const unet::OpCall op{"unet_overlay_u8_batch"};
+  if (!framesDev || !masksDev || !lutHost || !overlayOutDev) return op.refuse("a null pointer");
   if (n <= 0 || height <= 0 || width <= 0 || maskH <= 0 || maskW <= 0)
-    return unet::op_fail(UNET_ERR_INVALID_ARG, "invalid argument: n and every size must be positive");
+    return op.refuse("n and every size must be positive");
   if (!std::isfinite(alpha) || !std::isfinite(beta) || !std::isfinite(gamma))
-    return unet::op_fail(UNET_ERR_INVALID_ARG, "invalid argument: alpha, beta and gamma must be finite");
-  if (!image_fits(height, width, 3) || !image_fits(maskH, maskW, 1))
-    return unet::op_fail(UNET_ERR_SHAPE, "an image must be smaller than 2^31 bytes");
+    return op.refuse("alpha, beta and gamma must be finite");
+  if (!unet::fits_int(3ull * height * width) || !unet::fits_int((unsigned long long)maskH * maskW))
+    return op.refuse("an image must be smaller than 2^31 bytes", UNET_ERR_SHAPE);
   if ((height != maskH || width != maskW) && width > unet::VIDEO_MAX_RESIZE_WIDTH)
-    return unet::op_fail(UNET_ERR_SHAPE, "the destination of a resize is at most VIDEO_MAX_RESIZE_WIDTH wide");
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return unet::op_fail(UNET_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
+    return op.refuse("the destination of a resize is at most VIDEO_MAX_RESIZE_WIDTH wide", UNET_ERR_SHAPE);
+  if (int rc = op.on(device)) return rc;
   unet::VideoLut lut;   // by value in the kernel's arguments: the caller's table is free once this returns
   memcpy(lut.w, lutHost, sizeof(lut.w));
-  return video_done(unet::launch_overlay_batch(framesDev, n, height, width, masksDev, maskH, maskW, lut, alpha, beta,
-                                               gamma, overlayOutDev, maskOutDev, (hipStream_t)stream));
+  return op.done(unet::launch_overlay_batch(framesDev, n, height, width, masksDev, maskH, maskW, lut, alpha, beta, gamma,
+                                            overlayOutDev, maskOutDev, (hipStream_t)stream));
 }
 
 }  // extern "C"

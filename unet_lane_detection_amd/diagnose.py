@@ -18,7 +18,6 @@ The arithmetic is stated in include/unet_hip.h and, in numpy, in tests/diagnose_
 """
 from __future__ import annotations
 
-import ctypes as C
 import inspect
 
 import numpy as np
@@ -28,14 +27,6 @@ from . import _lib
 
 FRAME_WORDS, PROB_WORDS = 8, 4
 DARK_LIMIT, BRIGHT_LIMIT, BLUR_LIMIT = 50.0, 200.0, 100.0     # the reference's
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _device_of(t, device):
@@ -131,9 +122,8 @@ def frame_records(frames_dev, n, height, width, row_stride=0, bgr=True, out=None
         raise ValueError("the frames tensor is shorter than n * height rows of row_stride bytes")
     if out is None:
         out = torch.empty((int(n), FRAME_WORDS), dtype=torch.int64, device=frames_dev.device)
-    rc = _lib.load().unet_frame_stats_u8_batch(frames_dev.device.index, _ptr(frames_dev), int(n), int(height), int(width),
-                                               int(row_stride or 0), 1 if bgr else 0, _ptr(out), _stream(frames_dev.device))
-    _lib.check(rc, "unet_frame_stats_u8_batch")
+    _lib.call("unet_frame_stats_u8_batch", frames_dev.device, frames_dev, int(n), int(height), int(width),
+              int(row_stride or 0), 1 if bgr else 0, out)
     return out
 
 
@@ -222,9 +212,7 @@ def prob_records(probs_dev, threshold=0.5, out=None):
     numel = probs_dev.numel() // n
     if out is None:
         out = torch.empty((n, PROB_WORDS), dtype=torch.int64, device=probs_dev.device)
-    rc = _lib.load().unet_prob_stats_f32_batch(probs_dev.device.index, _ptr(probs_dev), n, numel, float(threshold),
-                                               _ptr(out), _stream(probs_dev.device))
-    _lib.check(rc, "unet_prob_stats_f32_batch")
+    _lib.call("unet_prob_stats_f32_batch", probs_dev.device, probs_dev, n, numel, float(threshold), out)
     return out
 
 

@@ -83,11 +83,7 @@ def combine(probs_list, weights=None, threshold=0.5, return_probs=True, return_m
         w = (C.c_float * k)(*[float(v) for v in wa])
     out = torch.empty(shape, dtype=torch.float32, device=dev) if return_probs else None
     mask = torch.empty(shape, dtype=torch.uint8, device=dev) if return_mask else None
-    rc = _lib.load().unet_ensemble_combine(dev.index, ptrs, k, w, ps[0].numel(), float(threshold),
-                                           C.c_void_p(out.data_ptr() if return_probs else 0),
-                                           C.c_void_p(mask.data_ptr() if return_mask else 0),
-                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    _lib.check(rc, "unet_ensemble_combine")
+    _lib.call("unet_ensemble_combine", dev, ptrs, k, w, ps[0].numel(), float(threshold), out, mask)
     if return_probs and return_mask:
         return out, mask
     return out if return_probs else mask
@@ -191,7 +187,7 @@ class Ensemble:
 
         from . import _lib, metrics
         return metrics.sweep_batches(_lib.load(), self.device, frames, targets, batch, thresholds, "probability",
-                                     lambda: C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),
+                                     lambda: _lib.stream(self.device),
                                      lambda f: self.run_u8(f) if f.dtype == torch.uint8 else self.forward(f))
 
     # ---- status and lifetime ---------------------------------------------------------------------------------------

@@ -28,14 +28,6 @@ LANE_ROWS_MAX = 64      # UNET_LANE_ROWS_MAX
 BOX_SIZES = (1, 3, 5, 7)
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 class HSVLaneExtractor:
     """The reference's colour-threshold lane extractor on the device; the defaults are its constants."""
 
@@ -60,10 +52,9 @@ class HSVLaneExtractor:
         frames = frames.to(self.device).contiguous()
         n, h, w = (int(v) for v in frames.shape[:3])
         out = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
-        rc = self._lib.unet_hsv_lanes_u8_batch(self.device.index, _ptr(frames), n, h, w, 1 if bgr else 0,
-                                               self.lower.ctypes.data_as(C.c_void_p), self.upper.ctypes.data_as(C.c_void_p),
-                                               self.close_ksize, self.open_ksize, _ptr(out), _stream(self.device))
-        _lib.check(rc, "unet_hsv_lanes_u8_batch")
+        _lib.call("unet_hsv_lanes_u8_batch", self.device, frames, n, h, w, 1 if bgr else 0,
+                  self.lower.ctypes.data_as(C.c_void_p), self.upper.ctypes.data_as(C.c_void_p), self.close_ksize,
+                  self.open_ksize, out)
         return out
 
     def evaluate(self, frames, targets, batch=None, bgr=True):
@@ -72,7 +63,7 @@ class HSVLaneExtractor:
         IoU, precision, recall and F1 next to `UNetHIP.sweep(...).at(0.5)`."""
         from . import metrics
         return metrics.sweep_batches(self._lib, self.device, frames, targets, batch, (0.5,), "probability",
-                                     lambda: _stream(self.device),
+                                     lambda: _lib.stream(self.device),
                                      lambda f: self.extract(f, bgr=bgr).to(torch.float32) / 255.0)
 
 
@@ -89,10 +80,8 @@ def lane_sums(masks_dev, scan_rows, level=127):
     n, h, w = (int(v) for v in masks_dev.shape)
     rows = np.ascontiguousarray(scan_rows, dtype=np.int32).reshape(-1)
     out = torch.empty((n, rows.size, 2), dtype=torch.int32, device=masks_dev.device)   # the kernel's uint32 pairs
-    rc = _lib.load().unet_lane_center_u8_batch(masks_dev.device.index, _ptr(masks_dev), n, h, w,
-                                               rows.ctypes.data_as(C.POINTER(C.c_int)), int(rows.size), int(level),
-                                               _ptr(out), _stream(masks_dev.device))
-    _lib.check(rc, "unet_lane_center_u8_batch")
+    _lib.call("unet_lane_center_u8_batch", masks_dev.device, masks_dev, n, h, w, rows.ctypes.data_as(C.POINTER(C.c_int)),
+              int(rows.size), int(level), out)
     return out
 
 
@@ -229,12 +218,9 @@ class LaneFollowPipeline:
                                           width=msg.width)
         frame = torch.empty((1, out_size[1], out_size[0], 3), dtype=torch.uint8, device=self.stage.device)
         minv = np.ascontiguousarray(np.linalg.inv(self.matrix))
-        rc = self.stage._lib.unet_ipm_prestage_u8(self.stage.device.index, _ptr(rows), msg.height, msg.width, msg.step,
-                                                  1 if msg.encoding == "bgr8" else 0,
-                                                  minv.ctypes.data_as(C.POINTER(C.c_double)), self.warp_size[0],
-                                                  self.warp_size[1], out_size[0], out_size[1], _ptr(frame),
-                                                  self.stage._stream())
-        _lib.check(rc, "unet_ipm_prestage_u8")
+        _lib.call("unet_ipm_prestage_u8", self.stage.device, rows, msg.height, msg.width, msg.step,
+                  1 if msg.encoding == "bgr8" else 0, minv.ctypes.data_as(C.POINTER(C.c_double)), self.warp_size[0],
+                  self.warp_size[1], out_size[0], out_size[1], frame)
         return frame
 
     def mask_on_device(self, msg):

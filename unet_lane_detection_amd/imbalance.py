@@ -18,14 +18,11 @@ import numpy as np
 def positive_counts(masks_u8, threshold=127, device=0):
     """masks_u8: (n, ...) uint8, numpy array or torch tensor (host or device) -> int64 numpy array of n counts of
     pixels with mask > threshold.  One device pass, exact."""
-    import ctypes as C
-
     import torch
 
     from . import _lib
     if not torch.cuda.is_available():
         raise RuntimeError("positive_counts needs a HIP device; there is no CPU fallback (pass counts= to the host helpers)")
-    lib = _lib.load()
     m = torch.as_tensor(masks_u8)
     if m.dtype != torch.uint8:
         raise TypeError(f"masks must be uint8, got {m.dtype}")
@@ -36,10 +33,7 @@ def positive_counts(masks_u8, threshold=127, device=0):
     m = m.contiguous()
     n = int(m.shape[0])
     counts = torch.empty(n, dtype=torch.int64, device=m.device)
-    stream = C.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)
-    rc = lib.unet_mask_positive_counts(m.device.index, C.c_void_p(m.data_ptr()), n, m.numel() // n, int(threshold),
-                                       C.c_void_p(counts.data_ptr()), stream)
-    _lib.check(rc, "unet_mask_positive_counts")
+    _lib.call("unet_mask_positive_counts", m.device, m, n, m.numel() // n, int(threshold), counts)
     return counts.cpu().numpy()
 
 

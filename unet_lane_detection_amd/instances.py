@@ -21,7 +21,6 @@ numbering is unpinned.  No CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
@@ -32,14 +31,6 @@ from .lanefit import FIT_WORDS, FitConfig, LaneFit
 
 LABEL_WORDS = 16          # UNET_LABEL_WORDS
 COMPONENTS_MAX = 65536
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 @dataclass(frozen=True)
@@ -188,10 +179,8 @@ def label_records(masks_dev, level=127, connectivity=8, max_components=1024):
     labels = torch.empty((n, h, w), dtype=torch.int32, device=dev)
     header = torch.empty((n, 4), dtype=torch.int64, device=dev)
     records = torch.empty((n, cap, LABEL_WORDS), dtype=torch.int64, device=dev)
-    rc = _lib.load().unet_label_u8_batch(dev.index, _ptr(masks_dev), n, h, w, int(level), int(connectivity),
-                                         _ptr(labels), cap, _ptr(header), _ptr(records), _ptr(work), work.numel(),
-                                         _stream(dev))
-    _lib.check(rc, "unet_label_u8_batch")
+    _lib.call("unet_label_u8_batch", dev, masks_dev, n, h, w, int(level), int(connectivity), labels, cap, header, records,
+              work, work.numel())
     return labels, header, records
 
 
@@ -219,10 +208,8 @@ def clean(masks_dev, cfg=CleanConfig()):
     dev = labels.device
     keep = torch.empty((n, cap), dtype=torch.uint8, device=dev)
     out = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
-    rc = _lib.load().unet_keep_components_u8_batch(dev.index, _ptr(labels), n, h, w, _ptr(header), _ptr(records), cap,
-                                                   int(cfg.min_area), int(cfg.min_height), int(cfg.min_width),
-                                                   int(cfg.keep_largest), _ptr(keep), _ptr(out), _stream(dev))
-    _lib.check(rc, "unet_keep_components_u8_batch")
+    _lib.call("unet_keep_components_u8_batch", dev, labels, n, h, w, header, records, cap, int(cfg.min_area),
+              int(cfg.min_height), int(cfg.min_width), int(cfg.keep_largest), keep, out)
     return out, _to_components(labels, header, records, h, w), keep
 
 

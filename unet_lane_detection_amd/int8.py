@@ -80,8 +80,7 @@ def minmax_pass(float_model, frames, batch=8):
     for i in range(0, frames.shape[0], batch):
         f = frames[i:i + batch].to(float_model.device).contiguous()
         n, hh, ww, _ = f.shape
-        rc = lib.unet_forward_u8_ranges(h, C.c_void_p(f.data_ptr()), n, hh, ww, buf,
-                                        C.c_void_p(torch.cuda.current_stream(float_model.device).cuda_stream))
+        rc = lib.unet_forward_u8_ranges(h, _lib.ptr(f), n, hh, ww, buf, _lib.stream(float_model.device))
         _lib.check(rc, "unet_forward_u8_ranges", h)
         r = np.frombuffer(buf, dtype=np.float32).reshape(nt, 2)
         lo = np.minimum(lo, r[:, 0])
@@ -105,9 +104,8 @@ def histogram_pass(float_model, frames, spans, bins=quant.HIST_BINS, batch=8):
     for i in range(0, frames.shape[0], batch):
         f = frames[i:i + batch].to(float_model.device).contiguous()
         n, hh, ww, _ = f.shape
-        rc = lib.unet_forward_u8_histograms(h, C.c_void_p(f.data_ptr()), n, hh, ww, spans.ctypes.data_as(C.c_void_p),
-                                            int(bins), C.c_void_p(hist_dev.data_ptr()),
-                                            C.c_void_p(torch.cuda.current_stream(float_model.device).cuda_stream))
+        rc = lib.unet_forward_u8_histograms(h, _lib.ptr(f), n, hh, ww, spans.ctypes.data_as(C.c_void_p), int(bins),
+                                            _lib.ptr(hist_dev), _lib.stream(float_model.device))
         _lib.check(rc, "unet_forward_u8_histograms", h)
         elements += [n * (hh >> level) * (ww >> level) * c for c, level in shapes]
     return hist_dev, elements
@@ -144,10 +142,7 @@ def prob_mae(probs_a, probs_b):
     a, b = probs_a.contiguous(), probs_b.contiguous()
     n = int(a.shape[0])
     acc = torch.zeros(n, dtype=torch.float64, device=a.device)
-    rc = _lib.load().unet_prob_mae_accumulate(a.device.index, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), n,
-                                              a.numel() // n, C.c_void_p(acc.data_ptr()),
-                                              C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
-    _lib.check(rc, "unet_prob_mae_accumulate")
+    _lib.call("unet_prob_mae_accumulate", a.device, a, b, n, a.numel() // n, acc)
     return acc / (a.numel() // n)
 
 
@@ -262,9 +257,9 @@ class UNetInt8:
         logits = torch.empty((n, 1, h, w), dtype=torch.float32, device=self.device)
         probs = torch.empty_like(logits) if return_probs else None
         mask = torch.empty((n, h, w), dtype=torch.uint8, device=self.device) if return_mask else None
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        p = _lib.ptr
         rc = self._lib.unet_i8_forward_u8(self._h, p(frames), n, h, w, p(logits), p(probs), p(mask), _logit(threshold),
-                                          C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+                                          _lib.stream(self.device))
         self._check(rc, "unet_i8_forward_u8")
         return _pack(logits, probs, mask, return_probs, return_mask)
 
@@ -273,7 +268,7 @@ class UNetInt8:
         from . import metrics
         self._require_live()
         return metrics.evaluate_batches(self._lib, self.device, frames, targets, batch, threshold,
-                                        lambda: C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),
+                                        lambda: _lib.stream(self.device),
                                         self.run_u8)
 
     def sweep(self, frames, targets, thresholds=DEFAULT_THRESHOLDS, batch=None):
@@ -283,7 +278,7 @@ class UNetInt8:
         from . import metrics
         self._require_live()
         return metrics.sweep_batches(self._lib, self.device, frames, targets, batch, thresholds, "logit",
-                                     lambda: C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),
+                                     lambda: _lib.stream(self.device),
                                      self.run_u8)
 
     def read_tensor(self, name, n, h, w):

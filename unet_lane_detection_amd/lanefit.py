@@ -21,7 +21,6 @@ be equal to: parity with any outside implementation of the sliding-window search
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from dataclasses import dataclass
 
@@ -33,14 +32,6 @@ from . import _lib
 FIT_WORDS = 16            # UNET_LANE_FIT_WORDS
 FIT_WINDOWS_MAX = 64      # UNET_LANE_FIT_WINDOWS_MAX
 INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 @dataclass(frozen=True)
@@ -76,11 +67,8 @@ def lane_fit_records(masks_dev, cfg=FitConfig(), prior=None):
             raise ValueError("prior must be (n, 2, h) int32")
         table = table.to(masks_dev.device).contiguous()
     out = torch.empty((n, 2, FIT_WORDS), dtype=torch.int64, device=masks_dev.device)
-    rc = _lib.load().unet_lane_fit_u8_batch(masks_dev.device.index, _ptr(masks_dev), n, h, w, int(cfg.level),
-                                            min(int(cfg.n_windows), h), int(cfg.margin), int(cfg.min_pixels),
-                                            _ptr(table) if table is not None else None, _ptr(out),
-                                            _stream(masks_dev.device))
-    _lib.check(rc, "unet_lane_fit_u8_batch")
+    _lib.call("unet_lane_fit_u8_batch", masks_dev.device, masks_dev, n, h, w, int(cfg.level), min(int(cfg.n_windows), h),
+              int(cfg.margin), int(cfg.min_pixels), table, out)
     return out
 
 

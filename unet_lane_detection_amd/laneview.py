@@ -35,14 +35,6 @@ LAYER_AREA, LAYER_MARKING, LAYER_CURVE = 1, 2, 3      # the layer plane: 3 + i i
 A_LIMIT, B_LIMIT, C_LIMIT = 1 << 30, 1 << 45, 1 << 57     # |A|, |B|, |C| stay below these
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 @dataclass(frozen=True)
 class ViewConfig:
     """alpha, beta, gamma, area, marking, thickness: the style (include/unet_hip.h); colours are in the frame's own
@@ -209,10 +201,6 @@ def lane_view(frames_dev, matrix, warp_size, masks_dev=None, curves=None, cfg=Vi
     style = cfg.style()
     view = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
     plane = torch.empty((n, h, w), dtype=torch.uint8, device=dev) if layers else None
-    rc = _lib.load().unet_lane_view_u8_batch(dev.index, _ptr(frames_dev), n, h, w, step,
-                                             m.ctypes.data_as(C.POINTER(C.c_double)), warp_w, warp_h,
-                                             _ptr(masks_dev) if masks_dev is not None else None, int(cfg.level),
-                                             _ptr(table) if table is not None else None, k, C.byref(style), _ptr(view),
-                                             _ptr(plane) if plane is not None else None, _stream(dev))
-    _lib.check(rc, "unet_lane_view_u8_batch")
+    _lib.call("unet_lane_view_u8_batch", dev, frames_dev, n, h, w, step, m.ctypes.data_as(C.POINTER(C.c_double)), warp_w,
+              warp_h, masks_dev, int(cfg.level), table, k, C.byref(style), view, plane)
     return (view, plane) if layers else view

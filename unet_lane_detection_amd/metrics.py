@@ -132,9 +132,8 @@ def accumulate(lib, device_index, logits, targets, acc, stream, threshold=0.5, l
         raise ValueError("logits and targets differ in size")
     if isinstance(loss_cfg, LossSpec):
         cfg = loss_cfg.to_c()
-        rc = lib.unet_seg_metrics_accumulate_cfg(int(device_index), C.c_void_p(logits.data_ptr()),
-                                                 C.c_void_p(targets.data_ptr()), u8, logits.numel(), _logit(threshold),
-                                                 C.byref(cfg), C.c_void_p(acc.data_ptr()), stream)
+        rc = lib.unet_seg_metrics_accumulate_cfg(int(device_index), _lib.ptr(logits), _lib.ptr(targets), u8, logits.numel(),
+                                                 _logit(threshold), C.byref(cfg), _lib.ptr(acc), stream)
         _lib.check(rc, "unet_seg_metrics_accumulate_cfg")
         return
     kind, bce_w, dice_w, pos_w, smooth = loss_cfg if loss_cfg else ("bce", 1.0, 0.0, 1.0, 1e-6)
@@ -142,9 +141,8 @@ def accumulate(lib, device_index, logits, targets, acc, stream, threshold=0.5, l
         mode, bce_w, dice_w, pos_w = 0, 1.0, 0.0, 1.0
     else:
         mode = 1
-    rc = lib.unet_seg_metrics_accumulate(int(device_index), C.c_void_p(logits.data_ptr()), C.c_void_p(targets.data_ptr()),
-                                         u8, logits.numel(), _logit(threshold), mode, bce_w, dice_w, pos_w, smooth,
-                                         C.c_void_p(acc.data_ptr()), stream)
+    rc = lib.unet_seg_metrics_accumulate(int(device_index), _lib.ptr(logits), _lib.ptr(targets), u8, logits.numel(),
+                                         _logit(threshold), mode, bce_w, dice_w, pos_w, smooth, _lib.ptr(acc), stream)
     _lib.check(rc, "unet_seg_metrics_accumulate")
 
 
@@ -311,9 +309,8 @@ def sweep_accumulate(lib, device_index, scores, targets, thresholds, counts, str
     t = np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1)
     if counts.dtype != torch.int64 or counts.numel() != 2 * (t.size + 1) or counts.device != scores.device:
         raise ValueError(f"counts must be {2 * (t.size + 1)} int64 on the scores' device")
-    rc = lib.unet_score_sweep_accumulate(int(device_index), C.c_void_p(scores.data_ptr()), C.c_void_p(targets.data_ptr()),
-                                         u8, scores.numel(), t.ctypes.data_as(C.POINTER(C.c_float)), int(t.size),
-                                         C.c_void_p(counts.data_ptr()), stream)
+    rc = lib.unet_score_sweep_accumulate(int(device_index), _lib.ptr(scores), _lib.ptr(targets), u8, scores.numel(),
+                                         t.ctypes.data_as(C.POINTER(C.c_float)), int(t.size), _lib.ptr(counts), stream)
     _lib.check(rc, "unet_score_sweep_accumulate")
 
 

@@ -95,9 +95,6 @@ class UNetHIP:
         if self._h is None:
             raise RuntimeError("UNetHIP has been released")
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def reserve(self, n, h, w):
         self._require_live()
         _lib.check(self._lib.unet_reserve(self._h, n, h, w), "unet_reserve", self._h)
@@ -110,10 +107,6 @@ class UNetHIP:
         probs = torch.empty_like(logits) if want_probs else None
         mask = torch.empty((n, h, w), dtype=torch.uint8, device=self.device) if want_mask else None
         return logits, probs, mask
-
-    @staticmethod
-    def _ptr(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
     PRECISIONS = ("fp32", "f16x3", "f16q8", "bf16")
 
@@ -130,8 +123,8 @@ class UNetHIP:
         if precision not in fns:
             raise ValueError(f"precision={precision!r}: forward() takes one of {sorted(fns)}")
         fn = fns[precision]
-        rc = fn(self._h, self._ptr(image), n, h, w, self._ptr(logits), self._ptr(probs),
-                self._ptr(mask), _logit(threshold), self._stream())
+        p = _lib.ptr
+        rc = fn(self._h, p(image), n, h, w, p(logits), p(probs), p(mask), _logit(threshold), _lib.stream(self.device))
         _lib.check(rc, f"unet_forward_f32[{precision}]", self._h)
         return _pack(logits, probs, mask, return_probs, return_mask)
 
@@ -157,8 +150,8 @@ class UNetHIP:
         # thread-local switch of the library (include/unet_hip.h), set for this call of this thread
         prev = self._lib.unet_set_x3_cross_fp8(1 if precision == "f16q8" else 0) if precision in ("f16x3", "f16q8") else None
         try:
-            rc = fn(self._h, self._ptr(frames), n, h, w, self._ptr(logits), self._ptr(probs),
-                    self._ptr(mask), _logit(threshold), self._stream())
+            p = _lib.ptr
+            rc = fn(self._h, p(frames), n, h, w, p(logits), p(probs), p(mask), _logit(threshold), _lib.stream(self.device))
         finally:
             if prev is not None:
                 self._lib.unet_set_x3_cross_fp8(prev)
@@ -174,7 +167,8 @@ class UNetHIP:
         at the end.  Returns metrics.SegMetrics."""
         from . import metrics
         self._require_live()
-        return metrics.evaluate_batches(self._lib, self.device, frames, targets, batch, threshold, self._stream,
+        return metrics.evaluate_batches(self._lib, self.device, frames, targets, batch, threshold,
+                                        lambda: _lib.stream(self.device),
                                         lambda f: self.run_u8(f, precision=precision) if f.dtype == torch.uint8
                                         else self.forward(f, precision=precision))
 
@@ -186,7 +180,8 @@ class UNetHIP:
         Returns metrics.ThresholdSweep: `.best()` is the tier's own operating point, `.at(0.5)` what evaluate counts."""
         from . import metrics
         self._require_live()
-        return metrics.sweep_batches(self._lib, self.device, frames, targets, batch, thresholds, "logit", self._stream,
+        return metrics.sweep_batches(self._lib, self.device, frames, targets, batch, thresholds, "logit",
+                                     lambda: _lib.stream(self.device),
                                      lambda f: self.run_u8(f, precision=precision) if f.dtype == torch.uint8
                                      else self.forward(f, precision=precision))
 
@@ -215,7 +210,7 @@ class UNetHIP:
         parity and the frames should be re-run with precision="fp32"."""
         self._require_live()
         if current_stream_only:
-            return int(self._lib.unet_device_error_on(self._h, self._stream()))
+            return int(self._lib.unet_device_error_on(self._h, _lib.stream(self.device)))
         return int(self._lib.unet_device_error(self._h))
 
     def release(self):

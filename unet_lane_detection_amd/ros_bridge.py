@@ -55,10 +55,6 @@ def get_perspective_transform(src, dst):
     return np.append(np.linalg.solve(a, b), 1.0).reshape(3, 3)
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
 class CameraStage:
     """The two GPU kernels behind the C ABI, on torch device buffers."""
 
@@ -67,9 +63,6 @@ class CameraStage:
             raise RuntimeError("the camera stage needs a HIP device; there is no CPU fallback")
         self._lib = _lib.load()
         self.device = torch.device("cuda", int(device))
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def prestage(self, img, matrix, warp_size, out_size=(224, 224), encoding="bgr8", step=None):
         """img: (H,W,3) uint8 device tensor (or a flat byte tensor with `step`); matrix: 3x3 source->destination;
@@ -84,11 +77,9 @@ class CameraStage:
             raise ValueError("img must be (H,W,3) uint8")
         minv = np.ascontiguousarray(np.linalg.inv(np.asarray(matrix, dtype=np.float64)))
         out = torch.empty((out_size[1], out_size[0], 3), dtype=torch.uint8, device=self.device)
-        rc = self._lib.unet_ipm_prestage_u8(self.device.index, _ptr(img), h, w, int(step), 1 if encoding == "bgr8" else 0,
-                                            minv.ctypes.data_as(C.POINTER(C.c_double)), int(warp_size[0]),
-                                            int(warp_size[1]), int(out_size[0]), int(out_size[1]), _ptr(out),
-                                            self._stream())
-        _lib.check(rc, "unet_ipm_prestage_u8")
+        _lib.call("unet_ipm_prestage_u8", self.device, img, h, w, int(step), 1 if encoding == "bgr8" else 0,
+                  minv.ctypes.data_as(C.POINTER(C.c_double)), int(warp_size[0]), int(warp_size[1]), int(out_size[0]),
+                  int(out_size[1]), out)
         return out
 
     def resize(self, img, out_size):
@@ -98,9 +89,7 @@ class CameraStage:
         h, w = int(img.shape[0]), int(img.shape[1])
         shape = (out_size[1], out_size[0]) if img.dim() == 2 else (out_size[1], out_size[0], cn)
         out = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        rc = self._lib.unet_resize_u8(self.device.index, _ptr(img), h, w, cn, int(out_size[0]), int(out_size[1]), _ptr(out),
-                                      self._stream())
-        _lib.check(rc, "unet_resize_u8")
+        _lib.call("unet_resize_u8", self.device, img, h, w, cn, int(out_size[0]), int(out_size[1]), out)
         return out
 
 
@@ -182,15 +171,12 @@ class LanePipelineGPU:
     def _process(self, msg, guarded):
         rows = self.msg_to_device(msg)
         # (H, step) bytes viewed as (H, W, 3) with a row pitch: the kernel takes the pitch separately
-        lib = self.stage._lib
         out_w, out_h = self.input_size
         frame = torch.empty((1, out_h, out_w, 3), dtype=torch.uint8, device=self.stage.device)
         minv = np.ascontiguousarray(np.linalg.inv(self.matrix))
-        rc = lib.unet_ipm_prestage_u8(self.stage.device.index, _ptr(rows), msg.height, msg.width, msg.step,
-                                      1 if msg.encoding == "bgr8" else 0, minv.ctypes.data_as(C.POINTER(C.c_double)),
-                                      self.warp_size[0], self.warp_size[1], out_w, out_h, _ptr(frame),
-                                      self.stage._stream())
-        _lib.check(rc, "unet_ipm_prestage_u8")
+        _lib.call("unet_ipm_prestage_u8", self.stage.device, rows, msg.height, msg.width, msg.step,
+                  1 if msg.encoding == "bgr8" else 0, minv.ctypes.data_as(C.POINTER(C.c_double)), self.warp_size[0],
+                  self.warp_size[1], out_w, out_h, frame)
         mask = self._infer(frame, guarded)
         if mask is None:   # np.zeros(original_shape, uint8): original_shape is the warped image's (src/unet.py:31, :87)
             host = np.zeros((self.warp_size[1], self.warp_size[0]), dtype=np.uint8)

@@ -94,15 +94,11 @@ class UNetTrainer:
         self.num_batches_tracked = 0
         self._loss_cfg = None
         self._metric = torch.zeros(4, dtype=torch.float32, device=self.device)
-        rc = self._lib.unet_train_attach(h, self._p(self.params), self._p(self.grads), self._p(self.exp_avg),
-                                         self._p(self.exp_avg_sq), self._p(self.bn))
+        rc = self._lib.unet_train_attach(h, _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg),
+                                         _lib.ptr(self.exp_avg_sq), _lib.ptr(self.bn))
         _lib.check(rc, "unet_train_attach", h)
         if self.overlap and dp.world(self.group)[1] > 1:
             self._enable_overlap()
-
-    @staticmethod
-    def _p(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
     def set_loss(self, kind="bce", bce_weight=0.5, dice_weight=0.5, pos_weight=3.0, smooth=1e-6, focal_weight=None,
                  alpha=0.25, gamma=2.0):
@@ -149,13 +145,8 @@ class UNetTrainer:
         targets = targets.to(self.device, torch.float32).contiguous()
         if logits.numel() != targets.numel():
             raise ValueError("logits and targets differ in size")
-        rc = self._lib.unet_dice_metric(self.device.index, self._p(logits), self._p(targets), logits.numel(),
-                                        _logit(threshold), smooth, self._p(self._metric), self._stream())
-        _lib.check(rc, "unet_dice_metric")
+        _lib.call("unet_dice_metric", self.device, logits, targets, logits.numel(), _logit(threshold), smooth, self._metric)
         return self._metric[:1].clone()
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ---- one step, in the reference's order ------------------------------------------------------
     def forward_backward(self, images, targets, return_logits=False):
@@ -172,8 +163,8 @@ class UNetTrainer:
             n, _, h, w = images.shape
             fn = self._lib.unet_train_forward_backward_f32
         logits = torch.empty((n, 1, h, w), dtype=torch.float32, device=self.device) if return_logits else None
-        rc = fn(self._h, self._p(images), self._p(targets), n, h, w, self._p(self.loss_terms), self._p(logits),
-                self._stream())
+        rc = fn(self._h, _lib.ptr(images), _lib.ptr(targets), n, h, w, _lib.ptr(self.loss_terms), _lib.ptr(logits),
+                _lib.stream(self.device))
         self._fb_rc = int(rc)
         if rc != 0 and self._defer_fb_error:    # step() under data parallelism: the ranks have to fail together
             return logits
@@ -214,7 +205,8 @@ class UNetTrainer:
     def optimizer_step(self, grad_scale=1.0):
         self.step_count += 1
         rc = self._lib.unet_train_adam_step(self._h, self.step_count, self.lr, self.betas[0], self.betas[1], self.eps,
-                                            self.weight_decay, 1 if self.decoupled else 0, grad_scale, self._stream())
+                                            self.weight_decay, 1 if self.decoupled else 0, grad_scale,
+                                            _lib.stream(self.device))
         _lib.check(rc, "unet_train_adam_step", self._h)
 
     def reset_optimizer(self):
@@ -230,7 +222,7 @@ class UNetTrainer:
         UNET_ERR_HIP after a kernel-side failure, UNET_ERR_RANGE when an f16x3 activation left the fp16 range
         (include/unet_hip.h)."""
         if current_stream_only:
-            return int(self._lib.unet_device_error_on(self._h, self._stream()))
+            return int(self._lib.unet_device_error_on(self._h, _lib.stream(self.device)))
         return int(self._lib.unet_device_error(self._h))
 
     def step(self, images, targets):
@@ -279,7 +271,7 @@ class UNetTrainer:
         if self._fb_rc != 0:     # failed at its entry: nothing (or not everything) was launched
             self._bucket[:1].fill_(1.0)
         else:
-            _lib.check(self._lib.unet_device_status_to(self._h, self._p(self._bucket), self._stream()),
+            _lib.check(self._lib.unet_device_status_to(self._h, _lib.ptr(self._bucket), _lib.stream(self.device)),
                        "unet_device_status_to", self._h)
         scale = self.allreduce_grads()
         failed = float(self._bucket[0].item())               # waits for the trainer's stream: backward + exchange
@@ -311,10 +303,7 @@ class UNetTrainer:
 
     def _grad_pass(self, dst, a, b=None, record=False):
         rec = self.grad_record if record else None
-        rc = self._lib.unet_grad_accumulate_f32(self.device.index, self._p(dst), self._p(a), self._p(b), dst.numel(),
-                                                self._p(rec), self._p(self._grad_work if record else None),
-                                                self._stream())
-        _lib.check(rc, "unet_grad_accumulate_f32")
+        _lib.call("unet_grad_accumulate_f32", self.device, dst, a, b, dst.numel(), rec, self._grad_work if record else None)
 
     def optimizer_step_rec(self, grad_scale=1.0):
         """optimizer_step with the multiplier formed on the device from self.grad_record (unet_train_adam_step_rec):
@@ -323,7 +312,7 @@ class UNetTrainer:
         max_norm = float("inf") if self.max_grad_norm is None else float(self.max_grad_norm)
         rc = self._lib.unet_train_adam_step_rec(self._h, self.step_count, self.lr, self.betas[0], self.betas[1],
                                                 self.eps, self.weight_decay, 1 if self.decoupled else 0, grad_scale,
-                                                max_norm, self._p(self.grad_record), self._stream())
+                                                max_norm, _lib.ptr(self.grad_record), _lib.stream(self.device))
         _lib.check(rc, "unet_train_adam_step_rec", self._h)
 
     def clip_coefficient(self, grad_scale, sumsq):
@@ -405,7 +394,7 @@ class UNetTrainer:
                 if self._latched_rc != 0:
                     self._bucket[:1].fill_(1.0)
                 else:
-                    _lib.check(self._lib.unet_device_status_to(self._h, self._p(self._bucket), self._stream()),
+                    _lib.check(self._lib.unet_device_status_to(self._h, _lib.ptr(self._bucket), _lib.stream(self.device)),
                                "unet_device_status_to", self._h)
             if accumulated:  # the two-bucket overlap follows the backward pass, which this bucket no longer does
                 dp.allreduce_flat_sum(self._bucket, self.group)
@@ -459,7 +448,7 @@ class UNetTrainer:
         for name in ("step_count", "num_batches_tracked", "lr", "accum_steps", "max_grad_norm", "skip_nonfinite"):
             setattr(self, name, s[name])
         self._pending, self._latched_rc = 0, 0
-        _lib.check(self._lib.unet_train_repack(self._h, self._stream()), "unet_train_repack", self._h)
+        _lib.check(self._lib.unet_train_repack(self._h, _lib.stream(self.device)), "unet_train_repack", self._h)
 
     # ---- validation (reference README.md:2087-2112) and the loop around both (README.md:2185-2231) ----------
     def eval_logits(self, images):
@@ -474,7 +463,8 @@ class UNetTrainer:
             n, _, h, w = images.shape
             fn = self._lib.unet_train_eval_f32
         logits = torch.empty((n, 1, h, w), dtype=torch.float32, device=self.device)
-        _lib.check(fn(self._h, self._p(images), n, h, w, self._p(logits), self._stream()), "unet_train_eval", self._h)
+        _lib.check(fn(self._h, _lib.ptr(images), n, h, w, _lib.ptr(logits), _lib.stream(self.device)), "unet_train_eval",
+                   self._h)
         return logits
 
     def validate(self, batches, threshold=0.5, return_logits=False):
@@ -490,7 +480,7 @@ class UNetTrainer:
         kept = []
         for images, targets in batches:
             logits = self.eval_logits(images)
-            metrics.accumulate(self._lib, self.device.index, logits, torch.as_tensor(targets), acc, self._stream(),
+            metrics.accumulate(self._lib, self.device.index, logits, torch.as_tensor(targets), acc, _lib.stream(self.device),
                                threshold=threshold, loss_cfg=self._loss_cfg)
             if return_logits:
                 kept.append(logits)
@@ -521,7 +511,7 @@ class UNetTrainer:
         for images, targets in batches:
             logits = self.eval_logits(images)
             metrics.sweep_accumulate(self._lib, self.device.index, logits, torch.as_tensor(targets), t, counts,
-                                     self._stream())
+                                     _lib.stream(self.device))
         rc = self.device_error(current_stream_only=True)
         if rc != 0:
             raise _lib.UnetError(rc, "unet_device_error: the sweep is invalid, no metrics are returned",
@@ -581,7 +571,7 @@ class UNetTrainer:
             if "decoupled_weight_decay" in group:
                 self.decoupled = bool(group["decoupled_weight_decay"])
         # packed MFMA operands follow the parameters; the TrainState (loss configuration, workspace) stays
-        _lib.check(self._lib.unet_train_repack(self._h, self._stream()), "unet_train_repack", self._h)
+        _lib.check(self._lib.unet_train_repack(self._h, _lib.stream(self.device)), "unet_train_repack", self._h)
         return rest
 
     def grad_dict(self):

@@ -36,10 +36,6 @@ def jet_table():
     return ((np.clip(765 - 2 * np.abs(4 * i - 255 * c), 0, 510) + 1) // 2).astype(np.uint8)
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
 class FramePipeline:
     """BGR frames -> (overlay, mask) through a `UNetHIP` (on the tier `precision`) or a `UNetInt8`.
 
@@ -82,16 +78,11 @@ class FramePipeline:
             self.corrector = FrameCorrector(correct, device=self.device)
 
     # ---- the three stages, each on torch's current stream -----------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _resize(self, frames):
         n, h, w, _ = frames.shape
         in_w, in_h = self.input_size
         small = torch.empty((n, in_h, in_w, 3), dtype=torch.uint8, device=self.device)
-        rc = self._lib.unet_resize_u8_batch(self.device.index, _ptr(frames), n, h, w, 3, 1, in_w, in_h, _ptr(small),
-                                            self._stream())
-        _lib.check(rc, "unet_resize_u8_batch")
+        _lib.call("unet_resize_u8_batch", self.device, frames, n, h, w, 3, 1, in_w, in_h, small)
         return small
 
     def _network(self, small):
@@ -116,11 +107,9 @@ class FramePipeline:
 
     def _overlay(self, frames, mask_small, overlay, mask):
         n, h, w, _ = frames.shape
-        rc = self._lib.unet_overlay_u8_batch(self.device.index, _ptr(frames), n, h, w, _ptr(mask_small),
-                                             int(mask_small.shape[1]), int(mask_small.shape[2]),
-                                             self.lut.ctypes.data_as(C.c_void_p), self.alpha, self.beta, self.gamma,
-                                             _ptr(overlay), _ptr(mask), self._stream())
-        _lib.check(rc, "unet_overlay_u8_batch")
+        _lib.call("unet_overlay_u8_batch", self.device, frames, n, h, w, mask_small, int(mask_small.shape[1]),
+                  int(mask_small.shape[2]), self.lut.ctypes.data_as(C.c_void_p), self.alpha, self.beta, self.gamma, overlay,
+                  mask)
 
     def _launch(self, frames, overlay, mask):
         if self.corrector is not None:
