@@ -122,6 +122,25 @@ def test_build_staleness_is_by_content(tmp_path, monkeypatch):
     monkeypatch.setenv("UNET_HIPCC_FLAGS", "-DUNET_WS_STAMPS=1")
     hf.write_text(record)
     assert build.is_stale()                       # same sources, other flags
+    monkeypatch.undo()
+    # one object of a rebuild: kept while the digest over its own dependency list, the flags and the compiler line holds
+    deps = {"unet_hip.cpp": "a" * 64, "unet_x3.inc": "b" * 64, "conv_x3_ws.h": "c" * 64}
+    flags, cc = ["-O3", "-c"], "HIP version: 1"
+    rec = build.object_digest(deps, flags, cc)
+    assert len(rec) == 64 and rec == build.object_digest(dict(reversed(deps.items())), flags, cc)
+    assert build.object_is_current(rec, deps, flags, cc)                                   # same dependencies: skip
+    assert not build.object_is_current(None, deps, flags, cc)                              # no record
+    assert not build.object_is_current(rec, {**deps, "unet_x3.inc": "d" * 64}, flags, cc)  # one changed dependency
+    assert not build.object_is_current(rec, {**deps, "unet_x3.inc": None}, flags, cc)      # ... or one that is gone
+    assert not build.object_is_current(rec, {**deps, "launch.h": "e" * 64}, flags, cc)     # ... or one more
+    assert not build.object_is_current(rec, deps, flags + ["-DUNET_WS_STAMPS=1"], cc)      # other flags
+    assert not build.object_is_current(rec, deps, ["-O3 -c"], cc)                          # (not the same as two flags)
+    assert not build.object_is_current(rec, deps, flags, "HIP version: 2")                 # another compiler
+    assert 1 <= build.jobs() <= 16
+    monkeypatch.setenv("MAX_JOBS", "3")
+    assert build.jobs() <= 3
+    monkeypatch.setenv("MAX_JOBS", "64")
+    assert build.jobs() <= 16
 
 
 def test_bench_profiler_labels_map_to_kernel_instances():

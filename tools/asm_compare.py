@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
-"""Compare two device-only assembly listings of the library, kernel by kernel.
+"""Compare two sets of device-only assembly listings of the library, kernel by kernel.
 
-    hipcc <build.py's FLAGS without -shared> --cuda-device-only -S -o parent.s unet_hip.cpp     (at each commit)
-    python tools/asm_compare.py parent.s this.s [--only SUBSTRING] [--all]
+    hipcc <build.py's FLAGS without -shared> --cuda-device-only -S -o parent/NAME.s NAME.cpp
+        (at each commit, for each NAME.cpp of build.py's SOURCES: one listing per source)
+    python tools/asm_compare.py parent this [--only SUBSTRING] [--all]
+    python tools/asm_compare.py parent/unet_hip.cpp.s this/unet_hip.cpp.s,this/launch_conv_x3_ws.cpp.s
+
+A side is a comma-separated list of listings and of directories of listings (*.s), all taken together; a kernel symbol
+that occurs in more than one listing of a side is an error (the library would carry it in two code objects).
 
 Per kernel symbol: whether the text is identical, the register / spill / scratch figures of both builds from the
 metadata, and, where the text differs, the instruction totals and the mnemonics whose counts differ.  Text and counts
@@ -10,6 +15,8 @@ only; the __hip_cuid_* symbol (a per-build id) is ignored.  Exit status 1 if a k
 figure of the second listing is above the first's (ABOVE) or the count of a mnemonic of one of CLASSES differs (CLASS)."""
 import argparse
 import collections
+import glob
+import os
 import re
 import sys
 
@@ -55,18 +62,35 @@ def parse(path):
     return bodies, figures
 
 
+def parse_side(side):
+    """parse() over the listings of one side, merged; a kernel in two of them ends the run"""
+    bodies, figures, where = {}, {}, {}
+    paths = []
+    for item in side.split(","):
+        paths += sorted(glob.glob(os.path.join(item, "*.s"))) if os.path.isdir(item) else [item]
+    for path in paths:
+        b, f = parse(path)
+        twice = sorted(set(b) & set(bodies))
+        if twice:
+            raise SystemExit("\n".join(f"TWICE: {k} in {where[k]} and {path}" for k in twice))
+        bodies.update(b)
+        figures.update(f)
+        where.update(dict.fromkeys(b, path))
+    return bodies, figures
+
+
 def mnemonics(body):
     return collections.Counter(s.split()[0] for s in body if not s.endswith(":"))
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("first")
+    ap.add_argument("first", help="listings and directories of listings, comma-separated")
     ap.add_argument("second")
     ap.add_argument("--only", default="", help="kernels whose symbol contains this")
     ap.add_argument("--all", action="store_true", help="list the identical kernels too")
     args = ap.parse_args()
-    (b0, f0), (b1, f1) = parse(args.first), parse(args.second)
+    (b0, f0), (b1, f1) = parse_side(args.first), parse_side(args.second)
     bad = sorted(set(b0) ^ set(b1))
     for k in bad:
         print(f"ONLY IN {'first' if k in b0 else 'second'}: {k}")

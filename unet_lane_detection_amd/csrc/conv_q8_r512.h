@@ -14,8 +14,8 @@
 //
 // Data: the hi plane is the f16x3 tier's; the lo plane's place (same offset, same 2 bytes per element) is taken by
 // the "q plane": per pixel and 32-channel block 64 bytes = fp8(x_hi / 8) of the 32 channels, then fp8(256 x_lo)
-// (planes_to_q8_kernel below, or a producer's epilogue).  The structure is conv_x3_r512.h's (read that header first; the
-// shared pieces are in wave_tile.h, the rest is repeated here because helpers changed its register allocation); what is
+// (planes_to_q8_kernel of plane_kernels.h, or a producer's epilogue).  The structure is conv_x3_r512.h's (read that
+// header first; the shared pieces are in wave_tile.h, the rest is repeated here because helpers changed its register allocation); what is
 // this kernel's own:
 //  * the q plane is staged with its own bank swizzle (16-byte part ^ bit 2 of the pixel position): a lane reads 32
 //    contiguous bytes of a pixel as two ds_read_b128, conflict free at the same pitches (tools/lds_conflicts.py --q8);
@@ -74,7 +74,7 @@ __device__ __forceinline__ void mfma_q8_acc(f32x4& c, const i32x8& a, const i32x
 #endif
 }
 
-// ---- q plane from the two fp16 planes: one thread per (pixel, 16 channels) ----
+// ---- four values of a q plane (planes_to_q8_kernel, plane_kernels.h, and the epilogues that write one) ----
 __device__ __forceinline__ uint32_t q8_pack4(float a, float b, float c, float d) {
   a = __builtin_amdgcn_fmed3f(a, -448.f, 448.f);
   b = __builtin_amdgcn_fmed3f(b, -448.f, 448.f);
@@ -83,108 +83,6 @@ __device__ __forceinline__ uint32_t q8_pack4(float a, float b, float c, float d)
   int r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
   r = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, r, true);
   return (uint32_t)r;
-}
-__global__ __launch_bounds__(256) void planes_to_q8_kernel(const uint16_t* __restrict__ hi, size_t loOff, size_t nPix,
-                                                           int C, int ld, uint8_t* __restrict__ q) {
-  // hi / lo planes: pixel stride ld halfs, C channels used (C % 32 == 0); q: pixel stride ld * 2 bytes
-  const size_t per = (size_t)(C / 16);
-  const float hs = __builtin_ldexpf(1.f, kQ8HiShift), ls = __builtin_ldexpf(1.f, kQ8LoShift);
-  for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < nPix * per; t += (size_t)gridDim.x * 256) {
-    const size_t p = t / per;
-    const int g = (int)(t - p * per);   // 16-channel group
-    const uint16_t* src = hi + p * ld + g * 16;
-    typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
-    const f16x8v h0 = *reinterpret_cast<const f16x8v*>(src), h1 = *reinterpret_cast<const f16x8v*>(src + 8);
-    const f16x8v l0 = *reinterpret_cast<const f16x8v*>(src + loOff), l1 = *reinterpret_cast<const f16x8v*>(src + loOff + 8);
-    uint4 oh, ol;
-    oh.x = q8_pack4((float)h0[0] * hs, (float)h0[1] * hs, (float)h0[2] * hs, (float)h0[3] * hs);
-    oh.y = q8_pack4((float)h0[4] * hs, (float)h0[5] * hs, (float)h0[6] * hs, (float)h0[7] * hs);
-    oh.z = q8_pack4((float)h1[0] * hs, (float)h1[1] * hs, (float)h1[2] * hs, (float)h1[3] * hs);
-    oh.w = q8_pack4((float)h1[4] * hs, (float)h1[5] * hs, (float)h1[6] * hs, (float)h1[7] * hs);
-    ol.x = q8_pack4((float)l0[0] * ls, (float)l0[1] * ls, (float)l0[2] * ls, (float)l0[3] * ls);
-    ol.y = q8_pack4((float)l0[4] * ls, (float)l0[5] * ls, (float)l0[6] * ls, (float)l0[7] * ls);
-    ol.z = q8_pack4((float)l1[0] * ls, (float)l1[1] * ls, (float)l1[2] * ls, (float)l1[3] * ls);
-    ol.w = q8_pack4((float)l1[4] * ls, (float)l1[5] * ls, (float)l1[6] * ls, (float)l1[7] * ls);
-    uint8_t* dst = q + p * (size_t)ld * 2 + (g >> 1) * 64 + (g & 1) * 16;
-    *reinterpret_cast<uint4*>(dst) = oh;
-    *reinterpret_cast<uint4*>(dst + 32) = ol;
-  }
-}
-
-// MaxPool2d(2,2) on planes for the f16q8 tier: x (N,H,W,ldi: the first `c` channels) -> y (N,H/2,W/2,c), as
-// maxpool2x2_planes_kernel (same values: the maximum of hi + lo, split again), and the q planes of either tensor while
-// their bytes are in registers anyway: srcQ - the input's q plane is written over its lo plane, in place (its remaining
-// consumer is a convolution of this tier; a thread owns a whole 32-channel block, whose 64 lo bytes are exactly the
-// block's q bytes); dstQ - the output gets its q plane instead of its lo plane.  One thread per output pixel and block.
-__global__ __launch_bounds__(256) void maxpool2x2_planes_q8_kernel(uint16_t* __restrict__ src, size_t srcLo, int n, int h,
-                                                                   int w, int c, int ldi, uint16_t* __restrict__ dst,
-                                                                   size_t dstLo, int srcQ, int dstQ) {
-  const int nb = c / 32;
-  const size_t total = (size_t)n * (h / 2) * (w / 2) * nb;
-  const size_t stride = (size_t)gridDim.x * 256;
-  const float hs = __builtin_ldexpf(1.f, kQ8HiShift), ls = __builtin_ldexpf(1.f, kQ8LoShift);
-  auto q_block = [&](const uint32_t* ph, const uint32_t* pl, uint4* out) __attribute__((always_inline)) {
-    // 16 packed pairs hi, 16 packed pairs lo -> [hi8 x 32][lo8 x 32]
-    uint32_t qh[8], ql[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float a0, a1, a2, a3, b0, b1, b2, b3;
-      merge_pk_f16(ph[2 * e], 0u, a0, a1);
-      merge_pk_f16(ph[2 * e + 1], 0u, a2, a3);
-      merge_pk_f16(pl[2 * e], 0u, b0, b1);
-      merge_pk_f16(pl[2 * e + 1], 0u, b2, b3);
-      qh[e] = q8_pack4(a0 * hs, a1 * hs, a2 * hs, a3 * hs);
-      ql[e] = q8_pack4(b0 * ls, b1 * ls, b2 * ls, b3 * ls);
-    }
-    out[0] = make_uint4(qh[0], qh[1], qh[2], qh[3]);
-    out[1] = make_uint4(qh[4], qh[5], qh[6], qh[7]);
-    out[2] = make_uint4(ql[0], ql[1], ql[2], ql[3]);
-    out[3] = make_uint4(ql[4], ql[5], ql[6], ql[7]);
-  };
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    const int b = (int)(i % nb);
-    size_t p = i / nb;
-    const int xo = (int)(p % (w / 2));
-    p /= (w / 2);
-    const int yo = (int)(p % (h / 2));
-    const int nn = (int)(p / (h / 2));
-    float m[32];
-#pragma unroll
-    for (int e = 0; e < 32; ++e) m[e] = -3.4e38f;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      uint16_t* sp = src + ((((size_t)nn * h + 2 * yo + (d >> 1)) * w + 2 * xo + (d & 1)) * (size_t)ldi + b * 32);
-      uint32_t ph[16], pl[16];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const uint4 vh = reinterpret_cast<const uint4*>(sp)[q], vl = reinterpret_cast<const uint4*>(sp + srcLo)[q];
-        ph[4 * q] = vh.x, ph[4 * q + 1] = vh.y, ph[4 * q + 2] = vh.z, ph[4 * q + 3] = vh.w;
-        pl[4 * q] = vl.x, pl[4 * q + 1] = vl.y, pl[4 * q + 2] = vl.z, pl[4 * q + 3] = vl.w;
-      }
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        float a, bb;
-        merge_pk_f16(ph[e], pl[e], a, bb);
-        m[2 * e] = fmaxf(m[2 * e], a);
-        m[2 * e + 1] = fmaxf(m[2 * e + 1], bb);
-      }
-      if (srcQ) q_block(ph, pl, reinterpret_cast<uint4*>(sp + srcLo));
-    }
-    uint32_t oh[16], ol[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) split_pk_f16(m[2 * e], m[2 * e + 1], oh[e], ol[e]);
-    uint16_t* dp = dst + ((((size_t)nn * (h / 2) + yo) * (w / 2) + xo) * (size_t)c + b * 32);
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      reinterpret_cast<uint4*>(dp)[q] = make_uint4(oh[4 * q], oh[4 * q + 1], oh[4 * q + 2], oh[4 * q + 3]);
-    if (dstQ) {
-      q_block(oh, ol, reinterpret_cast<uint4*>(dp + dstLo));
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        reinterpret_cast<uint4*>(dp + dstLo)[q] = make_uint4(ol[4 * q], ol[4 * q + 1], ol[4 * q + 2], ol[4 * q + 3]);
-    }
-  }
 }
 
 // EPI: 0 = store the two fp16 planes (a.out / a.outLo); 4 = store the hi plane and, in the lo plane's place, the q plane of

@@ -532,267 +532,4 @@ __global__ __launch_bounds__(512, 1) void conv3x3_x3_ws_kernel(const ConvX3Args 
   if (EPI != 3) x3_report_range(amax, a.err);
 }
 
-// Second half of a split-K convolution: y = act(scale * sum_ks partial[ks] + shift) written as hi / lo planes (pixel
-// stride ldo halfs, channel offset co_off).  partial: [kSplit][P][C] fp32, dense.
-__global__ __launch_bounds__(256) void x3_splitk_finish_kernel(const float* __restrict__ partial, int kSplit, size_t P,
-                                                               int C, const float* __restrict__ scale,
-                                                               const float* __restrict__ shift, int relu,
-                                                               uint32_t* __restrict__ outHi, size_t outLo2, int ldo,
-                                                               int co_off, unsigned* err) {
-  float amax = 0.f;
-  const int c4 = C >> 2;
-  const size_t total = P * c4;
-  const size_t stride = (size_t)gridDim.x * 256;
-  const size_t slab = P * (size_t)C;
-  const float floorV = relu ? 0.f : -3.4e38f;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    const size_t p = i / c4;
-    const int c = (int)(i - p * c4) * 4;
-    // kSplit is a power of two >= 2: pairs of independent loads in flight, added in a fixed order
-    const float* src = partial + p * C + c;
-    f32x4 v = *reinterpret_cast<const f32x4*>(src) + *reinterpret_cast<const f32x4*>(src + slab);
-    for (int k = 2; k < kSplit; k += 4) {
-      const f32x4 a0 = *reinterpret_cast<const f32x4*>(src + k * slab);
-      const f32x4 a1 = *reinterpret_cast<const f32x4*>(src + (k + 1) * slab);
-      f32x4 a2 = (f32x4){0.f, 0.f, 0.f, 0.f}, a3 = a2;
-      if (k + 2 < kSplit) {
-        a2 = *reinterpret_cast<const f32x4*>(src + (k + 2) * slab);
-        a3 = *reinterpret_cast<const f32x4*>(src + (k + 3) * slab);
-      }
-      v += (a0 + a1) + (a2 + a3);
-    }
-    const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + c), sh = *reinterpret_cast<const f32x4*>(shift + c);
-    float y[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) y[e] = fmaxf(fmaf(v[e], sc[e], sh[e]), floorV);
-    uint32_t h0, l0, h1, l1;
-    split_pk_f16(y[0], y[1], h0, l0, amax);
-    split_pk_f16(y[2], y[3], h1, l1, amax);
-    const size_t o = (p * (size_t)ldo + co_off + c) >> 1;
-    *reinterpret_cast<uint2*>(outHi + o) = make_uint2(h0, h1);
-    *reinterpret_cast<uint2*>(outHi + outLo2 + o) = make_uint2(l0, l1);
-  }
-  x3_report_range(amax, err);
-}
-
-// Device-side repack of fp32 PyTorch-layout 3x3 weights into this kernel's hi/lo fragment order (training: after every
-// optimizer step).  mode 0: forward, W(co, ci, t) = w[(co*cin + ci)*9 + t] with w (cout, cin, 3, 3); mode 1: input
-// gradient, a convolution with the roles of the channels swapped and the taps flipped: its "cout" is the forward
-// cin and W(n, k, t) = w[(k*coutD + n)*9 + (8 - t)] with w (cin = k range, coutD = n range, 3, 3).  No pre-scaling: an
-// fp16 subnormal lo part costs a few bits of the 22, far inside the training tolerance.
-__global__ __launch_bounds__(256) void pack_x3_kernel(const float* __restrict__ w, uint16_t* __restrict__ out, int cout,
-                                                      int cin, int mode) {
-  const int nCh = cin / 32;
-  const size_t total = (size_t)(cout / 64) * nCh * 9 * 4 * 64;
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    const int lane = (int)(i & 63);
-    size_t r0 = i >> 6;
-    const int cs = (int)(r0 & 3);
-    r0 >>= 2;
-    const int t = (int)(r0 % 9);
-    r0 /= 9;
-    const int kc = (int)(r0 % nCh);
-    const int ct = (int)(r0 / nCh);
-    const int j = lane & 15, lq = lane >> 4;
-    const int co = 64 * ct + 16 * (j >> 2) + 4 * cs + (j & 3);
-    const int tr = t / 3, kx = t - tr * 3;
-    uint32_t hi[4], lo[4];
-#pragma unroll
-    for (int e2 = 0; e2 < 4; ++e2) {
-      float v[2];
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int ci = kc * 32 + lq * 8 + e2 * 2 + e;
-        v[e] = mode == 0 ? w[((size_t)co * cin + ci) * 9 + t] : w[((size_t)ci * cout + co) * 9 + (8 - t)];
-      }
-      split_pk_f16(v[0], v[1], hi[e2], lo[e2]);
-    }
-    uint16_t* base = out + ((((size_t)ct * nCh + kc) * 3 + tr) * (size_t)(2 * 3 * 4 * 64 * 8));
-    *reinterpret_cast<uint4*>(base + (((size_t)0 * 3 + kx) * 4 + cs) * 64 * 8 + lane * 8) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-    *reinterpret_cast<uint4*>(base + (((size_t)1 * 3 + kx) * 4 + cs) * 64 * 8 + lane * 8) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-  }
-}
-
-// The same packing, one block per (channel tile of 64, chunk of 32) with the tile's 18,432 weights brought through LDS:
-// they are 64 runs of 1,152 contiguous bytes (mode 0: rows co, 32 ci x 9 taps each) or 32 runs of 2,304 bytes (mode 1,
-// the input-gradient operator: rows are the forward co = this operator's ci, 64 forward ci x 9 taps each), where
-// pack_x3_kernel gathers them 4 bytes at a time (0.4 ms per training step for the 34 packs; this one is bound by the
-// 0.5 GB it moves).  Launch with (cout / 64) * (cin / 32) blocks of 256 threads and kPackX3LdsBytes of dynamic LDS.
-constexpr int kPackX3LdsBytes = 64 * (288 + 4) * 4;   // 74,752 (mode 1: 32 x (576 + 4) x 4 = 74,240)
-__device__ __forceinline__ void pack_x3_lds_tile(const float* __restrict__ w, uint16_t* __restrict__ out, int cout, int cin,
-                                                 int mode, int tileIdx, float* tileW) {
-  const int nCh = cin / 32;
-  const int ct = tileIdx / nCh, kc = tileIdx - ct * nCh;
-  const int tid = threadIdx.x;
-  // rows x rowLen floats of the source, row pitch rowLen + 4 in LDS
-  const int rows = mode == 0 ? 64 : 32, rowLen = mode == 0 ? 288 : 576, pitch = rowLen + 4;
-  for (int i = tid; i < rows * (rowLen / 4); i += 256) {
-    const int r = i / (rowLen / 4), q = i - r * (rowLen / 4);
-    // mode 0: w[(co * cin + ci) * 9 + t], co = 64 ct + r, ci from 32 kc; mode 1: w[(ci * cout + co) * 9 + t] with this
-    // operator's ci = 32 kc + r as the forward co (row) and its co from 64 ct as the forward ci
-    const size_t src = mode == 0 ? ((size_t)(64 * ct + r) * cin + 32 * kc) * 9 : ((size_t)(32 * kc + r) * cout + 64 * ct) * 9;
-    *reinterpret_cast<float4*>(tileW + r * pitch + 4 * q) = *reinterpret_cast<const float4*>(w + src + 4 * q);
-  }
-  __syncthreads();
-  for (int i = tid; i < 9 * 4 * 64; i += 256) {
-    const int lane = i & 63;
-    const int cs = (i >> 6) & 3;
-    const int t = i >> 8;
-    const int j = lane & 15, lq = lane >> 4;
-    const int col = 16 * (j >> 2) + 4 * cs + (j & 3);   // this operator's co within the tile
-    const int tr = t / 3, kx = t - tr * 3;
-    uint32_t hi[4], lo[4];
-#pragma unroll
-    for (int e2 = 0; e2 < 4; ++e2) {
-      float v[2];
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int k = lq * 8 + e2 * 2 + e;   // this operator's ci within the chunk
-        v[e] = mode == 0 ? tileW[col * pitch + k * 9 + t] : tileW[k * pitch + col * 9 + (8 - t)];
-      }
-      split_pk_f16(v[0], v[1], hi[e2], lo[e2]);
-    }
-    uint16_t* base = out + ((((size_t)ct * nCh + kc) * 3 + tr) * (size_t)(2 * 3 * 4 * 64 * 8));
-    *reinterpret_cast<uint4*>(base + (((size_t)0 * 3 + kx) * 4 + cs) * 64 * 8 + lane * 8) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-    *reinterpret_cast<uint4*>(base + (((size_t)1 * 3 + kx) * 4 + cs) * 64 * 8 + lane * 8) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-  }
-}
-
-__global__ __launch_bounds__(256) void pack_x3_lds_kernel(const float* __restrict__ w, uint16_t* __restrict__ out, int cout,
-                                                          int cin, int mode) {
-  extern __shared__ __attribute__((aligned(16))) float tileW[];
-  pack_x3_lds_tile(w, out, cout, cin, mode, (int)blockIdx.x, tileW);
-}
-
-// All of a network's packs in one launch: block b belongs to the table entry e with start[e] <= b < start[e + 1] and
-// is tile b - start[e] of it (the training step re-packs 34 operators after every optimizer step: as 34 launches they
-// cost their launch gaps)
-struct PackX3Desc {
-  const float* w;
-  uint16_t* out;
-  int cout, cin, mode;
-};
-__global__ __launch_bounds__(256) void pack_x3_lds_multi_kernel(const PackX3Desc* __restrict__ descs,
-                                                                const unsigned* __restrict__ start, int n) {
-  extern __shared__ __attribute__((aligned(16))) float tileW[];
-  int lo = 0, hi = n - 1;   // the entry whose block range holds blockIdx.x
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (start[mid] <= blockIdx.x)
-      lo = mid;
-    else
-      hi = mid - 1;
-  }
-  const PackX3Desc d = descs[lo];
-  pack_x3_lds_tile(d.w, d.out, d.cout, d.cin, d.mode, (int)(blockIdx.x - start[lo]), tileW);
-}
-
-// ---- plane helpers (test entry points and the unfused fallbacks) ----
-
-// fp32 NHWC (pixel stride ld, `c` channels used) -> hi/lo planes with the same geometry
-__global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, size_t nvec2,
-                                                           uint32_t* __restrict__ hi, uint32_t* __restrict__ lo,
-                                                           unsigned* err = nullptr) {
-  float amax = 0.f;
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec2; i += stride) {
-    const float2 v = reinterpret_cast<const float2*>(x)[i];
-    uint32_t h, l;
-    split_pk_f16(v.x, v.y, h, l, amax);
-    hi[i] = h;
-    lo[i] = l;
-  }
-  x3_report_range(amax, err);
-}
-
-// The same split for a tensor whose magnitudes sit far below the fp16 range (activation gradients: ~1e-7): every
-// value is first multiplied by 2^k with k chosen from the tensor's max |x| (`absmaxKey`: its float bits, produced by
-// the kernel that wrote x) so that the maximum lands in [2^13, 2^14); 2^-k goes to *invOut for the consumer's epilogue.
-// Power-of-two scaling is exact.
-__global__ __launch_bounds__(256) void split_planes_scaled_kernel(const float* __restrict__ x, size_t nvec2,
-                                                                  uint32_t* __restrict__ hi, uint32_t* __restrict__ lo,
-                                                                  const unsigned* __restrict__ absmaxKey,
-                                                                  float* __restrict__ invOut) {
-  const unsigned key = *absmaxKey;
-  int k = 0;
-  if ((key >> 23) != 0 && (key >> 23) < 255) k = 13 - ((int)(key >> 23) - 127);   // normal, finite maximum
-  k = k > 100 ? 100 : (k < -100 ? -100 : k);
-  const float up = ldexpf(1.f, k);
-  if (blockIdx.x == 0 && threadIdx.x == 0) *invOut = ldexpf(1.f, -k);
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec2; i += stride) {
-    const float2 v = reinterpret_cast<const float2*>(x)[i];
-    uint32_t h, l;
-    split_pk_f16(v.x * up, v.y * up, h, l);
-    hi[i] = h;
-    lo[i] = l;
-  }
-}
-
-__global__ __launch_bounds__(256) void merge_planes_kernel(const uint32_t* __restrict__ hi,
-                                                           const uint32_t* __restrict__ lo, size_t nvec2,
-                                                           float* __restrict__ y) {
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec2; i += stride) {
-    float a, b;
-    merge_pk_f16(hi[i], lo[i], a, b);
-    reinterpret_cast<float2*>(y)[i] = make_float2(a, b);
-  }
-}
-
-// MaxPool2d(2,2) on planes (fallback when the producer could not fuse it): x (N,H,W,ldi) -> y (N,H/2,W/2,C)
-__global__ __launch_bounds__(256) void maxpool2x2_planes_kernel(const uint32_t* __restrict__ hi, size_t inLo2, int n,
-                                                                int h, int w, int c, int ldi,
-                                                                uint32_t* __restrict__ out, size_t outLo2) {
-  const int c2 = c / 2, ld2 = ldi / 2;
-  const size_t total = (size_t)n * (h / 2) * (w / 2) * c2;
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    const int cc = (int)(i % c2);
-    size_t p = i / c2;
-    const int xo = (int)(p % (w / 2));
-    p /= (w / 2);
-    const int yo = (int)(p % (h / 2));
-    const int nn = (int)(p / (h / 2));
-    float m0 = -3.4e38f, m1 = -3.4e38f;
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-      for (int dx = 0; dx < 2; ++dx) {
-        const size_t o = (((size_t)nn * h + 2 * yo + dy) * w + 2 * xo + dx) * ld2 + cc;
-        float a, b;
-        merge_pk_f16(hi[o], hi[o + inLo2], a, b);
-        m0 = fmaxf(m0, a);
-        m1 = fmaxf(m1, b);
-      }
-    uint32_t qh, ql;
-    split_pk_f16(m0, m1, qh, ql);
-    out[i] = qh;
-    out[i + outLo2] = ql;
-  }
-}
-
-// 1x1 head on planes (fallback when the last convolution could not fuse it): x (npix, C) planes -> logits
-__global__ __launch_bounds__(256) void head1x1_planes_kernel(const uint32_t* __restrict__ hi, size_t inLo2,
-                                                             const float* __restrict__ w, float bias, size_t npix,
-                                                             int c, float* __restrict__ logits,
-                                                             float* __restrict__ probs, uint8_t* __restrict__ mask,
-                                                             float thr) {
-  const size_t stride = (size_t)gridDim.x * 256;
-  const int c2 = c / 2;
-  for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += stride) {
-    float z = bias;
-    for (int i = 0; i < c2; ++i) {
-      float a, b;
-      merge_pk_f16(hi[p * c2 + i], hi[p * c2 + i + inLo2], a, b);
-      z = fmaf(a, w[2 * i], z);
-      z = fmaf(b, w[2 * i + 1], z);
-    }
-    if (logits) logits[p] = z;
-    if (probs) probs[p] = 1.f / (1.f + __expf(-z));
-    if (mask) mask[p] = z > thr ? 255 : 0;
-  }
-}
-
 }  // namespace unet

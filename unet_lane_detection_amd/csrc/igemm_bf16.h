@@ -292,42 +292,6 @@ __global__ __launch_bounds__(256, 2) void igemm_bf16_kernel(const ConvArgsBf a) 
 
 // ---- bf16 helpers of the forward path ------------------------------------------------------------------
 
-// MaxPool2d(2,2) on bf16 NHWC (8 channels = 16 bytes per thread); max of bf16 values is exact.
-__global__ __launch_bounds__(256) void maxpool2x2_bf16_kernel(const uint16_t* __restrict__ in,
-                                                              uint16_t* __restrict__ out, int n, int h, int w, int c,
-                                                              int ldi) {
-  const int c8 = c >> 3;
-  const int oh = h >> 1, ow = w >> 1;
-  const size_t total = (size_t)n * oh * ow * c8;
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    const int cv = (int)(i % c8);
-    size_t t = i / c8;
-    const int ox = (int)(t % ow);
-    t /= ow;
-    const int oy = (int)(t % oh);
-    const size_t img = t / oh;
-    const uint16_t* p = in + ((img * h + (size_t)oy * 2) * w + (size_t)ox * 2) * (size_t)ldi + cv * 8;
-    bf16x8 v[4];
-    v[0] = *reinterpret_cast<const bf16x8*>(p);
-    v[1] = *reinterpret_cast<const bf16x8*>(p + ldi);
-    v[2] = *reinterpret_cast<const bf16x8*>(p + (size_t)w * ldi);
-    v[3] = *reinterpret_cast<const bf16x8*>(p + (size_t)w * ldi + ldi);
-    bf16x8 m;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float best = -3.4e38f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float f = __builtin_bit_cast(float, (uint32_t)(uint16_t)v[k][e] << 16);
-        best = f > best ? f : best;
-      }
-      m[e] = (short)(__builtin_bit_cast(uint32_t, best) >> 16);
-    }
-    *reinterpret_cast<bf16x8*>(out + i * 8) = m;
-  }
-}
-
 // 1x1 head on bf16 activations: fp32 dot + bias -> fp32 logits (+ optional sigmoid / threshold).
 template <int LPP>
 __global__ __launch_bounds__(256) void head1x1_bf16_kernel(const uint16_t* __restrict__ in,

@@ -165,24 +165,6 @@ int pack_first_bf16x3(std::string& err, uint16_t** dst, const float* w, int f0) 
   return upload_bf(err, dst, pw);
 }
 
-template <int TAPS, int MODE>
-hipError_t launch_bf(const unet::ConvArgsBf& a, dim3 grid, int ms, int ns, hipStream_t s) {
-  constexpr int NLD7 = 6, NLD4 = 4;
-#define LB(MS_, NS_, NLD_)                                                                                       \
-  hipLaunchKernelGGL((unet::igemm_bf16_kernel<TAPS, MS_, NS_, NLD_, MODE>), grid, dim3(256),                     \
-                     std::max<size_t>((size_t)2 * NLD_ * 256 * 16 + 64, (size_t)MS_ * 16 * (32 * NS_ + 4) * 4), s, a)
-  if (ms == 7 && ns == 4)
-    LB(7, 4, NLD7);
-  else if (ms == 7)
-    LB(7, 2, NLD7);
-  else if (ns == 4)
-    LB(4, 4, NLD4);
-  else
-    LB(4, 2, NLD4);
-#undef LB
-  return hipGetLastError();
-}
-
 struct BfFuse {
   uint16_t* pool = nullptr;         // fused 2x2 max-pool output (set to nullptr by run_gemm_bf if it could not fuse)
   const float* headW = nullptr;     // fused 1x1 head
@@ -236,16 +218,6 @@ bool conv_bf_r512_eligible(const GemmOpBf& op, int n, int h, int w, int mode) {
   if (mode == 0 || mode == 1) return false;
   return mode == 2 || conv_bf_r512_plan(op, n, h, w).items >= 128;
 }
-template <int TWX, int WPX>
-hipError_t launch_bf_r512(const unet::ConvBfRArgs& a, int grid, bool flat, hipStream_t s) {
-  using S = unet::BfRShape<TWX>;
-  void (*kern)(unet::ConvBfRArgs) = flat ? unet::conv3x3_bf16_r512_kernel<TWX, WPX, true>
-                                         : unet::conv3x3_bf16_r512_kernel<TWX, WPX, false>;
-  hipError_t e = ensure_dyn_lds((const void*)kern, S::LDS_BYTES);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), (size_t)S::LDS_BYTES, s, a);
-  return hipGetLastError();
-}
 hipError_t run_conv_bf_r512(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo,
                             int coOff, hipStream_t s) {
   const BfR512Plan p = conv_bf_r512_plan(op, n, h, w);
@@ -274,11 +246,7 @@ hipError_t run_conv_bf_r512(const GemmOpBf& op, const uint16_t* in, int n, int h
   const int grid = (int)std::max<long>(8, std::min<long>(256, p.items / 8 * 8));
   const double px = (double)n * h * w;
   prof_begin("conv3x3_r512_bf16", 2.0 * px * 9 * op.cin * op.cout, 2.0 * (px * op.cin + px * op.cout + 9.0 * op.cin * op.cout), s);
-  hipError_t e;
-  if (p.twx == 28)
-    e = p.wpx == 1 ? launch_bf_r512<28, 1>(a, grid, p.flat, s) : launch_bf_r512<28, 2>(a, grid, p.flat, s);
-  else
-    e = p.wpx == 1 ? launch_bf_r512<14, 1>(a, grid, p.flat, s) : launch_bf_r512<14, 2>(a, grid, p.flat, s);
+  const hipError_t e = unet::launch_bf_r512(a, grid, p.twx, p.wpx, p.flat, s);
   prof_end(s);
   return e;
 }
@@ -386,7 +354,6 @@ int bf_kernel_for(const GemmOpBf& op, int n, int h, int w, int force) {
 // Returns through `fusedPool` / `fusedHead` which of the requested epilogue fusions the launch performed.
 hipError_t run_conv_ws(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo, int coOff,
                        hipStream_t s, BfFuse* fuse, bool* fusedPool, bool* fusedHead) {
-  using S = unet::WsShape;
   unet::ConvWsArgs a;
   a.in = in;
   a.wt = op.wtWs;
@@ -443,19 +410,12 @@ hipError_t run_conv_ws(const GemmOpBf& op, const uint16_t* in, int n, int h, int
   a.stamps = stampBuf;
 #endif
   const int epi = a.headW ? 2 : (a.pool ? 1 : 0);
-  void (*kern)(unet::ConvWsArgs) = epi == 2   ? unet::conv3x3_bf16_ws_kernel<2>
-                                   : epi == 1 ? unet::conv3x3_bf16_ws_kernel<1>
-                                              : unet::conv3x3_bf16_ws_kernel<0>;
-  {
-    hipError_t e = ensure_dyn_lds((const void*)kern, S::LDS_BYTES);
-    if (e != hipSuccess) return e;
-  }
   const int work = a.pixTiles * a.coTiles;
   const int grid = std::min(256, work / 8 * 8);
   const double px = (double)n * h * w;
   prof_begin("conv3x3_ws_bf16", 2.0 * px * 9 * op.cin * op.cout,
              2.0 * (px * op.cin + px * op.cout + 9.0 * op.cin * op.cout), s);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), (size_t)S::LDS_BYTES, s, a);
+  const hipError_t e = unet::launch_bf_ws(a, grid, epi, s);
   prof_end(s);
 #if UNET_WS_STAMPS
   {
@@ -471,9 +431,8 @@ hipError_t run_conv_ws(const GemmOpBf& op, const uint16_t* in, int n, int h, int
             (t[0] - t[1] - t[2]) / tiles, t[1] / tiles, t[2] / tiles, t[6] / tiles, t[4] / tiles, t[5] / tiles);
   }
 #endif
-  return hipGetLastError();
+  return e;
 }
-
 
 // ---- the 2x2-wave kernel (igemm_bf16.h): every shape, the 3x3 convolution and the transposed convolution ----
 hipError_t run_igemm_bf(const GemmOpBf& op, const uint16_t* in, int n, int h, int w, uint16_t* out, int ldo, int coOff,
@@ -539,7 +498,7 @@ hipError_t run_igemm_bf(const GemmOpBf& op, const uint16_t* in, int n, int h, in
   prof_begin(op.taps == 9 ? "conv3x3_igemm_bf16" : "upconv2x2_igemm_bf16", 2.0 * px * op.taps * op.cin * nOut,
              2.0 * (px * op.cin + px * nOut + (double)op.taps * op.cin * nOut), s);
   dim3 grid((unsigned)((size_t)a.pixTiles * a.coTiles));
-  hipError_t e = (op.taps == 9) ? launch_bf<9, 0>(a, grid, t.ms, ns, s) : launch_bf<1, 1>(a, grid, t.ms, ns, s);
+  hipError_t e = unet::launch_bf(a, grid, op.taps, t.ms, ns, s);
   prof_end(s);
   return e;
 }

@@ -40,7 +40,8 @@
 #include "upconv_x3_r512.h"
 #include "upconv_x3_win.h"
 #include "conv_first_x3.h"
-#include "conv_x3_enc1.h"
+#include "conv_x3_enc1_args.h"
+#include "plane_kernels.h"
 #include "conv_i8.h"
 #include "wino_f32.h"
 #include "train_kernels.h"
@@ -51,11 +52,28 @@
 #include "camera_stage.h"
 #include "calib_kernels.h"
 #include "conv_h16.h"
+#include "launch.h"
 #include "op_entry.h"
+
+// Kernels that need more dynamic LDS than the default opt in once per (device, kernel): the attribute is per device.
+// Shared with the launch units (launch.h).
+hipError_t unet::ensure_dyn_lds(const void* fn, int bytes) {
+  static std::mutex mu;
+  static std::set<std::pair<int, const void*>> done;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> lk(mu);
+  if (done.count({dev, fn})) return hipSuccess;
+  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done.insert({dev, fn});
+  return e;
+}
 
 namespace {
 
 using unet::ConvArgs;
+using unet::ensure_dyn_lds;
 
 constexpr float kBnEps = 1e-5f;  // nn.BatchNorm2d default (reference README.md:1453)
 
@@ -146,20 +164,6 @@ thread_local Profiler* g_prof = nullptr;
 // the handle's device-visible error block: word 0 = a bounded spin gave up, word 1 = an activation of the f16x3 tier left
 // the fp16 range (conv_x3_ws.h, range watch)
 thread_local unsigned* g_errWord = nullptr;
-
-// Kernels that need more dynamic LDS than the default opt in once per (device, kernel): the attribute is per device.
-hipError_t ensure_dyn_lds(const void* fn, int bytes) {
-  static std::mutex mu;
-  static std::set<std::pair<int, const void*>> done;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  std::lock_guard<std::mutex> lk(mu);
-  if (done.count({dev, fn})) return hipSuccess;
-  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess) done.insert({dev, fn});
-  return e;
-}
 
 // Device error word for launches made outside a handle (the single-operator test entry points): one per device.
 unsigned* op_err_word() {

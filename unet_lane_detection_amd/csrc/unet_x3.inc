@@ -365,81 +365,6 @@ struct X3Path {
   }
 };
 
-// ---- the launches a plan can name: exactly the kernel instances the library carries ----
-template <int TW, int EPI, bool FLAT = false>
-hipError_t launch_conv_x3(const unet::ConvX3Args& a, int grid, hipStream_t s) {
-  using S = unet::X3Shape<TW>;
-  auto kern = unet::conv3x3_x3_ws_kernel<TW, EPI, FLAT>;
-  hipError_t e = ensure_dyn_lds((const void*)kern, S::LDS_BYTES);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), (size_t)S::LDS_BYTES, s, a);
-  return hipGetLastError();
-}
-template <int TW>
-hipError_t launch_conv_x3(const unet::ConvX3Args& a, int grid, int epi, bool flat, hipStream_t s) {
-  if (flat)
-    return epi == 0   ? launch_conv_x3<TW, 0, true>(a, grid, s)
-           : epi == 1 ? launch_conv_x3<TW, 1, true>(a, grid, s)
-                      : launch_conv_x3<TW, 3, true>(a, grid, s);
-  return epi == 0   ? launch_conv_x3<TW, 0>(a, grid, s)
-         : epi == 1 ? launch_conv_x3<TW, 1>(a, grid, s)
-         : epi == 2 ? launch_conv_x3<TW, 2>(a, grid, s)
-                    : launch_conv_x3<TW, 3>(a, grid, s);
-}
-
-// Second structure (conv_x3_r512.h): 224-pixel tiles of 8 x 28 or 16 x 14, one wave per SIMD
-template <int TWX, int WPX, int EPI, bool FLAT>
-hipError_t launch_conv_r512(const unet::ConvX3Args& a, int grid, hipStream_t s) {
-  using S = unet::X3RShape<TWX>;
-  auto kern = unet::conv3x3_x3_r512_kernel<TWX, WPX, EPI, FLAT>;
-  hipError_t e = ensure_dyn_lds((const void*)kern, S::LDS_BYTES);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), (size_t)S::LDS_BYTES, s, a);
-  return hipGetLastError();
-}
-template <int TWX, int WPX>
-hipError_t launch_conv_r512(const unet::ConvX3Args& a, int grid, bool flat, bool f32out, hipStream_t s) {
-  if (f32out) return flat ? launch_conv_r512<TWX, WPX, 3, true>(a, grid, s) : launch_conv_r512<TWX, WPX, 3, false>(a, grid, s);
-  return flat ? launch_conv_r512<TWX, WPX, 0, true>(a, grid, s) : launch_conv_r512<TWX, WPX, 0, false>(a, grid, s);
-}
-
-// Third structure (conv_x3_t448.h): 16 x 28 / 16 x 32 pixel tiles for the layers with 64 / 128 output channels
-template <int TWX, int WCO, int EPI, bool FLAT = false>
-hipError_t launch_conv_t448(const unet::ConvX3Args& a, int grid, hipStream_t s) {
-  using S = unet::X3TShape<TWX, unet::x3t_row_blocks(WCO)>;
-  constexpr int ldsBytes = FLAT ? S::LDS_BYTES_FLAT : S::LDS_BYTES_PLAIN;
-  auto kern = unet::conv3x3_x3_t448_kernel<TWX, WCO, EPI, FLAT>;
-  hipError_t e = ensure_dyn_lds((const void*)kern, ldsBytes);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), (size_t)ldsBytes, s, a);
-  return hipGetLastError();
-}
-template <int TWX, int WCO>
-hipError_t launch_conv_t448(const unet::ConvX3Args& a, int grid, int epi, bool flat, hipStream_t s) {
-  if constexpr (WCO == 1) {
-    if (epi == 2) return launch_conv_t448<TWX, 1, 2>(a, grid, s);
-  }
-  if constexpr (WCO == 4) {
-    if (flat)
-      return epi == 0 ? launch_conv_t448<TWX, 4, 0, true>(a, grid, s)
-           : epi == 1 ? launch_conv_t448<TWX, 4, 1, true>(a, grid, s)
-                      : launch_conv_t448<TWX, 4, 3, true>(a, grid, s);
-  }
-  return epi == 0 ? launch_conv_t448<TWX, WCO, 0>(a, grid, s)
-       : epi == 1 ? launch_conv_t448<TWX, WCO, 1>(a, grid, s)
-                  : launch_conv_t448<TWX, WCO, 3>(a, grid, s);
-}
-
-template <int TWX, int EPI, bool FLAT>
-hipError_t launch_conv_q8(const unet::ConvQ8Args& a, int grid, hipStream_t s) {
-  using S = unet::X3RShape<TWX>;
-  auto kern = unet::conv3x3_q8_r512_kernel<TWX, EPI, FLAT>;
-  hipError_t e = ensure_dyn_lds((const void*)kern, S::LDS_BYTES);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), (size_t)S::LDS_BYTES, s, a);
-  return hipGetLastError();
-}
-
 // The forced form of the test entry points' tile_width argument, decoded here and nowhere else (what each ABI integer
 // stands for: DESIGN.md, section 4.15, "The forced form")
 struct X3Force {
@@ -684,33 +609,18 @@ void x3_conv_label(const X3ConvPlan& p, char* buf, size_t cap) {
   }
 }
 
+// One launch of the plan's instance, through the structure's launch unit (launch.h)
 hipError_t launch_conv_plan(const X3ConvPlan& p, const unet::ConvQ8Args& a, hipStream_t s) {
   const X3Path& k = p.path;
   const int grid = p.grid, tw = k.tileW;
   const bool flat = k.flat != 0;
   switch (k.structure) {
-    case kX3T448:
-      if (tw == 32) return launch_conv_t448<32, 1>(a, grid, k.epi, false, s);
-      return k.waves == 4   ? launch_conv_t448<28, 4>(a, grid, k.epi, flat, s)
-             : k.waves == 2 ? launch_conv_t448<28, 2>(a, grid, k.epi, false, s)
-                            : launch_conv_t448<28, 1>(a, grid, k.epi, false, s);
-    case kX3Q8:
-      if (tw == 14) return k.epi == 4 ? launch_conv_q8<14, 4, true>(a, grid, s) : launch_conv_q8<14, 0, true>(a, grid, s);
-      if (k.epi == 4) return flat ? launch_conv_q8<28, 4, true>(a, grid, s) : launch_conv_q8<28, 4, false>(a, grid, s);
-      return flat ? launch_conv_q8<28, 0, true>(a, grid, s) : launch_conv_q8<28, 0, false>(a, grid, s);
-    case kX3R512: {
-      const bool f32 = k.epi == 3, w1 = k.waves == 1;
-      switch (tw) {
-        case 28: return w1 ? launch_conv_r512<28, 1>(a, grid, flat, f32, s) : launch_conv_r512<28, 2>(a, grid, flat, f32, s);
-        case 14: return w1 ? launch_conv_r512<14, 1>(a, grid, flat, f32, s) : launch_conv_r512<14, 2>(a, grid, flat, f32, s);
-        case 32: return w1 ? launch_conv_r512<32, 1>(a, grid, flat, f32, s) : launch_conv_r512<32, 2>(a, grid, flat, f32, s);
-        case 16: return launch_conv_r512<16, 1>(a, grid, flat, f32, s);
-        default: return launch_conv_r512<8, 1>(a, grid, flat, f32, s);
-      }
-    }
+    case kX3T448: return unet::launch_conv_t448(a, grid, tw, k.waves, k.epi, flat, s);
+    case kX3Q8: return unet::launch_conv_q8(a, grid, tw, k.epi, flat, s);
+    case kX3R512: return unet::launch_conv_r512(a, grid, tw, k.waves, flat, k.epi == 3, s);
     case kX3Ws: {
       const int epi = k.kSplit > 1 ? 3 : k.epi;   // split-K items write raw fp32 partial sums
-      return tw == 32 ? launch_conv_x3<32>(a, grid, epi, flat, s) : launch_conv_x3<16>(a, grid, epi, flat, s);
+      return unet::launch_conv_x3(a, grid, tw, epi, flat, s);
     }
     default: return hipErrorInvalidValue;
   }
@@ -931,20 +841,10 @@ hipError_t launch_upconv_plan(const X3UpconvPlan& p, unet::UpconvX3Args a, const
   a.nChunks = cin / 32, a.coTiles = p.coTiles, a.pixTiles = p.pixTiles, a.abSplit = p.abSplit;
   const double px = (double)npix, cols = MODE == 0 ? 4.0 * cout : (double)cout;
   const bool r512 = p.path.structure == kX3R512;
-  void (*kern)(const unet::UpconvX3Args);
-  if (!r512)
-    kern = unet::upconv2x2_x3_ws_kernel<MODE>;
-  else if constexpr (MODE == 0)
-    kern = p.outQ ? unet::upconv2x2_x3_r512_kernel<0, true> : unet::upconv2x2_x3_r512_kernel<0>;
-  else
-    kern = unet::upconv2x2_x3_r512_kernel<1>;
-  const int lds = r512 ? unet::UpconvX3RShape::LDS_BYTES : unet::UpconvX3Shape::LDS_BYTES;
-  const hipError_t e = ensure_dyn_lds((const void*)kern, lds);
-  if (e != hipSuccess) return e;
   prof_begin(label, 2.0 * px * cin * cols, 4.0 * (px * cin + px * cols), s);
-  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(r512 ? 256 : 512), (size_t)lds, s, a);
+  const hipError_t e = unet::launch_upconv_x3(a, p.grid, r512, MODE, p.outQ, s);
   prof_end(s);
-  return hipGetLastError();
+  return e;
 }
 
 // in: planes (n,h,w,op.cin) -> out planes (n,2h,2w) with pixel stride ldo at channel offset coOff.
@@ -1406,14 +1306,9 @@ hipError_t run_dec_step_x3(const DecStepX3& st, const X3DecStepPlan& p, const X3
     a.tilesX = p.tilesX, a.tilesY = p.tilesY, a.pixTiles = p.pixTiles, a.coTiles = p.coTiles;
     a.nS = f / 32, a.nX = 2 * f / 32;
     a.err = g_errWord ? g_errWord : op_err_word();
-    void (*kern)(const unet::UpcatX3Args) = p.wco == 2 ? unet::upcat_conv3x3_dec_f16x3_kernel<2> : unet::upcat_conv3x3_dec_f16x3_kernel<1>;
     // executed multiply-adds: 9 f^2 (skip) + 8 f^2 (x: 4 taps x 2f) per pixel
     prof_begin(p.label[0], 2.0 * px * 17.0 * f * f, 4.0 * (px * f + px / 4 * 2 * f + px * f) + 2.0 * (9.0 * f * f + 32.0 * f * f), s);
-    hipError_t e = ensure_dyn_lds((const void*)kern, unet::X3DShape::LDS_BYTES);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), (size_t)unet::X3DShape::LDS_BYTES, s, a);
-      e = hipGetLastError();
-    }
+    const hipError_t e = unet::launch_upcat_dec(a, p.grid, p.wco, s);
     prof_end(s);
     return e;
   }
@@ -1427,16 +1322,10 @@ hipError_t run_dec_step_x3(const DecStepX3& st, const X3DecStepPlan& p, const X3
     a.npix = (long)n * h * w, a.h = h, a.w = w, a.Cin = 2 * f, a.Cout = f, a.ldo = io.ldCat, a.co_off = io.upOff;
     a.nChunks = 2 * f / 32, a.coTiles = p.deep.coTiles, a.pixTiles = p.deep.pixTiles, a.abSplit = 1;
     a.err = g_errWord ? g_errWord : op_err_word();
-    const bool w14 = p.deep.wmax == 14;
-    void (*kern)(const unet::UpconvX3Args) = w14 ? unet::upconv2x2_x3_win_kernel<14> : unet::upconv2x2_x3_win_kernel<28>;
-    const int lds = w14 ? unet::UpconvX3WShape<14>::LDS_BYTES : unet::UpconvX3WShape<28>::LDS_BYTES;
-    hipError_t e = ensure_dyn_lds((const void*)kern, lds);
-    if (e != hipSuccess) return e;
     // executed multiply-adds: 4 taps x 2f per output pixel and channel; x read, P written, the window weights
     prof_begin(p.label[0], 2.0 * px * 8.0 * f * f, 4.0 * (pxLo * 2 * f + px * f) + 2.0 * 32.0 * f * f, s);
-    hipLaunchKernelGGL(kern, dim3(p.deep.grid), dim3(256), (size_t)lds, s, a);
+    const hipError_t e = unet::launch_upconv_win(a, p.deep.grid, p.deep.wmax == 14, s);
     prof_end(s);
-    e = hipGetLastError();
     if (e != hipSuccess || p.nLaunch == 1) return e;
   }
   const X3ConvPlan& c = p.deep.conv;
@@ -1449,17 +1338,11 @@ hipError_t run_dec_step_x3(const DecStepX3& st, const X3DecStepPlan& p, const X3
   a.coTiles = c.coTiles, a.coGroup = c.coGroup, a.nChunks = c.nChunks, a.kSplit = 1, a.chunksTotal = f / 32;
   a.err = g_errWord ? g_errWord : op_err_word();
   a.ldi = io.ldCat, a.ldAdd = io.ldCat, a.add = io.cat + io.upOff, a.addLo = io.catLo, a.addScale = op.addScale;
-  const bool flat = c.path.flat != 0;
-  using S = unet::X3TShape<28, unet::x3t_row_blocks(4)>;
-  void (*kern)(const unet::ConvX3AddArgs) = flat ? unet::conv3x3_x3_t448add_kernel<true> : unet::conv3x3_x3_t448add_kernel<false>;
-  const int lds = flat ? S::LDS_BYTES_FLAT : S::LDS_BYTES_PLAIN;
-  const hipError_t e = ensure_dyn_lds((const void*)kern, lds);
-  if (e != hipSuccess) return e;
   // the skip half's 3x3 convolution; the skip and P read, the output written
   prof_begin(p.label[1], 2.0 * px * 9.0 * f * f, 4.0 * (px * f + px * f + px * f) + 2.0 * 9.0 * f * f, s);
-  hipLaunchKernelGGL(kern, dim3(c.grid), dim3(256), (size_t)lds, s, a);
+  const hipError_t e = unet::launch_conv_t448add(a, c.grid, c.path.flat != 0, s);
   prof_end(s);
-  return hipGetLastError();
+  return e;
 }
 
 // First convolution on conv_first_x3.h: uint8 (N,H,W,3) frames (u8) or an fp32 NCHW image -> planes (N,H,W,op.cout) with
@@ -1545,17 +1428,14 @@ hipError_t run_enc1_x3(const X3Enc1Plan& p, const GemmOpX3& op1, const GemmOpX3&
   a.wt1 = op1.wt, a.scale1 = op1.scale, a.shift1 = op1.shift, a.relu1 = op1.relu;
   a.m0 = mean ? mean[0] : 0.f, a.m1 = mean ? mean[1] : 0.f, a.m2 = mean ? mean[2] : 0.f;
   a.s0 = stdv ? stdv[0] : 1.f, a.s1 = stdv ? stdv[1] : 1.f, a.s2 = stdv ? stdv[2] : 1.f;
-  auto kern = unet::conv3x3_enc1_x3_kernel;
-  const hipError_t e = ensure_dyn_lds((const void*)kern, unet::X3Enc1Shape::LDS_BYTES);
-  if (e != hipSuccess) return e;
   // the algorithmic flops of both convolutions (the halo's recomputed pixels are not counted); the frames read, the
   // planes and their pooled copy written
   const double px = (double)io.n * io.h * io.w;
   prof_begin("conv3x3_enc1_f16x3", 2.0 * px * (27.0 * 64 + 9.0 * 64 * 64), 3.0 * px + 4.0 * px * 64 + px * 64, s);
-  hipLaunchKernelGGL(kern, dim3(c.grid), dim3(256), (size_t)unet::X3Enc1Shape::LDS_BYTES, s, a);
+  const hipError_t e = unet::launch_conv_enc1(a, c.grid, s);
   prof_end(s);
   if (path) *path = c.path;
-  return hipGetLastError();
+  return e;
 }
 
 }  // namespace

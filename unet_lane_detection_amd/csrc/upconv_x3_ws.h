@@ -237,71 +237,4 @@ __global__ __launch_bounds__(512, 1) void upconv2x2_x3_ws_kernel(const UpconvX3A
   if (MODE == 0) x3_report_range(amax, a.err);
 }
 
-// ConvTranspose2d weight (Cin, Cout, 2, 2) fp32 -> the kernel's operand layout
-// [coTile(64)][chunk(32)][plane(2)][ab(4)][cs(4)][lane][8], un-prescaled (training: re-derived on the device after every
-// optimizer step; the host packer of the inference tier pre-scales per output channel)
-// Operand of the transposed convolution's INPUT gradient as a MODE 1 GEMM: K = 4 * cout rows k = ab * cout + co,
-// N = cin columns n = ci, W_d[k][n] = w[ci][co][ab]; layout [tile(256 columns)][chunk(32 k)][plane][group(4)][cs][lane][8]
-// with zeros for columns >= cin (cin = 128 fills half a tile).
-__global__ __launch_bounds__(256) void pack_upconv_dgrad_x3_kernel(const float* __restrict__ w, uint16_t* __restrict__ out,
-                                                                   int cin, int cout) {
-  const int K = 4 * cout, nCh = K / 32;
-  const int nT = (cin + 255) / 256;
-  const size_t total = (size_t)nT * nCh * 16 * 64;
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    const int lane = (int)(i & 63);
-    size_t r0 = i >> 6;
-    const int cs = (int)(r0 & 3);
-    const int grp = (int)((r0 >> 2) & 3);
-    r0 >>= 4;
-    const int kc = (int)(r0 % nCh);
-    const int ct = (int)(r0 / nCh);
-    const int j = lane & 15, lq = lane >> 4;
-    const int n = 256 * ct + 64 * grp + 16 * (j >> 2) + 4 * cs + (j & 3);   // = ci
-    uint32_t hi[4], lo[4];
-#pragma unroll
-    for (int e2 = 0; e2 < 4; ++e2) {
-      float v[2] = {0.f, 0.f};
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int k = kc * 32 + lq * 8 + e2 * 2 + e;
-        const int ab = k / cout, co = k - ab * cout;
-        if (n < cin) v[e] = w[((size_t)n * cout + co) * 4 + ab];
-      }
-      split_pk_f16(v[0], v[1], hi[e2], lo[e2]);
-    }
-    uint16_t* base = out + ((size_t)ct * nCh + kc) * (size_t)(2 * 16 * 64 * 8);
-    *reinterpret_cast<uint4*>(base + ((size_t)0 * 16 + grp * 4 + cs) * 64 * 8 + lane * 8) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-    *reinterpret_cast<uint4*>(base + ((size_t)1 * 16 + grp * 4 + cs) * 64 * 8 + lane * 8) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-  }
-}
-
-__global__ __launch_bounds__(256) void pack_upconv_x3_kernel(const float* __restrict__ w, uint16_t* __restrict__ out,
-                                                             int cin, int cout) {
-  const int nCh = cin / 32;
-  const size_t total = (size_t)(cout / 64) * nCh * 16 * 64;
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    const int lane = (int)(i & 63);
-    size_t r0 = i >> 6;
-    const int cs = (int)(r0 & 3);
-    const int ab = (int)((r0 >> 2) & 3);
-    r0 >>= 4;
-    const int kc = (int)(r0 % nCh);
-    const int ct = (int)(r0 / nCh);
-    const int j = lane & 15, lq = lane >> 4;
-    const int co = 64 * ct + 16 * (j >> 2) + 4 * cs + (j & 3);
-    uint32_t hi[4], lo[4];
-#pragma unroll
-    for (int e2 = 0; e2 < 4; ++e2) {
-      const int ci = kc * 32 + lq * 8 + e2 * 2;
-      split_pk_f16(w[((size_t)ci * cout + co) * 4 + ab], w[((size_t)(ci + 1) * cout + co) * 4 + ab], hi[e2], lo[e2]);
-    }
-    uint16_t* base = out + ((size_t)ct * nCh + kc) * (size_t)(2 * 16 * 64 * 8);
-    *reinterpret_cast<uint4*>(base + ((size_t)0 * 16 + ab * 4 + cs) * 64 * 8 + lane * 8) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-    *reinterpret_cast<uint4*>(base + ((size_t)1 * 16 + ab * 4 + cs) * 64 * 8 + lane * 8) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-  }
-}
-
 }  // namespace unet
