@@ -46,12 +46,13 @@ typedef enum unet_status {
 } unet_status;
 
 #define UNET_MAX_DEPTH 6
+#define UNET_MAX_CLASSES 8
 
 /* Network description = constructor arguments of the reference's float model,
  * `UNet(in_channels, out_channels, features)` (reference README.md:1424). */
 typedef struct unet_config {
   int32_t in_channels;              /* 3 */
-  int32_t out_channels;             /* 1 (only 1 is supported by the head kernel) */
+  int32_t out_channels;             /* 1: the reference's lane head; 2..UNET_MAX_CLASSES: the multi-class head (below) */
   int32_t depth;                    /* len(features), 1..UNET_MAX_DEPTH */
   int32_t features[UNET_MAX_DEPTH]; /* e.g. {64,128,256,512} */
   int32_t device;                   /* HIP device index (reference: device_id string, rknn_executor.py:5) */
@@ -288,6 +289,94 @@ int unet_train_eval_u8(unet_handle_t h, const uint8_t* frames_dev, int n, int he
                        void* stream);
 int unet_train_eval_f32(unet_handle_t h, const float* image_nchw_dev, int n, int height, int width, float* logits_dev,
                         void* stream);
+
+/* ---- multi-class segmentation: out_channels = K, 2 <= K <= UNET_MAX_CLASSES (csrc/multiclass_kernels.h) ----------
+ * The reference's roadmap (multi-lane classification, lane + drivable area) on the network as it is: the 1x1 head has K
+ * rows, a pixel's class is the argmax of its K logits, training minimises softmax cross-entropy (+ Dice).  A handle with
+ * out_channels == 1 runs exactly what it ran before; every entry point below returns UNET_ERR_INVALID_ARG for it, and
+ * the single-class entry points (the unet_forward_* family of every tier, the training step with float targets, the
+ * unet_train_set_loss pair) return UNET_ERR_INVALID_ARG for a handle with K > 1, each with a text for unet_last_error,
+ * before any device is touched.  The K-class forward exists on the fp32 and f16x3 tiers, the training step on the
+ * training handle (which dispatches its convolutions as for K == 1); the bf16, f16q8, int8 and hybrid inference tiers
+ * are single-class.
+ *
+ * Forward.  precision: 0 = the fp32 tier, 1 = the f16x3 tier (its last convolution stores operand planes and the K-way
+ * head reads them; needs what unet_forward_u8_x3 needs, and the f16q8 switch off).  Every output is optional:
+ *   logits_dev (N,K,H,W) fp32, NCHW like the torch module      probs_dev (N,K,H,W) = softmax over K
+ *   labels_dev (N,H,W) uint8 = argmax (ties to the lowest class; a NaN logit never wins)
+ *   mask_dev   (N,H,W) uint8 = 255 where the label is mask_class, else 0: the byte plane the lane-following, instance,
+ *              lane-fit and video stages take. */
+int unet_forward_classes_u8(unet_handle_t h, const uint8_t* frames_dev, int n, int height, int width, int precision,
+                            float* logits_dev, float* probs_dev, uint8_t* labels_dev, int mask_class, uint8_t* mask_dev,
+                            void* stream);
+int unet_forward_classes_f32(unet_handle_t h, const float* image_nchw_dev, int n, int height, int width, int precision,
+                             float* logits_dev, float* probs_dev, uint8_t* labels_dev, int mask_class, uint8_t* mask_dev,
+                             void* stream);
+
+/* The class loss.  A pixel is valid if its label is below K and is not ignore_index (-1: none).
+ *   CE    = sum_valid cw[t] (logsumexp(z) - z_t) / sum_valid cw[t]       F.cross_entropy(weight=, ignore_index=), mean
+ *   Dice  = 1 - mean_k (2 sum_valid p_k [t = k] + smooth) / (sum_valid p_k + sum_valid [t = k] + smooth),  p = softmax(z)
+ *   total = ce_weight CE + dice_weight Dice
+ * Deviations from torch, both on purpose: a label >= K that is not the ignore index is treated as ignored and counted
+ * (torch raises); with no valid weight (the CE denominator is 0) the CE term and its gradient are 0 (torch gives NaN).
+ * Domain: ce_weight, dice_weight >= 0 and not both 0; smooth > 0; class_weight[0..K) >= 0 and finite; ignore_index -1
+ * or 0..255; NaN and Inf are rejected.  Inside it no finite logit produces NaN or Inf. */
+typedef struct unet_class_loss_config {
+    float ce_weight, dice_weight, smooth;
+    float class_weight[UNET_MAX_CLASSES];
+    int ignore_index;
+} unet_class_loss_config;
+
+/* The loss of a K-class training handle (default: ce_weight 1, dice_weight 0, smooth 1, class weights 1, no ignore
+ * index).  The configuration is checked first (UNET_ERR_INVALID_ARG), then the state (UNET_ERR_STATE without
+ * unet_train_attach). */
+int unet_train_set_class_loss(unet_handle_t h, const unet_class_loss_config* cfg);
+
+/* The training step of a K-class handle: as unet_train_forward_backward_u8 / _f32 with labels_dev (N,H,W) uint8 in place of
+ * the float targets.  loss_dev receives four floats {total, ce, dice, number of out-of-range labels}; logits_dev
+ * (optional) the (N,K,H,W) logits.  Profile records: "headk", "class_loss_grad", "headk_bwd".  On a K-class handle
+ * unet_train_eval_u8 / _f32 write (N,K,H,W) logits. */
+int unet_train_forward_backward_labels_u8(unet_handle_t h, const uint8_t* frames_dev, const uint8_t* labels_dev, int n,
+                                          int height, int width, float* loss_dev, float* logits_dev, void* stream);
+int unet_train_forward_backward_labels_f32(unet_handle_t h, const float* image_nchw_dev, const uint8_t* labels_dev, int n,
+                                           int height, int width, float* loss_dev, float* logits_dev, void* stream);
+
+/* Confusion matrix of one batch ADDED TO acc_dev: k * k unsigned 64-bit counts owned (and zeroed before the first batch)
+ * by the caller, acc_dev[t * k + p] = pixels of true class t predicted as p, over the pixels whose true label is below k
+ * and is not ignore_index and whose prediction is below k.  Integers throughout: exact.  work_dev: unet_confusion_work_bytes
+ * bytes on the device, the caller's.  A bare device ordinal; only enqueues on `stream`; bad arguments are refused with
+ * UNET_ERR_INVALID_ARG and a text for unet_op_last_error, before any device is touched.  numel at most 2^40. */
+size_t unet_confusion_work_bytes(void);
+int unet_confusion_accumulate(int device, const uint8_t* pred_dev, const uint8_t* truth_dev, size_t numel, int k,
+                              int ignore_index, unsigned long long* acc_dev, void* work_dev, void* stream);
+
+/* Labels and class mask of stored logits (n,k,pixels_per_image), e.g. those of unet_train_eval_*: the argmax and the byte
+ * plane of the forward above; either output optional.  The class loss of stored logits against labels (n,
+ * pixels_per_image) uint8: loss_dev[4] as the training step's, dlogits_dev (n,k,pixels_per_image) or NULL for the loss
+ * alone (a validation loop); work_dev: unet_class_loss_work_bytes bytes on the device, 8-byte aligned, the caller's.  Both
+ * take a bare device ordinal, only enqueue on `stream` and refuse bad arguments (a configuration outside its domain
+ * included) with UNET_ERR_INVALID_ARG and a text for unet_op_last_error, before any device is touched. */
+int unet_class_labels_f32(int device, const float* logits_dev, int n, int k, size_t pixels_per_image, uint8_t* labels_dev,
+                          int mask_class, uint8_t* mask_dev, void* stream);
+size_t unet_class_loss_work_bytes(void);
+int unet_class_loss_grad(int device, const float* logits_dev, const uint8_t* labels_dev, int n, int k,
+                         size_t pixels_per_image, const unet_class_loss_config* cfg, float* loss_dev, float* dlogits_dev,
+                         void* work_dev, void* stream);
+
+/* Test entry points of the multi-class kernels: weights and bias from host memory, scratch of the call's own, the stream
+ * synchronised before they return.  x / a / d_a: (n*h*w, c) dense fp32, 16-byte aligned, c % 4 == 0, k * c <= 4096.
+ * unet_op_headk: the outputs of the forward above, each optional.  unet_op_headk_backward: d_a[p,c] = sum_k
+ * dl[k,p] w[k,c] (optional), d_w[k,c] = sum_p dl[k,p] a[p,c], d_b[k] = sum_p dl[k,p], all on the device. */
+int unet_op_headk(int device, const float* x_dev, int n, int h, int w, int c, int k, const float* w_host,
+                  const float* b_host, float* logits_dev, float* probs_dev, uint8_t* labels_dev, int mask_class,
+                  uint8_t* mask_dev, void* stream);
+/* ... and from the f16x3 tier's operand planes: x_dev = fp16 hi plane (n*h*w, c), the lo plane x_lo halfs behind it (the
+ * layout of unet_op_head1x1_x3_planes); c % 8 == 0; the input is hi + lo. */
+int unet_op_headk_x3_planes(int device, const uint16_t* x_dev, size_t x_lo, int n, int h, int w, int c, int k,
+                            const float* w_host, const float* b_host, float* logits_dev, float* probs_dev,
+                            uint8_t* labels_dev, int mask_class, uint8_t* mask_dev, void* stream);
+int unet_op_headk_backward(int device, const float* dlogits_dev, const float* a_dev, const float* w_host, int n, int h,
+                           int w, int c, int k, float* d_a_dev, float* d_w_dev, float* d_b_dev, void* stream);
 
 /* Segmentation metrics and validation loss of one batch as one device reduction, added to running accumulators: the
  * body of the reference's validate() loop (README.md:2101-2110: criterion, compute_dice :2115-2120, per-batch values
@@ -837,6 +926,12 @@ int unet_resize_u8(int device, const uint8_t* src_dev, int height, int width, in
 int unet_augment_u8(int device, const uint8_t* images_dev, const uint8_t* masks_dev, int n_source, int height, int width,
                     const void* params_dev, int n_out, int mask_threshold, uint8_t* images_out_dev,
                     float* targets_out_dev, void* stream);
+/* The label mode of the same launch (multi-class training): labels_dev (n_source, height, width) uint8 class labels are
+ * warped like the masks, and labels_out_dev (n_out, height, width) uint8 receives the nearest-sampled byte itself, no
+ * threshold.  The images are what unet_augment_u8 writes, bit for bit.  Neither pointer may be NULL. */
+int unet_augment_u8_labels(int device, const uint8_t* images_dev, const uint8_t* labels_dev, int n_source, int height,
+                           int width, const void* params_dev, int n_out, uint8_t* images_out_dev,
+                           uint8_t* labels_out_dev, void* stream);
 /* sizeof one record, so a binding can check its layout against the library */
 size_t unet_augment_param_bytes(void);
 

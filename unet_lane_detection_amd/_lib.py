@@ -44,6 +44,20 @@ class LossConfig(C.Structure):
     ]
 
 
+UNET_MAX_CLASSES = 8
+
+
+class ClassLossConfig(C.Structure):
+    """unet_class_loss_config of include/unet_hip.h"""
+    _fields_ = [
+        ("ce_weight", C.c_float),
+        ("dice_weight", C.c_float),
+        ("smooth", C.c_float),
+        ("class_weight", C.c_float * UNET_MAX_CLASSES),
+        ("ignore_index", C.c_int),
+    ]
+
+
 class LaneViewStyle(C.Structure):
     """unet_lane_view_style of include/unet_hip.h"""
     _fields_ = [
@@ -256,6 +270,8 @@ SIGNATURES = {
                                  C.c_void_p]),
     "unet_augment_u8": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "unet_augment_u8_labels": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "unet_augment_param_bytes": (C.c_size_t, []),
     "unet_resize_u8_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p]),
@@ -301,6 +317,31 @@ SIGNATURES = {
     "unet_op_maxpool2x2": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "unet_op_head1x1": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float,
                                   C.c_void_p, C.c_void_p]),
+    # multi-class segmentation (csrc/multiclass_kernels.h)
+    "unet_forward_classes_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "unet_forward_classes_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "unet_train_set_class_loss": (C.c_int, [C.c_void_p, C.POINTER(ClassLossConfig)]),
+    "unet_train_forward_backward_labels_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "unet_train_forward_backward_labels_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "unet_confusion_work_bytes": (C.c_size_t, []),
+    "unet_confusion_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
+    "unet_op_headk": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "unet_op_headk_x3_planes": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p]),
+    "unet_class_loss_work_bytes": (C.c_size_t, []),
+    "unet_class_loss_grad": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t,
+                                       C.POINTER(ClassLossConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "unet_class_labels_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p]),
+    "unet_op_headk_backward": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -212,9 +212,10 @@ def gaussian_blur(img, ksize):
     return ((acc + (1 << (shift - 1))) >> shift).astype(np.uint8)
 
 
-def apply_model(images, masks, params, mask_threshold=127):
+def apply_model(images, masks, params, mask_threshold=127, labels=False):
     """images (n_source,H,W,3) uint8, masks (n_source,H,W) uint8 or None, params a PARAMS_DTYPE table ->
-    (images (n,H,W,3) uint8, targets (n,1,H,W) float32 or None)."""
+    (images (n,H,W,3) uint8, targets (n,1,H,W) float32 or None).  labels=True (multi-class training): the masks hold
+    class labels and the second output is the warped byte itself, (n,H,W) uint8 - no threshold."""
     images = np.asarray(images)
     if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] != 3:
         raise ValueError("images must be (n, H, W, 3) uint8")
@@ -228,7 +229,11 @@ def apply_model(images, masks, params, mask_threshold=127):
         masks = masks.reshape(ns, h, w)
     validate_params(params, ns)
     out = np.empty((params.size, h, w, 3), dtype=np.uint8)
-    tgt = np.empty((params.size, 1, h, w), dtype=np.float32) if masks is not None else None
+    if labels and masks is None:
+        raise ValueError("labels=True needs the label planes")
+    tgt = None
+    if masks is not None:
+        tgt = np.empty((params.size, h, w), dtype=np.uint8) if labels else np.empty((params.size, 1, h, w), dtype=np.float32)
     for i, p in enumerate(params):
         img = warp_image(images[p["src"]], p["m"])
         if p["flags"] & FLAG_BC:
@@ -238,7 +243,9 @@ def apply_model(images, masks, params, mask_threshold=127):
         if p["blur"] > 1:
             img = gaussian_blur(img, p["blur"])
         out[i] = img
-        if tgt is not None:
+        if tgt is not None and labels:
+            tgt[i] = warp_mask(masks[p["src"]], p["m"])
+        elif tgt is not None:
             tgt[i, 0] = warp_mask(masks[p["src"]], p["m"]) > mask_threshold
     return out, tgt
 
@@ -246,7 +253,7 @@ def apply_model(images, masks, params, mask_threshold=127):
 # ---------------------------------------------------------------------------------------------------------------
 # the kernel behind torch tensors
 # ---------------------------------------------------------------------------------------------------------------
-def _apply_device(images, masks, params, mask_threshold, out):
+def _apply_device(images, masks, params, mask_threshold, out, labels=False):
     import torch
 
     from . import _lib
@@ -263,18 +270,25 @@ def _apply_device(images, masks, params, mask_threshold, out):
     validate_params(params, ns)
     n = int(params.size)
     dev = images.device
+    if labels and masks is None:
+        raise ValueError("labels=True needs the label planes")
+    tgt_shape, tgt_dtype = ((n, h, w), torch.uint8) if labels else ((n, 1, h, w), torch.float32)
     if out is None:
         out_img = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
-        out_tgt = torch.empty((n, 1, h, w), dtype=torch.float32, device=dev) if masks is not None else None
+        out_tgt = torch.empty(tgt_shape, dtype=tgt_dtype, device=dev) if masks is not None else None
     else:
         out_img, out_tgt = out
         if out_img.shape != (n, h, w, 3) or out_img.dtype != torch.uint8 or not out_img.is_contiguous() or out_img.device != dev:
             raise ValueError("out[0] must be a contiguous (n, H, W, 3) uint8 tensor on the images' device")
-        if masks is not None and (out_tgt is None or out_tgt.shape != (n, 1, h, w) or out_tgt.dtype != torch.float32
+        if masks is not None and (out_tgt is None or out_tgt.shape != tgt_shape or out_tgt.dtype != tgt_dtype
                                   or not out_tgt.is_contiguous() or out_tgt.device != dev):
-            raise ValueError("out[1] must be a contiguous (n, 1, H, W) float32 tensor on the images' device")
+            raise ValueError("out[1] must be a contiguous (n, 1, H, W) float32 tensor - with labels=True (n, H, W) uint8 - "
+                             "on the images' device")
     # the table goes up on the launch's own stream, ahead of it
     table = torch.from_numpy(np.ascontiguousarray(params).view(np.uint8).copy()).to(dev)
+    if labels:
+        _lib.call("unet_augment_u8_labels", dev, images, masks, ns, h, w, table, n, out_img, out_tgt)
+        return out_img, out_tgt
     _lib.call("unet_augment_u8", dev, images, masks, ns, h, w, table, n, int(mask_threshold), out_img,
               out_tgt if masks is not None else None)
     return out_img, (out_tgt if masks is not None else None)
@@ -335,20 +349,21 @@ class Augmenter:
         p["blur"] = np.where(blur, size, 1)
         return p
 
-    def apply(self, images, masks, params=None, out=None):
+    def apply(self, images, masks, params=None, out=None, labels=False):
         """-> (images uint8 (n,H,W,3), targets float32 (n,1,H,W) or None without masks).  Torch tensors on the device
         go through the kernel, numpy arrays through the model; anything else is an error.  params None draws one
-        record per given image; out = (images, targets) tensors to write into (device path)."""
+        record per given image; out = (images, targets) tensors to write into (device path).  labels=True: the masks
+        are class-label planes and come back warped as they are, uint8 (n,H,W), for a K-class trainer."""
         if params is None:
             params = self.sample_params(len(images), len(images))
         if isinstance(images, np.ndarray):
             if out is not None:
                 raise ValueError("out= is for device tensors")
-            return apply_model(images, masks, params, self.mask_threshold)
+            return apply_model(images, masks, params, self.mask_threshold, labels=labels)
         import torch
         if not isinstance(images, torch.Tensor) or not images.is_cuda:
             raise TypeError("images must be a numpy array (the CPU model) or a torch tensor on the GPU (the kernel)")
-        return _apply_device(images, masks, params, self.mask_threshold, out)
+        return _apply_device(images, masks, params, self.mask_threshold, out, labels=labels)
 
 
 class DeviceDataset:
@@ -394,7 +409,9 @@ class AugmentedBatches:
     in the kernel through the parameter table's source index: no indexed copy precedes it.  Under an initialised
     process group the augmenter is re-seeded with seed + rank, so the ranks draw different streams."""
 
-    def __init__(self, dataset, batch_size, augmenter, sampler=None, drop_last=False, rank=None):
+    def __init__(self, dataset, batch_size, augmenter, sampler=None, drop_last=False, rank=None, labels=False):
+        """labels=True: the data set's masks are class-label planes; the batches carry uint8 (n,H,W) labels"""
+        self.labels = bool(labels)
         self.images, self.masks = _arrays(dataset)
         self.batch_size, self.sampler, self.drop_last = int(batch_size), sampler, bool(drop_last)
         if self.batch_size <= 0 or len(self.images) == 0:
@@ -418,16 +435,17 @@ class AugmentedBatches:
         self.last_order = order
         for idx in _batches(order, self.batch_size, self.drop_last):
             params = self.augmenter.sample_params(len(idx), n, idx)
-            yield self.augmenter.apply(self.images, self.masks, params)
+            yield self.augmenter.apply(self.images, self.masks, params, labels=self.labels)
 
 
-def val_batches(dataset, batch_size, mask_threshold=127):
+def val_batches(dataset, batch_size, mask_threshold=127, labels=False):
     """The reference's `val_transform` (README.md:2051-2055): no augmentation, frames in order, masks thresholded to
-    targets.  Returns a callable for loop.fit / trainer.validate."""
+    targets (labels=True: class-label planes passed through as uint8 (n,H,W)).  Returns a callable for loop.fit /
+    trainer.validate."""
     images, masks = _arrays(dataset)
     plain = Augmenter(mask_threshold=mask_threshold)
 
     def epoch():
         for idx in _batches(np.arange(len(images)), int(batch_size), False):
-            yield plain.apply(images, masks, identity_params(len(idx), idx))
+            yield plain.apply(images, masks, identity_params(len(idx), idx), labels=labels)
     return epoch

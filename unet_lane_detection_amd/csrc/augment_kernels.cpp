@@ -107,11 +107,14 @@ __device__ __forceinline__ uint32_t augment_pixel(const uint8_t* __restrict__ im
   return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16);
 }
 
+// LABELS: `targets` is a uint8 (n, H, W) plane that receives the nearest-sampled mask byte itself (class labels) instead
+// of the float (n, 1, H, W) plane of thresholded values; everything else is the same code
+template <bool LABELS>
 __global__ __launch_bounds__(THREADS) void augment_kernel(const uint8_t* __restrict__ images, const uint8_t* __restrict__ masks,
                                                           int nSource, int height, int width,
                                                           const AugmentParams* __restrict__ params, int tilesX, int tilesY,
                                                           int maskThreshold, uint8_t* __restrict__ out,
-                                                          float* __restrict__ targets) {
+                                                          void* __restrict__ targets) {
   __shared__ uint32_t stage[SH * SW];   // tile + halo before the blur
   __shared__ uint2 rows[SH * TW];       // horizontal sums: x = R | G << 16, y = B (each <= 255 * 64)
   __shared__ uint32_t tile[TH * TW];    // the finished tile
@@ -204,7 +207,12 @@ __global__ __launch_bounds__(THREADS) void augment_kernel(const uint8_t* __restr
         int X, Y;
         fixed_coords(P, height, width, tx0 + lx, ty0 + ly, X, Y);
         const int xx = reflect101((X + 16) >> 5, width), yy = reflect101((Y + 16) >> 5, height);
-        targets[((size_t)n * height + (ty0 + ly)) * width + tx0 + lx] = (int)msk[(size_t)yy * width + xx] > maskThreshold ? 1.f : 0.f;
+        const size_t o = ((size_t)n * height + (ty0 + ly)) * width + tx0 + lx;
+        const uint8_t m = msk[(size_t)yy * width + xx];
+        if constexpr (LABELS)
+          static_cast<uint8_t*>(targets)[o] = m;
+        else
+          static_cast<float*>(targets)[o] = (int)m > maskThreshold ? 1.f : 0.f;
       }
     }
   }
@@ -214,12 +222,16 @@ __global__ __launch_bounds__(THREADS) void augment_kernel(const uint8_t* __restr
 
 hipError_t launch_augment(const uint8_t* images, const uint8_t* masks, int nSource, int height, int width,
                           const AugmentParams* params, int nOut, int maskThreshold, uint8_t* out, float* targets,
-                          hipStream_t s) {
+                          uint8_t* labels, hipStream_t s) {
   const int tilesX = (width + TW - 1) / TW, tilesY = (height + TH - 1) / TH;
   const unsigned long long blocks = (unsigned long long)tilesX * tilesY * (unsigned long long)nOut;
   if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(augment_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, images, masks, nSource, height, width, params,
-                     tilesX, tilesY, maskThreshold, out, targets);
+  if (labels)
+    hipLaunchKernelGGL(augment_kernel<true>, dim3((unsigned)blocks), dim3(THREADS), 0, s, images, masks, nSource, height, width,
+                       params, tilesX, tilesY, maskThreshold, out, (void*)labels);
+  else
+    hipLaunchKernelGGL(augment_kernel<false>, dim3((unsigned)blocks), dim3(THREADS), 0, s, images, masks, nSource, height, width,
+                       params, tilesX, tilesY, maskThreshold, out, (void*)targets);
   return hipGetLastError();
 }
 
@@ -241,7 +253,23 @@ int unet_augment_u8(int device, const uint8_t* imagesDev, const uint8_t* masksDe
   if (int rc = op.on(device)) return rc;
   const hipError_t e = unet::launch_augment(imagesDev, masksDev, nSource, height, width,
                                             static_cast<const unet::AugmentParams*>(paramsDev), nOut, maskThreshold,
-                                            imagesOutDev, targetsOutDev, (hipStream_t)stream);
+                                            imagesOutDev, targetsOutDev, nullptr, (hipStream_t)stream);
+  const int rc = op.done(e);
+  return e == hipErrorInvalidValue ? UNET_ERR_INVALID_ARG : rc;   // a grid the launch itself refuses
+}
+
+// the label mode: the warped mask's byte itself (a class label) to a uint8 (nOut, H, W) plane
+int unet_augment_u8_labels(int device, const uint8_t* imagesDev, const uint8_t* labelsDev, int nSource, int height, int width,
+                           const void* paramsDev, int nOut, uint8_t* imagesOutDev, uint8_t* labelsOutDev, void* stream) {
+  const unet::OpCall op{"unet_augment_u8_labels"};
+  if (!imagesDev || !labelsDev || !paramsDev || !imagesOutDev || !labelsOutDev || nOut <= 0 || nSource <= 0)
+    return op.refuse("refused by the entry point's checks");
+  if (height < unet::AUG_MIN_SIDE || width < unet::AUG_MIN_SIDE || height > unet::AUG_MAX_SIDE || width > unet::AUG_MAX_SIDE)
+    return op.refuse("height and width must lie between AUG_MIN_SIDE and AUG_MAX_SIDE", UNET_ERR_SHAPE);
+  if (int rc = op.on(device)) return rc;
+  const hipError_t e = unet::launch_augment(imagesDev, labelsDev, nSource, height, width,
+                                            static_cast<const unet::AugmentParams*>(paramsDev), nOut, 0, imagesOutDev, nullptr,
+                                            labelsOutDev, (hipStream_t)stream);
   const int rc = op.done(e);
   return e == hipErrorInvalidValue ? UNET_ERR_INVALID_ARG : rc;   // a grid the launch itself refuses
 }

@@ -28,9 +28,10 @@ constexpr int AUG_MIN_SIDE = 8;       // reflect-101 with the blur's 3-pixel hal
 constexpr int AUG_MAX_SIDE = 32768;   // 1/32-pixel coordinates stay inside an int
 
 // images (nSource,H,W,3) u8, masks (nSource,H,W) u8 or null, params nOut records on the device ->
-// out (nOut,H,W,3) u8 and, with masks, targets (nOut,1,H,W) float = mask > threshold.
+// out (nOut,H,W,3) u8 and, with masks, targets (nOut,1,H,W) float = mask > threshold - or, with `labels` given (the
+// label mode: targets is then ignored), labels (nOut,H,W) u8 = the nearest-sampled mask byte itself.
 hipError_t launch_augment(const uint8_t* images, const uint8_t* masks, int nSource, int height, int width,
                           const AugmentParams* params, int nOut, int maskThreshold, uint8_t* out, float* targets,
-                          hipStream_t s);
+                          uint8_t* labels, hipStream_t s);
 
 }  // namespace unet

@@ -695,6 +695,7 @@ int unet_set_bf16_persistent(int mode) {
 int unet_forward_u8_bf16(unet_handle_t h, const uint8_t* frames, int n, int height, int width, float* logits,
                          float* probs, uint8_t* mask, float thr, void* stream) {
   if (!h || !frames) return UNET_ERR_INVALID_ARG;
+  if (int rc = single_class_only(h, "unet_forward_u8_bf16")) return rc;
   if (!h->finalized) {
     h->err = "unet_finalize has not been called";
     return UNET_ERR_STATE;

@@ -54,6 +54,7 @@
 #include "conv_h16.h"
 #include "launch.h"
 #include "op_entry.h"
+#include "multiclass_kernels.h"
 
 // Kernels that need more dynamic LDS than the default opt in once per (device, kernel): the attribute is per device.
 // Shared with the launch units (launch.h).
@@ -575,6 +576,7 @@ struct unet_ctx {
   std::vector<GemmOp> dec;  // 2 per level (decoder order)
   float* headW = nullptr;
   float headB = 0.f;
+  float* headBk = nullptr;   // out_channels > 1: the K biases on the device
 
   GrowBuf ws;   // workspace
 
@@ -637,12 +639,36 @@ struct unet_ctx {
     for (auto* v : {&enc, &bott, &up, &dec})
       for (auto& op : *v) op.free_dev();
     if (headW) hipFree(headW);
-    headW = nullptr;
+    if (headBk) hipFree(headBk);
+    headW = headBk = nullptr;
     ws.release();
   }
 };
 
 namespace {
+
+// Single-class and K-class handles have entry points of their own (include/unet_hip.h, "multi-class segmentation"): the
+// refusal of a call on the other kind, before any device is touched.  UNET_OK where the call may go on.
+int single_class_only(unet_ctx* h, const char* who) {
+  if (!h || h->cfg.out_channels == 1) return UNET_OK;
+  h->err = std::string(who) + ": this entry point serves out_channels == 1; a handle with " +
+           std::to_string(h->cfg.out_channels) + " classes runs unet_forward_classes_* and unet_train_forward_backward_labels_*";
+  return UNET_ERR_INVALID_ARG;
+}
+int multi_class_only(unet_ctx* h, const char* who) {
+  if (!h || h->cfg.out_channels > 1) return UNET_OK;
+  h->err = std::string(who) + ": this entry point serves out_channels >= 2; the handle has the single-class head";
+  return UNET_ERR_INVALID_ARG;
+}
+
+// what a K-class forward writes (every pointer optional)
+struct ClassOut {
+  float* logits = nullptr;
+  float* probs = nullptr;
+  uint8_t* labels = nullptr;
+  int maskClass = 0;
+  uint8_t* mask = nullptr;
+};
 
 // Profiler and error word of handle `h` become the calling thread's launch context for the scope's lifetime.
 struct LaunchScope {
@@ -743,7 +769,7 @@ int fold_bn_and_build(unet_ctx* h, GemmOp& op, const std::string& prefix, int co
 }
 
 int forward_common(unet_ctx* h, int n, int height, int width, float* logits, float* probs, uint8_t* mask,
-                   float thr, hipStream_t s, const WsPlan& p) {
+                   float thr, hipStream_t s, const WsPlan& p, const ClassOut* classes = nullptr) {
   const unet_config& c = h->cfg;
   LaunchScope scope(h);
   float* ws = reinterpret_cast<float*>(h->ws.p);
@@ -808,8 +834,18 @@ int forward_common(unet_ctx* h, int n, int height, int width, float* logits, flo
     probe(4 + 2 * D + 2 * j, tmpB, (size_t)n * ch * cw, f, f);
     cur = tmpB;
   }
-  HIPCHK(h->err, run_head(cur, h->headW, h->headB, (size_t)n * height * width, c.features[0], logits, probs, mask,
-                          thr, s));
+  if (classes) {   // out_channels > 1
+    const size_t npx = (size_t)n * height * width;
+    prof_begin("headk", 2.0 * npx * c.features[0] * c.out_channels, 4.0 * npx * c.features[0], s);
+    const hipError_t e = unet::launch_headk(cur, h->headW, h->headBk, n, (size_t)height * width, c.features[0], c.out_channels,
+                                            classes->logits, classes->probs, classes->labels, classes->maskClass,
+                                            classes->mask, s);
+    prof_end(s);
+    HIPCHK(h->err, e);
+  } else {
+    HIPCHK(h->err, run_head(cur, h->headW, h->headB, (size_t)n * height * width, c.features[0], logits, probs, mask,
+                            thr, s));
+  }
   HIPCHK(h->err, histStatus);
   return h->async_error();
 }
@@ -841,14 +877,16 @@ const char* unet_version(void) { return "unet_hip 0.1 (gfx950, fp32 MFMA implici
 
 int unet_create(const unet_config* cfg, unet_handle_t* out) {
   if (!cfg || !out) return UNET_ERR_INVALID_ARG;
-  if (cfg->depth < 1 || cfg->depth > UNET_MAX_DEPTH || cfg->out_channels != 1 || cfg->in_channels < 1 ||
-      cfg->in_channels > 4)
+  if (cfg->depth < 1 || cfg->depth > UNET_MAX_DEPTH || cfg->out_channels < 1 || cfg->out_channels > UNET_MAX_CLASSES ||
+      cfg->in_channels < 1 || cfg->in_channels > 4)
     return UNET_ERR_INVALID_ARG;
   for (int i = 0; i < cfg->depth; ++i)
     if (cfg->features[i] <= 0 || cfg->features[i] % 4) return UNET_ERR_INVALID_ARG;
   for (int i = 0; i + 1 < cfg->depth; ++i)  // ConvTranspose2d(2f -> f) feeds on the level below: widths must double
     if (cfg->features[i + 1] != 2 * cfg->features[i]) return UNET_ERR_INVALID_ARG;
   if (cfg->device < 0) return UNET_ERR_INVALID_ARG;  // the device itself is first touched by unet_finalize
+  // the K-way head keeps its K * f0 weights in LDS (csrc/multiclass_kernels.h)
+  if (cfg->out_channels > 1 && (long long)cfg->out_channels * cfg->features[0] > unet::MC_MAX_WEIGHTS) return UNET_ERR_INVALID_ARG;
   auto* h = new unet_ctx();
   h->cfg = *cfg;
   h->spec = build_spec(*cfg);
@@ -925,6 +963,9 @@ int unet_finalize(unet_handle_t h) {
   h->headW = nullptr;
   if ((rc = upload(h->err, &h->headW, h->params["output.weight"]))) return rc;
   h->headB = h->params["output.bias"][0];
+  if (h->headBk) hipFree(h->headBk);
+  h->headBk = nullptr;
+  if (c.out_channels > 1 && (rc = upload(h->err, &h->headBk, h->params["output.bias"]))) return rc;
   h->finalized = true;
   return UNET_OK;
 }
@@ -958,7 +999,8 @@ static int forward_prologue(unet_handle_t h, const void* in, int n, int height, 
 
 int unet_forward_u8(unet_handle_t h, const uint8_t* frames, int n, int height, int width, float* logits,
                     float* probs, uint8_t* mask, float thr, void* stream) {
-  int rc = forward_prologue(h, frames, n, height, width);
+  int rc = single_class_only(h, "unet_forward_u8");
+  if (!rc) rc = forward_prologue(h, frames, n, height, width);
   if (rc) return rc;
   if (h->cfg.in_channels != 3) {
     h->err = "uint8 frames need in_channels == 3";
@@ -977,7 +1019,8 @@ int unet_forward_u8(unet_handle_t h, const uint8_t* frames, int n, int height, i
 
 int unet_forward_f32(unet_handle_t h, const float* image, int n, int height, int width, float* logits, float* probs,
                      uint8_t* mask, float thr, void* stream) {
-  int rc = forward_prologue(h, image, n, height, width);
+  int rc = single_class_only(h, "unet_forward_f32");
+  if (!rc) rc = forward_prologue(h, image, n, height, width);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   const WsPlan p = plan_ws(h->cfg, n, height, width);
@@ -986,6 +1029,67 @@ int unet_forward_f32(unet_handle_t h, const float* image, int n, int height, int
                      reinterpret_cast<float*>(h->ws.p) + p.x0, n, (size_t)height * width, h->cfg.in_channels);
   HIPCHK(h->err, hipGetLastError());
   return forward_common(h, n, height, width, logits, probs, mask, thr, s, p);
+}
+
+// csrc/unet_x3.inc
+namespace {
+int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int width, float* logits, float* probs,
+               uint8_t* mask, float thr, hipStream_t s, const ClassOut* classes);
+}
+
+// the checks of a K-class forward that need no device
+static int classes_prologue(unet_handle_t h, const char* who, int precision, int maskClass, const uint8_t* mask) {
+  if (!h) return UNET_ERR_INVALID_ARG;
+  if (int rc = multi_class_only(h, who)) return rc;
+  if (precision != 0 && precision != 1) {
+    h->err = std::string(who) + ": the K-class forward runs on the fp32 tier (precision 0) and the f16x3 tier (1)";
+    return UNET_ERR_INVALID_ARG;
+  }
+  if (mask && (maskClass < 0 || maskClass >= h->cfg.out_channels)) {
+    h->err = std::string(who) + ": mask_class must name a class of the handle";
+    return UNET_ERR_INVALID_ARG;
+  }
+  return UNET_OK;
+}
+
+int unet_forward_classes_u8(unet_handle_t h, const uint8_t* frames, int n, int height, int width, int precision,
+                            float* logits, float* probs, uint8_t* labels, int maskClass, uint8_t* mask, void* stream) {
+  int rc = classes_prologue(h, "unet_forward_classes_u8", precision, maskClass, mask);
+  if (rc) return rc;
+  ClassOut co;
+  co.logits = logits, co.probs = probs, co.labels = labels, co.maskClass = maskClass, co.mask = mask;
+  if (precision == 1) return forward_x3(h, frames, true, n, height, width, nullptr, nullptr, nullptr, 0.f, (hipStream_t)stream, &co);
+  if ((rc = forward_prologue(h, frames, n, height, width))) return rc;
+  if (h->cfg.in_channels != 3) {
+    h->err = "uint8 frames need in_channels == 3";
+    return UNET_ERR_INVALID_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const WsPlan p = plan_ws(h->cfg, n, height, width);
+  const size_t npix = (size_t)n * height * width;
+  const unet_config& c = h->cfg;
+  hipLaunchKernelGGL(unet::pack_u8_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, frames,
+                     reinterpret_cast<float*>(h->ws.p) + p.x0, npix, c.input_mean[0], c.input_mean[1], c.input_mean[2],
+                     c.input_std[0], c.input_std[1], c.input_std[2]);
+  HIPCHK(h->err, hipGetLastError());
+  return forward_common(h, n, height, width, nullptr, nullptr, nullptr, 0.f, s, p, &co);
+}
+
+int unet_forward_classes_f32(unet_handle_t h, const float* image, int n, int height, int width, int precision,
+                             float* logits, float* probs, uint8_t* labels, int maskClass, uint8_t* mask, void* stream) {
+  int rc = classes_prologue(h, "unet_forward_classes_f32", precision, maskClass, mask);
+  if (rc) return rc;
+  ClassOut co;
+  co.logits = logits, co.probs = probs, co.labels = labels, co.maskClass = maskClass, co.mask = mask;
+  if (precision == 1) return forward_x3(h, image, false, n, height, width, nullptr, nullptr, nullptr, 0.f, (hipStream_t)stream, &co);
+  if ((rc = forward_prologue(h, image, n, height, width))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const WsPlan p = plan_ws(h->cfg, n, height, width);
+  const size_t npix = (size_t)n * height * width;
+  hipLaunchKernelGGL(unet::pack_nchw_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, image,
+                     reinterpret_cast<float*>(h->ws.p) + p.x0, n, (size_t)height * width, h->cfg.in_channels);
+  HIPCHK(h->err, hipGetLastError());
+  return forward_common(h, n, height, width, nullptr, nullptr, nullptr, 0.f, s, p, &co);
 }
 
 int unet_destroy(unet_handle_t h) {

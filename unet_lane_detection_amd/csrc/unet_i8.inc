@@ -837,6 +837,7 @@ int unet_num_range_tensors(unet_handle_t h) { return h ? 3 + 4 * h->cfg.depth : 
 int unet_forward_u8_ranges(unet_handle_t h, const uint8_t* frames, int n, int height, int width, float* rangesHost,
                            void* stream) {
   if (!h || !frames || !rangesHost) return UNET_ERR_INVALID_ARG;
+  if (int rc = single_class_only(h, "unet_forward_u8_ranges")) return rc;
   const int nt = unet_num_range_tensors(h);
   HIPCHK(h->err, hipSetDevice(h->cfg.device));
   std::vector<unsigned> init((size_t)nt * 2);
@@ -885,6 +886,7 @@ int unet_op_histogram_f32(int device, const float* x, size_t npix, int c, int ld
 int unet_forward_u8_histograms(unet_handle_t h, const uint8_t* frames, int n, int height, int width,
                                const float* spansHost, int bins, unsigned long long* histDev, void* stream) {
   if (!h || !frames || !spansHost || !histDev) return UNET_ERR_INVALID_ARG;
+  if (int rc = single_class_only(h, "unet_forward_u8_histograms")) return rc;
   if (!unet::histogram_bins_supported(bins)) {
     h->err = "histogram bins must be a power of two from 64 to 4096";
     return UNET_ERR_INVALID_ARG;

@@ -153,6 +153,9 @@ struct TrainState {
   float bceW = 1.f, diceW = 0.f, posWeight = 1.f, diceSmooth = 1e-6f;
   float focalW = 0.f, focalAlpha = 0.25f, focalGamma = 2.f;   // mode 2 only (loss_kernels.h)
   float* lossCoef = nullptr; // 2 floats (device) for the Dice gradient
+  // out_channels > 1 (multiclass_kernels.h): the class loss and its reduction scratch, allocated by the first step
+  unet::ClassLossParams classLoss{1.f, 0.f, 1.f, {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f}, -1};
+  void* classWork = nullptr;
   hipStream_t commStream = nullptr;   // data-parallel overlap: see unet_train_set_comm_stream
   hipEvent_t lateGradsReady = nullptr;
   SideStream side;            // the weight gradients' stream (train_side_mode)
@@ -481,8 +484,8 @@ TrainPlan plan_train(const unet_config& c, int n, int h, int w) {
     slabX3(fb, fb / 2, pxb);
     slabX3(fb, fb, pxb);
   }
-  p.logits = take(px0);
-  p.dlogits = take(px0);
+  p.logits = take(px0 * c.out_channels);
+  p.dlogits = take(px0 * c.out_channels);
   p.gA = take(maxAct);
   p.gB = take(maxAct);
   p.gZ = take(maxAct);
@@ -1265,7 +1268,7 @@ int forward_walk(unet_ctx* h, Pass pass, int n, int height, int width, float* lo
   };
   // the 1x1 head: train lets it ride in the last unit's BatchNorm pass (64 channels; the same A/B switch as the pooling
   // fusions), eval always launches it
-  const bool headInUnit = train && c.features[0] == 64 && train_pool_fused();
+  const bool headInUnit = train && c.out_channels == 1 && c.features[0] == 64 && train_pool_fused();
 
   const float* cur = ws + p.x0;   // fp32 activation, or planes where PM says so
   int ch = height, cw = width;
@@ -1326,7 +1329,14 @@ int forward_walk(unet_ctx* h, Pass pass, int n, int height, int width, float* lo
     if ((rc = unit(T->dec[2 * j + 1], ws + p.decA1[l], PM, ch, cw, ws + p.decZ2[l], last))) return rc;
     cur = ws + p.decA2[l];
   }
-  if (!headInUnit)
+  if (c.out_channels > 1) {   // the K-way head on the fp32 activation of the last unit: logits (N,K,H,W)
+    const size_t P0 = (size_t)n * height * width;
+    prof_begin("headk", 2.0 * P0 * c.features[0] * c.out_channels, 4.0 * P0 * (c.features[0] + c.out_channels), s);
+    const hipError_t e = unet::launch_headk(cur, T->params + T->offHeadW, T->params + T->offHeadB, n, (size_t)height * width,
+                                            c.features[0], c.out_channels, logits, nullptr, nullptr, 0, nullptr, s);
+    prof_end(s);
+    HIPCHK(h->err, e);
+  } else if (!headInUnit)
     HIPCHK(h->err, run_head(cur, T->params + T->offHeadW, 0.f, (size_t)n * height * width, c.features[0], logits, nullptr,
                             nullptr, 0.f, s, T->params + T->offHeadB));
   return UNET_OK;
@@ -1365,6 +1375,19 @@ int run_loss_grad(unet_ctx* h, const float* targets, size_t P0, float* lossDev, 
     prof_end(s);
     HIPCHK(h->err, hipGetLastError());
   }
+  return UNET_OK;
+}
+
+// out_channels > 1: the class loss over (N,K,H,W) logits against uint8 labels, its terms to lossDev, its gradient to dlogits
+int run_class_loss_grad(unet_ctx* h, const uint8_t* labels, int n, size_t hw, float* lossDev, hipStream_t s, const TrainPlan& p) {
+  TrainState* T = h->train;
+  float* ws = reinterpret_cast<float*>(T->ws.p);
+  if (!T->classWork) HIPCHK(h->err, hipMalloc(&T->classWork, unet::class_loss_work_bytes()));
+  prof_begin("class_loss_grad", 0.0, (8.0 * h->cfg.out_channels + 2.0) * n * hw, s);
+  const hipError_t e = unet::launch_class_loss_grad(ws + p.logits, labels, n, hw, h->cfg.out_channels, T->classLoss, T->classWork,
+                                                    lossDev, ws + p.dlogits, s);
+  prof_end(s);
+  HIPCHK(h->err, e);
   return UNET_OK;
 }
 
@@ -1448,8 +1471,15 @@ int backward_decoder(unet_ctx* h, int n, int height, int width, hipStream_t s, c
   // The gradient w.r.t. the last unit's activation is dlogits[p] * w_head[c]: its BatchNorm backward forms that product
   // itself instead of reading a P0 x f0 buffer written here (3 x 4 bytes per element less; same bits).  A debug snapshot
   // keeps the buffer.
-  const bool headRank1 = T->dbgStage < 0;
-  {  // head: dW, db; dA (dense f0) into gA unless headRank1
+  const bool headRank1 = T->dbgStage < 0 && c.out_channels == 1;
+  if (c.out_channels > 1) {   // K-way head: dA dense into gA, dW (K, f0) and db (K) through block partials
+    prof_begin("headk_bwd", 4.0 * P0 * f0 * c.out_channels, 4.0 * P0 * (2 * f0 + c.out_channels), s);
+    const hipError_t e = unet::launch_headk_backward(ws + p.dlogits, ws + p.decA2[0], T->params + T->offHeadW, n,
+                                                     (size_t)height * width, f0, c.out_channels, gA, ws + p.partial,
+                                                     T->grads + T->offHeadW, T->grads + T->offHeadB, s);
+    prof_end(s);
+    HIPCHK(h->err, e);
+  } else {  // head: dW, db; dA (dense f0) into gA unless headRank1
     const int nb = red_blocks(P0);
     prof_begin("head_bwd", 0.0, 4.0 * P0 * ((headRank1 ? 1 : 2) * f0 + 1), s);
     hipLaunchKernelGGL(unet::head_bwd_kernel, dim3(nb), dim3(256), 0, s, ws + p.dlogits, ws + p.decA2[0],
@@ -1531,8 +1561,9 @@ int backward_encoder(unet_ctx* h, int n, int height, int width, hipStream_t s, c
   return UNET_OK;
 }
 
-int train_forward_backward(unet_ctx* h, int n, int height, int width, const float* targets, float* lossDev,
-                           float* logitsOut, hipStream_t s, const TrainPlan& p) {
+// targets: float (N,1,H,W) of a single-class handle; labels: uint8 (N,H,W) of a K-class handle - the other one null
+int train_forward_backward(unet_ctx* h, int n, int height, int width, const float* targets, const uint8_t* labels,
+                           float* lossDev, float* logitsOut, hipStream_t s, const TrainPlan& p) {
   TrainState* T = h->train;
   LaunchScope scope(h);
   float* ws = reinterpret_cast<float*>(T->ws.p);
@@ -1541,8 +1572,10 @@ int train_forward_backward(unet_ctx* h, int n, int height, int width, const floa
   if ((rc = repack_if_switched(h, s))) return rc;
   if ((rc = forward_walk(h, Pass::Train, n, height, width, ws + p.logits, s, p))) return rc;
   if (logitsOut)
-    HIPCHK(h->err, hipMemcpyAsync(logitsOut, ws + p.logits, P0 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if ((rc = run_loss_grad(h, targets, P0, lossDev, s, p))) return rc;
+    HIPCHK(h->err, hipMemcpyAsync(logitsOut, ws + p.logits, P0 * h->cfg.out_channels * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if ((rc = labels ? run_class_loss_grad(h, labels, n, (size_t)height * width, lossDev, s, p)
+                   : run_loss_grad(h, targets, P0, lossDev, s, p)))
+    return rc;
   // backward.  Whatever return ends it, the caller's stream has been joined with the side stream and no slot is left
   // busy: a caller that reuses the workspace, the gradients or the slab after an error meets no weight gradient in flight
   SideJoinOnExit joinOnExit{T->side, s};
@@ -1604,6 +1637,7 @@ static void train_free(unet_ctx* h) {
   if (T->zeros) hipFree(T->zeros);
   if (T->statArena) hipFree(T->statArena);
   if (T->lossCoef) hipFree(T->lossCoef);
+  if (T->classWork) hipFree(T->classWork);
   if (T->evalArena) hipFree(T->evalArena);
   if (T->evalDescs) hipFree(T->evalDescs);
   if (T->lateGradsReady) hipEventDestroy(T->lateGradsReady);
@@ -1799,6 +1833,7 @@ int unet_train_attach(unet_handle_t h, float* params, float* grads, float* expAv
 }
 
 int unet_train_set_loss(unet_handle_t h, int mode, float bceWeight, float diceWeight, float posWeight, float smooth) {
+  if (int rc = single_class_only(h, "unet_train_set_loss")) return rc;
   if (!h || !h->train || (mode != 0 && mode != 1)) return UNET_ERR_INVALID_ARG;
   h->train->lossMode = mode;
   h->train->bceW = bceWeight;
@@ -1818,6 +1853,7 @@ unet::LossParams loss_params_of(const unet_loss_config& c) {
 // loss_kernels.h, its parameters checked before anything else (so the check needs no attached training state).
 int unet_train_set_loss_cfg(unet_handle_t h, const unet_loss_config* cfg) {
   if (!h || !cfg) return UNET_ERR_INVALID_ARG;
+  if (int rc = single_class_only(h, "unet_train_set_loss_cfg")) return rc;
   if (cfg->mode == 0 || cfg->mode == 1)
     return unet_train_set_loss(h, cfg->mode, cfg->bce_weight, cfg->dice_weight, cfg->pos_weight, cfg->smooth);
   if (cfg->mode != 2 || !unet::loss_params_valid(loss_params_of(*cfg))) return UNET_ERR_INVALID_ARG;
@@ -1890,7 +1926,8 @@ size_t unet_train_workspace_bytes(unet_handle_t h, int n, int height, int width)
 int unet_train_forward_backward_u8(unet_handle_t h, const uint8_t* frames, const float* targets, int n, int height,
                                    int width, float* lossDev, float* logitsDev, void* stream) {
   TrainPlan p;
-  int rc = train_prologue(h, frames, targets, lossDev, n, height, width, p);
+  int rc = single_class_only(h, "unet_train_forward_backward_u8");
+  if (!rc) rc = train_prologue(h, frames, targets, lossDev, n, height, width, p);
   if (rc) return rc;
   if (h->cfg.in_channels != 3) return UNET_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
@@ -1900,20 +1937,70 @@ int unet_train_forward_backward_u8(unet_handle_t h, const uint8_t* frames, const
                      reinterpret_cast<float*>(h->train->ws.p) + p.x0, npix, c.input_mean[0], c.input_mean[1],
                      c.input_mean[2], c.input_std[0], c.input_std[1], c.input_std[2]);
   HIPCHK(h->err, hipGetLastError());
-  return train_forward_backward(h, n, height, width, targets, lossDev, logitsDev, s, p);
+  return train_forward_backward(h, n, height, width, targets, nullptr, lossDev, logitsDev, s, p);
 }
 
 int unet_train_forward_backward_f32(unet_handle_t h, const float* image, const float* targets, int n, int height,
                                     int width, float* lossDev, float* logitsDev, void* stream) {
   TrainPlan p;
-  int rc = train_prologue(h, image, targets, lossDev, n, height, width, p);
+  int rc = single_class_only(h, "unet_train_forward_backward_f32");
+  if (!rc) rc = train_prologue(h, image, targets, lossDev, n, height, width, p);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   const size_t npix = (size_t)n * height * width;
   hipLaunchKernelGGL(unet::pack_nchw_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, image,
                      reinterpret_cast<float*>(h->train->ws.p) + p.x0, n, (size_t)height * width, h->cfg.in_channels);
   HIPCHK(h->err, hipGetLastError());
-  return train_forward_backward(h, n, height, width, targets, lossDev, logitsDev, s, p);
+  return train_forward_backward(h, n, height, width, targets, nullptr, lossDev, logitsDev, s, p);
+}
+
+// The step of a K-class handle: uint8 labels (N,H,W) in place of the float targets, the class loss in place of BCE
+int unet_train_forward_backward_labels_u8(unet_handle_t h, const uint8_t* frames, const uint8_t* labels, int n, int height,
+                                          int width, float* lossDev, float* logitsDev, void* stream) {
+  TrainPlan p;
+  int rc = multi_class_only(h, "unet_train_forward_backward_labels_u8");
+  if (!rc) rc = train_prologue(h, frames, reinterpret_cast<const float*>(labels), lossDev, n, height, width, p);
+  if (rc) return rc;
+  if (h->cfg.in_channels != 3) return UNET_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t npix = (size_t)n * height * width;
+  const unet_config& c = h->cfg;
+  hipLaunchKernelGGL(unet::pack_u8_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, frames,
+                     reinterpret_cast<float*>(h->train->ws.p) + p.x0, npix, c.input_mean[0], c.input_mean[1],
+                     c.input_mean[2], c.input_std[0], c.input_std[1], c.input_std[2]);
+  HIPCHK(h->err, hipGetLastError());
+  return train_forward_backward(h, n, height, width, nullptr, labels, lossDev, logitsDev, s, p);
+}
+
+int unet_train_forward_backward_labels_f32(unet_handle_t h, const float* image, const uint8_t* labels, int n, int height,
+                                           int width, float* lossDev, float* logitsDev, void* stream) {
+  TrainPlan p;
+  int rc = multi_class_only(h, "unet_train_forward_backward_labels_f32");
+  if (!rc) rc = train_prologue(h, image, reinterpret_cast<const float*>(labels), lossDev, n, height, width, p);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t npix = (size_t)n * height * width;
+  hipLaunchKernelGGL(unet::pack_nchw_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s, image,
+                     reinterpret_cast<float*>(h->train->ws.p) + p.x0, n, (size_t)height * width, h->cfg.in_channels);
+  HIPCHK(h->err, hipGetLastError());
+  return train_forward_backward(h, n, height, width, nullptr, labels, lossDev, logitsDev, s, p);
+}
+
+// The loss of a K-class handle: the configuration is checked first, so that answer does not depend on the handle's state
+int unet_train_set_class_loss(unet_handle_t h, const unet_class_loss_config* cfg) {
+  if (!h || !cfg) return UNET_ERR_INVALID_ARG;
+  if (int rc = multi_class_only(h, "unet_train_set_class_loss")) return rc;
+  unet::ClassLossParams lp;
+  lp.ceW = cfg->ce_weight, lp.diceW = cfg->dice_weight, lp.smooth = cfg->smooth, lp.ignore = cfg->ignore_index;
+  for (int k = 0; k < UNET_MAX_CLASSES; ++k) lp.cw[k] = cfg->class_weight[k];
+  if (!unet::class_loss_params_valid(lp, h->cfg.out_channels)) {
+    h->err = "unet_train_set_class_loss: weights >= 0 and not both 0, smooth > 0, class weights >= 0 and finite, "
+             "ignore_index -1 or 0..255";
+    return UNET_ERR_INVALID_ARG;
+  }
+  if (!h->train) return UNET_ERR_STATE;
+  h->train->classLoss = lp;
+  return UNET_OK;
 }
 
 int unet_train_adam_step(unet_handle_t h, int step, float lr, float beta1, float beta2, float eps, float weightDecay,

@@ -1558,9 +1558,9 @@ int x3_build(unet_ctx* h) {
   }
   {   // the 1x1 head reads the last activation: its scale goes into the head's weights
     const int f0 = c.features[0];
-    const auto& hw = P["output.weight"];
-    std::vector<float> hs(f0);
-    for (int i = 0; i < f0; ++i) hs[i] = hw[i] / (useAct ? cur.act[i] : 1.f);
+    const auto& hw = P["output.weight"];   // (out_channels, f0): every row by the same scales
+    std::vector<float> hs(hw.size());
+    for (size_t i = 0; i < hs.size(); ++i) hs[i] = hw[i] / (useAct ? cur.act[i % f0] : 1.f);
     if ((rc = upload(h->err, &X->headW, hs))) return rc;
   }
   return UNET_OK;
@@ -1601,9 +1601,17 @@ WsPlanX3 plan_ws_x3(const unet_config& c, int n, int h, int w) {
   return p;
 }
 
+// classes: the outputs of a K-class handle (unet_forward_classes_*: the head never rides in the last convolution, which
+// stores its operand planes, and the K-way head reads them); null for the single-class entry points
 int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int width, float* logits, float* probs,
-               uint8_t* mask, float thr, hipStream_t s) {
+               uint8_t* mask, float thr, hipStream_t s, const ClassOut* classes) {
   if (!h || !input) return UNET_ERR_INVALID_ARG;
+  if (!classes)
+    if (int rc = single_class_only(h, u8 ? "unet_forward_u8_x3" : "unet_forward_f32_x3")) return rc;
+  if (classes && g_x3CrossFp8 == 1) {
+    h->err = "the K-class forward runs on the fp32 and f16x3 tiers; the f16q8 switch (unet_set_x3_cross_fp8) is on";
+    return UNET_ERR_INVALID_ARG;
+  }
   if (!h->finalized) {
     h->err = "unet_finalize has not been called";
     return UNET_ERR_STATE;
@@ -1728,7 +1736,7 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
     const int l = c.depth - 1 - j;
     const int f = c.features[l];
     // ConvTranspose writes the upper channel half of the concat buffer: torch.cat([skip, x]) elided
-    const bool headNext = j == c.depth - 1 && f == 64;
+    const bool headNext = j == c.depth - 1 && f == 64 && !classes;
     // the step's form (x3_plan_dec_step): composed (conv_x3_dec.h) or deep (upconv_x3_win.h + the addend epilogue), it
     // reads the skip half of the concat buffer and x itself and writes tmpA like conv1; else the two kernels below
     const DecStepX3& st = X->dec[j];
@@ -1772,7 +1780,15 @@ int forward_x3(unet_ctx* h, const void* input, bool u8, int n, int height, int w
     }
     cur = &p.tmpB;
   }
-  if (!headFused) {
+  if (classes) {
+    const int f0 = c.features[0];
+    prof_begin("headk_f16x3", 2.0 * npix * f0 * c.out_channels, 4.0 * npix * f0, s);
+    const hipError_t e = unet::launch_headk_planes(U(*cur), cur->elems, X->headW, h->headBk, n, (size_t)height * width, f0,
+                                                   c.out_channels, classes->logits, classes->probs, classes->labels,
+                                                   classes->maskClass, classes->mask, s);
+    prof_end(s);
+    HIPCHK(h->err, e);
+  } else if (!headFused) {
     const int f0 = c.features[0];
     prof_begin("head1x1_f16x3", 2.0 * npix * f0, 4.0 * npix * f0 + 4.0 * npix, s);
     hipLaunchKernelGGL(unet::head1x1_planes_kernel, dim3(grid_for(npix)), dim3(256), 0, s,
@@ -1832,12 +1848,12 @@ extern "C" {
 
 int unet_forward_u8_x3(unet_handle_t h, const uint8_t* frames, int n, int height, int width, float* logits,
                        float* probs, uint8_t* mask, float thr, void* stream) {
-  return forward_x3(h, frames, true, n, height, width, logits, probs, mask, thr, (hipStream_t)stream);
+  return forward_x3(h, frames, true, n, height, width, logits, probs, mask, thr, (hipStream_t)stream, nullptr);
 }
 
 int unet_forward_f32_x3(unet_handle_t h, const float* image, int n, int height, int width, float* logits,
                         float* probs, uint8_t* mask, float thr, void* stream) {
-  return forward_x3(h, image, false, n, height, width, logits, probs, mask, thr, (hipStream_t)stream);
+  return forward_x3(h, image, false, n, height, width, logits, probs, mask, thr, (hipStream_t)stream, nullptr);
 }
 
 // ---- single operators of the tier (test entry points): fp32 NHWC in / out, planes internally ----

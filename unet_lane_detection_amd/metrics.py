@@ -113,6 +113,158 @@ class SegMetrics:
                                             self.pixel_accuracy, self.batches, self.pixels))
 
 
+# ---- multi-class: confusion matrix (include/unet_hip.h, unet_confusion_accumulate) ---------------------------------
+class ClassLossSpec:
+    """ce_weight * CrossEntropy(class_weights, ignore_index) + dice_weight * softmax Dice(smooth): the loss of a K-class
+    trainer (unet_class_loss_config of include/unet_hip.h) as UNetTrainer.set_loss keeps it for the validation pass."""
+    __slots__ = ("kind", "ce_weight", "dice_weight", "smooth", "class_weights", "ignore_index")
+
+    def __init__(self, kind="ce", ce_weight=1.0, dice_weight=0.0, smooth=1.0, class_weights=None, ignore_index=None):
+        self.kind = kind
+        self.ce_weight, self.dice_weight, self.smooth = float(ce_weight), float(dice_weight), float(smooth)
+        self.class_weights = None if class_weights is None else tuple(float(v) for v in class_weights)
+        self.ignore_index = -1 if ignore_index is None else int(ignore_index)
+
+    def to_c(self, classes):
+        from . import _lib
+        cw = self.class_weights if self.class_weights is not None else (1.0,) * classes
+        if len(cw) != classes:
+            raise ValueError(f"class_weights has {len(cw)} entries for {classes} classes")
+        cfg = _lib.ClassLossConfig()
+        cfg.ce_weight, cfg.dice_weight, cfg.smooth, cfg.ignore_index = self.ce_weight, self.dice_weight, self.smooth, self.ignore_index
+        for k in range(_lib.UNET_MAX_CLASSES):
+            cfg.class_weight[k] = cw[k] if k < classes else 0.0
+        return cfg
+
+    def __repr__(self):
+        return "ClassLossSpec(%s)" % ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__)
+
+
+def _ratio_array(num, den):
+    num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+    return np.where(den == 0, 1.0, num / np.where(den == 0, 1.0, den))
+
+
+class ClassMetrics:
+    """Metrics of a K-class validation pass from the pooled confusion counts (counts[t, p]: pixels of true class t
+    predicted as p; pure numpy).  An empty denominator gives 1.0, as in SegMetrics.  The loss terms are means of the
+    per-batch values."""
+
+    def __init__(self, counts, loss_sums=(0.0, 0.0, 0.0), batches=0, invalid=0):
+        c = np.asarray(counts)
+        k = int(round(np.sqrt(c.size)))
+        if k * k != c.size:
+            raise ValueError("ClassMetrics takes K * K counts")
+        self.counts = np.rint(c.astype(np.float64)).astype(np.int64).reshape(k, k)
+        self.classes = k
+        self.batches = int(batches)
+        self.invalid = int(invalid)
+        self._loss = tuple(float(v) for v in loss_sums)
+
+    def _mean(self, i):
+        return self._loss[i] / self.batches if self.batches else float("nan")
+
+    @property
+    def loss(self):
+        return self._mean(0)
+
+    @property
+    def ce(self):
+        return self._mean(1)
+
+    @property
+    def dice_loss(self):
+        return self._mean(2)
+
+    @property
+    def pixels(self):
+        return int(self.counts.sum())
+
+    @property
+    def iou(self):
+        """per class: TP / (TP + FP + FN)"""
+        tp = np.diag(self.counts)
+        return _ratio_array(tp, self.counts.sum(0) + self.counts.sum(1) - tp)
+
+    @property
+    def class_dice(self):
+        """per class: 2 TP / (2 TP + FP + FN)"""
+        tp = np.diag(self.counts)
+        return _ratio_array(2 * tp, self.counts.sum(0) + self.counts.sum(1))
+
+    @property
+    def miou(self):
+        return float(self.iou.mean())
+
+    @property
+    def dice(self):
+        """mean per-class Dice from the counts: what loop.fit picks its best model by"""
+        return float(self.class_dice.mean())
+
+    @property
+    def pixel_acc(self):
+        return _ratio(int(np.trace(self.counts)), int(self.counts.sum()))
+
+    pixel_accuracy = pixel_acc
+
+    def as_dict(self):
+        return {"loss": self.loss, "ce": self.ce, "dice_loss": self.dice_loss, "dice": self.dice, "miou": self.miou,
+                "iou": self.iou.tolist(), "pixel_acc": self.pixel_acc, "batches": self.batches, "pixels": self.pixels,
+                "invalid": self.invalid}
+
+    def __repr__(self):
+        return "ClassMetrics(loss=%.6f, dice=%.6f, miou=%.6f, pixel_acc=%.6f, batches=%d, pixels=%d)" % (
+            self.loss, self.dice, self.miou, self.pixel_acc, self.batches, self.pixels)
+
+
+class ConfusionMatrix:
+    """K x K confusion counts kept on the device: accumulate(pred, truth) adds one batch of uint8 label planes
+    (unet_confusion_accumulate: integers, no host synchronisation); counts() reads them."""
+
+    def __init__(self, classes, device=0, ignore_index=None):
+        import torch
+
+        from . import _lib
+        if not 1 <= int(classes) <= _lib.UNET_MAX_CLASSES:
+            raise ValueError(f"classes must be 1..{_lib.UNET_MAX_CLASSES}")
+        self.classes = int(classes)
+        self.ignore_index = -1 if ignore_index is None else int(ignore_index)
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        self._lib = _lib.load()
+        self.acc = torch.zeros(self.classes * self.classes, dtype=torch.int64, device=self.device)
+        self._work = torch.empty(int(self._lib.unet_confusion_work_bytes()) // 4, dtype=torch.int32, device=self.device)
+
+    def reset(self):
+        self.acc.zero_()
+
+    def accumulate(self, pred, truth):
+        import torch
+
+        from . import _lib
+        if pred.dtype != torch.uint8 or truth.dtype != torch.uint8:
+            raise ValueError("pred and truth must be uint8 label planes")
+        pred, truth = pred.to(self.device).contiguous(), truth.to(self.device).contiguous()
+        if pred.numel() != truth.numel():
+            raise ValueError("pred and truth differ in size")
+        _lib.call("unet_confusion_accumulate", self.device, pred, truth, pred.numel(), self.classes, self.ignore_index,
+                  self.acc, self._work)
+
+    def counts(self):
+        return self.acc.cpu().numpy().reshape(self.classes, self.classes)
+
+    def metrics(self):
+        return ClassMetrics(self.counts())
+
+    def iou(self):
+        return self.metrics().iou
+
+    def miou(self):
+        return self.metrics().miou
+
+    def pixel_accuracy(self):
+        return self.metrics().pixel_acc
+
+
 def accumulate(lib, device_index, logits, targets, acc, stream, threshold=0.5, loss_cfg=None):
     """Add one batch to the device accumulators `acc` (16 float64 on the logits' device).  logits: float32 device
     tensor; targets: float (0/1) or uint8 (0 / non-zero) tensor of the same number of elements.  loss_cfg: what

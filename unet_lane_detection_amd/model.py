@@ -35,16 +35,41 @@ def infer_features(state_dict):
     return feats
 
 
+def infer_out_channels(state_dict):
+    """1 for the reference's lane head, K for a K-class head: the rows of output.weight"""
+    w = state_dict.get("output.weight") if hasattr(state_dict, "get") else None
+    return int(w.shape[0]) if w is not None else 1
+
+
+# the arithmetic tiers a K-class model runs on -> the ABI's precision argument (include/unet_hip.h)
+CLASS_PRECISIONS = {"fp32": 0, "f16x3": 1}
+
+
+def _single_class_only(flag, name):
+    if flag:
+        raise ValueError(f"{name} belongs to the single-class head; a K-class model takes return_labels / mask_class")
+
+
+def _multi_class_only(return_labels, mask_class):
+    if return_labels or mask_class is not None:
+        raise ValueError("return_labels / mask_class belong to a K-class model (out_channels > 1)")
+
+
 class UNetHIP:
     """U-Net forward on one MI355X through libunet_hip.so."""
 
-    def __init__(self, state_dict=None, features=None, device=0, in_channels=3, out_channels=1):
+    def __init__(self, state_dict=None, features=None, device=0, in_channels=3, out_channels=None):
+        """out_channels: 1 (the reference's lane head) or K = 2..8 classes; by default what the state dict's
+        output.weight has (1 without a state dict)."""
         if not torch.cuda.is_available():
             raise RuntimeError("UNetHIP needs a HIP device; there is no CPU fallback")
         self._lib = _lib.load()
         if features is None:
             features = infer_features(state_dict) if state_dict is not None else list(DEFAULT_FEATURES)
         self.features = [int(f) for f in features]
+        if out_channels is None:
+            out_channels = infer_out_channels(state_dict) if state_dict is not None else 1
+        self.out_channels = int(out_channels)
         self.device_index = int(device)
         self.device = torch.device("cuda", self.device_index)
         cfg = _lib.UnetConfig()
@@ -65,7 +90,8 @@ class UNetHIP:
     @classmethod
     def from_checkpoint(cls, model_path, device=0):
         """Model from a float checkpoint file: bare state_dict, the reference's wrapped form
-        {'model_state_dict': ...} (README.md:2208-2213), .npz, or 'seed:<int>' test weights."""
+        {'model_state_dict': ...} (README.md:2208-2213), .npz, or 'seed:<int>' test weights.  The class count is the
+        row count of the file's output.weight."""
         from .py_utils.rknn_executor import load_float_state_dict
         return cls(load_float_state_dict(model_path), device=device)
 
@@ -110,14 +136,42 @@ class UNetHIP:
 
     PRECISIONS = ("fp32", "f16x3", "f16q8", "bf16")
 
-    def forward(self, image, return_probs=False, return_mask=False, threshold=0.5, precision="fp32"):
+    def _forward_classes(self, fn, where, x, n, h, w, return_probs, return_labels, mask_class, precision):
+        """The forward of a K-class model: logits (N,K,H,W) [, softmax (N,K,H,W)] [, labels (N,H,W) uint8 = argmax]
+        [, (N,H,W) uint8 plane, 255 where the label is mask_class - what follow / instances / lanefit / video take]"""
+        if precision not in CLASS_PRECISIONS:
+            raise ValueError(f"precision={precision!r}: a {self.out_channels}-class model runs on one of {sorted(CLASS_PRECISIONS)}")
+        k = self.out_channels
+        if mask_class is not None and not 0 <= int(mask_class) < k:
+            raise ValueError(f"mask_class={mask_class!r}: the model has classes 0..{k - 1}")
+        logits = torch.empty((n, k, h, w), dtype=torch.float32, device=self.device)
+        probs = torch.empty_like(logits) if return_probs else None
+        labels = torch.empty((n, h, w), dtype=torch.uint8, device=self.device) if return_labels else None
+        mask = torch.empty((n, h, w), dtype=torch.uint8, device=self.device) if mask_class is not None else None
+        p = _lib.ptr
+        rc = fn(self._h, p(x), n, h, w, CLASS_PRECISIONS[precision], p(logits), p(probs), p(labels),
+                int(mask_class) if mask_class is not None else 0, p(mask), _lib.stream(self.device))
+        _lib.check(rc, f"{where}[{precision}]", self._h)
+        out = [t for t in (logits, probs, labels, mask) if t is not None]
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def forward(self, image, return_probs=False, return_mask=False, threshold=0.5, precision="fp32", return_labels=False,
+                mask_class=None):
         """image: (N,3,H,W) float32 on this device, already normalised -> logits (N,1,H,W).
-        precision "fp32" (exact fp32 MFMA) or "f16x3" (split operands, same accuracy class)."""
+        precision "fp32" (exact fp32 MFMA) or "f16x3" (split operands, same accuracy class).
+        A K-class model (out_channels > 1) returns logits (N,K,H,W) and, where asked, the softmax (return_probs), the
+        argmax labels (return_labels) and the byte plane of one class (mask_class); return_mask / threshold belong to the
+        single-class head."""
         self._require_live()
         if image.dim() != 4:
             raise ValueError("image must be (N,C,H,W)")
         image = image.to(self.device, torch.float32).contiguous()
         n, c, h, w = image.shape
+        if self.out_channels > 1:
+            _single_class_only(return_mask, "return_mask")
+            return self._forward_classes(self._lib.unet_forward_classes_f32, "unet_forward_classes_f32", image, n, h, w,
+                                         return_probs, return_labels, mask_class, precision)
+        _multi_class_only(return_labels, mask_class)
         logits, probs, mask = self._outputs(n, h, w, return_probs, return_mask)
         fns = {"fp32": self._lib.unet_forward_f32, "f16x3": self._lib.unet_forward_f32_x3}
         if precision not in fns:
@@ -130,7 +184,8 @@ class UNetHIP:
 
     __call__ = forward
 
-    def run_u8(self, frames, return_probs=False, return_mask=False, threshold=0.5, precision="fp32"):
+    def run_u8(self, frames, return_probs=False, return_mask=False, threshold=0.5, precision="fp32", return_labels=False,
+               mask_class=None):
         """frames: (N,H,W,3) uint8 RGB on this device, un-normalised -> logits (N,1,H,W).
         precision "fp32" (default: exact fp32 MFMA), "f16x3" (fp16 hi + lo operands, three MFMAs per product: the
         same accuracy class at 3/16 of the MFMA cost), "f16q8" (f16x3 with the cross terms of the wide 3x3 convolutions
@@ -140,6 +195,11 @@ class UNetHIP:
             raise ValueError("frames must be (N,H,W,3) uint8")
         frames = frames.to(self.device).contiguous()
         n, h, w, _ = frames.shape
+        if self.out_channels > 1:   # as forward(): logits (N,K,H,W) [, probs] [, labels] [, class mask]
+            _single_class_only(return_mask, "return_mask")
+            return self._forward_classes(self._lib.unet_forward_classes_u8, "unet_forward_classes_u8", frames, n, h, w,
+                                         return_probs, return_labels, mask_class, precision)
+        _multi_class_only(return_labels, mask_class)
         logits, probs, mask = self._outputs(n, h, w, return_probs, return_mask)
         fns = {"fp32": self._lib.unet_forward_u8, "f16x3": self._lib.unet_forward_u8_x3,
                "f16q8": self._lib.unet_forward_u8_x3, "bf16": self._lib.unet_forward_u8_bf16}

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib, checkpoint, dp, loop, metrics
-from .model import infer_features
+from .model import infer_features, infer_out_channels
 from .state import INPUT_MEAN, INPUT_STD
 
 
@@ -27,9 +27,10 @@ class UNetTrainer:
             raise RuntimeError("UNetTrainer needs a HIP device; there is no CPU fallback")
         self._lib = _lib.load()
         self.features = infer_features(state_dict)
+        self.out_channels = infer_out_channels(state_dict)   # 1: the lane head; K > 1: classes, labels, the class loss
         self.device = torch.device("cuda", int(device))
         cfg = _lib.UnetConfig()
-        cfg.in_channels, cfg.out_channels, cfg.depth = in_channels, 1, len(self.features)
+        cfg.in_channels, cfg.out_channels, cfg.depth = in_channels, self.out_channels, len(self.features)
         for i, f in enumerate(self.features):
             cfg.features[i] = f
         cfg.device = int(device)
@@ -91,8 +92,11 @@ class UNetTrainer:
         self.exp_avg_sq = torch.zeros_like(self.params)
         self.loss_terms = torch.zeros(4, dtype=torch.float32, device=self.device)   # total, bce, dice, focal
         self.loss = self.loss_terms[:1]
+        # what the four slots hold: a K-class trainer reports (total, ce, dice, labels out of range)
+        self.loss_term_names = ("total", "bce", "dice", "focal") if self.out_channels == 1 else ("total", "ce", "dice", "invalid")
         self.num_batches_tracked = 0
-        self._loss_cfg = None
+        self._loss_cfg = None if self.out_channels == 1 else metrics.ClassLossSpec()
+        self._class_work = None
         self._metric = torch.zeros(4, dtype=torch.float32, device=self.device)
         rc = self._lib.unet_train_attach(h, _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.exp_avg),
                                          _lib.ptr(self.exp_avg_sq), _lib.ptr(self.bn))
@@ -101,7 +105,7 @@ class UNetTrainer:
             self._enable_overlap()
 
     def set_loss(self, kind="bce", bce_weight=0.5, dice_weight=0.5, pos_weight=3.0, smooth=1e-6, focal_weight=None,
-                 alpha=0.25, gamma=2.0):
+                 alpha=0.25, gamma=2.0, ce_weight=None, class_weights=None, ignore_index=None):
         """The reference's `criterion = ...` line (INTEGRATION.md has the mapping).
         'bce': BCEWithLogitsLoss (reference README.md:1694-1709, BASELINE.json config);
         'bce_dice': the training script's BCEDiceLoss(0.5, 0.5, pos_weight=3) (README.md:1855-1893, :2169-2170);
@@ -110,7 +114,22 @@ class UNetTrainer:
         'focal_dice': focal_weight (default 0.5) * FocalLoss + dice_weight * DiceLoss - the table's choice for masks
         under 5 % lane (README.md:1949);
         'combo': bce_weight * BCE(pos_weight) + focal_weight * Focal + dice_weight * Dice, all three weights given.
-        self.loss_terms then holds (total, bce, dice, focal); every term is reported whatever its weight."""
+        self.loss_terms then holds (total, bce, dice, focal); every term is reported whatever its weight.
+        A K-class trainer takes 'ce': ce_weight (default 1) * F.cross_entropy(weight=class_weights,
+        ignore_index=ignore_index), or 'ce_dice': ce_weight (default 0.5) * that + dice_weight * the softmax Dice loss
+        over the classes with `smooth` (include/unet_hip.h has the formulas); self.loss_terms then holds (total, ce,
+        dice, number of labels out of range)."""
+        if kind in ("ce", "ce_dice") or self.out_channels > 1:
+            if kind not in ("ce", "ce_dice"):
+                raise ValueError(f"{kind!r}: a {self.out_channels}-class trainer takes 'ce' or 'ce_dice'")
+            if self.out_channels == 1:
+                raise ValueError(f"{kind!r} needs a K-class model (output.weight with K > 1 rows)")
+            wc = (1.0 if kind == "ce" else 0.5) if ce_weight is None else ce_weight
+            spec = metrics.ClassLossSpec(kind, wc, 0.0 if kind == "ce" else dice_weight, smooth, class_weights, ignore_index)
+            cfg = spec.to_c(self.out_channels)
+            _lib.check(self._lib.unet_train_set_class_loss(self._h, C.byref(cfg)), "unet_train_set_class_loss", self._h)
+            self._loss_cfg = spec
+            return
         if kind == "bce":
             rc = self._lib.unet_train_set_loss(self._h, 0, 1.0, 0.0, 1.0, smooth)
         elif kind == "bce_dice":
@@ -150,19 +169,28 @@ class UNetTrainer:
 
     # ---- one step, in the reference's order ------------------------------------------------------
     def forward_backward(self, images, targets, return_logits=False):
-        """images: (N,H,W,3) uint8 frames or (N,3,H,W) float32 normalised; targets (N,1,H,W) float 0/1.
-        Fills self.grads (zero_grad + backward) and self.loss; returns the logits if asked."""
+        """images: (N,H,W,3) uint8 frames or (N,3,H,W) float32 normalised; targets (N,1,H,W) float 0/1 - for a K-class
+        trainer (N,H,W) uint8 class labels.  Fills self.grads (zero_grad + backward) and self.loss; returns the logits
+        ((N,K,H,W) for K classes) if asked."""
         dp.broadcast_buffers(self.bn, self.group)
-        targets = targets.to(self.device, torch.float32).contiguous()
+        multi = self.out_channels > 1
+        if multi:
+            if targets.dtype != torch.uint8:
+                raise ValueError("a K-class trainer takes uint8 label planes (N,H,W)")
+            targets = targets.to(self.device).contiguous()
+        else:
+            targets = targets.to(self.device, torch.float32).contiguous()
         images = images.to(self.device).contiguous()
         if images.dtype == torch.uint8:
             n, h, w, _ = images.shape
-            fn = self._lib.unet_train_forward_backward_u8
+            fn = self._lib.unet_train_forward_backward_labels_u8 if multi else self._lib.unet_train_forward_backward_u8
         else:
             images = images.to(torch.float32)
             n, _, h, w = images.shape
-            fn = self._lib.unet_train_forward_backward_f32
-        logits = torch.empty((n, 1, h, w), dtype=torch.float32, device=self.device) if return_logits else None
+            fn = self._lib.unet_train_forward_backward_labels_f32 if multi else self._lib.unet_train_forward_backward_f32
+        if multi and targets.numel() != n * h * w:
+            raise ValueError("labels must be (N,H,W), one byte per pixel of the images")
+        logits = torch.empty((n, self.out_channels, h, w), dtype=torch.float32, device=self.device) if return_logits else None
         rc = fn(self._h, _lib.ptr(images), _lib.ptr(targets), n, h, w, _lib.ptr(self.loss_terms), _lib.ptr(logits),
                 _lib.stream(self.device))
         self._fb_rc = int(rc)
@@ -201,6 +229,11 @@ class UNetTrainer:
         dp.allreduce_flat_sum(self._bucket[:self.STATUS_PAD + self._split], self.group)
         main.wait_stream(self._comm)            # the optimizer step needs both buckets
         return 1.0 / ws
+
+    def loss_dict(self):
+        """The terms of the last step by name (one host read): total / bce / dice / focal, for a K-class trainer
+        total / ce / dice / invalid."""
+        return dict(zip(self.loss_term_names, (float(v) for v in self.loss_terms.cpu())))
 
     def optimizer_step(self, grad_scale=1.0):
         self.step_count += 1
@@ -453,7 +486,8 @@ class UNetTrainer:
     # ---- validation (reference README.md:2087-2112) and the loop around both (README.md:2185-2231) ----------
     def eval_logits(self, images):
         """Eval-mode forward (running statistics, nothing of the training state written) on the parameters as they are
-        on the device right now; images as forward_backward takes them -> logits (N,1,H,W) on the device."""
+        on the device right now; images as forward_backward takes them -> logits (N,1,H,W) on the device, (N,K,H,W) for a
+        K-class trainer."""
         images = images.to(self.device).contiguous()
         if images.dtype == torch.uint8:
             n, h, w, _ = images.shape
@@ -462,7 +496,7 @@ class UNetTrainer:
             images = images.to(torch.float32)
             n, _, h, w = images.shape
             fn = self._lib.unet_train_eval_f32
-        logits = torch.empty((n, 1, h, w), dtype=torch.float32, device=self.device)
+        logits = torch.empty((n, self.out_channels, h, w), dtype=torch.float32, device=self.device)
         _lib.check(fn(self._h, _lib.ptr(images), n, h, w, _lib.ptr(logits), _lib.stream(self.device)), "unet_train_eval",
                    self._h)
         return logits
@@ -475,7 +509,13 @@ class UNetTrainer:
         BatchNorm buffers are not broadcast.  Under a process group every rank validates its own batches and the
         accumulators are summed, so all ranks return the same SegMetrics.  Raises like step() when the device reports
         a failed launch or an activation beyond the fp16 range for the pass.  With return_logits: (SegMetrics, [logits
-        per batch])."""
+        per batch]).
+        A K-class trainer takes (images, uint8 labels) batches and returns metrics.ClassMetrics: the labels are the
+        argmax of the eval logits, the confusion matrix is filled on the device (unet_confusion_accumulate) and gives
+        per-class IoU, miou, pixel_acc and dice (the mean per-class Dice, what loop.fit compares); the loss terms are
+        those of set_loss.  With return_logits: (ClassMetrics, [logits per batch])."""
+        if self.out_channels > 1:
+            return self._validate_classes(batches, return_logits)
         acc = torch.zeros(metrics.NUM_ACCUMULATORS, dtype=torch.float64, device=self.device)
         kept = []
         for images, targets in batches:
@@ -496,6 +536,56 @@ class UNetTrainer:
                                  "are returned", self._lib.unet_last_error(self._h).decode() if rc else "")
         host[metrics.NUM_ACCUMULATORS - 1] = 0.0
         m = metrics.SegMetrics(host)
+        return (m, kept) if return_logits else m
+
+    def predict_labels(self, logits, mask_class=None):
+        """(N,K,H,W) logits -> (N,H,W) uint8 argmax labels on the device (ties to the lowest class); with mask_class
+        also the byte plane that is 255 where the label is that class."""
+        n, k, h, w = logits.shape
+        labels = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
+        mask = torch.empty_like(labels) if mask_class is not None else None
+        _lib.call("unet_class_labels_f32", self.device, logits, n, k, h * w, labels, int(mask_class or 0), mask)
+        return labels if mask is None else (labels, mask)
+
+    def _validate_classes(self, batches, return_logits):
+        k = self.out_channels
+        spec = self._loss_cfg
+        cfg = spec.to_c(k)
+        cm = metrics.ConfusionMatrix(k, self.device, None if spec.ignore_index < 0 else spec.ignore_index)
+        if self._class_work is None:
+            self._class_work = torch.empty(int(self._lib.unet_class_loss_work_bytes()) // 8, dtype=torch.float64,
+                                           device=self.device)
+        terms = torch.zeros(4, dtype=torch.float32, device=self.device)
+        sums = torch.zeros(4, dtype=torch.float64, device=self.device)
+        kept, nb = [], 0
+        for images, labels in batches:
+            labels = torch.as_tensor(labels)
+            if labels.dtype != torch.uint8:
+                raise ValueError("a K-class trainer validates against uint8 label planes (N,H,W)")
+            labels = labels.to(self.device).contiguous()
+            logits = self.eval_logits(images)
+            n, _, h, w = logits.shape
+            if labels.numel() != n * h * w:
+                raise ValueError("labels must be (N,H,W), one byte per pixel of the images")
+            _lib.call("unet_class_loss_grad", self.device, logits, labels, n, k, h * w, C.byref(cfg), terms, None,
+                      self._class_work)
+            sums += terms
+            cm.accumulate(self.predict_labels(logits), labels)
+            nb += 1
+            if return_logits:
+                kept.append(logits)
+        rc = self.device_error(current_stream_only=True)
+        # counts (exact below 2^53), the loss sums, the batches and this rank's status in one float64 vector
+        acc = torch.cat([cm.acc.to(torch.float64), sums, torch.tensor([float(nb), 1.0 if rc else 0.0], dtype=torch.float64,
+                                                                       device=self.device)])
+        _, ws = dp.world(self.group)
+        if ws > 1:
+            dp.allreduce_accumulators(acc, self.group)
+        host = acc.cpu().numpy()
+        if rc != 0 or host[-1] != 0.0:
+            raise _lib.UnetError(rc or _lib.UNET_ERR_HIP, "unet_device_error: the validation pass is invalid, no metrics "
+                                 "are returned", self._lib.unet_last_error(self._h).decode() if rc else "")
+        m = metrics.ClassMetrics(host[:k * k], host[k * k:k * k + 3], int(round(host[-2])), int(round(host[k * k + 3])))
         return (m, kept) if return_logits else m
 
     def sweep(self, batches, thresholds=metrics.DEFAULT_THRESHOLDS):
