@@ -604,6 +604,46 @@ int unet_op_maxpool2x2_bf16(int device, const uint16_t* x_dev, int n, int h, int
 int unet_op_head1x1_bf16(int device, const uint16_t* x_dev, int n, int h, int w, int c, const float* w_host, float bias,
                          float thr, float* logits_dev, float* probs_dev, uint8_t* mask_dev, void* stream);
 
+/* The exact-fp32 tier's operators on the paths the network runs (test entry points, tests/test_f32_ops_gpu.py; the
+ * network runs the same packing, dispatch and kernels: csrc/igemm_f32.h, csrc/wino_f32.h, csrc/elementwise.h).
+ * Activations are fp32 NHWC device tensors; weights, scale / shift and bias are fp32 HOST arrays in PyTorch layout.  cin,
+ * cout: multiples of 4.  ldo: pixel stride of y in floats (0 = cout, dense), co_off: the first channel written; both
+ * multiples of 4, co_off + cout <= ldo; channels outside [co_off, co_off + cout) are not touched.
+ * path_out (optional int[8]) receives {algorithm that ran (1 direct, 2 Winograd), MS, NS, TH, TW (Winograd: 0, 0, THt,
+ * TWt), grid blocks, coGroup, pool fused}.  The entry points that can launch the Winograd kernel read the device error
+ * word back after the stream is synchronised: a bounded wave-progress wait that gave up is UNET_ERR_HIP (and says so in
+ * unet_op_last_error); this holds for unet_op_conv3x3 as well.
+ *
+ * y = relu?(conv3x3(x, w) * scale + shift): x (N,H,W,cin) -> y (N,H,W,ldo); w_host (cout,cin,3,3).  algo: 0 = what the
+ * forward picks (Winograd where cin % 16 == 0 and H, W are even, unless unet_set_winograd(0)), 1 = direct, 2 = Winograd;
+ * a forced Winograd on a shape it does not take is UNET_ERR_INVALID_ARG and launches nothing.  y_pool (optional, H and
+ * W even): dense (N,H/2,W/2,cout) MaxPool2d(2,2) of y - written from the output registers by the Winograd kernel, by the
+ * pooling kernel reading y with pixel stride ldo after the direct kernel, as the forward's encoder does. */
+int unet_op_conv3x3_f32(int device, const float* x_dev, int n, int h, int w, int cin, const float* w_host,
+                        const float* scale_host, const float* shift_host, int cout, int relu, int algo, int ldo, int co_off,
+                        float* y_dev, float* y_pool_dev, int* path_out, void* stream);
+/* ConvTranspose2d k=2 s=2 with bias: x (N,H,W,cin) -> y (N,2H,2W,ldo), channels [co_off, co_off + cout);
+ * w_host (cin,cout,2,2). */
+int unet_op_upconv2x2_f32(int device, const float* x_dev, int n, int h, int w, int cin, const float* w_host,
+                          const float* bias_host, int cout, int ldo, int co_off, float* y_dev, int* path_out, void* stream);
+/* Plain 1x1 convolution (the training step's input gradient of the transposed convolution): w_host (cout,cin). */
+int unet_op_conv1x1_f32(int device, const float* x_dev, int n, int h, int w, int cin, const float* w_host, int cout, int ldo,
+                        int co_off, float* y_dev, int* path_out, void* stream);
+/* MaxPool2d(2,2): channels [0, c) of x (N,H,W,ldi) -> dense y (N,H/2,W/2,c); c, ldi multiples of 4 (ldi 0 = c). */
+int unet_op_maxpool2x2_f32(int device, const float* x_dev, int n, int h, int w, int c, int ldi, float* y_dev, void* stream);
+/* The 1x1 head on dense (N,H,W,c): logits / probs (N,H,W) fp32, mask (N,H,W) uint8 = 255 where logit > thr; each
+ * optional, at least one. */
+int unet_op_head1x1_f32(int device, const float* x_dev, int n, int h, int w, int c, const float* w_host, float bias,
+                        float thr, float* logits_dev, float* probs_dev, uint8_t* mask_dev, void* stream);
+/* The input packers: is_u8 != 0: uint8 (N,H,W,3) frames -> (u8 - mean) / std; else fp32 (N,3,H,W) copied -> y (N,H,W,4)
+ * fp32 with pad channel +0.0.  mean_host / std_host: 3 floats each (u8 only). */
+int unet_op_pack_input_f32(int device, const void* src_dev, int is_u8, int n, int h, int w, const float* mean_host,
+                           const float* std_host, float* y_dev, void* stream);
+/* Test hook, host arithmetic only (no device call): the launch the fp32 tier makes for query[7] = {taps (9 = 3x3 conv,
+ * 1 = transposed conv, 2 = plain 1x1), n, h, w, cin, cout, algo (as unet_op_conv3x3_f32; taps 9 only)} -> plan_out[8], the
+ * fields of path_out (pool fused = 0).  The same functions decide the launches themselves. */
+int unet_host_plan_conv_f32(const int* query, int n_query, int* plan_out, int n_plan);
+
 /* One decoder step of the split-operand tier - ConvTranspose2d(2f -> f, k2, s2, bias) -> cat([skip, up]) ->
  * Conv3x3(2f -> f) -> scale/shift (+ ReLU) (reference README.md:1476-1479) - as the composed operator
  * (csrc/conv_x3_dec.h: the transposed convolution folded into the 3x3 convolution's up half on the host, float64).

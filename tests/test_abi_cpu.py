@@ -134,6 +134,52 @@ def test_train_x3_entry_points_check_arguments_first(lib):
     assert lib.unet_op_wgrad3x3_x3(0, q, q, 1, 8, 8, 96, 64, q, 0, None) == 1
 
 
+def test_f32_entry_points_check_arguments_first(lib):
+    """the fp32 tier's entry points (tests/test_f32_ops_gpu.py) reject what they cannot run before touching a device, and
+    then fail at the device selection (an ordinal the runtime refuses: no device is touched)"""
+    f = (C.c_float * 64)()
+    q = C.cast(f, C.c_void_p)
+    bad = 1 << 20
+
+    def conv(dev=0, x=q, cin=16, cout=8, h=4, w=4, algo=0, ldo=0, off=0, y=q, pool=None, n=1):
+        return lib.unet_op_conv3x3_f32(dev, x, n, h, w, cin, q, q, q, cout, 1, algo, ldo, off, y, pool, None, None)
+    assert conv(x=None) == 1 and conv(y=None) == 1 and conv(cin=6) == 1 and conv(cout=6) == 1 and conv(n=0) == 1
+    assert conv(algo=3) == 1 and conv(algo=-1) == 1
+    assert conv(algo=2, cin=4) == 1 and conv(algo=2, h=3) == 1 and conv(algo=2, w=5) == 1     # Winograd cannot take these
+    assert conv(ldo=8, off=4) == 1 and conv(ldo=18, off=0) == 1 and conv(ldo=16, off=2) == 1 and conv(off=8) == 1
+    assert conv(ldo=16, off=-4) == 1 and conv(pool=q, h=3) == 1 and conv(pool=q, w=5) == 1
+    assert lib.unet_op_last_error().startswith(b"invalid argument")
+    assert conv(dev=bad) == 4 and conv(dev=bad, algo=2, ldo=16, off=8, pool=q) == 4 and conv(dev=bad, algo=1, cin=4) == 4
+    assert b"hipSetDevice" in lib.unet_op_last_error()
+
+    def up(dev=0, x=q, cin=16, cout=8, ldo=0, off=0, y=q):
+        return lib.unet_op_upconv2x2_f32(dev, x, 1, 4, 4, cin, q, q, cout, ldo, off, y, None, None)
+    assert up(x=None) == 1 and up(y=None) == 1 and up(cin=2) == 1 and up(cout=10) == 1
+    assert up(ldo=8, off=4) == 1 and up(ldo=12, off=2) == 1 and up(off=4) == 1
+    assert up(dev=bad) == 4 and up(dev=bad, ldo=16, off=8) == 4
+
+    def c1(dev=0, x=q, cin=16, cout=8, ldo=0, off=0, y=q):
+        return lib.unet_op_conv1x1_f32(dev, x, 1, 4, 4, cin, q, cout, ldo, off, y, None, None)
+    assert c1(x=None) == 1 and c1(y=None) == 1 and c1(cin=2) == 1 and c1(cout=10) == 1 and c1(ldo=8, off=4) == 1
+    assert c1(dev=bad) == 4
+
+    def pool(dev=0, x=q, h=4, w=4, c=8, ldi=0, y=q):
+        return lib.unet_op_maxpool2x2_f32(dev, x, 1, h, w, c, ldi, y, None)
+    assert pool(x=None) == 1 and pool(y=None) == 1 and pool(h=3) == 1 and pool(w=5) == 1 and pool(c=6) == 1
+    assert pool(ldi=4) == 1 and pool(ldi=10) == 1
+    assert pool(dev=bad) == 4 and pool(dev=bad, ldi=16) == 4
+
+    def head(dev=0, x=q, c=8, w=q, logits=q, probs=None, mask=None):
+        return lib.unet_op_head1x1_f32(dev, x, 1, 2, 2, c, w, 0.0, 0.0, logits, probs, mask, None)
+    assert head(x=None) == 1 and head(w=None) == 1 and head(c=6) == 1 and head(logits=None) == 1     # no output at all
+    assert head(dev=bad) == 4 and head(dev=bad, logits=None, mask=q) == 4
+
+    def pack(dev=0, src=q, is_u8=1, mean=q, std=q, y=q, h=2):
+        return lib.unet_op_pack_input_f32(dev, src, is_u8, 1, h, 2, mean, std, y, None)
+    assert pack(src=None) == 1 and pack(y=None) == 1 and pack(mean=None) == 1 and pack(std=None) == 1 and pack(h=0) == 1
+    assert pack(dev=bad) == 4 and pack(dev=bad, is_u8=0, mean=None, std=None) == 4
+
+
 def test_op_last_error_names_the_failing_call(lib):
     """a handle-less entry point that fails leaves its text for unet_op_last_error, per thread: a device ordinal the
     runtime refuses (no device is touched, with or without GPUs) in one entry point of each of three files"""

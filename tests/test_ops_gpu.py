@@ -33,8 +33,11 @@ def _hp(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-# (N, Cin, Cout, H, W): covers CK=4 and CK=16 paths, both tile sizes, ragged tiles, image-straddling
-# tiles (H=14, 28), partial channel tiles (Cout < 64) and multi-chunk K.
+# (N, Cin, Cout, H, W): covers CK=4 and CK=16 paths, ragged tiles, image-straddling tiles (H=14, 28), partial channel
+# tiles (Cout < 64) and multi-chunk K (up to 32 chunks).  Of the direct kernel's instances these shapes select the
+# 224-pixel tile (MS 7, NS 2) and the 128-pixel tile with 64 channels (MS 4, NS 2), never the 128-channel tile (MS 4,
+# NS 4); the Winograd runs have grids of 2 to 28 blocks, with the full 16 x 8 tile grid only at 224 x 224.  Every
+# instance, the strided outputs and the fused pool are covered by tests/test_f32_ops_gpu.py.
 CONV_CASES = [
     (2, 4, 8, 32, 32),
     (1, 4, 64, 16, 16),

@@ -5,7 +5,10 @@
 //   TAPS = 9 : 3x3 cross-correlation, stride 1, pad 1      (M = pixels, K = 9*Cin, N = Cout)
 //   TAPS = 1 : ConvTranspose2d k=2 s=2 as a 1x1 GEMM        (M = input pixels, K = Cin, N = 4*Cout)
 // Arithmetic is v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 accumulate,
-// k-ordered fma chain (same numerics class as the fp32 oracle).
+// k-ordered fma chain.  Against float64 an fp32 emulation of this order stays within
+// 2.57 * 2^-24 * sqrt(K) * B per accumulator (B = sqrt(sum of the squared terms), measured over
+// K = 4 .. 9216 by tests/test_f32_model_cpu.py); tests/test_f32_ops_gpu.py holds the kernel to
+// 4 x that plus 7.5 ulp of the result.
 //
 // Data layout
 //   activations : NHWC fp32, pixel stride = Cin (padded to a multiple of CK)

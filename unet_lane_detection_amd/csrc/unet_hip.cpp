@@ -296,14 +296,74 @@ WinoTile choose_wino_tile(int gt, int wt) {
   return best;
 }
 
-bool wino_applicable(const GemmOp& op, int h, int w) {
-  return op.taps == 9 && op.wtWino && (h % 2 == 0) && (w % 2 == 0) && wino_enabled();
-}
+// the Winograd kernel takes 3x3 convolutions with transformed weights (Cin % 16 == 0) on even maps ...
+bool wino_takes(const GemmOp& op, int h, int w) { return op.taps == 9 && op.wtWino && (h % 2 == 0) && (w % 2 == 0); }
+// ... and runs them unless unet_set_winograd / UNET_NO_WINOGRAD switched it off
+bool wino_applicable(const GemmOp& op, int h, int w) { return wino_takes(op, h, w) && wino_enabled(); }
 // the Winograd kernel addresses its input with 32-bit float4 indices
-bool wino_fits(const GemmOp& op, int n, int h, int w) { return (double)n * h * w * op.cin < 17179869184.0; }
+bool wino_fits(int n, int h, int w, int cin) { return (double)n * h * w * cin < 17179869184.0; }
+bool wino_fits(const GemmOp& op, int n, int h, int w) { return wino_fits(n, h, w, op.cin); }
+
+// GEMM N of an operator, padded to the channel tile: 3x3 conv and plain 1x1 over cout, the transposed conv over its
+// four (a,b) groups of coutPad columns
+inline int gemm_n_total(bool upconv, int cout) {
+  const int cols = upconv ? 4 * round_up(cout, 16) : cout;
+  return round_up(cols, cols >= 128 ? 128 : 64);
+}
+
+// One launch of the fp32 tier's GEMM-shaped operators: the template instance and its grid.  Decided here, for
+// run_direct / run_wino, for the path_out of the unet_op_*_f32 test entry points and for unet_host_plan_conv_f32.
+struct F32Plan {
+  int algo = 0;            // 1: igemm_f32_kernel, 2: wino_f32_kernel
+  int ms = 0, ns = 0;      // direct: MS, NS of the instance (Winograd: 0)
+  int th = 0, tw = 0;      // direct: pixel tile TH x TW; Winograd: tile grid THt x TWt of one block
+  int tilesX = 0, pixTiles = 0, coTiles = 0, coGroup = 1;
+  int grid = 0;            // blocks
+};
+
+inline int co_group_of(int coTiles) {
+  for (int g : {8, 4, 2})
+    if (coTiles % g == 0) return g;
+  return 1;
+}
+
+F32Plan plan_direct(int n, int h, int w, int ck, bool halo, int nTotal) {
+  const TileChoice t = choose_tile(n * h, w, ck, halo);
+  F32Plan p;
+  p.algo = 1;
+  p.ms = t.ms;
+  // The packed fragment order does not depend on NS, so the channel tile is a launch-time choice:
+  // 128 columns with the 128-pixel tile, 64 with the 224-pixel tile (224x128 does not fit 256 VGPRs).
+  p.ns = (t.ms == 4 && nTotal % 128 == 0) ? 4 : 2;
+  p.th = t.th;
+  p.tw = t.tw;
+  p.tilesX = (w + t.tw - 1) / t.tw;
+  p.pixTiles = p.tilesX * ((n * h + t.th - 1) / t.th);
+  p.coTiles = nTotal / (32 * p.ns);
+  p.coGroup = co_group_of(p.coTiles);
+  p.grid = (int)((size_t)p.pixTiles * p.coTiles);
+  return p;
+}
+
+F32Plan plan_wino(int n, int h, int w, int nTotal) {
+  const int gt = n * (h / 2), wt = w / 2;
+  const WinoTile t = choose_wino_tile(gt, wt);
+  F32Plan p;
+  p.algo = 2;
+  p.th = t.tht;
+  p.tw = t.twt;
+  p.tilesX = (wt + t.twt - 1) / t.twt;
+  p.pixTiles = p.tilesX * ((gt + t.tht - 1) / t.tht);
+  p.coTiles = nTotal / 32;
+  p.coGroup = co_group_of(p.coTiles);
+  p.grid = (int)((size_t)p.pixTiles * p.coTiles);
+  return p;
+}
 
 hipError_t run_wino(const GemmOp& op, const float* in, int n, int h, int w, float* out, int ldo, int coOff,
-                    float* pool, hipStream_t s) {
+                    float* pool, hipStream_t s, F32Plan* planOut = nullptr) {
+  const F32Plan p = plan_wino(n, h, w, op.nTotal);
+  if (planOut) *planOut = p;
   unet::WinoArgs a;
   a.in = in;
   a.wt = op.wtWino;
@@ -318,21 +378,14 @@ hipError_t run_wino(const GemmOp& op, const float* in, int n, int h, int w, floa
   a.Cout = op.cout;
   a.ldo = ldo;
   a.co_off = coOff;
-  const int gt = n * (h / 2), wt = w / 2;
-  const WinoTile t = choose_wino_tile(gt, wt);
-  a.THt = t.tht;
-  a.TWt = t.twt;
-  a.tilesX = (wt + t.twt - 1) / t.twt;
+  a.THt = p.th;
+  a.TWt = p.tw;
+  a.tilesX = p.tilesX;
   a.nChunks = op.cin / 16;
   a.relu = op.relu;
-  a.pixTiles = a.tilesX * ((gt + t.tht - 1) / t.tht);
-  a.coTiles = op.nTotal / 32;
-  a.coGroup = 1;
-  for (int g : {8, 4, 2})
-    if (a.coTiles % g == 0) {
-      a.coGroup = g;
-      break;
-    }
+  a.pixTiles = p.pixTiles;
+  a.coTiles = p.coTiles;
+  a.coGroup = p.coGroup;
   // keep a pixel tile's channel tiles on one XCD so the input tile crosses the fabric once, not once per XCD
   // (measured +0.6 % frames/s over spreading them, on every layer; UNET_WINO_XCD=0 restores the spread)
   static const int xcdMode = [] { const char* e = getenv("UNET_WINO_XCD"); return e ? atoi(e) : -1; }();
@@ -345,18 +398,17 @@ hipError_t run_wino(const GemmOp& op, const float* in, int n, int h, int w, floa
   const double px = (double)n * h * w;
   prof_begin(op.nameWino ? op.nameWino : "conv3x3_wino_f32", 2.0 * px * 9 * op.cinReal * op.cout,
              4.0 * (px * op.cinReal + px * op.cout + 9.0 * op.cinReal * op.cout), s);
-  hipLaunchKernelGGL((unet::wino_f32_kernel<2>), dim3((unsigned)((size_t)a.pixTiles * a.coTiles)),
-                     dim3(unet::WINO_THREADS), unet::WINO_LDS_BYTES, s, a);
+  hipLaunchKernelGGL((unet::wino_f32_kernel<2>), dim3((unsigned)p.grid), dim3(unet::WINO_THREADS),
+                     unet::WINO_LDS_BYTES, s, a);
   prof_end(s);
   return hipGetLastError();
 }
 
-// in: (N,H,W,op.cin) -> out with pixel stride ldo at channel offset coOff
-hipError_t run_gemm_op(const GemmOp& op, const float* in, int n, int h, int w, float* out, int ldo, int coOff,
-                       hipStream_t s, int outBf16 = 0) {
-  if (!outBf16 && wino_applicable(op, h, w) && wino_fits(op, n, h, w))
-    return run_wino(op, in, n, h, w, out, ldo, coOff, nullptr, s);
-  const TileChoice t = choose_tile(n * h, w, op.ck, op.taps == 9);
+// the direct kernel: in (N,H,W,op.cin) -> out with pixel stride ldo at channel offset coOff
+hipError_t run_direct(const GemmOp& op, const float* in, int n, int h, int w, float* out, int ldo, int coOff,
+                      hipStream_t s, int outBf16 = 0, F32Plan* planOut = nullptr) {
+  const F32Plan p = plan_direct(n, h, w, op.ck, op.taps == 9, op.nTotal);
+  if (planOut) *planOut = p;
   ConvArgs a;
   a.in = in;
   a.wt = op.wt;
@@ -371,25 +423,16 @@ hipError_t run_gemm_op(const GemmOp& op, const float* in, int n, int h, int w, f
   a.CoutPad = op.coutPad;
   a.ldo = ldo;
   a.co_off = coOff;
-  a.TH = t.th;
-  a.TW = t.tw;
-  a.tilesX = (w + t.tw - 1) / t.tw;
+  a.TH = p.th;
+  a.TW = p.tw;
+  a.tilesX = p.tilesX;
   a.nChunks = op.cin / op.ck;
   a.relu = op.relu;
   a.out_bf16 = outBf16;
-  const int tilesY = (n * h + t.th - 1) / t.th;
-  // The packed fragment order does not depend on NS, so the channel tile is a launch-time choice:
-  // 128 columns with the 128-pixel tile, 64 with the 224-pixel tile (224x128 does not fit 256 VGPRs).
-  const int ns = (t.ms == 4 && op.nTotal % 128 == 0) ? 4 : 2;
-  a.pixTiles = a.tilesX * tilesY;
-  a.coTiles = op.nTotal / (32 * ns);
-  a.coGroup = 1;
-  for (int g : {8, 4, 2})
-    if (a.coTiles % g == 0) {
-      a.coGroup = g;
-      break;
-    }
-  dim3 grid((unsigned)((size_t)a.pixTiles * a.coTiles));
+  a.pixTiles = p.pixTiles;
+  a.coTiles = p.coTiles;
+  a.coGroup = p.coGroup;
+  dim3 grid((unsigned)p.grid);
   // algorithmic work of this launch: 2*MAC flops on the real (unpadded) channel counts; bytes = read the
   // input once + write the output once + the weights once
   const double px = (double)n * h * w;
@@ -399,15 +442,23 @@ hipError_t run_gemm_op(const GemmOp& op, const float* in, int n, int h, int w, f
   prof_begin(op.name ? op.name : (op.taps == 9 ? "conv3x3_igemm_f32" : "upconv2x2_igemm_f32"), flops, bytes, s);
   hipError_t e;
   if (op.taps == 9) {
-    e = (op.ck == 16) ? launch_cfg<16, 9, 0>(a, grid, t.ms, ns, s) : launch_cfg<4, 9, 0>(a, grid, t.ms, ns, s);
+    e = (op.ck == 16) ? launch_cfg<16, 9, 0>(a, grid, p.ms, p.ns, s) : launch_cfg<4, 9, 0>(a, grid, p.ms, p.ns, s);
   } else {
     if (op.plain)
-      e = (op.ck == 16) ? launch_cfg<16, 1, 0>(a, grid, t.ms, ns, s) : launch_cfg<4, 1, 0>(a, grid, t.ms, ns, s);
+      e = (op.ck == 16) ? launch_cfg<16, 1, 0>(a, grid, p.ms, p.ns, s) : launch_cfg<4, 1, 0>(a, grid, p.ms, p.ns, s);
     else
-      e = (op.ck == 16) ? launch_cfg<16, 1, 1>(a, grid, t.ms, ns, s) : launch_cfg<4, 1, 1>(a, grid, t.ms, ns, s);
+      e = (op.ck == 16) ? launch_cfg<16, 1, 1>(a, grid, p.ms, p.ns, s) : launch_cfg<4, 1, 1>(a, grid, p.ms, p.ns, s);
   }
   prof_end(s);
   return e;
+}
+
+// in: (N,H,W,op.cin) -> out with pixel stride ldo at channel offset coOff
+hipError_t run_gemm_op(const GemmOp& op, const float* in, int n, int h, int w, float* out, int ldo, int coOff,
+                       hipStream_t s, int outBf16 = 0) {
+  if (!outBf16 && wino_applicable(op, h, w) && wino_fits(op, n, h, w))
+    return run_wino(op, in, n, h, w, out, ldo, coOff, nullptr, s);
+  return run_direct(op, in, n, h, w, out, ldo, coOff, s, outBf16);
 }
 
 // Pack W into [subtile][chunk][tap][lane][KPL]; column -> (source fetch) is given by `col(n, ci, tap)`.
@@ -448,7 +499,7 @@ int build_conv3x3(std::string& err, GemmOp& op, const float* w, int cout, int ci
   op.cin = round_up(cinReal, op.ck);
   op.cout = cout;
   op.coutPad = round_up(cout, 16);
-  op.nTotal = round_up(cout, cout >= 128 ? 128 : 64);
+  op.nTotal = gemm_n_total(false, cout);
   op.relu = relu;
   auto packed = pack_fragments(op.nTotal, op.cin, op.ck, 9, [&](int n, int ci, int t) -> float {
     if (n >= cout || ci >= cinReal) return 0.f;
@@ -488,7 +539,7 @@ int build_upconv(std::string& err, GemmOp& op, const float* w, int cinReal, int 
   op.cin = round_up(cinReal, op.ck);
   op.cout = cout;
   op.coutPad = round_up(cout, 16);
-  op.nTotal = round_up(4 * op.coutPad, 4 * op.coutPad >= 128 ? 128 : 64);
+  op.nTotal = gemm_n_total(true, cout);
   op.relu = 0;
   const int cp = op.coutPad;
   auto packed = pack_fragments(op.nTotal, op.cin, op.ck, 1, [&](int n, int ci, int) -> float {
@@ -1289,13 +1340,26 @@ struct OpRangeScope {
 // synchronised (also after a failure: the scratch is freed when the caller returns) unless kOpNoSync says that the entry
 // point is asynchronous; then an armed `range` is read into *rangeOut.  A failure leaves its text in g_opErr and is
 // UNET_ERR_HIP, or with kOpMapCodes UNET_ERR_INVALID_ARG / UNET_ERR_NOMEM for the runtime's codes of those names.
-enum : unsigned { kOpNoSync = 1, kOpMapCodes = 2 };
+// kOpWaitWord: the call may have launched wino_f32_kernel with the per-device error word (op_err_word): word 0 is read
+// back after the synchronisation, and a bounded wait that gave up is UNET_ERR_HIP with a text that says so; the word is
+// cleared for the next call.
+enum : unsigned { kOpNoSync = 1, kOpMapCodes = 2, kOpWaitWord = 4 };
 int op_done(hipError_t e, hipStream_t s, unsigned flags = 0, OpRangeScope* range = nullptr, int* rangeOut = nullptr) {
   if (!(flags & kOpNoSync)) {
     const hipError_t es = hipStreamSynchronize(s);
     if (e == hipSuccess) e = es;
   }
   if (e == hipSuccess && range) e = range->read(rangeOut);
+  if (e == hipSuccess && (flags & kOpWaitWord) && !(flags & kOpNoSync)) {
+    unsigned* word = g_errWord ? g_errWord : op_err_word();
+    unsigned gaveUp = 0;
+    if (word) e = hipMemcpy(&gaveUp, word, sizeof(gaveUp), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && gaveUp) {
+      hipMemset(word, 0, sizeof(unsigned));
+      g_opErr = "a bounded wave-progress wait gave up inside wino_f32_kernel: the results of this call are invalid";
+      return UNET_ERR_HIP;
+    }
+  }
   if (e == hipSuccess) return UNET_OK;
   g_opErr = hipGetErrorString(e);
   if (flags & kOpMapCodes) {
@@ -1303,6 +1367,55 @@ int op_done(hipError_t e, hipStream_t s, unsigned flags = 0, OpRangeScope* range
     if (e == hipErrorOutOfMemory) return UNET_ERR_NOMEM;
   }
   return UNET_ERR_HIP;
+}
+
+}  // namespace
+
+namespace {
+
+// plain 1x1 convolution (an ordinary GEMM over the pixels): w (O,I), no scale / shift
+int build_conv1x1(std::string& err, GemmOp& op, const float* w, int cout, int cin) {
+  op.free_dev();
+  op.taps = 1;
+  op.plain = 1;
+  op.cinReal = cin;
+  op.ck = (cin % 16 == 0) ? 16 : 4;
+  op.cin = round_up(cin, op.ck);
+  op.cout = cout;
+  op.coutPad = round_up(cout, 16);
+  op.nTotal = gemm_n_total(false, cout);
+  auto packed = pack_fragments(op.nTotal, op.cin, op.ck, 1, [&](int nn, int ci, int) -> float {
+    return (nn < cout && ci < cin) ? w[(size_t)nn * cin + ci] : 0.f;
+  });
+  std::vector<float> sc(op.nTotal, 1.f), sh(op.nTotal, 0.f);
+  int rc = upload(err, &op.wt, packed);
+  if (!rc) rc = upload(err, &op.scale, sc);
+  if (!rc) rc = upload(err, &op.shift, sh);
+  return rc;
+}
+
+// the output slice of the unet_op_*_f32 entry points: ldo 0 = dense; else channels [coOff, coOff + cout) of ldo
+bool f32_slice_ok(int cout, int& ldo, int coOff) {
+  if (ldo == 0) {
+    ldo = cout;
+    return coOff == 0;
+  }
+  return ldo % 4 == 0 && coOff % 4 == 0 && coOff >= 0 && coOff + cout <= ldo;
+}
+
+// path_out of the unet_op_*_f32 entry points and the plan of unet_host_plan_conv_f32
+void f32_plan_to_ints(const F32Plan& p, bool poolFused, int* out) {
+  const int v[8] = {p.algo, p.ms, p.ns, p.th, p.tw, p.grid, p.coGroup, poolFused ? 1 : 0};
+  std::copy(v, v + 8, out);
+}
+
+// Which kernel a 3x3 convolution of the fp32 tier runs: 1 direct, 2 Winograd, 0 = the forced choice cannot take the
+// shape.  algo 0: run_gemm_op's / the encoder's choice; 1 / 2: forced (a forced Winograd ignores unet_set_winograd).
+int f32_conv_algo(int algo, int n, int h, int w, int cin) {
+  const bool takes = cin % 16 == 0 && h % 2 == 0 && w % 2 == 0 && wino_fits(n, h, w, cin);
+  if (algo == 2) return takes ? 2 : 0;
+  if (algo == 1) return 1;
+  return takes && wino_enabled() ? 2 : 1;
 }
 
 }  // namespace
@@ -1318,7 +1431,7 @@ int unet_op_conv3x3(int device, const float* x, int n, int h, int w, int cin, co
   hipStream_t s = (hipStream_t)stream;
   OpGuard<GemmOp> g;
   const int rc = build_conv3x3(g_opErr, g.op, wHost, cout, cin, scale, shift, relu);
-  return rc ? rc : op_done(run_gemm_op(g.op, x, n, h, w, y, cout, 0, s), s);
+  return rc ? rc : op_done(run_gemm_op(g.op, x, n, h, w, y, cout, 0, s), s, kOpWaitWord);
 }
 
 int unet_op_upconv2x2(int device, const float* x, int n, int h, int w, int cin, const float* wHost,
@@ -1337,23 +1450,8 @@ int unet_op_conv1x1(int device, const float* x, int n, int h, int w, int cin, co
   HIPCHK(g_opErr, hipSetDevice(device));
   hipStream_t s = (hipStream_t)stream;
   OpGuard<GemmOp> g;
-  GemmOp& op = g.op;
-  op.taps = 1;
-  op.plain = 1;
-  op.cinReal = cin;
-  op.ck = (cin % 16 == 0) ? 16 : 4;
-  op.cin = round_up(cin, op.ck);
-  op.cout = cout;
-  op.coutPad = round_up(cout, 16);
-  op.nTotal = round_up(cout, cout >= 128 ? 128 : 64);
-  auto packed = pack_fragments(op.nTotal, op.cin, op.ck, 1, [&](int nn, int ci, int) -> float {
-    return (nn < cout && ci < cin) ? wHost[(size_t)nn * cin + ci] : 0.f;
-  });
-  std::vector<float> sc(op.nTotal, 1.f), sh(op.nTotal, 0.f);
-  int rc = upload(g_opErr, &op.wt, packed);
-  if (!rc) rc = upload(g_opErr, &op.scale, sc);
-  if (!rc) rc = upload(g_opErr, &op.shift, sh);
-  return rc ? rc : op_done(run_gemm_op(op, x, n, h, w, y, cout, 0, s), s);
+  const int rc = build_conv1x1(g_opErr, g.op, wHost, cout, cin);
+  return rc ? rc : op_done(run_gemm_op(g.op, x, n, h, w, y, cout, 0, s), s);
 }
 
 int unet_op_maxpool2x2(int device, const float* x, int n, int h, int w, int c, float* y, void* stream) {
@@ -1373,6 +1471,114 @@ int unet_op_head1x1(int device, const float* x, int n, int h, int w, int c, cons
   hipError_t e = sc.upload(&wd, wHost, (size_t)c);
   if (e == hipSuccess) e = run_head(x, wd, bias, (size_t)n * h * w, c, logits, nullptr, nullptr, 0.f, s);
   return op_done(e, s);
+}
+
+// ---- the fp32 tier on the network's own paths (include/unet_hip.h; tests/test_f32_ops_gpu.py) ----
+
+int unet_op_conv3x3_f32(int device, const float* x, int n, int h, int w, int cin, const float* wHost, const float* scale,
+                        const float* shift, int cout, int relu, int algo, int ldo, int coOff, float* y, float* yPool,
+                        int* pathOut, void* stream) {
+  if (!x || !wHost || !scale || !shift || !y || n < 1 || h < 1 || w < 1 || cin < 4 || cout < 4 || cin % 4 || cout % 4 ||
+      algo < 0 || algo > 2 || !f32_slice_ok(cout, ldo, coOff) || (yPool && (h % 2 || w % 2)))
+    return op_bad_args();
+  const int ran = f32_conv_algo(algo, n, h, w, cin);
+  if (!ran) return op_bad_args();   // a forced Winograd on a shape it does not take
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  OpGuard<GemmOp> g;
+  const int rc = build_conv3x3(g_opErr, g.op, wHost, cout, cin, scale, shift, relu);
+  if (rc) return rc;
+  F32Plan plan;
+  hipError_t e;
+  if (ran == 2) {   // the pooled copy from the output registers, as the encoder's second convolutions
+    e = run_wino(g.op, x, n, h, w, y, ldo, coOff, yPool, s, &plan);
+  } else {          // ... and as their else branch: the direct kernel, then the pool over the slice it wrote
+    e = run_direct(g.op, x, n, h, w, y, ldo, coOff, s, 0, &plan);
+    if (e == hipSuccess && yPool) e = run_maxpool(y + coOff, yPool, n, h, w, cout, ldo, s);
+  }
+  if (pathOut) f32_plan_to_ints(plan, ran == 2 && yPool, pathOut);
+  return op_done(e, s, kOpWaitWord);
+}
+
+int unet_op_upconv2x2_f32(int device, const float* x, int n, int h, int w, int cin, const float* wHost, const float* bias,
+                          int cout, int ldo, int coOff, float* y, int* pathOut, void* stream) {
+  if (!x || !wHost || !bias || !y || n < 1 || h < 1 || w < 1 || cin < 4 || cout < 4 || cin % 4 || cout % 4 ||
+      !f32_slice_ok(cout, ldo, coOff))
+    return op_bad_args();
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  OpGuard<GemmOp> g;
+  const int rc = build_upconv(g_opErr, g.op, wHost, cin, cout, bias);
+  if (rc) return rc;
+  F32Plan plan;
+  const hipError_t e = run_direct(g.op, x, n, h, w, y, ldo, coOff, s, 0, &plan);
+  if (pathOut) f32_plan_to_ints(plan, false, pathOut);
+  return op_done(e, s);
+}
+
+int unet_op_conv1x1_f32(int device, const float* x, int n, int h, int w, int cin, const float* wHost, int cout, int ldo,
+                        int coOff, float* y, int* pathOut, void* stream) {
+  if (!x || !wHost || !y || n < 1 || h < 1 || w < 1 || cin < 4 || cout < 4 || cin % 4 || cout % 4 ||
+      !f32_slice_ok(cout, ldo, coOff))
+    return op_bad_args();
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  OpGuard<GemmOp> g;
+  const int rc = build_conv1x1(g_opErr, g.op, wHost, cout, cin);
+  if (rc) return rc;
+  F32Plan plan;
+  const hipError_t e = run_direct(g.op, x, n, h, w, y, ldo, coOff, s, 0, &plan);
+  if (pathOut) f32_plan_to_ints(plan, false, pathOut);
+  return op_done(e, s);
+}
+
+int unet_op_maxpool2x2_f32(int device, const float* x, int n, int h, int w, int c, int ldi, float* y, void* stream) {
+  if (ldi == 0) ldi = c;
+  if (!x || !y || n < 1 || h < 2 || w < 2 || c < 4 || c % 4 || h % 2 || w % 2 || ldi % 4 || ldi < c) return op_bad_args();
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  return op_done(run_maxpool(x, y, n, h, w, c, ldi, s), s);
+}
+
+int unet_op_head1x1_f32(int device, const float* x, int n, int h, int w, int c, const float* wHost, float bias, float thr,
+                        float* logits, float* probs, uint8_t* mask, void* stream) {
+  if (!x || !wHost || (!logits && !probs && !mask) || n < 1 || h < 1 || w < 1 || c < 4 || c % 4) return op_bad_args();
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  OpScratch sc(s);
+  float* wd = nullptr;
+  hipError_t e = sc.upload(&wd, wHost, (size_t)c);
+  if (e == hipSuccess) e = run_head(x, wd, bias, (size_t)n * h * w, c, logits, probs, mask, thr, s);
+  return op_done(e, s);
+}
+
+int unet_op_pack_input_f32(int device, const void* src, int isU8, int n, int h, int w, const float* mean, const float* stdv,
+                           float* y, void* stream) {
+  if (!src || !y || n < 1 || h < 1 || w < 1 || (isU8 && (!mean || !stdv))) return op_bad_args();
+  HIPCHK(g_opErr, hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t npix = (size_t)n * h * w;
+  if (isU8)   // as unet_forward_u8
+    hipLaunchKernelGGL(unet::pack_u8_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s,
+                       reinterpret_cast<const uint8_t*>(src), y, npix, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2]);
+  else        // as unet_forward_f32, in_channels == 3
+    hipLaunchKernelGGL(unet::pack_nchw_nhwc4_kernel, dim3(grid_for(npix)), dim3(256), 0, s,
+                       reinterpret_cast<const float*>(src), y, n, (size_t)h * w, 3);
+  return op_done(hipGetLastError(), s);
+}
+
+int unet_host_plan_conv_f32(const int* query, int nQuery, int* planOut, int nPlan) {
+  if (!query || nQuery != 7 || !planOut || nPlan != 8) return op_bad_args();
+  const int taps = query[0], n = query[1], h = query[2], w = query[3], cin = query[4], cout = query[5], algo = query[6];
+  if ((taps != 9 && taps != 1 && taps != 2) || n < 1 || h < 1 || w < 1 || cin < 4 || cout < 4 || cin % 4 || cout % 4 ||
+      algo < 0 || algo > 2 || (taps != 9 && algo == 2))
+    return op_bad_args();
+  const int ck = (cin % 16 == 0) ? 16 : 4;   // as the build_* functions
+  const int nTotal = gemm_n_total(taps == 1, cout);
+  const int ran = taps == 9 ? f32_conv_algo(algo, n, h, w, cin) : 1;
+  if (!ran) return op_bad_args();
+  f32_plan_to_ints(ran == 2 ? plan_wino(n, h, w, nTotal) : plan_direct(n, h, w, ck, taps == 9, nTotal), false, planOut);
+  return UNET_OK;
 }
 
 }  // extern "C"
