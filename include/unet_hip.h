@@ -296,9 +296,10 @@ int unet_train_eval_f32(unet_handle_t h, const float* image_nchw_dev, int n, int
  * out_channels == 1 runs exactly what it ran before; every entry point below returns UNET_ERR_INVALID_ARG for it, and
  * the single-class entry points (the unet_forward_* family of every tier, the training step with float targets, the
  * unet_train_set_loss pair) return UNET_ERR_INVALID_ARG for a handle with K > 1, each with a text for unet_last_error,
- * before any device is touched.  The K-class forward exists on the fp32 and f16x3 tiers, the training step on the
- * training handle (which dispatches its convolutions as for K == 1); the bf16, f16q8, int8 and hybrid inference tiers
- * are single-class.
+ * before any device is touched.  The K-class forward exists on the fp32 and f16x3 tiers and on the int8 tier with its
+ * hybrid units (the unet_i8_* section below: a quantised model is K-class when its head arrays have K rows), the training
+ * step on the training handle (which dispatches its convolutions as for K == 1); the bf16 and f16q8 inference tiers are
+ * single-class.
  *
  * Forward.  precision: 0 = the fp32 tier, 1 = the f16x3 tier (its last convolution stores operand planes and the K-way
  * head reads them; needs what unet_forward_u8_x3 needs, and the f16q8 switch off).  Every output is optional:
@@ -892,6 +893,31 @@ int unet_i8_read_tensor(unet_i8_handle_t h, const char* name, int8_t* dst_host, 
 int unet_i8_set_hybrid(unet_i8_handle_t h, int on);
 int unet_i8_tensor_dtype(unet_i8_handle_t h, const char* name);
 int unet_i8_read_tensor_f16(unet_i8_handle_t h, const char* name, uint16_t* dst_host, size_t cap_bytes, int* channels);
+/* K-class quantised models (csrc/i8_classes_kernels.h).  unet_i8_finalize takes the class count K from the entries of
+ * `output.bias_q` (1 .. UNET_MAX_CLASSES) and requires `output.w_q` (K rows of features[0] weights), `output.w_zp` and
+ * `output.mult` (K entries) - and for a hybrid head `output.w_h`, `.gain`, `.bias_f` - to agree with it: UNET_ERR_STATE
+ * with a text for unet_i8_last_error otherwise, before any device is touched.  unet_i8_out_channels: K, 0 before the
+ * first unet_i8_finalize.  A handle with K == 1 runs exactly what it ran before.
+ *
+ * unet_i8_forward_classes_u8: the forward of a handle with K >= 2.  Per pixel and class the single-class head's
+ * arithmetic, logit_k = float32(int32 accumulator_k) * (x_scale * w_scale[k]), one IEEE multiplication (a hybrid head:
+ * unet_lane_detection_amd/quant.py); every output is optional, at least one is required:
+ *   logits_dev (N,K,H,W) fp32, probs_dev (N,K,H,W) = softmax over K          16-byte aligned
+ *   labels_dev (N,H,W) uint8 = argmax, mask_dev (N,H,W) uint8 = 255 where the label is mask_class      4-byte aligned
+ * with the tie and NaN rule of unet_forward_classes_u8.  With labels_dev or mask_dev alone the head writes one byte per
+ * pixel.  UNET_ERR_INVALID_ARG with a text for a single-class handle, for no output at all, for mask_dev with mask_class
+ * outside 0 .. K-1 and for a misaligned output; unet_i8_forward_u8 returns UNET_ERR_INVALID_ARG with a text for a handle
+ * with K >= 2; all before any device is touched.
+ *
+ * unet_i8_run_head: the head alone on the last tensor of the handle's last forward (its n, height, width): the outputs
+ * of unet_i8_forward_u8 for K == 1 (labels_dev, mask_class unused), those of unet_i8_forward_classes_u8 otherwise
+ * (threshold_logit unused).  UNET_ERR_STATE when no forward has run since unet_i8_finalize. */
+int unet_i8_out_channels(unet_i8_handle_t h);
+int unet_i8_forward_classes_u8(unet_i8_handle_t h, const uint8_t* frames_dev, int n, int height, int width,
+                               float* logits_dev, float* probs_dev, uint8_t* labels_dev, int mask_class, uint8_t* mask_dev,
+                               void* stream);
+int unet_i8_run_head(unet_i8_handle_t h, float* logits_dev, float* probs_dev, uint8_t* labels_dev, int mask_class,
+                     uint8_t* mask_dev, float threshold_logit, void* stream);
 int unet_i8_destroy(unet_i8_handle_t h);
 const char* unet_i8_last_error(unet_i8_handle_t h);
 
@@ -902,6 +928,14 @@ const char* unet_i8_last_error(unet_i8_handle_t h);
 int unet_num_range_tensors(unet_handle_t h);
 int unet_forward_u8_ranges(unet_handle_t h, const uint8_t* frames_dev, int n, int height, int width,
                            float* ranges_host, void* stream);
+/* The same pass and the histogram pass below for a handle with out_channels >= 2 (UNET_ERR_INVALID_ARG with a text for a
+ * single-class handle, as the two single-class entry points refuse a K-class one).  The range tensors are those of
+ * quant.tensor_names() and none of them is the head's output: the record of a K-class model equals, bit for bit, that of
+ * a single-class model with the same body. */
+int unet_forward_classes_u8_ranges(unet_handle_t h, const uint8_t* frames_dev, int n, int height, int width,
+                                   float* ranges_host, void* stream);
+int unet_forward_classes_u8_histograms(unet_handle_t h, const uint8_t* frames_dev, int n, int height, int width,
+                                       const float* spans_host, int bins, unsigned long long* hist_dev, void* stream);
 
 /* Calibration beyond min/max (README.md:3407-3412 'mmse' / 'kl_divergence'): the distribution of every range tensor.
  * Binning rule (csrc/calib_kernels.cpp; quant.histogram_model restates it bit for bit): inv = float(bins) / (hi - lo)

@@ -159,6 +159,11 @@ SIGNATURES = {
     "unet_i8_finalize": (C.c_int, [C.c_void_p]),
     "unet_i8_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_float, C.c_void_p]),
+    "unet_i8_out_channels": (C.c_int, [C.c_void_p]),
+    "unet_i8_forward_classes_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "unet_i8_run_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
+                                   C.c_void_p]),
     "unet_i8_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     "unet_i8_set_hybrid": (C.c_int, [C.c_void_p, C.c_int]),
     "unet_i8_tensor_dtype": (C.c_int, [C.c_void_p, C.c_char_p]),
@@ -167,10 +172,14 @@ SIGNATURES = {
     "unet_i8_last_error": (C.c_char_p, [C.c_void_p]),
     "unet_num_range_tensors": (C.c_int, [C.c_void_p]),
     "unet_forward_u8_ranges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "unet_forward_classes_u8_ranges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_void_p]),
     "unet_op_histogram_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
                                         C.c_void_p, C.c_void_p]),
     "unet_forward_u8_histograms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                              C.c_void_p, C.c_void_p]),
+    "unet_forward_classes_u8_histograms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                     C.c_int, C.c_void_p, C.c_void_p]),
     "unet_prob_mae_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
     "unet_destroy": (C.c_int, [C.c_void_p]),
     "unet_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),

@@ -44,15 +44,15 @@ OBJDIR = os.path.join(CSRC, "build")
 # calibration, of the int8 tier's hybrid (fp16) units, of the video path, of the ensemble combine and threshold
 # sweep, of lane following (HSV extractor, scan-row centre), of the frame and output diagnostics, of the lane fit, of
 # the component labelling, of the lane view, of the frame correction, of the polygon rasteriser and of the gradient
-# pass (accumulation, norm, non-finite count) and of the multi-class head, loss and confusion matrix, code objects of
-# their own
+# pass (accumulation, norm, non-finite count), of the multi-class head, loss and confusion matrix and of the int8
+# tier's K-class head, code objects of their own
 SOURCES = ["unet_hip.cpp", "launch_conv_x3_r512.cpp", "launch_conv_x3_r512_w32.cpp", "launch_conv_x3_t448.cpp",
            "launch_conv_x3_t448_c.cpp", "launch_conv_x3_dec.cpp", "launch_conv_x3_ws.cpp", "launch_conv_q8_r512.cpp",
            "launch_upconv_x3.cpp", "launch_conv_bf16.cpp",
            "validate_kernels.cpp", "loss_kernels.cpp", "augment_kernels.cpp", "calib_kernels.cpp",
            "conv_h16.cpp", "video_kernels.cpp", "ensemble_kernels.cpp", "follow_kernels.cpp", "diagnose_kernels.cpp",
            "lanefit_kernels.cpp", "label_kernels.cpp", "laneview_kernels.cpp", "correct_kernels.cpp",
-           "annotate_kernels.cpp", "grad_kernels.cpp", "multiclass_kernels.cpp"]
+           "annotate_kernels.cpp", "grad_kernels.cpp", "multiclass_kernels.cpp", "i8_classes_kernels.cpp"]
 FLAGS = ["-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result",
          "-Wno-unused-value"]
 

@@ -68,30 +68,7 @@ struct HeadKArgs {
   uint8_t* mask;
 };
 
-// softmax and argmax of K logits (registers)
-template <int KP>
-__device__ __forceinline__ int softmax_argmax(const float (&z)[KP], int K, float (&p)[KP]) {
-  float m = -INFINITY, best = -INFINITY;
-  int label = 0;
-#pragma unroll
-  for (int k = 0; k < KP; ++k)
-    if (k < K) {
-      m = fmaxf(m, z[k]);
-      if (z[k] > best) {
-        best = z[k];
-        label = k;
-      }
-    }
-  float sum = 0.f;
-#pragma unroll
-  for (int k = 0; k < KP; ++k) {
-    p[k] = k < K ? expf(z[k] - m) : 0.f;
-    sum += p[k];
-  }
-#pragma unroll
-  for (int k = 0; k < KP; ++k) p[k] = p[k] / sum;
-  return label;
-}
+// softmax and argmax of K logits in registers: softmax_argmax of multiclass_kernels.h
 
 // (hi, lo) packed fp16 pairs -> the two fp32 values they stand for (merge_pk_f16 of conv_x3_ws.h)
 __device__ __forceinline__ void merge_pair(uint32_t hi, uint32_t lo, float& v0, float& v1) {

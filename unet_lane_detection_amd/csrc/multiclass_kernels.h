@@ -11,11 +11,50 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
 #include <cstddef>
 
 namespace unet {
 
 constexpr int MC_MAX_CLASSES = 8;       // == UNET_MAX_CLASSES
+
+// The class rule of every K-way head (the fp32 and f16x3 heads here, the int8 tier's in i8_classes_kernels.cpp), on K
+// logits in registers (KP = K rounded up).  argmax: scan from class 0 with `>` against -inf, so ties go to the lowest
+// index and a NaN never wins.
+template <int KP>
+__device__ __forceinline__ int class_argmax(const float (&z)[KP], int K) {
+  float best = -INFINITY;
+  int label = 0;
+#pragma unroll
+  for (int k = 0; k < KP; ++k)
+    if (k < K && z[k] > best) {
+      best = z[k];
+      label = k;
+    }
+  return label;
+}
+
+// softmax: exp(z_k - max z) / sum with expf and an IEEE division; returns the argmax.  Acc: the type the K exponentials
+// are added and divided in.  float (the fp32 and f16x3 heads): up to K - 1 roundings of the sum on top of expf's.  double
+// (the int8 tier's head, whose logits are exact and whose probabilities are held to 4 x 2^-24 of the float64 softmax at
+// K = 8 as well): the sum and the quotient are exact to fp32's precision, which leaves expf's error and one rounding.
+template <int KP, typename Acc = float>
+__device__ __forceinline__ int softmax_argmax(const float (&z)[KP], int K, float (&p)[KP]) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < KP; ++k)
+    if (k < K) m = fmaxf(m, z[k]);
+  Acc sum = 0;
+#pragma unroll
+  for (int k = 0; k < KP; ++k) {
+    p[k] = k < K ? expf(z[k] - m) : 0.f;
+    sum += (Acc)p[k];
+  }
+#pragma unroll
+  for (int k = 0; k < KP; ++k) p[k] = (float)((Acc)p[k] / sum);
+  return class_argmax<KP>(z, K);
+}
+
 constexpr int MC_MAX_WEIGHTS = 4096;    // K * C floats held in LDS by the head and its backward
 constexpr int MC_RED_BLOCKS = 1024;     // the most blocks a reduction uses (4 per CU)
 

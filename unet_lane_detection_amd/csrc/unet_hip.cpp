@@ -55,6 +55,8 @@
 #include "launch.h"
 #include "op_entry.h"
 #include "multiclass_kernels.h"
+#include "i8_classes_kernels.h"
+#include "i8_head_check.h"
 
 // Kernels that need more dynamic LDS than the default opt in once per (device, kernel): the attribute is per device.
 // Shared with the launch units (launch.h).

@@ -57,6 +57,19 @@ struct unet_i8_ctx {
   bool headHyb = false;
   uint16_t* headWh = nullptr;
   float headM = 0.f, headB = 0.f;
+  // classes of the head: 0 until unet_i8_finalize has read output.bias_q, 1 the single-class head (the scalars above), K >= 2
+  // the K-class head (i8_classes_kernels.h) with one entry per row in the device arrays below
+  int classes = 0;
+  int32_t *headWzpK = nullptr, *headBiasK = nullptr;
+  float *headMultK = nullptr, *headMK = nullptr, *headBK = nullptr;
+  void free_head() {
+    for (void* p : {(void*)headW, (void*)headWh, (void*)headWzpK, (void*)headBiasK, (void*)headMultK, (void*)headMK, (void*)headBK})
+      if (p) hipFree(p);
+    headW = nullptr;
+    headWh = nullptr;
+    headWzpK = headBiasK = nullptr;
+    headMultK = headMK = headBK = nullptr;
+  }
   std::map<std::string, I8Tensor> tensors;   // by name, incl. "im2col"
   GrowBuf ws;
   int wsN = 0, wsH = 0, wsW = 0;
@@ -66,11 +79,9 @@ struct unet_i8_ctx {
       for (auto& u : *v) u.free_dev();
     first.free_dev();
     if (lut) hipFree(lut);
-    if (headW) hipFree(headW);
-    if (headWh) hipFree(headWh);
+    free_head();
     ws.release();
-    lut = headW = nullptr;
-    headWh = nullptr;
+    lut = nullptr;
   }
 };
 
@@ -602,6 +613,10 @@ int unet_i8_load(unet_i8_handle_t h, const char* name, const void* data, size_t 
 
 int unet_i8_finalize(unet_i8_handle_t h) {
   if (!h) return UNET_ERR_INVALID_ARG;
+  // the class count and the head's arrays: host work, settled before a device is touched
+  h->classes = unet::i8_head_classes(h->arrays, h->features[0], i8_unit_hybrid(h, "output"), h->err);
+  if (!h->classes) return UNET_ERR_STATE;
+  const int K = h->classes;
   HIPCHK(h->err, hipSetDevice(h->device));
   const int d = h->depth;
   h->enc.assign(2 * d, I8Unit());
@@ -649,49 +664,113 @@ int unet_i8_finalize(unet_i8_handle_t h) {
     if ((rc = conv(h->dec[2 * j + 1], p + ".3", f, pad(f), f, false, dj + ".a", dj + ".b"))) return rc;
   }
   h->headHyb = i8_unit_hybrid(h, "output");
+  h->free_head();
+  const size_t c0 = (size_t)h->features[0];
   if (h->headHyb) {
     I8Unit hu;
     hu.in16 = h->f16Tensor["dec" + std::to_string(d - 1) + ".b"];
     std::vector<uint16_t> wh;
     std::vector<float> m, b;
-    if (!i8_get(h, "output.w_h", wh, h->features[0])) return UNET_ERR_STATE;
-    if ((rc = h16_get_common(h, hu, "output", 1, false, m, b))) return rc;
+    if (!i8_get(h, "output.w_h", wh, K * c0)) return UNET_ERR_STATE;
+    if ((rc = h16_get_common(h, hu, "output", K, false, m, b))) return rc;
     h->headM = m[0];
     h->headB = b[0];
-    if (h->headWh) hipFree(h->headWh);
-    h->headWh = nullptr;
     if ((rc = i8_upload(h->err, &h->headWh, wh))) return rc;
+    if (K > 1 && ((rc = i8_upload(h->err, &h->headMK, m)) || (rc = i8_upload(h->err, &h->headBK, b)))) return rc;
   }
   std::vector<int8_t> lut, hw;
-  std::vector<int32_t> s1;
-  std::vector<float> f1;
+  std::vector<int32_t> s1, wzpK, biasK;
+  std::vector<float> multK;
   if (!i8_get(h, "input.lut", lut, 768) || !i8_get(h, "input.zp", s1, 1)) return UNET_ERR_STATE;
   h->zin = s1[0];
   if (h->lut) hipFree(h->lut);
   h->lut = nullptr;
   if ((rc = i8_upload(h->err, &h->lut, lut))) return rc;
-  if (!i8_get(h, "output.w_q", hw, h->features[0]) || !i8_get(h, "output.w_zp", s1, 1)) return UNET_ERR_STATE;
-  h->headWzp = s1[0];
+  if (!i8_get(h, "output.w_q", hw, K * c0) || !i8_get(h, "output.w_zp", wzpK, K)) return UNET_ERR_STATE;
+  h->headWzp = wzpK[0];
   if (!i8_get(h, "output.x_zp", s1, 1)) return UNET_ERR_STATE;
   h->headXzp = s1[0];
-  if (!i8_get(h, "output.bias_q", s1, 1)) return UNET_ERR_STATE;
-  h->headBias = s1[0];
-  if (!i8_get(h, "output.mult", f1, 1)) return UNET_ERR_STATE;
-  h->headMult = f1[0];
-  if (h->headW) hipFree(h->headW);
-  h->headW = nullptr;
+  if (!i8_get(h, "output.bias_q", biasK, K)) return UNET_ERR_STATE;
+  h->headBias = biasK[0];
+  if (!i8_get(h, "output.mult", multK, K)) return UNET_ERR_STATE;
+  h->headMult = multK[0];
   if ((rc = i8_upload(h->err, &h->headW, hw))) return rc;
+  if (K > 1 && ((rc = i8_upload(h->err, &h->headWzpK, wzpK)) || (rc = i8_upload(h->err, &h->headBiasK, biasK)) ||
+                (rc = i8_upload(h->err, &h->headMultK, multK))))
+    return rc;
   h->finalized = true;
   return UNET_OK;
 }
 
-int unet_i8_forward_u8(unet_i8_handle_t h, const uint8_t* frames, int n, int height, int width, float* logits,
-                       float* probs, uint8_t* mask, float thr, void* stream) {
-  if (!h || !frames) return UNET_ERR_INVALID_ARG;
-  if (!h->finalized) {
-    h->err = "unet_i8_finalize has not been called";
-    return UNET_ERR_STATE;
+// what the head of one forward writes: the single-class outputs, or those of the K-class head
+struct I8HeadOut {
+  float* logits = nullptr;
+  float* probs = nullptr;
+  uint8_t* mask = nullptr;
+  float thr = 0.f;
+  uint8_t* labels = nullptr;
+  int maskClass = 0;
+};
+
+// the head on tensor `cur` of the last forward: head_i8_kernel / head_h16_kernel of a single-class model, the K-class
+// kernels of i8_classes_kernels.h otherwise
+static int i8_run_head(unet_i8_ctx* h, const I8Tensor& cur, size_t npix, size_t hw, const I8HeadOut& o, hipStream_t s) {
+  const int8_t* x = reinterpret_cast<const int8_t*>(h->ws.p + cur.off);
+  if (h->classes > 1) {
+    unet::HeadKI8Args a = {};
+    a.x = x;
+    a.ld = cur.ld;
+    a.C = h->features[0];
+    a.K = h->classes;
+    a.npix = npix;
+    a.hw = hw;
+    a.xzp = h->headXzp;
+    a.w = h->headW;
+    a.wzp = h->headWzpK;
+    a.bias = h->headBiasK;
+    a.mult = h->headMultK;
+    a.wh = h->headWh;
+    a.hm = h->headMK;
+    a.hb = h->headBK;
+    a.logits = o.logits;
+    a.probs = o.probs;
+    a.labels = o.labels;
+    a.mask = o.mask;
+    a.maskClass = o.maskClass;
+    HIPCHK(h->err, h->headHyb ? unet::launch_headk_h16(a, cur.f16, s) : unet::launch_headk_i8(a, s));
+  } else if (h->headHyb) {
+    HIPCHK(h->err, unet::launch_head_h16(x, cur.f16, cur.ld, h->features[0], npix, h->headWh, h->headXzp, h->headM, h->headB,
+                                         o.logits, o.probs, o.mask, o.thr, s));
+  } else {
+    hipLaunchKernelGGL(unet::head_i8_kernel, dim3(grid_for(npix)), dim3(256), 0, s, x, cur.ld, h->features[0], npix, h->headW,
+                       h->headWzp, h->headXzp, h->headBias, h->headMult, o.logits, o.probs, o.mask, o.thr);
+    HIPCHK(h->err, hipGetLastError());
   }
+  return UNET_OK;
+}
+
+// The refusals of a forward that need no device, in this order: the handle's kind (known once unet_i8_finalize has read
+// the head), the outputs asked for (i8_classes_args), the handle's state (i8_state_gate).  wantClasses: the caller is a
+// K-class entry point.
+static int i8_kind_gate(unet_i8_ctx* h, const char* who, bool wantClasses) {
+  if (h->classes && (h->classes > 1) != wantClasses) {
+    h->err = std::string(who) +
+             (wantClasses ? std::string(": this entry point serves a K-class model (2 or more entries in output.bias_q); the "
+                                        "handle has the single-class head and runs unet_i8_forward_u8")
+                          : ": this entry point serves the single-class head; a handle with " + std::to_string(h->classes) +
+                                " classes runs unet_i8_forward_classes_u8");
+    return UNET_ERR_INVALID_ARG;
+  }
+  return UNET_OK;
+}
+
+static int i8_state_gate(unet_i8_ctx* h) {
+  if (h->finalized) return UNET_OK;
+  h->err = "unet_i8_finalize has not been called";
+  return UNET_ERR_STATE;
+}
+
+static int i8_forward(unet_i8_ctx* h, const uint8_t* frames, int n, int height, int width, const I8HeadOut& out, void* stream) {
   const int m = 1 << h->depth;
   if (n <= 0 || height <= 0 || width <= 0) return UNET_ERR_INVALID_ARG;
   if (height % m || width % m) {
@@ -753,15 +832,70 @@ int unet_i8_forward_u8(unet_i8_handle_t h, const uint8_t* frames, int n, int hei
     HIPCHK(h->err, run(h->dec[2 * j + 1], da, ch, cw, db, 0));
     cur = &db;
   }
-  if (h->headHyb) {
-    HIPCHK(h->err, unet::launch_head_h16(P(*cur), cur->f16, cur->ld, h->features[0], npix, h->headWh, h->headXzp, h->headM,
-                                         h->headB, logits, probs, mask, thr, s));
-  } else {
-    hipLaunchKernelGGL(unet::head_i8_kernel, dim3(grid_for(npix)), dim3(256), 0, s, P(*cur), cur->ld, h->features[0], npix,
-                       h->headW, h->headWzp, h->headXzp, h->headBias, h->headMult, logits, probs, mask, thr);
-    HIPCHK(h->err, hipGetLastError());
+  return i8_run_head(h, *cur, npix, (size_t)height * width, out, s);
+}
+
+int unet_i8_forward_u8(unet_i8_handle_t h, const uint8_t* frames, int n, int height, int width, float* logits,
+                       float* probs, uint8_t* mask, float thr, void* stream) {
+  if (!h || !frames) return UNET_ERR_INVALID_ARG;
+  int rc = i8_kind_gate(h, "unet_i8_forward_u8", false);
+  if (!rc) rc = i8_state_gate(h);
+  if (rc) return rc;
+  I8HeadOut o;
+  o.logits = logits, o.probs = probs, o.mask = mask, o.thr = thr;
+  return i8_forward(h, frames, n, height, width, o, stream);
+}
+
+int unet_i8_out_channels(unet_i8_handle_t h) { return h ? h->classes : 0; }
+
+// the checks of the K-class outputs that need no device
+static int i8_classes_args(unet_i8_ctx* h, const char* who, const float* logits, const float* probs, const uint8_t* labels,
+                           int maskClass, const uint8_t* mask) {
+  if (!logits && !probs && !labels && !mask) {
+    h->err = std::string(who) + ": no output asked for (logits, probs, labels and mask are all null)";
+    return UNET_ERR_INVALID_ARG;
+  }
+  if (mask && h->classes && (maskClass < 0 || maskClass >= h->classes)) {
+    h->err = std::string(who) + ": mask_class must name a class of the handle (0 .. " + std::to_string(h->classes - 1) + ")";
+    return UNET_ERR_INVALID_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(probs)) % 16 ||
+      (reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(mask)) % 4) {
+    h->err = std::string(who) + ": logits and probs must be 16-byte aligned, labels and mask 4-byte aligned";
+    return UNET_ERR_INVALID_ARG;
   }
   return UNET_OK;
+}
+
+int unet_i8_forward_classes_u8(unet_i8_handle_t h, const uint8_t* frames, int n, int height, int width, float* logits,
+                               float* probs, uint8_t* labels, int maskClass, uint8_t* mask, void* stream) {
+  if (!h || !frames) return UNET_ERR_INVALID_ARG;
+  int rc = i8_kind_gate(h, "unet_i8_forward_classes_u8", true);
+  if (!rc) rc = i8_classes_args(h, "unet_i8_forward_classes_u8", logits, probs, labels, maskClass, mask);
+  if (!rc) rc = i8_state_gate(h);
+  if (rc) return rc;
+  I8HeadOut o;
+  o.logits = logits, o.probs = probs, o.labels = labels, o.maskClass = maskClass, o.mask = mask;
+  return i8_forward(h, frames, n, height, width, o, stream);
+}
+
+// The head alone, on the last tensor of the handle's last forward (its n, height, width): the outputs of unet_i8_forward_u8
+// for a single-class handle (labels and mask_class unused), those of unet_i8_forward_classes_u8 otherwise (the threshold
+// unused).  For timing the head and for comparing its output configurations with one another.
+int unet_i8_run_head(unet_i8_handle_t h, float* logits, float* probs, uint8_t* labels, int maskClass, uint8_t* mask, float thr,
+                     void* stream) {
+  if (!h) return UNET_ERR_INVALID_ARG;
+  if (!h->finalized || !h->ws.p || !h->wsN) {
+    h->err = "unet_i8_run_head: no forward has run on this handle since unet_i8_finalize";
+    return UNET_ERR_STATE;
+  }
+  if (h->classes > 1)
+    if (int rc = i8_classes_args(h, "unet_i8_run_head", logits, probs, labels, maskClass, mask)) return rc;
+  HIPCHK(h->err, hipSetDevice(h->device));
+  I8HeadOut o;
+  o.logits = logits, o.probs = probs, o.labels = labels, o.maskClass = maskClass, o.mask = mask, o.thr = thr;
+  const I8Tensor& cur = h->tensors.at("dec" + std::to_string(h->depth - 1) + ".b");
+  return i8_run_head(h, cur, (size_t)h->wsN * h->wsH * h->wsW, (size_t)h->wsH * h->wsW, o, (hipStream_t)stream);
 }
 
 // Copy one activation tensor of the last forward call to the host as dense NHWC int8 with its real channels
@@ -834,10 +968,19 @@ const char* unet_i8_last_error(unet_i8_handle_t h) { return h ? h->err.c_str() :
 // ---- calibration on the float handle: per-tensor (min, max) of one forward, for quant.quantize_model ----
 int unet_num_range_tensors(unet_handle_t h) { return h ? 3 + 4 * h->cfg.depth : 0; }
 
-int unet_forward_u8_ranges(unet_handle_t h, const uint8_t* frames, int n, int height, int width, float* rangesHost,
-                           void* stream) {
+// the float forward of a calibration pass: the handle's own kind of forward with no output asked for (the range tensors
+// are quant.tensor_names; none of them is the head's output)
+static int calib_forward(unet_handle_t h, const uint8_t* frames, int n, int height, int width, void* stream) {
+  if (h->cfg.out_channels > 1)
+    return unet_forward_classes_u8(h, frames, n, height, width, 0, nullptr, nullptr, nullptr, 0, nullptr, stream);
+  return unet_forward_u8(h, frames, n, height, width, nullptr, nullptr, nullptr, 0.f, stream);
+}
+
+// body of unet_forward_u8_ranges (single-class handles) and unet_forward_classes_u8_ranges (K-class handles)
+static int forward_ranges(unet_handle_t h, const char* who, bool classes, const uint8_t* frames, int n, int height, int width,
+                          float* rangesHost, void* stream) {
   if (!h || !frames || !rangesHost) return UNET_ERR_INVALID_ARG;
-  if (int rc = single_class_only(h, "unet_forward_u8_ranges")) return rc;
+  if (int rc = classes ? multi_class_only(h, who) : single_class_only(h, who)) return rc;
   const int nt = unet_num_range_tensors(h);
   HIPCHK(h->err, hipSetDevice(h->cfg.device));
   std::vector<unsigned> init((size_t)nt * 2);
@@ -851,7 +994,7 @@ int unet_forward_u8_ranges(unet_handle_t h, const uint8_t* frames, int n, int he
   h->rangeKeys = keys;
   // direct kernels only: the Winograd kernel fuses the pool and the algorithms agree to 3e-5 anyway; ranges are
   // taken on the tensors the forward materialises
-  const int rc = unet_forward_u8(h, frames, n, height, width, nullptr, nullptr, nullptr, 0.f, stream);
+  const int rc = calib_forward(h, frames, n, height, width, stream);
   h->rangeKeys = nullptr;
   int rc2 = UNET_OK;
   if (!rc) {
@@ -866,6 +1009,16 @@ int unet_forward_u8_ranges(unet_handle_t h, const uint8_t* frames, int n, int he
     }
   }
   return rc ? rc : rc2;
+}
+
+int unet_forward_u8_ranges(unet_handle_t h, const uint8_t* frames, int n, int height, int width, float* rangesHost,
+                           void* stream) {
+  return forward_ranges(h, "unet_forward_u8_ranges", false, frames, n, height, width, rangesHost, stream);
+}
+
+int unet_forward_classes_u8_ranges(unet_handle_t h, const uint8_t* frames, int n, int height, int width, float* rangesHost,
+                                   void* stream) {
+  return forward_ranges(h, "unet_forward_classes_u8_ranges", true, frames, n, height, width, rangesHost, stream);
 }
 
 // ---- histogram calibration ('mmse', 'kl_divergence'): the distribution of every range tensor over a given span ----
@@ -883,10 +1036,11 @@ int unet_op_histogram_f32(int device, const float* x, size_t npix, int c, int ld
 // The forward of unet_forward_u8_ranges with the probes in their second mode: tensor i (order: quant.tensor_names) is
 // binned over spans_host[2 i], spans_host[2 i + 1] into hist_dev[i * (bins + 1) ...], which accumulates across calls and
 // stays on the device.  No host synchronisation.
-int unet_forward_u8_histograms(unet_handle_t h, const uint8_t* frames, int n, int height, int width,
-                               const float* spansHost, int bins, unsigned long long* histDev, void* stream) {
+// body of unet_forward_u8_histograms (single-class handles) and unet_forward_classes_u8_histograms (K-class handles)
+static int forward_histograms(unet_handle_t h, const char* who, bool classes, const uint8_t* frames, int n, int height,
+                              int width, const float* spansHost, int bins, unsigned long long* histDev, void* stream) {
   if (!h || !frames || !spansHost || !histDev) return UNET_ERR_INVALID_ARG;
-  if (int rc = single_class_only(h, "unet_forward_u8_histograms")) return rc;
+  if (int rc = classes ? multi_class_only(h, who) : single_class_only(h, who)) return rc;
   if (!unet::histogram_bins_supported(bins)) {
     h->err = "histogram bins must be a power of two from 64 to 4096";
     return UNET_ERR_INVALID_ARG;
@@ -902,11 +1056,22 @@ int unet_forward_u8_histograms(unet_handle_t h, const uint8_t* frames, int n, in
   h->hist = histDev;
   h->histSpans = spansHost;
   h->histBins = bins;
-  const int rc = unet_forward_u8(h, frames, n, height, width, nullptr, nullptr, nullptr, 0.f, stream);
+  const int rc = calib_forward(h, frames, n, height, width, stream);
   h->hist = nullptr;
   h->histSpans = nullptr;
   h->histBins = 0;
   return rc;
+}
+
+int unet_forward_u8_histograms(unet_handle_t h, const uint8_t* frames, int n, int height, int width,
+                               const float* spansHost, int bins, unsigned long long* histDev, void* stream) {
+  return forward_histograms(h, "unet_forward_u8_histograms", false, frames, n, height, width, spansHost, bins, histDev, stream);
+}
+
+int unet_forward_classes_u8_histograms(unet_handle_t h, const uint8_t* frames, int n, int height, int width,
+                                       const float* spansHost, int bins, unsigned long long* histDev, void* stream) {
+  return forward_histograms(h, "unet_forward_classes_u8_histograms", true, frames, n, height, width, spansHost, bins, histDev,
+                            stream);
 }
 
 // compare_outputs (reference README.md:3512-3565): acc_dev[f] += sum over frame f of |pa - pb|, f < frames, each frame

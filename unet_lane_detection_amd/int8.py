@@ -8,10 +8,15 @@
   qmodel = quant.quantize_model(state_dict, ranges)        # README.md:3106-3116 scheme, host arithmetic on weights
   net = UNetInt8(qmodel, device=0); net.run_u8(frames)
   compare_outputs(float_model, net, frames)                # float-vs-int8 MAE of probabilities (README.md:3512-3565)
+  net.evaluate_classes(frames, labels)                     # K-class model: per-class IoU, mIoU, pixel accuracy of the tier
   units = choose_hybrid(float_model, state_dict, ranges, frames, k=3)      # not GOOD?  README.md:3466-3474, fourth remedy:
   qmodel = quant.quantize_model(state_dict, ranges, hybrid=units)          # those units in fp16 (hybrid quantisation)
 
-All arithmetic on activations runs in libunet_hip.so (csrc/conv_i8.h, csrc/conv_h16.h); there is no CPU fallback.
+A state dict whose output.weight has K = 2..8 rows gives a K-class quantised model (quantize_model emits the head's arrays
+with K rows): every function here takes it, and UNetInt8.run_u8 then has UNetHIP.run_u8's K-class outputs.
+
+All arithmetic on activations runs in libunet_hip.so (csrc/conv_i8.h, csrc/conv_h16.h, csrc/i8_classes_kernels.h); there is
+no CPU fallback.
 """
 from __future__ import annotations
 
@@ -22,7 +27,7 @@ import torch
 
 from . import _lib, quant
 from .metrics import DEFAULT_THRESHOLDS
-from .model import _logit, _pack
+from .model import _logit, _multi_class_only, _pack, _single_class_only
 
 
 def calibrate(float_model, frames_u8, batch=8, algorithm="normal", bins=quant.HIST_BINS, return_histograms=False):
@@ -31,7 +36,9 @@ def calibrate(float_model, frames_u8, batch=8, algorithm="normal", bins=quant.HI
     (README.md:3407-3412):
 
       "normal"          (min, max): the fp32 HIP tier with a min/max probe behind every layer
-                        (unet_forward_u8_ranges); frames are processed `batch` at a time and the ranges merged;
+                        (unet_forward_u8_ranges; unet_forward_classes_u8_ranges for a K-class float model, whose
+                        ranges are those of its body: the head's output carries none); frames are processed `batch`
+                        at a time and the ranges merged;
       "mmse",           that pass first; its ranges, widened to contain 0, are the spans of a second pass over the same
       "kl_divergence"   frames with a histogram of `bins` bins behind every layer (unet_forward_u8_histograms).  The
                         histograms stay on the device across batches and are read once; quant.range_from_histogram
@@ -67,6 +74,10 @@ def calibrate(float_model, frames_u8, batch=8, algorithm="normal", bins=quant.HI
     return (ranges, hists) if return_histograms else ranges
 
 
+def _classes(model):
+    return int(getattr(model, "out_channels", 1))
+
+
 def minmax_pass(float_model, frames, batch=8):
     """{tensor name: (min, max)} over `frames`: the range pass of calibrate (one host read per batch)."""
     lib = _lib.load()
@@ -77,11 +88,12 @@ def minmax_pass(float_model, frames, batch=8):
     lo = np.full(nt, np.inf)
     hi = np.full(nt, -np.inf)
     buf = (C.c_float * (2 * nt))()
+    entry = "unet_forward_classes_u8_ranges" if _classes(float_model) > 1 else "unet_forward_u8_ranges"
     for i in range(0, frames.shape[0], batch):
         f = frames[i:i + batch].to(float_model.device).contiguous()
         n, hh, ww, _ = f.shape
-        rc = lib.unet_forward_u8_ranges(h, _lib.ptr(f), n, hh, ww, buf, _lib.stream(float_model.device))
-        _lib.check(rc, "unet_forward_u8_ranges", h)
+        rc = getattr(lib, entry)(h, _lib.ptr(f), n, hh, ww, buf, _lib.stream(float_model.device))
+        _lib.check(rc, entry, h)
         r = np.frombuffer(buf, dtype=np.float32).reshape(nt, 2)
         lo = np.minimum(lo, r[:, 0])
         hi = np.maximum(hi, r[:, 1])
@@ -101,12 +113,13 @@ def histogram_pass(float_model, frames, spans, bins=quant.HIST_BINS, batch=8):
     hist_dev = torch.zeros((nt, bins + 1), dtype=torch.int64, device=float_model.device)
     elements = np.zeros(nt, dtype=np.int64)
     shapes = quant.tensor_shapes(float_model.features)
+    entry = "unet_forward_classes_u8_histograms" if _classes(float_model) > 1 else "unet_forward_u8_histograms"
     for i in range(0, frames.shape[0], batch):
         f = frames[i:i + batch].to(float_model.device).contiguous()
         n, hh, ww, _ = f.shape
-        rc = lib.unet_forward_u8_histograms(h, _lib.ptr(f), n, hh, ww, spans.ctypes.data_as(C.c_void_p), int(bins),
-                                            _lib.ptr(hist_dev), _lib.stream(float_model.device))
-        _lib.check(rc, "unet_forward_u8_histograms", h)
+        rc = getattr(lib, entry)(h, _lib.ptr(f), n, hh, ww, spans.ctypes.data_as(C.c_void_p), int(bins),
+                                 _lib.ptr(hist_dev), _lib.stream(float_model.device))
+        _lib.check(rc, entry, h)
         elements += [n * (hh >> level) * (ww >> level) * c for c, level in shapes]
     return hist_dev, elements
 
@@ -149,15 +162,19 @@ def prob_mae(probs_a, probs_b):
 def compare_outputs(float_model, int8_net, frames_u8, batch=8):
     """The reference's `compare_outputs` (README.md:3512-3565): per-frame MAE between the probabilities of the float
     tier (fp32) and of the int8 tier over `frames_u8` ((N,H,W,3) uint8).  The probabilities stay on the device, where
-    each frame's |difference| is summed in float64; one number per frame is read.  Returns OutputComparison."""
+    each frame's |difference| is summed in float64; one number per frame is read.  Returns OutputComparison.  Two K-class
+    models are compared on their softmax tensors: the mean runs over the K * H * W probabilities of a frame."""
     frames = torch.as_tensor(frames_u8)
     if float_model.device != int8_net.device:
         raise ValueError("compare_outputs needs both tiers on one device")
+    if _classes(float_model) != _classes(int8_net):
+        raise ValueError(f"compare_outputs: the float model has {_classes(float_model)} class(es), the int8 model "
+                         f"{_classes(int8_net)}")
     out = []
     for i in range(0, frames.shape[0], batch):
         f = frames[i:i + batch].to(float_model.device).contiguous()
-        _, pf = float_model.run_u8(f, return_probs=True)
-        _, pq = int8_net.run_u8(f, return_probs=True)
+        pf = float_model.run_u8(f, return_probs=True)[1]
+        pq = int8_net.run_u8(f, return_probs=True)[1]
         out.append(prob_mae(pf, pq))
     return OutputComparison(torch.cat(out).cpu().numpy())
 
@@ -201,7 +218,8 @@ def choose_hybrid(float_model, state_dict, ranges, frames_u8, k, batch=8):
 
 class UNetInt8:
     """Quantised U-Net forward on one MI355X (i8 MFMA; the units a model marks hybrid on f16 MFMA, csrc/conv_h16.h).
-    hybrid=False runs a model with hybrid units as pure int8."""
+    hybrid=False runs a model with hybrid units as pure int8.  out_channels: 1, or the K classes of a model whose head
+    arrays have K rows (csrc/i8_classes_kernels.h)."""
 
     def __init__(self, qmodel, device=0, hybrid=True):
         if not torch.cuda.is_available():
@@ -225,6 +243,7 @@ class UNetInt8:
             self._check(self._lib.unet_i8_load(h, k.encode(), a.ctypes.data_as(C.c_void_p), a.nbytes), f"unet_i8_load({k})")
         self._check(self._lib.unet_i8_set_hybrid(h, 1 if hybrid else 0), "unet_i8_set_hybrid")
         self._check(self._lib.unet_i8_finalize(h), "unet_i8_finalize")
+        self.out_channels = int(self._lib.unet_i8_out_channels(h))
 
     @classmethod
     def from_file(cls, path, device=0, hybrid=True):
@@ -247,13 +266,25 @@ class UNetInt8:
         if self._h is None:
             raise RuntimeError("UNetInt8 has been released")
 
-    def run_u8(self, frames, return_probs=False, return_mask=False, threshold=0.5):
-        """frames: (N,H,W,3) uint8 RGB on this device -> logits (N,1,H,W) float32 [, probabilities, mask]."""
+    def run_u8(self, frames, return_probs=False, return_mask=False, threshold=0.5, return_labels=False, mask_class=None):
+        """frames: (N,H,W,3) uint8 RGB on this device -> logits (N,1,H,W) float32 [, probabilities, mask].
+        A K-class model returns, as UNetHIP.run_u8 and in its order, logits (N,K,H,W) [, softmax (N,K,H,W)] [, labels
+        (N,H,W) uint8 = argmax] [, the (N,H,W) uint8 plane that is 255 where the label is mask_class]; return_mask and
+        threshold belong to the single-class head, return_labels and mask_class to a K-class model."""
         self._require_live()
+        if self.out_channels > 1:
+            _single_class_only(return_mask, "return_mask")
+            _single_class_only(threshold != 0.5, "threshold")
+            if mask_class is not None and not 0 <= int(mask_class) < self.out_channels:
+                raise ValueError(f"mask_class={mask_class!r}: the model has classes 0..{self.out_channels - 1}")
+        else:
+            _multi_class_only(return_labels, mask_class)
         if frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
             raise ValueError("frames must be (N,H,W,3) uint8")
         frames = frames.to(self.device).contiguous()
         n, h, w, _ = frames.shape
+        if self.out_channels > 1:
+            return self._run_classes(frames, n, h, w, True, return_probs, return_labels, mask_class)
         logits = torch.empty((n, 1, h, w), dtype=torch.float32, device=self.device)
         probs = torch.empty_like(logits) if return_probs else None
         mask = torch.empty((n, h, w), dtype=torch.uint8, device=self.device) if return_mask else None
@@ -262,6 +293,43 @@ class UNetInt8:
                                           _lib.stream(self.device))
         self._check(rc, "unet_i8_forward_u8")
         return _pack(logits, probs, mask, return_probs, return_mask)
+
+    def _run_classes(self, frames, n, h, w, want_logits, want_probs, want_labels, mask_class):
+        """unet_i8_forward_classes_u8 with the outputs asked for: the tensors in the order logits, probs, labels, mask"""
+        k = self.out_channels
+        logits = torch.empty((n, k, h, w), dtype=torch.float32, device=self.device) if want_logits else None
+        probs = torch.empty((n, k, h, w), dtype=torch.float32, device=self.device) if want_probs else None
+        labels = torch.empty((n, h, w), dtype=torch.uint8, device=self.device) if want_labels else None
+        mask = torch.empty((n, h, w), dtype=torch.uint8, device=self.device) if mask_class is not None else None
+        p = _lib.ptr
+        rc = self._lib.unet_i8_forward_classes_u8(self._h, p(frames), n, h, w, p(logits), p(probs), p(labels),
+                                                  int(mask_class) if mask_class is not None else 0, p(mask),
+                                                  _lib.stream(self.device))
+        self._check(rc, "unet_i8_forward_classes_u8")
+        out = [t for t in (logits, probs, labels, mask) if t is not None]
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def predict_labels(self, frames):
+        """frames: (N,H,W,3) uint8 RGB -> (N,H,W) uint8 labels of a K-class model and nothing else: the head writes one
+        byte per pixel (the deployment form; run_u8 always returns the logits as well)."""
+        self._require_live()
+        if self.out_channels < 2:
+            _multi_class_only(True, None)
+        if frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
+            raise ValueError("frames must be (N,H,W,3) uint8")
+        frames = frames.to(self.device).contiguous()
+        n, h, w, _ = frames.shape
+        return self._run_classes(frames, n, h, w, False, False, True, None)
+
+    def evaluate_classes(self, frames, labels_u8, batch=None, ignore_index=None):
+        """Per-class IoU, miou and pixel_acc (metrics.ClassMetrics) of the K-class int8 tier over uint8 `frames` against
+        `labels_u8` (N,H,W) uint8: as UNetHIP.evaluate_classes."""
+        from . import metrics
+        self._require_live()
+        if self.out_channels < 2:
+            _multi_class_only(True, None)
+        return metrics.evaluate_class_batches(self.device, self.out_channels, frames, labels_u8, batch, ignore_index,
+                                              self.predict_labels)
 
     def evaluate(self, frames, targets, threshold=0.5, batch=None):
         """Segmentation metrics of the int8 tier over uint8 `frames` against `targets`: as UNetHIP.evaluate."""

@@ -498,3 +498,22 @@ def evaluate_batches(lib, device, frames, targets, batch, threshold, stream_fn, 
         logits = forward_fn(frames[i:i + step].to(device).contiguous())
         accumulate(lib, device.index, logits, targets[i:i + step], acc, stream_fn(), threshold=threshold)
     return SegMetrics(acc.cpu().numpy())
+
+
+def evaluate_class_batches(device, classes, frames, labels, batch, ignore_index, labels_fn):
+    """Shared body of UNetHIP.evaluate_classes / UNetInt8.evaluate_classes: labels_fn(frames on the device) -> device
+    (N,H,W) uint8 argmax labels, counted batch by batch into one ConfusionMatrix on the device; the K * K counts are read
+    once, at the end.  Returns ClassMetrics (per-class IoU, miou, pixel_acc: what UNetTrainer.validate reports from its
+    matrix; the loss terms stay NaN, no loss is formed here)."""
+    import torch
+    frames, labels = torch.as_tensor(frames), torch.as_tensor(labels)
+    n = int(frames.shape[0])
+    if labels.dtype != torch.uint8:
+        raise ValueError("labels must be uint8 label planes (N,H,W)")
+    if int(labels.shape[0]) != n or labels.numel() != n * int(frames.shape[1]) * int(frames.shape[2]):
+        raise ValueError("labels must be (N,H,W), one byte per pixel of the frames")
+    step = n if not batch else int(batch)
+    cm = ConfusionMatrix(classes, device, ignore_index)
+    for i in range(0, n, step):
+        cm.accumulate(labels_fn(frames[i:i + step].to(device).contiguous()), labels[i:i + step])
+    return cm.metrics()

@@ -232,6 +232,18 @@ class UNetHIP:
                                         lambda f: self.run_u8(f, precision=precision) if f.dtype == torch.uint8
                                         else self.forward(f, precision=precision))
 
+    def evaluate_classes(self, frames, labels_u8, batch=None, ignore_index=None, precision="fp32"):
+        """What a tier costs a K-class model in IoU: per-class IoU, miou and pixel_acc (metrics.ClassMetrics) of the
+        argmax labels of `frames` ((N,H,W,3) uint8) on the tier `precision` ("fp32" or "f16x3") against `labels_u8`
+        (N,H,W) uint8, `batch` frames at a time (default: all at once); pixels labelled `ignore_index` are left out.
+        The labels stay on the device and go through metrics.ConfusionMatrix; K * K counts are read at the end."""
+        from . import metrics
+        self._require_live()
+        if self.out_channels < 2:
+            _multi_class_only(True, None)
+        return metrics.evaluate_class_batches(self.device, self.out_channels, frames, labels_u8, batch, ignore_index,
+                                              lambda f: self.run_u8(f, return_labels=True, precision=precision)[1])
+
     def sweep(self, frames, targets, thresholds=DEFAULT_THRESHOLDS, precision="fp32", batch=None):
         """Confusion counts and metrics of one arithmetic tier at every threshold of `thresholds` (probabilities,
         ascending; default metrics.DEFAULT_THRESHOLDS) in one forward of the set: frames, targets and batch as

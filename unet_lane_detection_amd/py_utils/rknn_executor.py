@@ -16,6 +16,10 @@ Behavioural contract kept from the reference:
     and returns a list whose first element is a float32 (N,1,H,W) array;
     like the deployed blob (last op ConvSigmoid) the values are
     probabilities, so the caller's logits guard (src/unet.py:63) stays inert;
+  * the container is single-class, like the reference's: `run` returns one
+    probability plane per frame.  A quantised file with a K-class head
+    (unet_lane_detection_amd.int8.UNetInt8 runs those) is refused when the
+    container is built;
   * after `release()`, `run` prints the reference's error line and returns []
     (rknn_executor.py:27-29); `release()` may be called twice
     (src/unet.py:148-150 calls it again from `__del__`).
@@ -102,6 +106,9 @@ class RKNN_model_container:
                         quantised = {k: z[k] for k in z.files}
             if quantised is not None:       # the deployed form: an int8 model (the reference loads an int8 .rknn blob)
                 from ..int8 import UNetInt8
+                if np.asarray(quantised["output.bias_q"]).size != 1:
+                    raise ValueError("the container serves the single-class head; a K-class quantised model runs through "
+                                     "unet_lane_detection_amd.int8.UNetInt8")
                 self.model = UNetInt8(quantised, device=dev)
                 self.precision, self._auto_tier = "int8", False
             else:

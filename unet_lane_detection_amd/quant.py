@@ -23,7 +23,9 @@ Scheme implemented here (the integer-exact contract of the int8 tier; oracle/int
     the blob, README.md:3110-3111);
   * requantisation: q_out = clamp(rint(float32(acc + bias_q) * float32(x_scale * w_scale[co] / y_scale)) + y_zp),
     float32 multiply and round-half-even, ReLU as the lower clamp y_zp;
-  * head (ConvSigmoid in the blob): logits = float32(acc + bias_q) * float32(x_scale * w_scale), then sigmoid.
+  * head (ConvSigmoid in the blob): logits = float32(acc + bias_q) * float32(x_scale * w_scale), then sigmoid.  A head
+    of K = 2..8 rows (multi-class segmentation) is K such rows - row k quantised as it would be alone, with its own
+    w_scale, w_zp, bias_q and mult - followed by softmax / argmax over the K logits.
 """
 from __future__ import annotations
 
@@ -446,7 +448,7 @@ def _put_hybrid(q, state_dict, ranges, feats, tq, hybrid):
 
 
 def _conv_f64(kind, x, w):
-    """float64 convolution of a unit: x (N,C,H,W); w (O,C,3,3) for 'conv', (I,O,2,2) for 'up', (1,C,1,1) for 'head'.
+    """float64 convolution of a unit: x (N,C,H,W); w (O,C,3,3) for 'conv', (I,O,2,2) for 'up', (K,C,1,1) for 'head'.
     Zero padding: positions outside the image contribute exactly 0."""
     import torch
     import torch.nn.functional as F
@@ -463,7 +465,8 @@ def unit_model(qmodel, key, x):
     x: (N,C,H,W); an int8 array is an int8 tensor (codes), any float array an fp16 tensor (its stored values); for a
     decoder's first convolution it is the whole concat tensor.  Returns a dict:
       'dtype'   'int8' | 'fp16' | 'fp32' (the head): how the unit's output is stored (tensor_dtypes of the model's set)
-      'y'       the stored output by this model: int8 codes, fp16 values (as float32) or float32 logits
+      'y'       the stored output by this model: int8 codes, fp16 values (as float32) or float32 logits ((N,K,H,W) for
+                a head of K rows)
     and for a hybrid unit also
       'v'       a m + b in float64 with the fp16-rounded weights, after the ReLU where the unit has one: unrounded
       'S'       m sum |w16| |x| + |b| per output element: what the rounding errors of the fp32 evaluation scale with
@@ -533,7 +536,7 @@ def hybrid_bound(out, y_scale=None):
 def hybrid_forward_model(qmodel, frames, taps=None):
     """The forward of a quantised model with its hybrid units, in float64 with the fp16-rounded weights (unit_model on
     every unit; max-pooling and the concat on stored values).  frames: (N,H,W,3) uint8.  Returns (logits float32
-    (N,1,H,W), {unit key: {'v', 'S', 'K'}} for the hybrid units).  taps, if a dict, receives every stored tensor by
+    (N,K,H,W) - K = 1 for the reference's head -, {unit key: {'v', 'S', 'K'}} for the hybrid units).  taps, if a dict, receives every stored tensor by
     name."""
     feats = [int(f) for f in qmodel["features"]]
     d = len(feats)
@@ -561,7 +564,13 @@ def hybrid_forward_model(qmodel, frames, taps=None):
     return logits, info
 
 
+def out_channels(qmodel):
+    """1 for the reference's lane head, K for a K-class quantised model: the entries of output.bias_q"""
+    return int(np.asarray(qmodel["output.bias_q"]).size)
+
+
 def save_quantized(path, qmodel):
+    """One .npz of the model's arrays; a K-class model's head arrays keep their K rows."""
     np.savez_compressed(path, **qmodel)
 
 

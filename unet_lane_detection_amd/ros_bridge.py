@@ -97,13 +97,17 @@ class LanePipelineGPU:
     """image_callback of the reference node (src/unet_ros_node.py:296-311) without rospy: ImageMsg -> mono8 ImageMsg."""
 
     def __init__(self, model, threshold=0.5, src_points=REF_SRC_POINTS, dst_points=REF_DST_POINTS,
-                 warp_size=REF_WARP_SIZE, input_size=(224, 224), precision="fp32", on_error="raise"):
-        """on_error: "raise" propagates every exception; "reference" reproduces the reference's failure handling:
+                 warp_size=REF_WARP_SIZE, input_size=(224, 224), precision="fp32", on_error="raise", mask_class=None):
+        """mask_class: the class of a K-class model (out_channels > 1) whose pixels are the published mask - required for
+        such a model, refused for a single-class one (video.check_mask_class).
+        on_error: "raise" propagates every exception; "reference" reproduces the reference's failure handling:
         an inference failure (exception or empty output from the model) yields an all-zero mask of the warped size
         (`RKNNLaneInference.predict`, src/unet.py:81-92) and any other failure of the callback is logged and
         nothing is published (`image_callback`'s try/except, src/unet_ros_node.py:293-338: process returns None)."""
         if on_error not in ("raise", "reference"):
             raise ValueError(on_error)
+        from .video import check_mask_class
+        self.mask_class = check_mask_class(model, mask_class)
         self.on_error = on_error
         self.last_error = None
         self.model = model                       # UNetHIP
@@ -142,7 +146,10 @@ class LanePipelineGPU:
         handing out stale pixels; a range report of the f16x3 tier (include/unet_hip.h, UNET_ERR_RANGE) re-runs the
         frame on the exact-fp32 tier and keeps the pipeline there."""
         for _ in range(2):
-            out = self.model.run_u8(frame, return_mask=True, threshold=self.threshold, precision=self.precision)
+            if self.mask_class is not None:   # a K-class model: (logits, byte plane of the class)
+                out = self.model.run_u8(frame, mask_class=self.mask_class, precision=self.precision)
+            else:
+                out = self.model.run_u8(frame, return_mask=True, threshold=self.threshold, precision=self.precision)
             rc = self.model.device_error()
             if rc == 0:
                 return out

@@ -36,6 +36,21 @@ def jet_table():
     return ((np.clip(765 - 2 * np.abs(4 * i - 255 * c), 0, 510) + 1) // 2).astype(np.uint8)
 
 
+def check_mask_class(model, mask_class):
+    """The argument checks of a pipeline that takes a model's mask: a K-class model (out_channels > 1) needs the class
+    whose byte plane it is to use, a single-class model takes none.  Returns mask_class as an int, or None."""
+    k = int(getattr(model, "out_channels", 1))
+    if k > 1:
+        if mask_class is None:
+            raise ValueError(f"the model has {k} classes: mask_class names the one whose pixels are the mask")
+        if not 0 <= int(mask_class) < k:
+            raise ValueError(f"mask_class={mask_class!r}: the model has classes 0..{k - 1}")
+        return int(mask_class)
+    if mask_class is not None:
+        raise ValueError("mask_class belongs to a K-class model (out_channels > 1)")
+    return None
+
+
 class FramePipeline:
     """BGR frames -> (overlay, mask) through a `UNetHIP` (on the tier `precision`) or a `UNetInt8`.
 
@@ -51,9 +66,12 @@ class FramePipeline:
     SLOTS = 3   # chunk k computes while k+1 is uploaded and k-1 is downloaded
 
     def __init__(self, model, threshold=0.5, input_size=(224, 224), precision="f16x3", lut=None, alpha=0.7, beta=0.3,
-                 gamma=0.0, diagnose=False, correct=None):
+                 gamma=0.0, diagnose=False, correct=None, mask_class=None):
         """input_size: (width, height) of the network's input; lut: (256, 3) uint8 in the frames' channel order
-        (default `jet_table()`); alpha, beta, gamma: cv2.addWeighted's."""
+        (default `jet_table()`); alpha, beta, gamma: cv2.addWeighted's.  mask_class: the class of a K-class model
+        (out_channels > 1) whose pixels are the mask - required for such a model, refused for a single-class one, whose
+        mask is `threshold`'s."""
+        self.mask_class = check_mask_class(model, mask_class)
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs a HIP device; there is no CPU fallback")
         self._lib = _lib.load()
@@ -86,6 +104,9 @@ class FramePipeline:
         return small
 
     def _network(self, small):
+        if self.mask_class is not None:   # a K-class model: the byte plane of one class stands where the thresholded mask stands
+            kw = {"precision": self.precision} if self._tiered else {}
+            return self.model.run_u8(small, mask_class=self.mask_class, **kw)[-1]
         if not self._tiered:
             return self.model.run_u8(small, return_mask=True, threshold=self.threshold)[-1]
         return self.model.run_u8(small, return_mask=True, threshold=self.threshold, precision=self.precision)[-1]
